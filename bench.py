@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Throughput of the PARSeq inference hot path on MI355X (BASELINE.json metric: images/sec of 32x128 crops, PARSeq-S,
-AR decode + 1 refinement iteration), with the roofline fraction of the dominant kernel, parity evidence for the very
+AR decode + 1 refinement iteration); with --full also the roofline fraction of the dominant kernel, parity evidence for the very
 outputs that were timed, and the CPU oracle timed on the same box.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 512] [--precision bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 512] [--precision bf16] [--full] [--dump-outputs DIR]
+
+A plain run measures the headline and nothing else: set-up, warm-up, ONE timed region of exactly K steps in flight, the line.
+`--full` adds everything else this file measures or checks: the repeats of the timed region (median reported), the one-at-a-time
+figure, natural early exit, per-kernel profile and roofline, the CPU oracle baseline, parity against the fp32 mode and the oracle,
+the exact and bf16 modes, BASELINE configs[3], batch-1 latency and the training step.  `--dump-outputs DIR` writes the last
+timed step's logits to DIR/logits.npy (float32) for output-for-output comparison of two builds.
 
 `--gpus N` with N > 1 launches the N ranks itself (re-exec under `python -m torch.distributed.run`, one process per GPU,
 RCCL over xGMI); when the driver already launched it under torch.distributed.run (WORLD_SIZE set) it runs as one rank.
@@ -53,6 +59,24 @@ def gemm_flops(family, B, cfg):
             'enc.fc2_gemm': 2.0 * M * E * F, 'enc.mlp_fused': 4.0 * M * E * F, 'dec.memory_kv_gemm': 2.0 * M * 2 * E * E,
             'enc.attention': attn, 'enc.attn_fused': 2.0 * M * 4 * E * E + attn, 'enc.layer_fused': layer,
             'enc.blocks_fused': layer * cfg.get('enc_depth', cfg.get('depth', 12))}.get(family)
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, logits):
+    """--dump-outputs: what a caller of the timed path receives from its last step — the logits — as out_dir/logits.npy (float32).
+    Above DUMP_CAP_BYTES a fixed seeded sample of crops is kept instead, their row numbers in out_dir/logits_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    x = logits.detach().float().cpu().contiguous()
+    row_bytes = x[0].numel() * 4
+    if x.numel() * 4 > DUMP_CAP_BYTES:
+        keep = DUMP_CAP_BYTES // (row_bytes + 8)
+        rows = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        x = x[rows]
+        np.save(os.path.join(out_dir, 'logits_rows.npy'), rows.double().numpy())
+    np.save(os.path.join(out_dir, 'logits.npy'), x.numpy())
 
 
 def cpu_baseline(name, sd_cpu, refine_iters, seconds=12.0, batch=64, check_images=None, check_max_length=25):
@@ -422,11 +446,19 @@ def main():
     ap.add_argument('--no-latency', action='store_true', help='skip the batch-1 latency leg (the reference\'s published operating point: NAR + 3 refine iters) reported as "latency_b1_nar3"')
     ap.add_argument('--no-train', action='store_true', help='skip the short training-step leg (SURVEY.md section 8f row N3 / BASELINE.json configs[4]) reported as "train"')
     ap.add_argument('--force-dist', action='store_true', help='self-test: initialise the RCCL process group and run the collectives even with one rank')
-    ap.add_argument('--repeats', type=int, default=5, help='repetitions of the K-step timed region; the median is reported, min / max alongside')
+    ap.add_argument('--full', action='store_true', help='run every leg besides the headline (see the module docstring); a plain run times the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s logits to DIR/logits.npy (float32)')
+    ap.add_argument('--repeats', type=int, default=None, help='repetitions of the K-step timed region; the median is reported, min / max alongside '
+                    '(default: 1, or 5 with --full)')
     ap.add_argument('--streams', type=int, default=3, help='batches in flight for `value` (independent workspaces on separate HIP streams; three measured best on one MI355X: '
                     '57.0 k vs 54.7 k with two or four in the exact mode, 128.7 k vs 121 k in bf16 — profiles/r04_streams_sweep.md); '
-                    'the one-call-at-a-time figure is always measured too and reported as sequential_value')
+                    'with --full the one-call-at-a-time figure is measured too and reported as sequential_value')
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile = args.no_parity = args.no_natural_exit = args.no_throughput_mode = True
+        args.no_config3 = args.no_latency = args.no_train = True
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -538,7 +570,10 @@ def main():
                            'ms_per_step_max': round(1e3 * srt[-1] / steps, 4)}
 
     elapsed, out, spread = repeated(model, images, args.streams, args.steps, args.warmup, args.repeats)
-    seq_elapsed, _, seq_spread = repeated(model, images, 1, args.steps, args.warmup, args.repeats) if args.streams > 1 else (elapsed, None, spread)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if args.full:
+        seq_elapsed, _, seq_spread = repeated(model, images, 1, args.steps, args.warmup, args.repeats) if args.streams > 1 else (elapsed, None, spread)
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * B * args.steps / elapsed
 
@@ -557,8 +592,8 @@ def main():
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4),
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': args.precision, 'data': 'synthetic' if not STUB else 'stub (PARSEQ_BENCH_STUB=1: plumbing self-test on CPU, no recognition work, value is meaningless)',
-        'sequential_value': round(world * B * args.steps / seq_elapsed, 1), 'sequential_ms_per_step': round(1e3 * seq_elapsed / args.steps, 4),
-        'repeats': {'value': spread, 'sequential_value': seq_spread},
+        **({'sequential_value': round(world * B * args.steps / seq_elapsed, 1), 'sequential_ms_per_step': round(1e3 * seq_elapsed / args.steps, 4)} if args.full else {}),
+        'repeats': {'value': spread, **({'sequential_value': seq_spread} if args.full else {})},
         'config': {'workload': f'{args.model} {args.precision}, {ih}x{iw} crops, {B} crops per step per GPU, AR decode '
                                f'({"natural exit" if args.natural_exit else "26 steps forced"}) + {args.refine_iters} refine iter '
                                f'({named if named else "not a BASELINE.json configuration"}); random-init weights (reference init, seed 0); '
@@ -748,7 +783,7 @@ def main():
             tr = {'error': f'{type(e).__name__}: {e}'}
         if rank == 0:
             result['train'] = tr
-    if rank == 0:
+    if rank == 0 and args.full:
         # the headline, unambiguous: `value` is the timed dtype's throughput; whether that dtype meets the north star's 1e-3 / argmax bar
         # on the timed weights and inputs is stated next to it, with the throughput of the mode that does
         par = result.get('parity') or {}
@@ -788,6 +823,7 @@ def main():
             result['tolerance_met_decidable'] = bool(par.get('decidable_crops', 0) > 0 and par.get('max_abs_vs_fp32_decidable', 1.0) <= 1e-3 and
                                                      par.get('argmax_agree_decidable') == 1.0 and par.get('nar_max_abs_vs_fp32', 1.0) <= 1e-3)
             result['decidable_crops_of'] = [par.get('decidable_crops'), par.get('crops')]
+    if rank == 0:
         print(json.dumps(result))
     if dist is not None:
         dist.destroy_process_group()

@@ -289,7 +289,7 @@ def test_bench_py_two_ranks_print_one_line_for_the_whole_job():
     """bench.py's own multi-rank path on CPU (PARSEQ_BENCH_STUB=1: gloo, a shape-only stand-in for the model): `--gpus 2` from a plain
     shell re-executes under torch.distributed.run on 127.0.0.1, both ranks run the timed loop with the uniform all-gather inside it,
     and rank 0 alone prints ONE JSON line whose value / config describe the whole job (2 x 512 crops per step)."""
-    rc, lines, out, err = _bench_line(['--gpus', '2', '--steps', '3', '--warmup', '1', '--repeats', '2'], {'PARSEQ_BENCH_STUB': '1'}, 600)
+    rc, lines, out, err = _bench_line(['--gpus', '2', '--steps', '3', '--warmup', '1', '--repeats', '2', '--full'], {'PARSEQ_BENCH_STUB': '1'}, 600)
     assert rc == 0, err
     assert len(lines) == 1, out
     d = lines[0]
@@ -307,19 +307,40 @@ def test_bench_py_refuses_a_world_size_that_contradicts_gpus():
     assert rc != 0 and not lines
 
 
+def test_bench_py_plain_run_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full bench.py times exactly --steps steps once and runs no other leg; --dump-outputs writes the last timed step's
+    logits as float32, identical from run to run with the same arguments (CPU, PARSEQ_BENCH_STUB=1)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out_dir = tmp_path / f'run{i}'
+        rc, lines, out, err = _bench_line(['--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(out_dir)], {'PARSEQ_BENCH_STUB': '1'}, 300)
+        assert rc == 0, err
+        assert len(lines) == 1, out
+        d = lines[0]
+        assert d['steps'] == 3 and d['repeats']['value']['n'] == 1 and d['repeats']['value']['steps_each'] == 3
+        assert abs(d['value'] - 512 * 3 / (d['ms_per_step'] * 3e-3)) <= 1e-3 * d['value']
+        assert not set(d) & {'sequential_value', 'natural_exit_value', 'kernel_families', 'cpu_baseline', 'parity', 'throughput_mode', 'config3',
+                             'latency_b1_nar3', 'train'}, sorted(d)
+        a = np.load(out_dir / 'logits.npy')
+        assert a.dtype == np.float32 and list(a.shape) == d['config']['output_shape']
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 @pytest.mark.gpu
 def test_bench_py_force_dist_runs_the_rccl_path_on_one_gpu():
     """The distributed path of bench.py on the one GPU a test box has: RCCL process group of one rank, the real all_gather_into_tensor
     inside the timed step, two batches in flight on separate streams next to the communicator's streams (GPU_MAX_HW_QUEUES=8, DESIGN.md
     section 6).  Short: 5 steps, no profile / CPU baseline / parity legs."""
-    rc, lines, out, err = _bench_line(['--force-dist', '--steps', '5', '--warmup', '2', '--repeats', '2', '--no-profile', '--no-cpu-baseline', '--no-parity', '--no-train', '--no-natural-exit', '--no-throughput-mode'],
+    rc, lines, out, err = _bench_line(['--force-dist', '--full', '--steps', '5', '--warmup', '2', '--repeats', '2', '--no-profile', '--no-cpu-baseline', '--no-parity', '--no-train', '--no-natural-exit', '--no-throughput-mode'],
                                       {}, 900)
     assert rc == 0, err
     assert len(lines) == 1, out
     d = lines[0]
     assert d['n_gpus'] == 1 and d['config']['output_shape'] == [512, 26, 95] and d['value'] > 0 and d['sequential_value'] > 0
     # the same run without the process group: the collectives must not change a bit of the logits (two batches in flight in both)
-    rc2, lines2, out2, err2 = _bench_line(['--steps', '5', '--warmup', '2', '--repeats', '2', '--no-profile', '--no-cpu-baseline', '--no-parity', '--no-train',
+    rc2, lines2, out2, err2 = _bench_line(['--full', '--steps', '5', '--warmup', '2', '--repeats', '2', '--no-profile', '--no-cpu-baseline', '--no-parity', '--no-train',
                                            '--no-natural-exit', '--no-throughput-mode'], {}, 900)
     assert rc2 == 0 and len(lines2) == 1, err2
     assert d['config']['steps_in_flight'] == lines2[0]['config']['steps_in_flight'] >= 2

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One entry point for everything this repository runs on an MI355X through gpurun:  gpurun --timeout N -- 'bash tools/gpu_run.sh <task> [args]'
 # Results land in gpurun_out/ (scratch, merged back by gpurun); what is worth keeping is copied to profiles/ by hand.  R = round tag of the file names.
-#   suite            smoke() + the whole GPU test suite + the default bench line (the driver's round-end commands)
+#   suite            smoke() + the whole GPU test suite + the full bench line (bench.py --full: every leg, not only the headline)
 #   tests <k-expr>   pytest -m gpu -k <expr>
 #   bench [args]     bench.py with the given arguments, the JSON line to gpurun_out/bench_<R>.json, headline keys printed
 #   ab <name=ENV=V,ENV=V> ...   short exact-mode bench runs under each environment (switch A/Bs on one box)
@@ -17,7 +17,7 @@ mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 R=${ROUND:-r06}
 task=$1; shift
-QUICK="--steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-parity --no-profile --no-train --no-natural-exit --no-throughput-mode --no-config3 --no-latency"
+QUICK="--full --steps 30 --warmup 5 --repeats 3 --no-cpu-baseline --no-parity --no-profile --no-train --no-natural-exit --no-throughput-mode --no-config3 --no-latency"
 headline() { python - "$1" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
@@ -33,7 +33,7 @@ case $task in
 suite)
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
   timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > gpurun_out/gpu_tests.log 2>&1; echo "pytest exit $?"; grep -v "^  File" gpurun_out/gpu_tests.log | tail -15
-  timeout 900 python bench.py > gpurun_out/bench_$R.json 2> gpurun_out/bench_$R.err; tail -2 gpurun_out/bench_$R.err; headline gpurun_out/bench_$R.json ;;
+  bash tools/gpu_run.sh bench --full ;;
 tests)
   timeout 1500 python -m pytest tests -m gpu -q --timeout 900 -k "$1" > gpurun_out/gpu_tests_k.log 2>&1; echo "pytest exit $?"; grep -v "^  File" gpurun_out/gpu_tests_k.log | tail -25 ;;
 bench)
@@ -45,7 +45,7 @@ ab)
 import json,sys; d=json.loads(sys.stdin.read()); print('$name: value', d['value'], 'seq', d['sequential_value'])"
   done ;;
 profiles)
-  P="--steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-parity --no-profile --no-train --no-natural-exit --no-throughput-mode --no-config3 --no-latency"
+  P="--steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --no-parity --no-profile --no-train --no-natural-exit --no-throughput-mode --no-config3 --no-latency --full"
   for prec in bf16x3 bf16; do
     rm -rf gpurun_out/prof_$prec
     timeout 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$prec -o p -- python bench.py --precision $prec $P > gpurun_out/prof_$prec.log 2>&1
@@ -101,7 +101,7 @@ train)
     rm -rf gpurun_out/tp_*
   fi ;;
 configs)
-  run() { timeout 300 python bench.py --no-cpu-baseline --no-parity --no-profile --no-train --no-natural-exit --no-throughput-mode --no-config3 --no-latency --steps 40 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$*', '->', d['value'], d['sequential_value'])"; }
+  run() { timeout 300 python bench.py --full --no-cpu-baseline --no-parity --no-profile --no-train --no-natural-exit --no-throughput-mode --no-config3 --no-latency --steps 40 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$*', '->', d['value'], d['sequential_value'])"; }
   run --batch 1024 --refine-iters 2; run --natural-exit; run --precision bf16; run --precision bf16 --batch 1024 --refine-iters 2
   run --precision fp32 --batch 128; run --model parseq-tiny; run --model vitstr --precision bf16; run --model parseq-patch16-224 --batch 64 --precision bf16
   run --batch 256; run --batch 128; run --model vitstr; run --model parseq-patch16-224 --batch 64; run --model parseq-tiny --precision bf16 ;;

@@ -44,7 +44,7 @@ def main():
         env['PARSEQ_BENCH_STUB'] = '1'
     rows = []
     for n in gpus:
-        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n)] + extra, env=env, capture_output=True, text=True, cwd=ROOT)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--full'] + extra, env=env, capture_output=True, text=True, cwd=ROOT)
         line = None
         for ln in r.stdout.splitlines():
             ln = ln.strip()
