@@ -39,7 +39,10 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 8
+#define PARSEQ_ABI_VERSION 9
+
+/* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
+#define PARSEQ_DEC_DEPTH_MAX 4
 
 typedef struct parseq_model parseq_model;   /* weights of one PARSeq instance on one device */
 typedef struct parseq_plan parseq_plan;     /* workspace + derived tables for (model, max_batch, precision) */
@@ -51,7 +54,7 @@ typedef struct parseq_config {
     int32_t patch_h, patch_w;      /* 4, 8 */
     int32_t embed_dim;             /* 384 (PARSeq-S), 192 (PARSeq-Ti) */
     int32_t enc_depth, enc_heads, enc_mlp_ratio;   /* 12, 6 | 3, 4 */
-    int32_t dec_depth, dec_heads, dec_mlp_ratio;   /* 1 (only value supported), 12 | 6, 4 */
+    int32_t dec_depth, dec_heads, dec_mlp_ratio;   /* 1 (the reference default; 1 .. PARSEQ_DEC_DEPTH_MAX), 12 | 6, 4 */
     int32_t num_tokens;            /* len(tokenizer) = 97 for the 94-char set; the head predicts num_tokens - 2 classes */
     int32_t max_label_length;      /* 25 */
     int32_t bos_id, eos_id, pad_id;/* 95, 0, 96  (strhub/data/utils.py:107-111) */
@@ -101,7 +104,7 @@ const char* parseq_last_error(void);
 
 /* ---- model: replaces the nn.Module parameter storage of strhub/models/parseq/model.py:56-67 ---------------------- */
 
-/* Validates the configuration (dec_depth == 1, head dims 64 / 32, embed_dim in {192, 384, 768}, 128 tokens) and the
+/* Validates the configuration (1 <= dec_depth <= PARSEQ_DEC_DEPTH_MAX, head dims 64 / 32, embed_dim in {192, 384, 768}, 128 tokens) and the
  * device architecture.  Allocates device storage for the fp32 master weights. */
 int parseq_model_create(const parseq_config* cfg, parseq_model** out);
 void parseq_model_destroy(parseq_model* m);
@@ -186,9 +189,20 @@ int parseq_decode_query(parseq_plan* p, const int32_t* tokens, int batch, int ct
                         const uint8_t* query_mask, const uint8_t* key_padding_mask, float* hidden_out, float* logits_out,
                         void* stream);
 
+/* (ABI 9) model.PARSeq.decode with every argument of the reference (model.py:86-103), including the content mask `tgt_mask`, which
+ * only a decoder deeper than one layer reads (layers 0 .. dec_depth - 2 update the content stream under it, modules.py:116-124).
+ * query: device fp32 [batch, q_len, embed_dim] (caller-supplied tgt_query; q_start must be 0) or NULL (pos_queries[q_start :
+ * q_start + q_len]).  query_mask: device uint8 [q_len, ctx_len] or NULL; content_mask: device uint8 [ctx_len, ctx_len] or NULL;
+ * key_padding_mask: device uint8 [batch, ctx_len] or NULL (non-zero = masked).  hidden_out: fp32 [batch, q_len, embed_dim] or NULL;
+ * logits_out: fp32 [batch, q_len, num_tokens - 2].  The three entry points above are this one with content_mask == NULL, i.e. the
+ * reference with tgt_mask=None; at dec_depth == 1 the content mask is ignored, exactly as the reference ignores it. */
+int parseq_decode_ex(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len, const float* query,
+                     const uint8_t* query_mask, const uint8_t* content_mask, const uint8_t* key_padding_mask, float* hidden_out,
+                     float* logits_out, void* stream);
+
 /* model.PARSeq.decode's `memory` argument (model.py:89): projects a caller-supplied encoder output — device fp32
  * [batch, tokens, embed_dim], as parseq_encode returns it (after the encoder's final norm) — to the decoder's cross-attention
- * K / V, replacing the ones cached by the last parseq_encode / parseq_forward on this plan.  The decode entry points then
+ * K / V of every decoder layer, replacing the ones cached by the last parseq_encode / parseq_forward on this plan.  The decode entry points then
  * attend to THIS memory until the next encode / forward / set_memory. */
 int parseq_set_memory(parseq_plan* p, const float* memory, int batch, void* stream);
 

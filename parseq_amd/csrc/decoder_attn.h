@@ -975,5 +975,63 @@ void dec_cross_attn_mfma_n_kernel(const float* __restrict__ qc, const bf16_t* __
 }
 template <int NT16> constexpr size_t dec_cross_attn_mfma_n_lds() { return (size_t)2 * (((NT16 + 1) / 2) * 32) * (DEC_HD + 2) * sizeof(bf16_t); }
 
-}  // namespace pq
+// ---- decoders deeper than one layer (dec_depth > 1) -------------------------------------------------------------------
+// From layer 1 on, the keys of both streams are the UPDATED content (modules.py:119-124), no longer a function of (position,
+// token id): nothing can be tabulated.  The K | V rows are projected at run time into kv[b][j][2E] (j < ld rows per image) and
+// this kernel scores explicit queries against them.  One workgroup of E threads per query row w = b * Lq + qi at absolute
+// position pos = i0 + qi; q[w][E] is the q-projection with bias and 1/sqrt(hd) applied (fp32).  Masks follow torch:
+// amask[pos * lda + j] != 0 or kpm[b * ldk + j] != 0  =>  key j gets -inf (a row with every key masked gives NaN, as in torch).
+// Scores, soft-max and the value mix are fp32 in every precision (<= 32 keys of 32 values per head).
+template <typename T, int E>
+__global__ __launch_bounds__(E)
+void dec_self_attn_kv_kernel(const float* __restrict__ q, const T* __restrict__ kv, int ld, const unsigned char* __restrict__ amask, int lda,
+                             const unsigned char* __restrict__ kpm, int ldk, int Lk, int i0, int Lq, T* __restrict__ out) {
+    constexpr int H = E / DEC_HD;
+    static_assert(DEC_MAXL == DEC_HD, "one (key, head) score per thread: H * DEC_MAXL == E");
+    __shared__ float sp[H][DEC_MAXL];
+    const int t = threadIdx.x;
+    const int w = blockIdx.x;
+    const int b = w / Lq, qi = w - b * Lq, pos = i0 + qi;
+    const T* kb = kv + (size_t)b * ld * (2 * E);
+    if (t < H * Lk) {                          // H * Lk <= H * 32 = E
+        const int j = t / H, h = t - j * H;
+        const bool masked = (amask && amask[(size_t)pos * lda + j]) || (kpm && kpm[(size_t)b * ldk + j]);
+        const float* qv = q + (size_t)w * E + h * DEC_HD;
+        const T* kr = kb + (size_t)j * (2 * E) + h * DEC_HD;
+        float sc = 0.f;
+#pragma unroll
+        for (int d = 0; d < DEC_HD; ++d) sc = fmaf(qv[d], to_f32(kr[d]), sc);
+        sp[h][j] = masked ? -INFINITY : sc;
+    }
+    __syncthreads();
+    if (t < H) {
+        float mx = -INFINITY;
+        for (int j = 0; j < Lk; ++j) mx = fmaxf(mx, sp[t][j]);
+        float sum = 0.f;
+        for (int j = 0; j < Lk; ++j) { const float p = expf(sp[t][j] - mx); sp[t][j] = p; sum += p; }
+        const float inv = 1.0f / sum;
+        for (int j = 0; j < Lk; ++j) sp[t][j] *= inv;
+    }
+    __syncthreads();
+    const int h = t / DEC_HD;
+    float acc = 0.f;
+    for (int j = 0; j < Lk; ++j) acc = fmaf(sp[h][j], to_f32(kb[(size_t)j * (2 * E) + E + t]), acc);
+    out[(size_t)w * E + t] = from_f32<T>(acc);
+}
 
+// Content-stream input of model.decode (model.py:95-97) for rows r = b * Lc + k, k < Lc, at absolute positions pos = i0 + k:
+// x[r] = sqrt(E) * emb[tok[b][pos]] (+ pos_queries[pos - 1] for pos > 0) — the same expression content_ln_kernel normalises.
+template <int E>
+__global__ __launch_bounds__(256)
+void content_embed_kernel(const float* __restrict__ emb, const float* __restrict__ posq, const int* __restrict__ tok, int ldt,
+                          int B, int Lc, int i0, float* __restrict__ x) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * Lc * E) return;
+    const int r = (int)(i / E), e = (int)(i - (size_t)r * E);
+    const int b = r / Lc, pos = i0 + (r - b * Lc);
+    float c = sqrtf((float)E) * emb[(size_t)tok[(size_t)b * ldt + pos] * E + e];
+    if (pos > 0) c = posq[(size_t)(pos - 1) * E + e] + c;
+    x[i] = c;
+}
+
+}  // namespace pq

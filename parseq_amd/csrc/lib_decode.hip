@@ -7,9 +7,11 @@
 // Cross-attention of Lq queries per image against the plan's cached memory K / V: tuned kernels for 128 memory tokens
 // (streaming AR kernel, MFMA multi-query kernel), the key-count-generic kernel otherwise.
 template <typename T, int E>
-static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, float scale, T* ca, const QAsm qa = QAsm{}) {
+static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, float scale, T* ca, const QAsm qa = QAsm{}, int layer = 0) {
     const int H = p->m->cfg.dec_heads, NK = p->m->tokens;
-    const T* kmem = reinterpret_cast<const T*>(p->kmem); const T* vmem = reinterpret_cast<const T*>(p->vmem);
+    // decoder layer `layer`'s K / V of memory (layers >= 1: dec_depth > 1, f32 / bf16 rows of the generic GEMM, never 24-bit)
+    const T* kmem = reinterpret_cast<const T*>(layer ? p->kmem_l[layer] : p->kmem); const T* vmem = reinterpret_cast<const T*>(layer ? p->vmem_l[layer] : p->vmem);
+    const bool kv24 = layer ? false : p->kv24;
     const float* qc_ = p->qc;
     if (qa.nsplit && (qa.nsplit != DS_QS || NK != 128 || Lq != 1)) return fail(PARSEQ_E_STATE, "cross-attention: split q-projection outside the AR step kernels");
     if (NK != 128) {
@@ -32,7 +34,7 @@ static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, flo
         hipLaunchKernelGGL((dec_cross_attn_generic_kernel<T>), dim3(B * H), dim3(128), lds, s, qc_, kmem, vmem, H, Lq, NK, scale, ca);
     } else if (Lq == 1) {
         if constexpr (sizeof(T) == 4 && E == 384) {
-            if (p->kv24) {
+            if (kv24) {
                 const auto kern = qa.nsplit ? dec_cross_attn_ar24_kernel<E, true> : dec_cross_attn_ar24_kernel<E, false>;
                 hipLaunchKernelGGL(kern, dim3(B), dim3(E), 0, s, qc_, qa, reinterpret_cast<const unsigned char*>(p->kmem),
                                    reinterpret_cast<const unsigned char*>(p->vmem), p->kv_plane_elems, scale, ca);
@@ -40,7 +42,7 @@ static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, flo
                 return 0;
             }
         }
-        if (p->kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows but no kernel for this geometry");
+        if (kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows but no kernel for this geometry");
         auto kern = dec_cross_attn_ar_kernel<T, E, false>;
         if constexpr (E <= 384) { if (qa.nsplit) kern = dec_cross_attn_ar_kernel<T, E, true>; }      // the split step exists for the fused AR loop's widths only
         else if (qa.nsplit) return fail(PARSEQ_E_STATE, "cross-attention: split q-projection at embed_dim %d", E);
@@ -48,11 +50,11 @@ static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, flo
     } else if constexpr (sizeof(T) == 2) {
         hipLaunchKernelGGL(dec_cross_attn_multi_mfma_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H);
     } else {
-        if (g_split && p->kv24)      // bf16x3: the matrix-core kernel on bf16 pairs, K / V from the 24-bit rows of the one-launch encoder's tail
+        if (g_split && kv24)      // bf16x3: the matrix-core kernel on bf16 pairs, K / V from the 24-bit rows of the one-launch encoder's tail
             hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<true>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, p->kv_plane_elems);
         else if (g_split)
             hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, (size_t)0);
-        else if (p->kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows outside the bf16x3 mode");
+        else if (kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows outside the bf16x3 mode");
         else
             hipLaunchKernelGGL((dec_cross_attn_multi_kernel<T>), dim3(B * H), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca);
     }
@@ -60,9 +62,30 @@ static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, flo
     return 0;
 }
 
+// decoder.norm + head of the query stream in p->t (rows b * Lq + qi -> logits[b][i0 + qi] of a [B][Ltot][C] tensor), and for an AR
+// step (argmax_mode != 0, Lq == 1) the greedy pick of position i0 into tok[:, i0 + 1] with the EOS bookkeeping
+template <typename T, int E>
+static int head_pass(parseq_plan* p, hipStream_t s, int B, int i0, int Lq, float* logits, int Ltot, int argmax_mode) {
+    const parseq_model* m = p->m;
+    const parseq_config& c = m->cfg;
+    const int M = B * Lq, C = m->classes;
+    const Weights<T> W = weights_of<T>(p);
+    int* eos_rows = p->counters; int* ar_len = p->counters + 1;
+    // decoder.norm fused into the head's A operand
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, m->p("decoder.norm.weight"), m->p("decoder.norm.bias"), c.dec_ln_eps,
+                     W.w("head.weight"), M, C, epi_store<float>(M, C, m->p("head.bias"), logits, C, 1.f, Lq, Ltot, i0), p->tn))); }
+    if (argmax_mode) {       // only meaningful for Lq == 1: greedy pick of position i0 into tok[:, i0 + 1]
+        hipLaunchKernelGGL(ar_argmax_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, Ltot, C, p->tok, LDT, i0, B, c.eos_id,
+                           p->eos_seen, eos_rows, ar_len, argmax_mode == 2 ? 1 : 0);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
 template <typename T, int E>
 static int decode_pass_e(parseq_plan* p, hipStream_t s, int B, int Lk, int i0, int Lq, const unsigned char* qmask, const unsigned char* kpm,
-                         float* logits, int Ltot, int argmax_mode, bool keep_t = false, const float* user_query = nullptr) {
+                         float* logits, int Ltot, int argmax_mode, bool keep_t = false, const float* user_query = nullptr, bool stream_only = false) {
+    // stream_only (dec_depth > 1): layer 0's query stream alone, left in p->t — the layer loop (deep_*) runs the deeper layers and the head
     const parseq_model* m = p->m;
     const parseq_config& c = m->cfg;
     const int M = B * Lq, Fd = E * c.dec_mlp_ratio, C = m->classes, npos = c.max_label_length + 1, H = c.dec_heads;
@@ -74,7 +97,7 @@ static int decode_pass_e(parseq_plan* p, hipStream_t s, int B, int Lk, int i0, i
     int* eos_rows = p->counters; int* ar_len = p->counters + 1;
     if constexpr (sizeof(T) == 2 && E <= 384) {
         // AR step (one unmasked query per image): two fused row-block kernels around the cross-attention (decoder_step.h)
-        if (Lq == 1 && !qmask && !kpm && C <= 128 && p->fused_step && p->wstep[0] && !keep_t && !user_query) {
+        if (Lq == 1 && !qmask && !kpm && C <= 128 && p->fused_step && p->wstep[0] && !keep_t && !user_query && !stream_only) {
             const dim3 grid((M + DS_ROWS - 1) / DS_ROWS), block(64 * DS_NW);
             static LdsAttr attr_pre, attr_post;
             HIPCHK(attr_pre.ensure(reinterpret_cast<const void*>(dec_step_pre_kernel<E>), dec_step_pre_lds<E>()));
@@ -155,15 +178,8 @@ static int decode_pass_e(parseq_plan* p, hipStream_t s, int B, int Lk, int i0, i
     { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, m->p(d + "norm2.weight"), m->p(d + "norm2.bias"), c.dec_ln_eps,
                      W.w(d + "linear1.weight"), M, Fd, epi_gelu<T>(M, Fd, m->p(d + "linear1.bias"), hdn, Fd), p->tn))); }
     { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{hdn, Fd}, W.w(d + "linear2.weight"), Fd, M, E, Fd, epi_resid(M, E, m->p(d + "linear2.bias"), p->t, E)))); }
-    // decoder.norm fused into the head's A operand
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, m->p("decoder.norm.weight"), m->p("decoder.norm.bias"), c.dec_ln_eps,
-                     W.w("head.weight"), M, C, epi_store<float>(M, C, m->p("head.bias"), logits, C, 1.f, Lq, Ltot, i0), p->tn))); }
-    if (argmax_mode) {       // only meaningful for Lq == 1: greedy pick of position i0 into tok[:, i0 + 1]
-        hipLaunchKernelGGL(ar_argmax_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, Ltot, C, p->tok, LDT, i0, B, c.eos_id,
-                           p->eos_seen, eos_rows, ar_len, argmax_mode == 2 ? 1 : 0);
-        HIPCHK(hipGetLastError());
-    }
-    return 0;
+    if (stream_only) return 0;
+    return head_pass<T, E>(p, s, B, i0, Lq, logits, Ltot, argmax_mode);
 }
 
 // One pass of the query stream (modules.py:55-98 with update_content=False, then decoder.norm and head) for queries
@@ -176,6 +192,130 @@ static int decode_pass(parseq_plan* p, hipStream_t s, int B, int Lk, int i0, int
         case 192: return decode_pass_e<T, 192>(p, s, B, Lk, i0, Lq, qmask, kpm, logits, Ltot, argmax_mode, keep_t, user_query);
         case 384: return decode_pass_e<T, 384>(p, s, B, Lk, i0, Lq, qmask, kpm, logits, Ltot, argmax_mode, keep_t, user_query);
         default:  return decode_pass_e<T, 768>(p, s, B, Lk, i0, Lq, qmask, kpm, logits, Ltot, argmax_mode, keep_t, user_query);
+    }
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// decoders deeper than one layer (dec_depth > 1): the reference's layer loop (modules.py:116-124)
+// -------------------------------------------------------------------------------------------------------------------
+// Layers 0 .. D-2 update the content stream (under the content mask), and layers 1 .. D-1 attend to that updated content, so from
+// layer 1 on nothing is a function of (position, token id) and the tables of the depth-1 path do not apply.  The plan holds the
+// content stream p->xc (f32, updated in place layer by layer) and, per layer l, the self-attention K | V rows of layer l's content
+// input, p->kvself[l][b][pos][2E] (T).  Layer 0's query stream keeps the depth-1 kernels (decode_pass_e, stream_only).
+
+// The content input of model.decode (model.py:95-97) for positions i0 .. i0 + Lc - 1 of every image into p->xc [B * Lc][E].
+template <int E>
+static int content_rows(parseq_plan* p, hipStream_t s, int B, int Lc, int i0) {
+    const parseq_model* m = p->m;
+    const size_t n = (size_t)B * Lc * E;
+    hipLaunchKernelGGL((content_embed_kernel<E>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->p("text_embed.embedding.weight"),
+                       m->p("pos_queries"), p->tok, LDT, B, Lc, i0, p->xc);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// K | V of norm_c(x) for layer l's self-attention (modules.py:115, 64): row r of x [M][E] is image r / period at position
+// offset + r % period, written to p->kvself[l][image][position][2E].
+template <typename T, int E>
+static int kv_rows(parseq_plan* p, hipStream_t s, int l, int M, const float* x, int period, int offset) {
+    const parseq_model* m = p->m;
+    const parseq_config& c = m->cfg;
+    const Weights<T> W = weights_of<T>(p);
+    const std::string d = "decoder.layers." + std::to_string(l) + ".";
+    ProfScope ps_(&p->prof, T_DEC_GEMM, s);
+    return run_ln_gemm<T, E>(s, x, m->p(d + "norm_c.weight"), m->p(d + "norm_c.bias"), c.dec_ln_eps, W.w(d + "self_attn.in_proj_weight") + (size_t)E * E,
+                             M, 2 * E, epi_store<T>(M, 2 * E, m->p(d + "self_attn.in_proj_bias") + E, reinterpret_cast<T*>(p->kvself[l]), 2 * E, 1.f,
+                                                    period, c.max_label_length + 1, offset), p->tn);
+}
+
+// One stream of layer l (DecoderLayer.forward_stream, modules.py:55-76) over the M = B * Lq rows of x [M][E] f32, updated in place:
+// self-attention of norm(x) — norm_c for the content stream, norm_q for the query stream — against the K | V rows of layer l's content
+// (keys j < Lk), cross-attention against layer l's memory K / V, MLP.  Row b * Lq + qi is absolute position i0 + qi (mask rows).
+template <typename T, int E>
+static int stream_layer(parseq_plan* p, hipStream_t s, int l, bool content, int B, int Lq, int i0, float* x, int Lk,
+                        const unsigned char* amask, const unsigned char* kpm) {
+    const parseq_model* m = p->m;
+    const parseq_config& c = m->cfg;
+    const int M = B * Lq, Fd = E * c.dec_mlp_ratio, npos = c.max_label_length + 1;
+    const Weights<T> W = weights_of<T>(p);
+    const std::string d = "decoder.layers." + std::to_string(l) + ".", nrm = d + (content ? "norm_c." : "norm_q.");
+    T* sa = reinterpret_cast<T*>(p->sa); T* ca = reinterpret_cast<T*>(p->ca); T* hdn = reinterpret_cast<T*>(p->hdn);
+    const float scale = sqrtf(1.0f / (float)DEC_HD);
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, m->p(nrm + "weight"), m->p(nrm + "bias"), c.dec_ln_eps,
+                     W.w(d + "self_attn.in_proj_weight"), M, E, epi_store<float>(M, E, m->p(d + "self_attn.in_proj_bias"), p->qc, E, scale), p->tn))); }
+    {
+        ProfScope ps_(&p->prof, T_DEC_SA, s);
+        hipLaunchKernelGGL((dec_self_attn_kv_kernel<T, E>), dim3(M), dim3(E), 0, s, p->qc, reinterpret_cast<const T*>(p->kvself[l]), npos,
+                           amask, LDT, kpm, LDT, Lk, i0, Lq, sa);
+        HIPCHK(hipGetLastError());
+    }
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{sa, E}, W.w(d + "self_attn.out_proj.weight"), E, M, E, E,
+                     epi_resid(M, E, m->p(d + "self_attn.out_proj.bias"), x, E)))); }
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, m->p(d + "norm1.weight"), m->p(d + "norm1.bias"), c.dec_ln_eps,
+                     W.w(d + "cross_attn.in_proj_weight"), M, E, epi_store<float>(M, E, m->p(d + "cross_attn.in_proj_bias"), p->qc, E), p->tn))); }
+    {
+        ProfScope ps_(&p->prof, T_DEC_CA, s);
+        CHK((run_cross_attention<T, E>(p, s, B, Lq, scale, ca, QAsm{}, l)));
+    }
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{ca, E}, W.w(d + "cross_attn.out_proj.weight"), E, M, E, E,
+                     epi_resid(M, E, m->p(d + "cross_attn.out_proj.bias"), x, E)))); }
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, m->p(d + "norm2.weight"), m->p(d + "norm2.bias"), c.dec_ln_eps,
+                     W.w(d + "linear1.weight"), M, Fd, epi_gelu<T>(M, Fd, m->p(d + "linear1.bias"), hdn, Fd), p->tn))); }
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{hdn, Fd}, W.w(d + "linear2.weight"), Fd, M, E, Fd,
+                     epi_resid(M, E, m->p(d + "linear2.bias"), x, E)))); }
+    return 0;
+}
+
+// model.decode + head over a whole context: content tokens p->tok[:, :Lc] under the content mask `cmask` ([npos][LDT], rows = content
+// positions), queries pos_queries[i0 : i0 + Lq] (or the caller's `user_query`) under `qmask`, key padding `kpm` for both streams.
+// NAR (Lc = 1, no masks), refinement (Lc = num_steps, cloze mask for both streams) and the decode entry points.
+template <typename T, int E>
+static int deep_pass_e(parseq_plan* p, hipStream_t s, int B, int Lc, int i0, int Lq, const unsigned char* qmask, const unsigned char* cmask,
+                       const unsigned char* kpm, float* logits, int Ltot, const float* user_query) {
+    const int D = p->m->cfg.dec_depth;
+    CHK(content_rows<E>(p, s, B, Lc, 0));
+    for (int l = 0; l < D; ++l) {
+        CHK((kv_rows<T, E>(p, s, l, B * Lc, p->xc, Lc, 0)));      // before the content update below reads and overwrites xc
+        if (l < D - 1) CHK((stream_layer<T, E>(p, s, l, true, B, Lc, 0, p->xc, Lc, cmask, kpm)));
+        if (l == 0) CHK((decode_pass_e<T, E>(p, s, B, Lc, i0, Lq, qmask, kpm, logits, Ltot, 0, false, user_query, true)));
+        else CHK((stream_layer<T, E>(p, s, l, false, B, Lq, i0, p->t, Lc, qmask, kpm)));
+    }
+    return head_pass<T, E>(p, s, B, i0, Lq, logits, Ltot, 0);
+}
+
+// AR step i (model.py:123-141) with the per-layer content cache: the content mask of the AR loop is causal (tgt_mask[:j, :j]), so the
+// content rows of positions < i are those of the previous steps.  Only row i is computed per layer — its K | V appended to
+// kvself[l][:, i], its update carried to the next layer in xc [B][E] — and the query of position i runs through every layer.
+// 3 D + 1 row-block passes per step (content row of layers 0 .. D-2, query of layers 0 .. D-1, K | V rows of every layer), no host sync.
+template <typename T, int E>
+static int deep_ar_step_e(parseq_plan* p, hipStream_t s, int B, int i, float* logits, int Ltot, int argmax_mode) {
+    const int D = p->m->cfg.dec_depth;
+    CHK(content_rows<E>(p, s, B, 1, i));
+    for (int l = 0; l < D; ++l) {
+        CHK((kv_rows<T, E>(p, s, l, B, p->xc, 1, i)));
+        if (l < D - 1) CHK((stream_layer<T, E>(p, s, l, true, B, 1, i, p->xc, i + 1, nullptr, nullptr)));
+        if (l == 0) CHK((decode_pass_e<T, E>(p, s, B, i + 1, i, 1, nullptr, nullptr, logits, Ltot, 0, false, nullptr, true)));
+        else CHK((stream_layer<T, E>(p, s, l, false, B, 1, i, p->t, i + 1, nullptr, nullptr)));
+    }
+    return head_pass<T, E>(p, s, B, i, 1, logits, Ltot, argmax_mode);
+}
+
+template <typename T>
+static int deep_pass(parseq_plan* p, hipStream_t s, int B, int Lc, int i0, int Lq, const unsigned char* qmask, const unsigned char* cmask,
+                     const unsigned char* kpm, float* logits, int Ltot, const float* user_query = nullptr) {
+    switch (p->m->cfg.embed_dim) {
+        case 192: return deep_pass_e<T, 192>(p, s, B, Lc, i0, Lq, qmask, cmask, kpm, logits, Ltot, user_query);
+        case 384: return deep_pass_e<T, 384>(p, s, B, Lc, i0, Lq, qmask, cmask, kpm, logits, Ltot, user_query);
+        default:  return deep_pass_e<T, 768>(p, s, B, Lc, i0, Lq, qmask, cmask, kpm, logits, Ltot, user_query);
+    }
+}
+
+template <typename T>
+static int deep_ar_step(parseq_plan* p, hipStream_t s, int B, int i, float* logits, int Ltot, int argmax_mode) {
+    switch (p->m->cfg.embed_dim) {
+        case 192: return deep_ar_step_e<T, 192>(p, s, B, i, logits, Ltot, argmax_mode);
+        case 384: return deep_ar_step_e<T, 384>(p, s, B, i, logits, Ltot, argmax_mode);
+        default:  return deep_ar_step_e<T, 768>(p, s, B, i, logits, Ltot, argmax_mode);
     }
 }
 
@@ -255,23 +395,28 @@ static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int 
     if (ar) {
         // model.py:119-147.  All num_steps steps are always run (no per-step host sync); the step at which the reference
         // would have stopped is recorded on the device and only truncates the returned view.
+        const bool deep = c.dec_depth > 1;      // the fused step is a depth-1 kernel; deeper decoders run deep_ar_step
         bool done = false;
         if constexpr (sizeof(T) == 2) {
-            if (p->wstep[0] && p->fused_step && C <= 128 && c.dec_mlp_ratio == 4) {
+            if (!deep && p->wstep[0] && p->fused_step && C <= 128 && c.dec_mlp_ratio == 4) {
                 if (c.embed_dim == 384) { CHK((ar_loop_fused<384>(p, s, B, num_steps, logits, testing, latency))); done = true; }
                 else if (c.embed_dim == 192) { CHK((ar_loop_fused<192>(p, s, B, num_steps, logits, testing, latency))); done = true; }
             }
         } else {
             // bf16x3: the same fused step on bf16 pairs (f32 tables, f32 memory K / V); the fp32 mode keeps the per-op kernels
-            if (p->precision == PARSEQ_BF16X3 && p->wstep[0] && p->fused_step && C <= 128 && c.dec_mlp_ratio == 4) {
+            if (!deep && p->precision == PARSEQ_BF16X3 && p->wstep[0] && p->fused_step && C <= 128 && c.dec_mlp_ratio == 4) {
                 if (c.embed_dim == 384) { CHK((ar_loop_fused<384, true>(p, s, B, num_steps, logits, testing, latency))); done = true; }
                 else if (c.embed_dim == 192) { CHK((ar_loop_fused<192, true>(p, s, B, num_steps, logits, testing, latency))); done = true; }
             }
         }
         for (int i = 0; !done && i < num_steps; ++i) {
             // greedy pick of position i into tok[:, i + 1] (+ EOS bookkeeping) rides on the step; the last step needs none
-            CHK((decode_pass<T>(p, s, B, i + 1, i, 1, nullptr, nullptr, logits, num_steps, i + 1 < num_steps ? (testing ? 2 : 1) : 0)));
+            const int argmax_mode = i + 1 < num_steps ? (testing ? 2 : 1) : 0;
+            if (deep) CHK((deep_ar_step<T>(p, s, B, i, logits, num_steps, argmax_mode)));
+            else CHK((decode_pass<T>(p, s, B, i + 1, i, 1, nullptr, nullptr, logits, num_steps, argmax_mode)));
         }
+    } else if (c.dec_depth > 1) {
+        CHK((deep_pass<T>(p, s, B, 1, 0, num_steps, nullptr, nullptr, nullptr, logits, num_steps)));
     } else {
         // model.py:148-152: context is <bos> only, all positions queried at once
         CHK((decode_pass<T>(p, s, B, 1, 0, num_steps, nullptr, nullptr, logits, num_steps)));
@@ -283,7 +428,11 @@ static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int 
         const int from_logits = (ar && it == 0) ? 0 : 1;
         hipLaunchKernelGGL(refine_prep_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, num_steps, C, p->tok, LDT, p->kpm, LDT, B, c.bos_id, c.eos_id, from_logits);
         HIPCHK(hipGetLastError());
-        CHK((decode_pass<T>(p, s, B, num_steps, 0, num_steps, p->cloze, p->kpm, logits, num_steps)));
+        // dec_depth > 1: the content stream under the same cloze-edited mask (model.py:117, 157: tgt_mask and query_mask are one tensor) over
+        // all num_steps positions, those past a row's first EOS key-padded.  After an AR early exit at L < num_steps that is the reference
+        // with tgt_mask[:L, :L] (it raises there: a [num_steps, num_steps] mask against L content tokens)
+        if (c.dec_depth > 1) CHK((deep_pass<T>(p, s, B, num_steps, 0, num_steps, p->cloze, p->cloze, p->kpm, logits, num_steps)));
+        else CHK((decode_pass<T>(p, s, B, num_steps, 0, num_steps, p->cloze, p->kpm, logits, num_steps)));
     }
     int L = num_steps;
     if (ar && testing && refine_iters == 0) {
@@ -346,7 +495,8 @@ extern "C" int parseq_forward(parseq_plan* p, const void* images, int images_dty
 }
 
 static int decode_entry(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len, const uint8_t* query_mask,
-                        const uint8_t* key_padding_mask, float* logits_out, float* hidden_out, void* stream, const float* user_query = nullptr) {
+                        const uint8_t* key_padding_mask, float* logits_out, float* hidden_out, void* stream, const float* user_query = nullptr,
+                        const uint8_t* content_mask = nullptr) {
     if (!p || !tokens || !logits_out) return fail(PARSEQ_E_INVALID, "null argument");
     if (p->m->vitstr) return fail(PARSEQ_E_INVALID, "ViTSTR has no decoder");
     DevGuard dg(p->m->device);
@@ -368,12 +518,21 @@ static int decode_entry(parseq_plan* p, const int32_t* tokens, int batch, int ct
         HIPCHK(hipMemcpy2DAsync(p->qmask_user + (size_t)q_start * LDT, LDT, query_mask, ctx_len, ctx_len, q_len, hipMemcpyDeviceToDevice, s));
         qm = p->qmask_user;
     }
+    const bool deep = p->m->cfg.dec_depth > 1;
+    const unsigned char* cm = nullptr;
+    if (content_mask && deep) {      // depth 1 never updates the content stream, so the reference never reads its mask (modules.py:119-124)
+        HIPCHK(hipMemcpy2DAsync(p->cmask_user, LDT, content_mask, ctx_len, ctx_len, ctx_len, hipMemcpyDeviceToDevice, s));
+        cm = p->cmask_user;
+    }
     const bool keep_t = hidden_out != nullptr;
     // decode_pass writes logits[b][q_start + qi] of a [B][Ltot][C] tensor (the forward's layout).  Here the caller's tensor is
     // [batch][q_len][C] with row qi: hand over the base shifted back by q_start rows, so that the rows written are exactly
     // [b * q_len + qi] (writing at b * q_len + q_start + qi ran q_start rows past the end of the buffer for q_start > 0).
     float* lbase = logits_out - (size_t)q_start * p->m->classes;
-    if (p->precision == PARSEQ_BF16) CHK((decode_pass<bf16_t>(p, s, batch, ctx_len, q_start, q_len, qm, kpm, lbase, q_len, 0, keep_t, user_query)));
+    if (deep) {
+        if (p->precision == PARSEQ_BF16) CHK((deep_pass<bf16_t>(p, s, batch, ctx_len, q_start, q_len, qm, cm, kpm, lbase, q_len, user_query)));
+        else CHK((deep_pass<float>(p, s, batch, ctx_len, q_start, q_len, qm, cm, kpm, lbase, q_len, user_query)));
+    } else if (p->precision == PARSEQ_BF16) CHK((decode_pass<bf16_t>(p, s, batch, ctx_len, q_start, q_len, qm, kpm, lbase, q_len, 0, keep_t, user_query)));
     else CHK((decode_pass<float>(p, s, batch, ctx_len, q_start, q_len, qm, kpm, lbase, q_len, 0, keep_t, user_query)));
     if (hidden_out) {      // model.decode's return value: decoder.norm of the query stream (modules.py:124), fp32
         const parseq_model* m = p->m;
@@ -404,6 +563,14 @@ extern "C" int parseq_decode_query(parseq_plan* p, const int32_t* tokens, int ba
     return decode_entry(p, tokens, batch, ctx_len, 0, q_len, query_mask, key_padding_mask, logits_out, hidden_out, stream, query);
 }
 
+extern "C" int parseq_decode_ex(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len, const float* query,
+                                const uint8_t* query_mask, const uint8_t* content_mask, const uint8_t* key_padding_mask, float* hidden_out,
+                                float* logits_out, void* stream) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    if (query && q_start != 0) return fail(PARSEQ_E_INVALID, "q_start %d with a caller-supplied query (must be 0)", q_start);
+    return decode_entry(p, tokens, batch, ctx_len, q_start, q_len, query_mask, key_padding_mask, logits_out, hidden_out, stream, query, content_mask);
+}
+
 // The cross-attention K / V of a caller-supplied encoder output (model.decode's `memory` argument, model.py:89): replaces the
 // K / V cached by the last parseq_encode on this plan.
 template <typename T>
@@ -421,13 +588,15 @@ static int set_memory_impl(parseq_plan* p, const float* memory, int B, hipStream
     } else {
         a = memory;
     }
-    const std::string d = "decoder.layers.0.cross_attn.";
-    EpiHeads<T> ek; static_cast<EpiBase&>(ek) = epi_base(M, 2 * E, m->p(d + "in_proj_bias") + E);
-    ek.seg[0] = reinterpret_cast<T*>(p->kmem); ek.seg[1] = reinterpret_cast<T*>(p->vmem); ek.seg[2] = nullptr;
-    ek.E = E; ek.heads = c.dec_heads; ek.hd = DEC_HD; ek.tokens = N; ek.tr_from = 2;
     p->kv24 = false;      // rows in the storage type from the generic GEMM
-    ProfScope ps_(&p->prof, T_KVMEM, s);
-    CHK((run_gemm<T>(s, ARowMajor<T>{a, E}, W.w(d + "in_proj_weight") + (size_t)E * E, E, M, 2 * E, E, ek, E % 128 != 0)));
+    for (int l = 0; l < c.dec_depth; ++l) {      // every decoder layer's K / V
+        const std::string d = "decoder.layers." + std::to_string(l) + ".cross_attn.";
+        EpiHeads<T> ek; static_cast<EpiBase&>(ek) = epi_base(M, 2 * E, m->p(d + "in_proj_bias") + E);
+        ek.seg[0] = reinterpret_cast<T*>(l ? p->kmem_l[l] : p->kmem); ek.seg[1] = reinterpret_cast<T*>(l ? p->vmem_l[l] : p->vmem); ek.seg[2] = nullptr;
+        ek.E = E; ek.heads = c.dec_heads; ek.hd = DEC_HD; ek.tokens = N; ek.tr_from = 2;
+        ProfScope ps_(&p->prof, T_KVMEM, s);
+        CHK((run_gemm<T>(s, ARowMajor<T>{a, E}, W.w(d + "in_proj_weight") + (size_t)E * E, E, M, 2 * E, E, ek, E % 128 != 0)));
+    }
     p->last_batch = B;
     return 0;
 }

@@ -81,7 +81,8 @@ static int encode_impl(parseq_plan* p, const TI* images, int B, float* memory_ou
         if constexpr (kBf16) {
             // parseq_forward (nobody asked for `memory` itself): the final LayerNorm and the decoder's K / V projection of memory ride
             // in the same launch (encoder_blocks.h kv_phase) and the encoder is done
-            const bool tail = p->fused_tail && memory_out == nullptr && !m->vitstr && c.dec_heads * DEC_HD == E;
+            // (a deeper decoder needs `memory` itself, for the K / V of every layer: no tail)
+            const bool tail = p->fused_tail && memory_out == nullptr && !m->vitstr && c.dec_heads * DEC_HD == E && c.dec_depth == 1;
             EncTailParams et = p->enc_tail;
             if (tail) { et.kmem = reinterpret_cast<bf16_t*>(p->kmem); et.vmem = reinterpret_cast<bf16_t*>(p->vmem); }
             EncHeadParams eh{nullptr, 0, 0, nullptr};
@@ -103,7 +104,7 @@ static int encode_impl(parseq_plan* p, const TI* images, int B, float* memory_ou
         // K / V projection of it — in one launch with x resident in registers (encoder_blocks_x3w.h: eight waves of 16 rows; encoder_blocks_x3.h: four of 32); the MLP hidden buffer (idle on this
         // path) is the launch's per-image scratch (the parked residual stream and the attention output, 384 KiB per image)
         if (g_split && one_launch_x3 && p->fused_blocks && !m->vitstr && E == 384 && c.enc_mlp_ratio == 4 && N == ATT_N && M % 128 == 0) {
-            const bool tail = p->fused_tail && memory_out == nullptr && c.dec_heads * DEC_HD == E;
+            const bool tail = p->fused_tail && memory_out == nullptr && c.dec_heads * DEC_HD == E && c.dec_depth == 1;
             x3::EncTailX3 et{p->enc_tail.norm_w, p->enc_tail.norm_b, p->enc_tail.wkv, p->enc_tail.bkv, nullptr, nullptr, p->enc_tail.heads};
             if (tail) { et.kmem = reinterpret_cast<float*>(p->kmem); et.vmem = reinterpret_cast<float*>(p->vmem); }
             // the tail's K / V rows as 24-bit floats (3 bytes per element: decoder_attn.h F24) — the cross-attention kernels of this
@@ -237,11 +238,11 @@ static int encode_impl(parseq_plan* p, const TI* images, int B, float* memory_ou
     { ProfScope ps_(&p->prof, T_LN, s); CHK((run_layernorm<T>(s, p->x, m->p(pe + "norm.weight"), m->p(pe + "norm.bias"), xn, memory_out, M, E, c.enc_ln_eps))); }
     p->last_batch = B;
     if (m->vitstr) return 0;          // no decoder: the head reads xn (parseq_vitstr_forward)
-    const std::string d = "decoder.layers.0.cross_attn.";
     p->kv24 = false;      // f32 / bf16 rows from the generic GEMM
-    {
+    for (int l = 0; l < c.dec_depth; ++l) {      // one GEMM per decoder layer (their K | V weight rows are not adjacent in the master)
+        const std::string d = "decoder.layers." + std::to_string(l) + ".cross_attn.";
         EpiHeads<T> ek; static_cast<EpiBase&>(ek) = epi_base(M, 2 * E, m->p(d + "in_proj_bias") + E);
-        ek.seg[0] = reinterpret_cast<T*>(p->kmem); ek.seg[1] = reinterpret_cast<T*>(p->vmem); ek.seg[2] = nullptr;
+        ek.seg[0] = reinterpret_cast<T*>(l ? p->kmem_l[l] : p->kmem); ek.seg[1] = reinterpret_cast<T*>(l ? p->vmem_l[l] : p->vmem); ek.seg[2] = nullptr;
         ek.E = E; ek.heads = c.dec_heads; ek.hd = DEC_HD; ek.tokens = N; ek.tr_from = 2;      // K and V both [b][h][key][32]
         ProfScope ps_(&p->prof, T_KVMEM, s);
         // the K | V boundary (column E) must fall on a tile edge: 64-wide tiles when E is not a multiple of 128 (PARSeq-Ti)

@@ -271,6 +271,14 @@ struct parseq_plan {
     unsigned char* cloze = nullptr;  // [npos][LDT]
     unsigned char* qmask_user = nullptr;  // [npos][LDT] staging for parseq_decode_logits
     int* counters = nullptr;       // [0] rows that have seen an EOS, [1] step at which the reference would have stopped (ar_len)
+    // dec_depth > 1 (sized at plan creation; null at depth 1): layer l's memory K / V (kmem_l[0] / vmem_l[0] are kmem / vmem), the
+    // self-attention K | V rows of every layer's content input [max_batch][npos][2E] in T (the AR loop's per-layer cache), the content
+    // stream [max_batch * npos][E] f32 (updated in place layer by layer) and the staging of a caller's content mask [npos][LDT]
+    void* kmem_l[PARSEQ_DEC_DEPTH_MAX] = {};
+    void* vmem_l[PARSEQ_DEC_DEPTH_MAX] = {};
+    void* kvself[PARSEQ_DEC_DEPTH_MAX] = {};
+    float* xc = nullptr;
+    unsigned char* cmask_user = nullptr;
     int last_batch = 0;            // batch of the most recent parseq_encode (kvmem valid for it)
     bool kv24 = false;             // what kmem / vmem hold right now: f32 rows, or (bf16x3 one-launch encoder with its tail) the 24-bit rows of decoder_attn.h
     size_t kv_plane_elems = 0;     // elements of one K (or V) plane at max_batch: the u8 plane sits this many 2-byte elements behind the u16 plane

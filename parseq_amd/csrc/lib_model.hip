@@ -18,7 +18,8 @@ extern "C" int parseq_model_create(const parseq_config* c, parseq_model** out) {
     const int E = c->embed_dim;
     const bool vitstr = c->arch == PARSEQ_ARCH_VITSTR;
     if (c->arch != PARSEQ_ARCH_PARSEQ && !vitstr) return fail(PARSEQ_E_INVALID, "arch=%d", c->arch);
-    if (!vitstr && c->dec_depth != 1) return fail(PARSEQ_E_INVALID, "dec_depth=%d: only the reference's dec_depth == 1 is supported", c->dec_depth);
+    if (!vitstr && (c->dec_depth < 1 || c->dec_depth > PARSEQ_DEC_DEPTH_MAX))
+        return fail(PARSEQ_E_INVALID, "dec_depth=%d outside the supported range [1, %d]", c->dec_depth, PARSEQ_DEC_DEPTH_MAX);
     if (E != 192 && E != 384 && E != 768) return fail(PARSEQ_E_INVALID, "embed_dim=%d not in {192, 384, 768}", E);
     if (c->enc_heads <= 0 || E / c->enc_heads != ATT_HD || E % c->enc_heads) return fail(PARSEQ_E_INVALID, "encoder head_dim must be 64 (embed_dim %d / heads %d)", E, c->enc_heads);
     if (!vitstr && (c->dec_heads <= 0 || E / c->dec_heads != 32 || E % c->dec_heads)) return fail(PARSEQ_E_INVALID, "decoder head_dim must be 32 (embed_dim %d / heads %d)", E, c->dec_heads);
@@ -60,14 +61,16 @@ extern "C" int parseq_model_create(const parseq_config* c, parseq_model** out) {
     }
     add_param(m, pe + "norm.weight", E); add_param(m, pe + "norm.bias", E);
     if (!vitstr) {
-        const std::string p = "decoder.layers.0.";
-        for (const char* a : {"self_attn.", "cross_attn."}) {
-            add_param(m, p + a + "in_proj_weight", (int64_t)3 * E * E); add_param(m, p + a + "in_proj_bias", 3 * E);
-            add_param(m, p + a + "out_proj.weight", (int64_t)E * E); add_param(m, p + a + "out_proj.bias", E);
+        for (int l = 0; l < c->dec_depth; ++l) {      // modules.py:101-104: decoder.layers.{l}.*, the reference's key order
+            const std::string p = "decoder.layers." + std::to_string(l) + ".";
+            for (const char* a : {"self_attn.", "cross_attn."}) {
+                add_param(m, p + a + "in_proj_weight", (int64_t)3 * E * E); add_param(m, p + a + "in_proj_bias", 3 * E);
+                add_param(m, p + a + "out_proj.weight", (int64_t)E * E); add_param(m, p + a + "out_proj.bias", E);
+            }
+            add_param(m, p + "linear1.weight", Fd * E); add_param(m, p + "linear1.bias", Fd);
+            add_param(m, p + "linear2.weight", E * Fd); add_param(m, p + "linear2.bias", E);
+            for (const char* n : {"norm1.", "norm2.", "norm_q.", "norm_c."}) { add_param(m, p + n + "weight", E); add_param(m, p + n + "bias", E); }
         }
-        add_param(m, p + "linear1.weight", Fd * E); add_param(m, p + "linear1.bias", Fd);
-        add_param(m, p + "linear2.weight", E * Fd); add_param(m, p + "linear2.bias", E);
-        for (const char* n : {"norm1.", "norm2.", "norm_q.", "norm_c."}) { add_param(m, p + n + "weight", E); add_param(m, p + n + "bias", E); }
         add_param(m, "decoder.norm.weight", E); add_param(m, "decoder.norm.bias", E);
     }
     add_param(m, "head.weight", (int64_t)m->classes * E); add_param(m, "head.bias", m->classes);
@@ -315,6 +318,15 @@ extern "C" int parseq_plan_create_ex(parseq_model* m, int max_batch, int precisi
     const size_t o_blocks = carve(off, (size_t)c.enc_depth * sizeof(EncBlockParams));
     const size_t o_posb = carve(off, N * E * 4);
     const size_t o_qfold = carve(off, (3 * E + npos) * 4);
+    // dec_depth > 1: memory K / V of layers 1 .. D-1, every layer's self-attention K | V rows, the content stream, a content-mask staging
+    const int D = m->vitstr ? 1 : c.dec_depth;
+    size_t o_kmem_l[PARSEQ_DEC_DEPTH_MAX] = {}, o_vmem_l[PARSEQ_DEC_DEPTH_MAX] = {}, o_kvself[PARSEQ_DEC_DEPTH_MAX] = {}, o_xc = 0, o_cmu = 0;
+    if (D > 1) {
+        for (int l = 1; l < D; ++l) { o_kmem_l[l] = carve(off, rows * E * ts); o_vmem_l[l] = carve(off, rows * E * ts); }
+        for (int l = 0; l < D; ++l) o_kvself[l] = carve(off, drows * 2 * E * ts);
+        o_xc = carve(off, drows * E * 4);
+        o_cmu = carve(off, npos * LDT);
+    }
     p->arena_bytes = off;
     if (alloc) {
         p->arena = static_cast<unsigned char*>(alloc(off, user));
@@ -335,6 +347,12 @@ extern "C" int parseq_plan_create_ex(parseq_model* m, int max_batch, int precisi
     p->blocks_dev = reinterpret_cast<EncBlockParams*>(a + o_blocks);
     p->posb = reinterpret_cast<float*>(a + o_posb);
     p->qfold = reinterpret_cast<float*>(a + o_qfold);
+    if (D > 1) {
+        p->kmem_l[0] = p->kmem; p->vmem_l[0] = p->vmem;
+        for (int l = 1; l < D; ++l) { p->kmem_l[l] = a + o_kmem_l[l]; p->vmem_l[l] = a + o_vmem_l[l]; }
+        for (int l = 0; l < D; ++l) p->kvself[l] = a + o_kvself[l];
+        p->xc = reinterpret_cast<float*>(a + o_xc); p->cmask_user = a + o_cmu;
+    }
     p->tok = (int*)(a + o_tok); p->kpm = a + o_kpm; p->eos_seen = a + o_eos; p->cloze = a + o_cloze; p->qmask_user = a + o_qmu; p->counters = (int*)(a + o_cnt);
     int r = pack_weights(p, (hipStream_t)stream);
     if (r != 0) { parseq_plan_destroy(p); return r; }

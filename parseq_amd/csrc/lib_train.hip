@@ -433,6 +433,7 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     if (!m || !memory || !tokens || !targets || !key_padding_mask || !query_masks || !loss_out || !grads || !dmemory || !workspace)
         return fail(PARSEQ_E_INVALID, "null argument");
     if (m->vitstr) return fail(PARSEQ_E_INVALID, "ViTSTR has no decoder");
+    if (m->cfg.dec_depth != 1) return fail(PARSEQ_E_INVALID, "dec_depth=%d: the training step has depth-1 decoder kernels only", m->cfg.dec_depth);
     for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
     m->grad_events_valid = false;      // a new step starts writing the flat gradient buffer: the previous step's segment events say nothing about it
     DevGuard dg(m->device);

@@ -443,8 +443,9 @@ class PARSeq(_NativeBacked):
         projection is still cached on the device); any other tensor is projected afresh; `None` means "the most recent
         `encode` / `forward`".  `tgt_query`: None (all positions `pos_queries[:, :L]`), a view `pos_queries[:, i:j]` (what
         `forward` and the training step pass — served from the position-query tables), or any other [N, Lq, E] / [1, Lq, E]
-        tensor (projected at call time).  `tgt_mask` only feeds the content-stream update, which a depth-1 decoder never
-        runs (modules.py:116-118), so it is ignored exactly as the reference ignores it."""
+        tensor (projected at call time).  `tgt_mask` ([L, L], True = masked) is the content mask: a decoder deeper than one layer
+        updates the content stream under it in layers 0 .. dec_depth - 2 (modules.py:116-124).  A depth-1 decoder never runs that
+        update, so there it has no effect, exactly as in the reference."""
         B, L = tgt.shape
         E = self._cfg['embed_dim']
         user_query = None
@@ -474,10 +475,14 @@ class PARSeq(_NativeBacked):
         qm = tgt_query_mask.to(device=self._device, dtype=torch.uint8).contiguous() if tgt_query_mask is not None else None
         if qm is not None and tuple(qm.shape) != (q_len, L):
             raise RuntimeError(f'tgt_query_mask shape {tuple(qm.shape)} != ({q_len}, {L})')
+        cm = self._content_mask(tgt_mask, L)
         hidden = torch.empty(B, q_len, E, dtype=torch.float32, device=self._device)
         logits = torch.empty(B, q_len, self._cfg['num_tokens'] - 2, dtype=torch.float32, device=self._device)
         lib, stream = _native.lib(), _native.stream_ptr(self._device)
-        if user_query is None:
+        if cm is not None:
+            _native.check(lib.parseq_decode_ex(plan, _native.ptr(tok), B, L, q_start, q_len, _native.ptr(user_query), _native.ptr(qm), _native.ptr(cm),
+                                               _native.ptr(kpm), _native.ptr(hidden), _native.ptr(logits), stream))
+        elif user_query is None:
             _native.check(lib.parseq_decode_hidden(plan, _native.ptr(tok), B, L, q_start, q_len, _native.ptr(qm), _native.ptr(kpm),
                                                    _native.ptr(hidden), _native.ptr(logits), stream))
         else:
@@ -485,11 +490,22 @@ class PARSeq(_NativeBacked):
                                                   _native.ptr(kpm), _native.ptr(hidden), _native.ptr(logits), stream))
         return hidden
 
+    def _content_mask(self, tgt_mask: Optional[Tensor], L: int) -> Optional[Tensor]:
+        """The content mask as the library takes it (uint8 [L, L] on the device), or None where it has no effect: no mask, or a
+        depth-1 decoder (which never updates the content stream)."""
+        if tgt_mask is None or self._cfg['dec_depth'] == 1:
+            return None
+        cm = tgt_mask.to(device=self._device, dtype=torch.uint8).contiguous()
+        if tuple(cm.shape) != (L, L):
+            raise RuntimeError(f'tgt_mask shape {tuple(cm.shape)} != ({L}, {L})')
+        return cm
+
     def decode_logits(self, tgt: Tensor, q_start: int, q_len: int, tgt_padding_mask: Optional[Tensor] = None,
-                      tgt_query_mask: Optional[Tensor] = None) -> Tensor:
+                      tgt_query_mask: Optional[Tensor] = None, tgt_mask: Optional[Tensor] = None) -> Tensor:
         """head(decode(...)) for queries pos_queries[q_start:q_start+q_len] against the content tokens `tgt`
         (model.py:86-103 + :138), using the memory of the most recent `encode` / `forward` on this model.
-        Per-stage parity hook; masks use torch's convention (True = masked)."""
+        Per-stage parity hook; masks use torch's convention (True = masked).  `tgt_mask`: the content mask [L, L] (read by
+        decoders deeper than one layer only, see `decode`)."""
         B, L = tgt.shape
         plan = self._plan(B)
         tok = tgt.to(device=self._device, dtype=torch.int32).contiguous()
@@ -497,7 +513,12 @@ class PARSeq(_NativeBacked):
         qm = tgt_query_mask.to(device=self._device, dtype=torch.uint8).contiguous() if tgt_query_mask is not None else None
         if qm is not None and tuple(qm.shape) != (q_len, L):
             raise RuntimeError(f'tgt_query_mask shape {tuple(qm.shape)} != ({q_len}, {L})')
+        cm = self._content_mask(tgt_mask, L)
         out = torch.empty(B, q_len, self._cfg['num_tokens'] - 2, dtype=torch.float32, device=self._device)
+        if cm is not None:
+            _native.check(_native.lib().parseq_decode_ex(plan, _native.ptr(tok), B, L, q_start, q_len, None, _native.ptr(qm), _native.ptr(cm),
+                                                         _native.ptr(kpm), None, _native.ptr(out), _native.stream_ptr(self._device)))
+            return out
         _native.check(_native.lib().parseq_decode_logits(plan, _native.ptr(tok), B, L, q_start, q_len, _native.ptr(qm),
                                                          _native.ptr(kpm), _native.ptr(out), _native.stream_ptr(self._device)))
         return out

@@ -165,7 +165,7 @@ def generate_attn_masks(perm: Tensor):
 
 def permutation_loss(system, images: Tensor, labels, perms: Optional[Tensor] = None):
     """Forward half of PARSeq.training_step (system.py:168-199) with dropout off: one `encode`, one teacher-forced decode
-    per permutation (the depth-1 decoder only reads the query mask), the cross-entropy of each weighted by its count of
+    per permutation (a depth-1 decoder only reads the query mask, a deeper one also the content mask), the cross-entropy of each weighted by its count of
     non-<pad> targets; <eos> targets are dropped after the first two permutations (:191-195).  Everything after the mask
     construction runs on the device (`parseq_decode_logits`, `parseq_cross_entropy`); no host synchronisation.
     Returns (loss, per-permutation losses [K], per-permutation target counts [K], perms)."""
@@ -177,6 +177,9 @@ def permutation_loss(system, images: Tensor, labels, perms: Optional[Tensor] = N
     tgt_in, tgt_out = tgt[:, :-1], tgt[:, 1:]
     L = tgt_in.shape[1]
     masks = torch.stack([generate_attn_masks(p)[1] for p in perms.cpu()]).to(torch.uint8).to(dev)       # one upload
+    # a deeper decoder also updates the content stream, under the content mask of the same permutation (modules.py:116-124)
+    deep = system.model._cfg['dec_depth'] > 1
+    cmasks = torch.stack([generate_attn_masks(p)[0] for p in perms.cpu()]).to(torch.uint8).to(dev) if deep else None
     padding = ((tgt_in == system.pad_id) | (tgt_in == system.eos_id))
     system.model.encode(images)                      # leaves the cross-attention K / V of these images on the device
     targets = [tgt_out.to(torch.int32).contiguous().view(-1),
@@ -186,7 +189,7 @@ def permutation_loss(system, images: Tensor, labels, perms: Optional[Tensor] = N
     counts = torch.empty(K, dtype=torch.int32, device=dev)
     ws = torch.empty(tgt_out.numel(), dtype=torch.float32, device=dev)
     for i in range(K):
-        logits = system.model.decode_logits(tgt_in, 0, L, padding, masks[i])
+        logits = system.model.decode_logits(tgt_in, 0, L, padding, masks[i], tgt_mask=cmasks[i] if deep else None)
         flat = logits.view(-1, logits.shape[-1])
         with _native.guard(flat):
             _native.check(_native.lib().parseq_cross_entropy(_native.ptr(flat), _native.ptr(targets[min(i // 2, 1)]), flat.shape[0],

@@ -42,6 +42,14 @@ class DecoderBackward:
         return self.workspace[off:off + numel]
 
 
+def check_trainable(system) -> None:
+    """The gradient path has depth-1 decoder kernels only: a deeper decoder (dec_depth > 1, inference only) is refused before any
+    device work."""
+    depth = system.model._cfg['dec_depth']
+    if depth != 1:
+        raise ValueError(f'dec_depth={depth}: training runs the depth-1 decoder kernels only (a deeper decoder is inference-only)')
+
+
 def param_views(native_model, flat: Tensor, shapes: Dict[str, Sequence[int]]) -> Dict[str, Tensor]:
     lib = _native.lib()
     out = {}
@@ -170,6 +178,7 @@ def decoder_backward(system, images: Tensor, labels, perms: Optional[Tensor] = N
     to the model's rate in training mode (`system.train()`) and to 0 in evaluation mode; `seed` (the step's dropout masks)
     defaults to a draw from the system's numpy generator.  `inputs`: the result of `prepare_decoder_inputs` when the caller made it
     earlier (loss_and_grads does, ahead of the encoder's forward)."""
+    check_trainable(system)
     lib = _native.lib()
     model = system.model
     dev = system.device
@@ -207,6 +216,7 @@ def loss_and_grads(system, images: Tensor, labels, perms: Optional[Tensor] = Non
     """Loss and the gradient of EVERY parameter for one batch — the state `loss.backward()` leaves after the reference's
     `training_step` (system.py:168-199), dropout off.  `images`: fp32 [B, 3, H, W] on the device, normalised.  Everything is enqueued on
     the CURRENT stream (`inputs`: prepared ahead by the caller — loss_and_grads_micro)."""
+    check_trainable(system)
     lib = _native.lib()
     model = system.model
     images = model._check_images(images)
@@ -243,6 +253,7 @@ def loss_and_grads_micro(system, images: Tensor, labels, perms: Optional[Tensor]
     Returns the first part's record with `flat` / `grads` / `loss` replaced by the batch's.  `flats`: gradient buffers of parts 1 .. n - 1 kept by the
     caller across steps (TrainStep does): a buffer allocated on a part's stream and read on the caller's would have to be handed between the
     caching allocator's per-stream pools every step (deferred frees, fresh hipMallocs — and their synchronisations — in the middle of the step)."""
+    check_trainable(system)
     model, dev = system.model, system.device
     images = model._check_images(images)
     B = images.shape[0]
@@ -302,6 +313,7 @@ class TrainStep:
                  warmup_pct: Optional[float] = None, clip_val: float = 20.0, betas=(0.9, 0.999), eps: float = 1e-8,
                  num_devices: Optional[int] = None, accumulate_grad_batches: int = 1, process_group=None, micro_batches: Optional[int] = None):
         import math
+        check_trainable(system)
         self.system = system
         self.total_steps = total_steps
         if num_devices is None:       # base.py:99 uses trainer.num_devices: default to the data-parallel world this step averages over
@@ -417,6 +429,7 @@ class _TrainingStepFunction(torch.autograd.Function):
 
 def training_step_loss(system, images: Tensor, labels, perms: Optional[Tensor] = None) -> Tensor:
     """The loss of `PARSeq.training_step` (system.py:168-199) as a differentiable scalar w.r.t. every parameter of the model."""
+    check_trainable(system)
     names = [k for k, _ in system.model.named_parameters()]
     if names != list(system.model.state_dict().keys()):
         raise RuntimeError('parameters and state_dict disagree (buffers?): the gradient buffer is laid out by state_dict order')
