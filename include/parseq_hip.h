@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 9
+#define PARSEQ_ABI_VERSION 10
 
 /* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
 #define PARSEQ_DEC_DEPTH_MAX 4
@@ -314,6 +314,17 @@ int parseq_train_encoder_forward(parseq_model* m, const float* images, int batch
 int parseq_train_encoder_backward(parseq_model* m, const float* dmemory, int batch, float* grads, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* (ABI 10) ViTSTR's training step (strhub/models/vitstr/system.py:75-79 -> base.py:194-204 forward_logits_loss): the encoder entries
+ * above take a ViTSTR model too (class token + pos_embed over tokens + 1 rows; the gradient of cls_token, pos_embed and patch_embed
+ * ACCUMULATED into `grads`); in between, this entry computes the head on token rows 1 .. T of every image of `memory`
+ * ([batch, tokens, E], after the encoder's final norm), the mean cross-entropy against `targets` (int32 [batch, T], ignore_index =
+ * pad_id; total_targets = the number of non-pad targets) into loss_out[0], ACCUMULATES the head.weight / head.bias gradients into
+ * `grads` and writes d loss / d memory into `dmemory` (zero on row 0 and past row T).  T <= max_label_length + 1.  Refuses a
+ * PARSeq model. */
+size_t parseq_train_vitstr_head_workspace_bytes(const parseq_model* m, int batch, int T);
+int parseq_train_vitstr_head(parseq_model* m, const float* memory, const int32_t* targets, int batch, int T, int total_targets,
+                             float* loss_out, float* grads, float* dmemory, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Gradient segments (ABI 5): the hook for overlapping the data-parallel all-reduce with the encoder's backward — what DDP's bucketed
  * reducer does under the reference's Trainer(strategy=DDPStrategy(...), reference train.py:65-71, 88-96).  The flat gradient buffer
  * becomes final piecewise: the decoder's part before parseq_train_encoder_backward starts, then the encoder's blocks from the last to
@@ -435,6 +446,13 @@ int parseq_op_mlp_variant(float* x, const float* gamma, const float* beta, const
  * out [bh / heads * 128, heads * 64] in `dtype`.  dtype = PARSEQ_BF16X3: f32 tensors, split-bf16 products. */
 int parseq_op_encoder_attention(const void* q, const void* k, const void* vt, void* out, int dtype, int bh, int heads,
                                 void* stream);
+/* (ABI 10) The training step's encoder self-attention alone, fp32 (exact products): `tokens` tokens of `heads` heads of width 64;
+ * qkv [batch * tokens, 3 E] (q | k | v per row, E = 64 heads), o [batch * tokens, E]; backward: d_o like o, dqkv like qkv (written).
+ * Past 128 tokens (up to 256) the key-streaming kernels run: the forward writes lse [batch, heads, tokens] (each query row's
+ * log-sum-exp of the scaled scores), the backward reads it and writes dsum [batch, heads, tokens] (rowsum(d_o * o)); at 128 tokens or
+ * fewer the step's resident kernels run and neither is touched.  *route (may be NULL): 1 for the key-streaming kernels, 0 otherwise. */
+int parseq_op_train_attention(const float* qkv, float* o, float* lse, const float* d_o, float* dqkv, float* dsum, int batch, int tokens,
+                              int heads, int backward, int* route, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,8 @@
 #include "lib_internal.h"
 
 #include "train_ops.h"
+#include "train_attn_wide.h"
+#include "train_vitstr.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // training step, decoder side: loss of system.py:168-199 and its gradients, fp32
@@ -326,6 +328,28 @@ static bool train_attn_is_dec_bf16(const TrainCtx& cx, const TrainAttnArgs& a, i
     return cx.bf16_ops && hd == TD_HD && a.Lq <= TD_Q && a.Lk <= TD_K && a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 &&
            a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv) && !getenv("PARSEQ_TRAIN_F32_ATTN");
 }
+// encoder self-attention past 128 tokens (train_attn_wide.h): head width 64, N in (128, 256], per-image queries, no masks, no dropout,
+// one pass per launch — the shapes no kernel above takes (train_attn_hd<64> holds at most 128 keys)
+static bool train_attn_is_wide(const TrainAttnArgs& a, int hd) {
+    return hd == TW_HD && a.Lk > 128 && a.Lk <= TW_MAXN && a.Lq == a.Lk && !a.qmask && !a.kmask && !a.drop.thresh && !a.pass_B && !a.pass_loop &&
+           a.q_bstride == (long)a.Lq * a.ldq;
+}
+static int train_attn_wide(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
+    if (!a.lse || (backward && !a.dsum)) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: no log-sum-exp / row-sum slot", a.Lk);
+    bool ok = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 && aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.o);
+    if (backward) ok = ok && a.d_o && a.dq && a.dk && a.dv && aligned16(a.d_o);
+    if (!ok) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: operands not laid out in 16-byte rows", a.Lk);
+    const dim3 grid((unsigned)((a.Lk + TW_BLK - 1) / TW_BLK), (unsigned)(B * a.H));
+    if (backward) {
+        hipLaunchKernelGGL(train_attn_wide_dq_kernel, grid, dim3(256), 0, cx.s, a);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(train_attn_wide_dkv_kernel, grid, dim3(256), 0, cx.s, a);
+    } else {
+        hipLaunchKernelGGL(train_attn_wide_fwd_kernel, grid, dim3(256), 0, cx.s, a);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 static int train_attn(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward, int hd) {
     if (cx.bf16_ops && hd == TD_HD && a.Lq <= TD_Q && a.Lk <= TD_K && a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 &&
         (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv))) && !getenv("PARSEQ_TRAIN_F32_ATTN"))
@@ -339,9 +363,26 @@ static int train_attn(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool ba
     if (a.o16 || a.dq16) return fail(PARSEQ_E_INVALID, "training attention: a bf16 output is only written by the encoder-shaped bf16 kernel");
     if (hd == 64 && a.Lq % 32 == 0 && a.Lk % 16 == 0 && a.Lk <= 128 && !a.qmask && !a.kmask && !a.drop.thresh && !getenv("PARSEQ_TRAIN_VALU_ATTN"))
         return train_attn_mfma(cx, a, B, backward);
+    if (train_attn_is_wide(a, hd)) return train_attn_wide(cx, a, B, backward);
     if (hd == 32) return train_attn_hd<32>(cx, a, B, backward);
     if (hd == 64) return train_attn_hd<64>(cx, a, B, backward);
     return fail(PARSEQ_E_INVALID, "training attention: head width %d not in {32, 64}", hd);
+}
+
+// The training step's encoder attention on its own (the kernels' unit test): the self-attention of `tokens` tokens, `heads` heads of 64,
+// q | k | v interleaved in qkv [batch * tokens, 3 E] (E = 64 heads), o [batch * tokens, E], fp32, exact products.
+extern "C" int parseq_op_train_attention(const float* qkv, float* o, float* lse, const float* d_o, float* dqkv, float* dsum, int batch, int tokens,
+                                         int heads, int backward, int* route, void* stream) {
+    CHK(check_arch());
+    if (!qkv || !o || batch <= 0 || tokens <= 0 || heads <= 0 || (backward && (!d_o || !dqkv))) return fail(PARSEQ_E_INVALID, "bad argument");
+    const int E = heads * TW_HD;
+    TrainAttnArgs a{};
+    a.q = qkv; a.q_bstride = (long)tokens * 3 * E; a.ldq = 3 * E; a.k = qkv + E; a.v = qkv + 2 * E; a.ldkv = 3 * E;
+    a.o = o; a.ldo = E; a.d_o = d_o; a.dq = dqkv; a.lddq = 3 * E; a.dk = dqkv ? dqkv + E : nullptr; a.dv = dqkv ? dqkv + 2 * E : nullptr;
+    a.lddkv = 3 * E; a.Lq = tokens; a.Lk = tokens; a.H = heads; a.scale = 1.0f / sqrtf((float)TW_HD); a.lse = lse; a.dsum = dsum;
+    if (route) *route = train_attn_is_wide(a, TW_HD) ? 1 : 0;
+    const TrainCtx cx{(hipStream_t)stream, nullptr, false, 0};
+    return train_attn(cx, a, batch, backward != 0, TW_HD);
 }
 
 // The K permutation passes of a step share every weight and differ in their masks, dropout sites and (after two passes) targets only
@@ -609,6 +650,8 @@ struct TrainEncoderLayout {          // offsets in floats
     size_t w16, w16_layer, d_x16, d_h16;      // bf16 shadows (train_enc_shadows): the Linear weights and their transposes ([layer][qkv, proj, fc1, fc2][W16 | Wt16]),
                                               // the residual-stream gradient and the fc1-output gradient
     size_t x(int i) const { return layer0 + i * layer_stride; }
+    size_t lse = 0, dsum = 0;        // past 128 tokens only (train_attn_wide.h): the attention's log-sum-exp [B, H, tokens] inside each layer's
+                                     // record, and the backward's D = rowsum(dO o O) [B, H, tokens] (one slot)
     size_t qkv, ao, x_mid, hpre, hact_l, n1, n2;     // offsets inside one layer's record (x at 0); hact_l, n1, n2: the GELU output and the two
                                              // LayerNorm outputs, kept for the backward (round 3: they used to be recomputed there — a 600 MB and two
                                              // 150 MB passes per block; the record grows from 10 E to 16 E floats per token per block)
@@ -624,10 +667,13 @@ static TrainEncoderLayout train_encoder_layout(const parseq_model* m, int B) {
     o.hpre = off - o.layer0; take(MS * F);
     o.hact_l = off - o.layer0; take(MS * F);
     o.n1 = off - o.layer0; take(MS * E); o.n2 = off - o.layer0; take(MS * E);
+    const bool wide = m->tokens > 128;          // the record at 128 tokens stays as it was, slot for slot
+    if (wide) { o.lse = off - o.layer0; take(MS * m->cfg.enc_heads); }
     o.layer_stride = off - o.layer0;
     off = o.layer0 + o.layer_stride * (size_t)m->cfg.enc_depth;
     o.x_last = take(MS * E); o.n = take(MS * E); o.hact = take(MS * F); o.d_x = take(MS * E); o.d_a = take(MS * E); o.d_h = take(MS * F);
     o.dqkv = take(MS * 3 * E); o.tmp = take(MS * E);
+    if (wide) o.dsum = take(MS * m->cfg.enc_heads);
     o.scratch_floats = train_scratch_floats(MS, E); o.scratch = take(o.scratch_floats);
     // the second scratch belongs to the backward's second stream, which only the bf16-operand mode has (the fp32 mode carves nothing for it)
     o.scratch2 = m->train_precision == PARSEQ_BF16 ? take(o.scratch_floats) : o.scratch;
@@ -644,7 +690,6 @@ extern "C" size_t parseq_train_encoder_workspace_bytes(const parseq_model* m, in
 
 static int train_encoder_check(const parseq_model* m, int batch, const void* workspace, size_t workspace_bytes) {
     if (!m || !workspace) return fail(PARSEQ_E_INVALID, "null argument");
-    if (m->vitstr) return fail(PARSEQ_E_INVALID, "the training step is built for PARSeq only");
     if (batch <= 0) return fail(PARSEQ_E_INVALID, "batch %d", batch);
     for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
     const size_t need = train_encoder_layout(m, batch).total * sizeof(float);
@@ -692,12 +737,13 @@ static EncShadowW enc_shadow_w(const TrainEncoderLayout& o, float* ws, int layer
     return EncShadowW{base + at[which], base + at[which] + n[which]};
 }
 
-static TrainAttnArgs enc_attn_args(const parseq_model* m, float* qkv, float* ao, const float* d_ao, float* dqkv) {
+static TrainAttnArgs enc_attn_args(const parseq_model* m, float* qkv, float* ao, const float* d_ao, float* dqkv, float* lse = nullptr, float* dsum = nullptr) {
     const int E = m->cfg.embed_dim, S = m->tokens;
     TrainAttnArgs a{};
     a.q = qkv; a.q_bstride = (long)S * 3 * E; a.ldq = 3 * E; a.k = qkv + E; a.v = qkv + 2 * E; a.ldkv = 3 * E;
     a.o = ao; a.ldo = E; a.d_o = d_ao; a.dq = dqkv; a.lddq = 3 * E; a.dk = dqkv ? dqkv + E : nullptr; a.dv = dqkv ? dqkv + 2 * E : nullptr;
     a.lddkv = 3 * E; a.kv_accumulate = 0; a.Lq = S; a.Lk = S; a.H = m->cfg.enc_heads; a.scale = 1.0f / sqrtf((float)ATT_HD);
+    a.lse = lse; a.dsum = dsum;
     return a;
 }
 
@@ -713,9 +759,19 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
     float* w = reinterpret_cast<float*>(workspace);
     auto P = [&](const std::string& key) { return m->p(m->enc + key); };
     const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
-    hipLaunchKernelGGL(patches_kernel, dim3(MS), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches);
-    HIPCHK(hipGetLastError());
-    CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed"), S, w + o.x(0), MS, E, PK));
+    if (m->vitstr) {
+        // S - 1 patch rows per image, S token rows: the class token in front (timm _pos_embed), assembled from the patch product in `tmp`
+        const int MP = batch * (S - 1);
+        hipLaunchKernelGGL(patches_kernel, dim3(MP), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches);
+        HIPCHK(hipGetLastError());
+        CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), nullptr, 0, w + o.tmp, MP, E, PK));
+        hipLaunchKernelGGL(vitstr_tokens_kernel, dim3(MS), dim3(256), 0, s, w + o.tmp, P("cls_token"), P("pos_embed"), w + o.x(0), S, E);
+        HIPCHK(hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(patches_kernel, dim3(MS), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches);
+        HIPCHK(hipGetLastError());
+        CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed"), S, w + o.x(0), MS, E, PK));
+    }
     const size_t elems = (size_t)MS * F;
     const bool shadows = train_enc_shadows(m), only16 = train_enc_bf16_only(m);
     m->enc_record_mode = (shadows ? 1 : 0) | (only16 ? 2 : 0);      // what the record's slots hold; the backward entry must read them the same way
@@ -801,7 +857,7 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
         }
         CHK(train_ln_fwd(s, x, P(p + "norm1.weight"), P(p + "norm1.bias"), x + o.n1, MS, E, eps));
         CHK(lin_fwd(cx, x + o.n1, P(p + "attn.qkv.weight"), P(p + "attn.qkv.bias"), nullptr, 0, qkv, MS, 3 * E, E));
-        CHK(train_attn(cx, enc_attn_args(m, qkv, ao, nullptr, nullptr), batch, false, ATT_HD));
+        CHK(train_attn(cx, enc_attn_args(m, qkv, ao, nullptr, nullptr, o.lse ? x + o.lse : nullptr), batch, false, ATT_HD));
         CHK(lin_fwd(cx, ao, P(p + "attn.proj.weight"), P(p + "attn.proj.bias"), x, MS, x_mid, MS, E, E));
         CHK(train_ln_fwd(s, x_mid, P(p + "norm2.weight"), P(p + "norm2.bias"), x + o.n2, MS, E, eps));
         float* hact_l = x + o.hact_l;
@@ -881,7 +937,7 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
                     (shadows ? 1 : 0) | (only16 ? 2 : 0));
     bf16_t* d_x16 = shadows ? reinterpret_cast<bf16_t*>(w + o.d_x16) : nullptr;
     bf16_t* d_h16 = shadows ? reinterpret_cast<bf16_t*>(w + o.d_h16) : nullptr;
-    const bool segs = m->cfg.enc_depth >= 2;
+    const bool segs = !m->vitstr && m->cfg.enc_depth >= 2;
     const bool two_streams = only16 && !getenv("PARSEQ_TRAIN_ONE_STREAM");
     hipStream_t side = nullptr;
     hipEvent_t* side_ev = nullptr;
@@ -985,14 +1041,73 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
         CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), tmp, MS, E, eps));   // d_x = d x_mid
         // x_mid = x + proj(attention(qkv(norm1(x))))
         CHK(lin_bwd(cx, ao, P(p + "attn.proj.weight"), d_x, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), d_a, MS, E, E));        // d_a = d ao
-        CHK(train_attn(cx, enc_attn_args(m, qkv, ao, d_a, dqkv), batch, true, ATT_HD));
+        CHK(train_attn(cx, enc_attn_args(m, qkv, ao, d_a, dqkv, o.lse ? x + o.lse : nullptr, o.lse ? w + o.dsum : nullptr), batch, true, ATT_HD));
         CHK(lin_bwd(cx, x + o.n1, P(p + "attn.qkv.weight"), dqkv, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), d_a, MS, 3 * E, E));
         CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), tmp, MS, E, eps));          // d_x = d x
     }
     CHK(colsum(cx, d_x, (long)S * E, batch, S * E, G("pos_embed"), true));
-    CHK(lin_bwd(cx, w + o.patches, P("patch_embed.proj.weight"), d_x, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), nullptr, MS, E, PK));
+    if (m->vitstr) {
+        // d cls_token = sum over the images of row 0; the patch embedding sees rows 1 .. S - 1 only (gathered into `tmp`)
+        const int MP = batch * (S - 1);
+        CHK(colsum(cx, d_x, (long)S * E, batch, E, G("cls_token"), true));
+        hipLaunchKernelGGL(gather_image_rows_kernel, dim3(MP), dim3(256), 0, s, d_x, S, 1, tmp, S - 1, E);
+        HIPCHK(hipGetLastError());
+        CHK(lin_bwd(cx, w + o.patches, P("patch_embed.proj.weight"), tmp, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), nullptr, MP, E, PK));
+    } else {
+        CHK(lin_bwd(cx, w + o.patches, P("patch_embed.proj.weight"), d_x, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), nullptr, MS, E, PK));
+    }
     if (segs) CHK(grad_event_record(m, m->cfg.enc_depth, s));      // block 0, patch_embed, pos_embed (and pos_queries): everything is final
     m->grad_events_valid = segs;
+    return 0;
+}
+
+// ---- training step, ViTSTR head and loss (strhub/models/base.py:194-204 forward_logits_loss, vitstr/system.py:75-82) ------------------
+// logits of tokens 1 .. T of every image (the class token's row is computed by the reference and dropped), cross-entropy over
+// C = num_classes with ignore_index = <pad>, mean over the kept targets; backward into head.* and d memory (zero on row 0 and past T).
+struct VitstrHeadLayout { size_t hin, logits, dh, row_loss, counts, scratch, scratch_floats, total; };
+static VitstrHeadLayout vitstr_head_layout(const parseq_model* m, int B, int T) {
+    const size_t E = m->cfg.embed_dim, C = m->classes, R = (size_t)B * T;
+    VitstrHeadLayout o;
+    size_t off = 0;
+    auto take = [&](size_t n) { const size_t at = off; off += (n + 63) / 64 * 64; return at; };
+    o.hin = take(R * E); o.logits = take(R * C); o.dh = take(R * E); o.row_loss = take(R); o.counts = take(1);
+    o.scratch_floats = train_scratch_floats(R, E); o.scratch = take(o.scratch_floats);
+    o.total = off;
+    return o;
+}
+extern "C" size_t parseq_train_vitstr_head_workspace_bytes(const parseq_model* m, int batch, int T) {
+    if (!m || batch <= 0 || T <= 0) return 0;
+    return vitstr_head_layout(m, batch, T).total * sizeof(float);
+}
+extern "C" int parseq_train_vitstr_head(parseq_model* m, const float* memory, const int32_t* targets, int batch, int T, int total_targets,
+                                        float* loss_out, float* grads, float* dmemory, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!m || !memory || !targets || !loss_out || !grads || !dmemory || !workspace) return fail(PARSEQ_E_INVALID, "null argument");
+    if (!m->vitstr) return fail(PARSEQ_E_INVALID, "parseq_train_vitstr_head on a PARSeq model (arch 0): use parseq_train_decoder");
+    const int S = m->tokens;
+    if (batch <= 0 || T < 1 || T > m->cfg.max_label_length + 1 || T + 1 > S || total_targets <= 0)
+        return fail(PARSEQ_E_INVALID, "bad shape: batch %d, %d target positions (1..%d), %d targets", batch, T, m->cfg.max_label_length + 1, total_targets);
+    for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
+    const VitstrHeadLayout o = vitstr_head_layout(m, batch, T);
+    if (workspace_bytes < o.total * sizeof(float)) return fail(PARSEQ_E_INVALID, "workspace: %zu bytes given, %zu needed", workspace_bytes, o.total * sizeof(float));
+    DevGuard dg(m->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int E = m->cfg.embed_dim, C = m->classes, R = batch * T;
+    float* w = reinterpret_cast<float*>(workspace);
+    auto G = [&](const std::string& key) { return grads + m->params[m->index.at(key)].offset; };
+    const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
+    float* hin = w + o.hin; float* logits = w + o.logits; float* dh = w + o.dh;
+    hipLaunchKernelGGL(gather_image_rows_kernel, dim3(R), dim3(256), 0, s, memory, S, 1, hin, T, E);
+    HIPCHK(hipGetLastError());
+    CHK(lin_fwd(cx, hin, m->p("head.weight"), m->p("head.bias"), nullptr, 0, logits, R, C, E));
+    hipLaunchKernelGGL(ce_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, targets, R, C, m->cfg.pad_id, w + o.row_loss);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, w + o.row_loss, targets, R, m->cfg.pad_id, loss_out, reinterpret_cast<int*>(w + o.counts));
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(ce_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, targets, R, C, m->cfg.pad_id, 1.0f / (float)total_targets);
+    HIPCHK(hipGetLastError());
+    CHK(lin_bwd(cx, hin, m->p("head.weight"), logits, G("head.weight"), G("head.bias"), dh, R, C, E));
+    hipLaunchKernelGGL(scatter_image_rows_kernel, dim3(batch * S), dim3(256), 0, s, dh, T, 1, dmemory, S, E);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

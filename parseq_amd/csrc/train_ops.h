@@ -1282,6 +1282,9 @@ struct TrainAttnArgs {
     // train_attn_dec_bf16_kernel only, with pass_B and kv_shared: the launch has pass_B * H workgroups and each walks pass_loop passes of its
     // image (K / V staged once, dK / dV summed over the passes in the accumulators and stored once, rows of image bl)
     int pass_loop = 0;
+    // train_attn_wide.h only (encoder self-attention past 128 tokens): each query row's log-sum-exp of the scaled scores, written by the
+    // forward and read by the backward, and the backward's D = rowsum(dO o O); both [B, H, Lq]
+    float* lse = nullptr; float* dsum = nullptr;
 };
 // (image over all passes, head) of a workgroup -> what the pass-batched launch indexes with; pass_B == 0 reduces to the plain launch
 struct TrainAttnIdx { int bf, bl, bkv, h; const unsigned char* qmask; unsigned site; unsigned long long dblock; };

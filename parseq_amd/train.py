@@ -42,9 +42,17 @@ class DecoderBackward:
         return self.workspace[off:off + numel]
 
 
+def is_vitstr(system) -> bool:
+    """A ViTSTR system (parseq_amd/vitstr.py): class token + per-token head, no decoder."""
+    from .vitstr import ViTSTR
+    return isinstance(system, ViTSTR)
+
+
 def check_trainable(system) -> None:
     """The gradient path has depth-1 decoder kernels only: a deeper decoder (dec_depth > 1, inference only) is refused before any
-    device work."""
+    device work.  ViTSTR has no decoder."""
+    if is_vitstr(system):
+        return
     depth = system.model._cfg['dec_depth']
     if depth != 1:
         raise ValueError(f'dec_depth={depth}: training runs the depth-1 decoder kernels only (a deeper decoder is inference-only)')
@@ -211,11 +219,68 @@ def decoder_backward(system, images: Tensor, labels, perms: Optional[Tensor] = N
                            workspace=workspace, _shape=(B, L, K), _model=native)
 
 
+def vitstr_targets(system, labels) -> Tensor:
+    """base.py:196-198 (forward_logits_loss): tokenizer.encode(labels)[:, 1:] on the host, T = longest label + 1 positions (<eos>
+    included).  A label longer than max_label_length is refused — the reference's head has max_label_length + 1 positions and its
+    cross-entropy fails on the shape mismatch."""
+    if not labels:
+        raise ValueError('an empty batch')
+    targets = system.tokenizer.encode(labels, None)[:, 1:]
+    if targets.shape[1] - 1 > system.max_label_length:
+        raise ValueError(f'a label of {targets.shape[1] - 1} characters exceeds max_label_length={system.max_label_length}')
+    return targets
+
+
+def _vitstr_loss_and_grads(system, images: Tensor, labels, flat: Optional[Tensor] = None) -> DecoderBackward:
+    """ViTSTR's training step (vitstr/system.py:75-79 -> base.py:194-204): the training encoder's forward (class token + 128 patch
+    tokens: the key-streaming attention of 129 tokens), `parseq_train_vitstr_head` (head on token rows 1 .. T, cross-entropy with
+    ignore_index = <pad>, gradient of head.* and of `memory`), the encoder's backward.  No dropout: timm's default rates are 0."""
+    targets = vitstr_targets(system, labels)                         # before any device work
+    lib = _native.lib()
+    model = system.model
+    images = model._check_images(images)
+    if images.dtype != torch.float32:
+        images = ((images.float() / 255.0) - 0.5) / 0.5 if images.dtype == torch.uint8 else images.float()
+    dev = images.device
+    B, T = targets.shape
+    if B != images.shape[0]:
+        raise ValueError(f'{len(labels)} labels for {images.shape[0]} images')
+    total = int((targets != system.pad_id).sum())
+    tgt_dev = targets.to(torch.int32).contiguous().to(dev)
+    native = model._sync_native().model
+    _set_train_precision(system, native)
+    n_tok = model.pos_embed.shape[1]
+    ws_bytes = lib.parseq_train_encoder_workspace_bytes(native, B)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    memory = torch.empty(B, n_tok, model._cfg['embed_dim'], dtype=torch.float32, device=dev)
+    stream = _native.stream_ptr(images)
+    _native.check(lib.parseq_train_encoder_forward(native, _native.ptr(images), B, _native.ptr(memory), _native.ptr(ws), ws_bytes, stream))
+    if flat is None:
+        flat = torch.zeros(lib.parseq_model_grad_elems(native), dtype=torch.float32, device=dev)
+    else:
+        flat.zero_()
+    dmemory = torch.empty_like(memory)
+    head_bytes = lib.parseq_train_vitstr_head_workspace_bytes(native, B, T)
+    head_ws = torch.empty(head_bytes // 4, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    _native.check(lib.parseq_train_vitstr_head(native, _native.ptr(memory), _native.ptr(tgt_dev), B, T, total, _native.ptr(loss), _native.ptr(flat),
+                                               _native.ptr(dmemory), _native.ptr(head_ws), head_bytes, stream))
+    _native.check(lib.parseq_train_encoder_backward(native, _native.ptr(dmemory), B, _native.ptr(flat), _native.ptr(ws), ws_bytes, stream))
+    shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
+    return DecoderBackward(loss=loss[0], perm_losses=loss[:0], grads=param_views(native, flat, shapes), flat=flat, dmemory=dmemory,
+                           perms=None, workspace=head_ws, memory=memory, _shape=(B, T, 0), _model=native)
+
+
 def loss_and_grads(system, images: Tensor, labels, perms: Optional[Tensor] = None, dropout: Optional[float] = None,
                    seed: Optional[int] = None, inputs: Optional[_DecoderInputs] = None, flat: Optional[Tensor] = None) -> DecoderBackward:
     """Loss and the gradient of EVERY parameter for one batch — the state `loss.backward()` leaves after the reference's
     `training_step` (system.py:168-199), dropout off.  `images`: fp32 [B, 3, H, W] on the device, normalised.  Everything is enqueued on
-    the CURRENT stream (`inputs`: prepared ahead by the caller — loss_and_grads_micro)."""
+    the CURRENT stream (`inputs`: prepared ahead by the caller — loss_and_grads_micro).  A ViTSTR system takes its own step
+    (_vitstr_loss_and_grads: no permutations, no dropout)."""
+    if is_vitstr(system):
+        if perms is not None or inputs is not None or dropout:
+            raise ValueError('ViTSTR has no permutations, decoder inputs or dropout')
+        return _vitstr_loss_and_grads(system, images, labels, flat)
     check_trainable(system)
     lib = _native.lib()
     model = system.model
@@ -314,6 +379,8 @@ class TrainStep:
                  num_devices: Optional[int] = None, accumulate_grad_batches: int = 1, process_group=None, micro_batches: Optional[int] = None):
         import math
         check_trainable(system)
+        if is_vitstr(system) and micro_batches is not None and micro_batches > 1:
+            raise ValueError(f'micro_batches={micro_batches}: the ViTSTR training step runs in one piece')
         self.system = system
         self.total_steps = total_steps
         if num_devices is None:       # base.py:99 uses trainer.num_devices: default to the data-parallel world this step averages over
@@ -370,6 +437,8 @@ class TrainStep:
         system, model = self.system, self.system.model
         distributed = self.process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized())
         parts = self._parts(images.shape[0], distributed)
+        if parts > 1 and is_vitstr(system):
+            raise ValueError(f'{parts} micro-batches: the ViTSTR training step runs in one piece')
         if parts > 1:
             if self._micro_streams is None or len(self._micro_streams) != parts - 1:
                 self._micro_streams = [torch.cuda.Stream(device=system.device) for _ in range(parts - 1)]
@@ -413,7 +482,7 @@ class _TrainingStepFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, system, images, labels, perms, *params):
-        res = loss_and_grads(system, images, labels, perms)
+        res = loss_and_grads(system, images, labels, perms)      # (ViTSTR: perms is None)
         ctx.grads = [res.grads[k] for k, _ in system.model.named_parameters()]
         return res.loss.clone()
 
@@ -428,7 +497,8 @@ class _TrainingStepFunction(torch.autograd.Function):
 
 
 def training_step_loss(system, images: Tensor, labels, perms: Optional[Tensor] = None) -> Tensor:
-    """The loss of `PARSeq.training_step` (system.py:168-199) as a differentiable scalar w.r.t. every parameter of the model."""
+    """The loss of `PARSeq.training_step` (system.py:168-199) — or of `ViTSTR.training_step` (vitstr/system.py:75-79) — as a
+    differentiable scalar w.r.t. every parameter of the model."""
     check_trainable(system)
     names = [k for k, _ in system.model.named_parameters()]
     if names != list(system.model.state_dict().keys()):

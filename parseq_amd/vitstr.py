@@ -91,7 +91,7 @@ class Model(_NativeBacked):
 
 
 class ViTSTR(nn.Module):
-    """strhub/models/vitstr/system.py:33-82 without the Lightning training glue (out of scope, row N3)."""
+    """strhub/models/vitstr/system.py:33-82 without the Lightning glue; `training_step` runs the library's training step."""
 
     def __init__(self, charset_train: str, charset_test: str, max_label_length: int, batch_size: int, lr: float,
                  warmup_pct: float, weight_decay: float, img_size: Sequence[int], patch_size: Sequence[int], embed_dim: int,
@@ -139,6 +139,16 @@ class ViTSTR(nn.Module):
 
     def forward_logits_loss(self, images: Tensor, labels):
         return forward_logits_loss(self, images, labels)
+
+    def training_step(self, batch, batch_idx):
+        """system.py:75-79: `forward_logits_loss(images, labels)[1]` as ONE autograd node whose backward deposits the gradient of every
+        parameter (forward and backward run fused on the device, parseq_amd/train.py; fp32 or `train_precision = 'bf16'`).  Under
+        `torch.no_grad()`: the forward-only loss through the inference kernels."""
+        images, labels = batch
+        if torch.is_grad_enabled():
+            from .train import training_step_loss
+            return training_step_loss(self, images, labels)
+        return self.forward_logits_loss(images, labels)[1]
 
     def validation_step(self, batch, batch_idx):
         return self._eval_step(batch, True)
