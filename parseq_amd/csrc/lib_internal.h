@@ -287,8 +287,6 @@ struct parseq_plan {
     bool fused_step = getenv("PARSEQ_NO_FUSED_STEP") == nullptr;   // diagnostics: fall back to the per-op AR step
     float* qfold = nullptr;        // [wbar E | cq E | bq2 E | c0 npos] of the split mid kernel (decoder_step.h dec_qfold_kernel), per weight set
     bool qsplit = getenv("PARSEQ_NO_QSPLIT") == nullptr;         // diagnostics: the mid kernel's start half on one workgroup per row tile
-    bool fused_attn = getenv("PARSEQ_NO_FUSED_ATTN") == nullptr;   // diagnostics: qkv panel GEMM + attention + proj GEMM instead of encoder_attn_fused.h
-    bool mlp_resident = getenv("PARSEQ_MLP_RELOAD") == nullptr;    // diagnostics: the fused MLP's first form (x re-read by the epilogue)
     bool fused_blocks = getenv("PARSEQ_NO_FUSED_BLOCKS") == nullptr;   // diagnostics: one launch per branch instead of encoder_blocks.h
     bool fused_x3 = getenv("PARSEQ_NO_FUSED_X3") == nullptr;
          // diagnostics: bf16x3 encoder through the per-op kernels instead of encoder_blocks_x3.h
@@ -377,41 +375,19 @@ static int run_gemm(hipStream_t s, const ALoad& a, const T* W, int ldw, int M, i
 }
 
 // out = epi(LayerNorm(x[M, E]; g, b, eps) W^T): the LayerNorm rides in the GEMM's A-operand loader (gemm.h ALayerNorm).  One
-// exception, now for speed only: bf16x3 products with the 128 x 128 tile configuration (M >= 4096) run the LayerNorm as its own
-// kernel into `scratch` ([M, E] f32) and the GEMM with the row-major loader — or, with -DPQ_X3_LN_STATS=1, a statistics-only pass
-// and the ALayerNormStats loader; both fused forms measured no faster than the separate launch (the split GEMM is bound by its LDS
-// staging pass, which the loader's arithmetic lengthens).  History: this combination used to give wrong values in rows 6, 7 mod 8 of
-// a tile whenever two workgroups shared a compute unit; the cause was in the loader's packed-f32 arithmetic (gemm.h ln_apply4),
-// not in the statistics prologue, and is fixed there — tools/x3_diag2.py is the reproducer, exact and deterministic since.
+// exception, for speed only: bf16x3 products with the 128 x 128 tile configuration (M >= 4096) run the LayerNorm as its own
+// kernel into `scratch` ([M, E] f32) and the GEMM with the row-major loader (the split GEMM is bound by its LDS staging pass, which
+// the loader's arithmetic lengthens).
 template <typename T, int E, typename Epi>
 static int run_ln_gemm(hipStream_t s, const float* x, const float* g, const float* b, float eps, const T* W, int M, int N, const Epi& epi, void* scratch) {
     if constexpr (sizeof(T) == 4) {
         if (g_split && M >= 4096) {
             if (!scratch) return fail(PARSEQ_E_STATE, "run_ln_gemm: no LayerNorm scratch");
-#ifndef PQ_X3_LN_STATS
-#define PQ_X3_LN_STATS 0
-#endif
-            if (PQ_X3_LN_STATS) {       // row statistics only (M x 2 floats); the GEMM's loader normalises from them
-                hipLaunchKernelGGL((ln_stats_kernel<E>), dim3((M + 3) / 4), dim3(256), 0, s, x, reinterpret_cast<float*>(scratch), M, eps);
-                HIPCHK(hipGetLastError());
-                return run_gemm<T>(s, ALayerNormStats<T, E>{x, g, b, reinterpret_cast<const float*>(scratch)}, W, E, M, N, E, epi);
-            }
             CHK((run_layernorm<float>(s, x, g, b, reinterpret_cast<float*>(scratch), nullptr, M, E, eps)));
             return run_gemm<T>(s, ARowMajor<T>{reinterpret_cast<const T*>(scratch), E}, W, E, M, N, E, epi);
         }
     }
     return run_gemm<T>(s, ALayerNorm<T, E>{x, g, b, eps, 0, nullptr}, W, E, M, N, E, epi);
-}
-
-// run_ln_gemm with the embedding width chosen at run time (the encoder's per-op path)
-template <typename T, typename Epi>
-static int run_ln_gemm_e(hipStream_t s, int E, const float* x, const float* g, const float* b, float eps, const T* W, int M, int N, const Epi& epi, void* scratch) {
-    switch (E) {
-        case 192: return run_ln_gemm<T, 192>(s, x, g, b, eps, W, M, N, epi, scratch);
-        case 384: return run_ln_gemm<T, 384>(s, x, g, b, eps, W, M, N, epi, scratch);
-        case 768: return run_ln_gemm<T, 768>(s, x, g, b, eps, W, M, N, epi, scratch);
-        default: return fail(PARSEQ_E_INVALID, "LayerNorm-fused GEMM: E=%d not in {192, 384, 768}", E);
-    }
 }
 
 static EpiBase epi_base(int M, int N, const float* bias) { EpiBase b; b.M = M; b.N = N; b.bias = bias; return b; }

@@ -23,11 +23,8 @@ struct TrainCtx {
 };
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// split-K: how many workgroups a product with few output tiles is cut into along the contraction (PARSEQ_TRAIN_SPLIT_TARGET overrides, for A/B)
-static int split_target() {
-    static const int t = [] { const char* e = getenv("PARSEQ_TRAIN_SPLIT_TARGET"); const int v = e ? atoi(e) : 0; return v >= 64 ? v : 512; }();
-    return t;
-}
+// split-K: how many workgroups a product with few output tiles is cut into along the contraction
+constexpr int SPLIT_TARGET = 512;
 
 // asum (optional): [M] += row sums of A over k, folded into the product when it takes the bf16 matrix-core kernel; returns through
 // *asum_done whether it did (the caller runs the column-sum kernel otherwise)
@@ -65,7 +62,7 @@ static int sgemm(const TrainCtx& cx, const float* A, long sam, long sak, const f
             return fail(PARSEQ_E_INVALID, "sgemm: shadow operands of a %d x %d x %d product are not laid out for the matrix-core kernels", M, N, K);
         int splits = 1;
         if (tiles < 256) {      // the same split as the fp32-in-memory path takes (32-deep stages), so that the two stay bit-identical
-            splits = std::min((split_target() + tiles - 1) / tiles, K / (4 * BG_BK));
+            splits = std::min((SPLIT_TARGET + tiles - 1) / tiles, K / (4 * BG_BK));
             splits = (int)std::min<size_t>((size_t)std::max(splits, 1), cx.scratch_floats / ((size_t)M * N + (size_t)M));
             splits = std::max(splits, 1);
         }
@@ -78,8 +75,7 @@ static int sgemm(const TrainCtx& cx, const float* A, long sam, long sak, const f
         void (*kern)(const SgemmArgs, int, float*, int, int);
         // whole 128 x 128 tiles (every product of the PARSeq-S / ViTSTR encoders): the four-workgroups-per-CU forms (train_ops.h); the buffer
         // loads' 32-bit byte offsets cover both operands with room to spare at any batch that fits the workspace
-        static const bool no_w4 = getenv("PARSEQ_TRAIN_GEMM_W3") != nullptr;
-        const bool whole = M % MG_BM == 0 && N % MG_BN == 0 && !no_w4 &&
+        const bool whole = M % MG_BM == 0 && N % MG_BN == 0 &&
                            (size_t)M * (size_t)std::max(sam, sak) < ((size_t)1 << 29) && (size_t)N * (size_t)std::max(sbn, sbk) < ((size_t)1 << 29) &&
                            (size_t)K * (size_t)std::max(sak, sbk) < ((size_t)1 << 29);
         if (both) kern = whole ? mfma_bgemm16_kernel<true> : mfma_bgemm16_kernel<false>;
@@ -110,7 +106,7 @@ static int sgemm(const TrainCtx& cx, const float* A, long sam, long sak, const f
         const int tiles = gm_ * gn_;
         int splits = 1;
         if (tiles < 256) {
-            splits = std::min((split_target() + tiles - 1) / tiles, K / (4 * bk));
+            splits = std::min((SPLIT_TARGET + tiles - 1) / tiles, K / (4 * bk));
             splits = (int)std::min<size_t>((size_t)std::max(splits, 1), cx.scratch_floats / ((size_t)M * N + (size_t)M));      // + the row-sum slots
             splits = std::max(splits, 1);
         }
@@ -232,11 +228,6 @@ static int lin_bwd16_dx(const TrainCtx& cx, const bf16_t* Wt16, const float* dy,
     return sgemm(cx, dy16 ? reinterpret_cast<const float*>(dy16) : dy, N, 1, reinterpret_cast<const float*>(Wt16), 1, N, nullptr, nullptr, 0, 0, dx, K, M, K, N,
                  1.f, false, nullptr, nullptr, dx_gelu_pre, nullptr, &ex);
 }
-static int lin_bwd16(const TrainCtx& cx, const bf16_t* x16, const bf16_t* Wt16, const float* dy, const bf16_t* dy16, float* dW, float* db, float* dx,
-                     bf16_t* dx16, int M, int N, int K, const float* dx_gelu_pre = nullptr, const bf16_t* dx_gelu_pre16 = nullptr) {
-    CHK(lin_bwd16_dw(cx, x16, dy, dy16, dW, db, M, N, K));
-    return lin_bwd16_dx(cx, Wt16, dy, dy16, dx, dx16, M, N, K, dx_gelu_pre, dx_gelu_pre16);
-}
 // dx = add + LayerNorm backward; dgamma += column sums of dy * xhat; dbeta += column sums of dy.  `tmp` is [rows, E] scratch.
 // dx16 (optional): dx again as bf16, the operand shadow of the dX product that follows.
 static int ln_bwd(const TrainCtx& cx, const float* x, const float* gamma, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta,
@@ -312,7 +303,7 @@ static int train_attn_dec_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int B
     if (a.pass_loop > 1 && !(a.pass_B > 0 && a.kv_shared && B == a.pass_B * a.pass_loop))
         return fail(PARSEQ_E_INVALID, "training attention: pass_loop needs pass_B, shared K / V and a batch of pass_B * pass_loop images");
     const int blocks = (a.pass_loop > 1 ? a.pass_B : B) * a.H;      // pass_loop: one workgroup per (image, head) walks the passes
-    const bool small = a.Lk <= 32 && !getenv("PARSEQ_TRAIN_ATTN_KT8");      // the self-attention: the 32-key instantiation (a quarter of the LDS, a third of the registers)
+    const bool small = a.Lk <= 32;      // the self-attention: the 32-key instantiation (a quarter of the LDS, a third of the registers)
     if (small) {
         if (backward) hipLaunchKernelGGL((train_attn_dec_bf16_kernel<true, 2>), dim3(blocks), dim3(128), train_attn_dec_lds(true, 2), s, a);
         else hipLaunchKernelGGL((train_attn_dec_bf16_kernel<false, 2>), dim3(blocks), dim3(128), train_attn_dec_lds(false, 2), s, a);
@@ -323,11 +314,9 @@ static int train_attn_dec_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int B
     HIPCHK(hipGetLastError());
     return 0;
 }
-// whether a decoder-shaped attention call (forward and backward) runs on train_attn_dec_bf16_kernel
-static bool train_attn_is_dec_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int hd) {
-    return cx.bf16_ops && hd == TD_HD && a.Lq <= TD_Q && a.Lk <= TD_K && a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 &&
-           a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv) && !getenv("PARSEQ_TRAIN_F32_ATTN");
-}
+// the shapes train_attn_dec_bf16_kernel takes (bf16-operand mode, head width 32, <= TD_Q queries, <= TD_K keys); the decoder's workspace
+// layout asks the same question of its cross-attention (train_decoder_layout's ca_loop)
+static bool train_attn_dec_bf16_shape(bool bf16_ops, int hd, int Lq, int Lk) { return bf16_ops && hd == TD_HD && Lq <= TD_Q && Lk <= TD_K; }
 // encoder self-attention past 128 tokens (train_attn_wide.h): head width 64, N in (128, 256], per-image queries, no masks, no dropout,
 // one pass per launch — the shapes no kernel above takes (train_attn_hd<64> holds at most 128 keys)
 static bool train_attn_is_wide(const TrainAttnArgs& a, int hd) {
@@ -350,23 +339,34 @@ static int train_attn_wide(const TrainCtx& cx, const TrainAttnArgs& a, int B, bo
     HIPCHK(hipGetLastError());
     return 0;
 }
+// Which kernel a training attention call runs, first match wins: the two bf16-operand kernels (decoder shapes, the 128-token encoder), the
+// fp32 matrix-core kernel (head width 64, up to 128 keys), the key-streaming kernels past 128 tokens, the VALU kernels; TA_NONE: no kernel
+enum TrainAttnRoute { TA_DEC_BF16, TA_ENC_BF16, TA_MFMA, TA_WIDE, TA_HD32, TA_HD64, TA_NONE };
+static TrainAttnRoute train_attn_route(const TrainCtx& cx, const TrainAttnArgs& a, int hd, bool backward) {
+    const bool rows4 = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv)));
+    if (train_attn_dec_bf16_shape(cx.bf16_ops, hd, a.Lq, a.Lk) && rows4 && a.q_bstride % 4 == 0) return TA_DEC_BF16;
+    if (cx.bf16_ops && hd == TB_HD && a.Lq == TB_N && a.Lk == TB_N && !a.qmask && !a.kmask && !a.drop.thresh && a.q_bstride == (long)a.Lq * a.ldq && rows4)
+        return TA_ENC_BF16;
+    if (hd == 64 && a.Lq % 32 == 0 && a.Lk % 16 == 0 && a.Lk <= 128 && !a.qmask && !a.kmask && !a.drop.thresh) return TA_MFMA;
+    if (train_attn_is_wide(a, hd)) return TA_WIDE;
+    if (hd == 32) return TA_HD32;
+    if (hd == 64) return TA_HD64;
+    return TA_NONE;
+}
 static int train_attn(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward, int hd) {
-    if (cx.bf16_ops && hd == TD_HD && a.Lq <= TD_Q && a.Lk <= TD_K && a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 &&
-        (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv))) && !getenv("PARSEQ_TRAIN_F32_ATTN"))
-        return train_attn_dec_bf16(cx, a, B, backward);
+    const TrainAttnRoute r = train_attn_route(cx, a, hd, backward);
+    if (r == TA_DEC_BF16) return train_attn_dec_bf16(cx, a, B, backward);
     if (a.pass_loop > 1) return fail(PARSEQ_E_INVALID, "training attention: pass_loop is train_attn_dec_bf16_kernel's alone");
     if (a.pass_B && hd != TD_HD) return fail(PARSEQ_E_INVALID, "training attention: several passes per launch only at the decoder's head width");
-    if (cx.bf16_ops && hd == TB_HD && a.Lq == TB_N && a.Lk == TB_N && !a.qmask && !a.kmask && !a.drop.thresh && a.q_bstride == (long)a.Lq * a.ldq &&
-        a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv))) &&
-        !getenv("PARSEQ_TRAIN_F32_ATTN"))
-        return train_attn_bf16(cx, a, B, backward);
+    if (r == TA_ENC_BF16) return train_attn_bf16(cx, a, B, backward);
     if (a.o16 || a.dq16) return fail(PARSEQ_E_INVALID, "training attention: a bf16 output is only written by the encoder-shaped bf16 kernel");
-    if (hd == 64 && a.Lq % 32 == 0 && a.Lk % 16 == 0 && a.Lk <= 128 && !a.qmask && !a.kmask && !a.drop.thresh && !getenv("PARSEQ_TRAIN_VALU_ATTN"))
-        return train_attn_mfma(cx, a, B, backward);
-    if (train_attn_is_wide(a, hd)) return train_attn_wide(cx, a, B, backward);
-    if (hd == 32) return train_attn_hd<32>(cx, a, B, backward);
-    if (hd == 64) return train_attn_hd<64>(cx, a, B, backward);
-    return fail(PARSEQ_E_INVALID, "training attention: head width %d not in {32, 64}", hd);
+    switch (r) {
+        case TA_MFMA: return train_attn_mfma(cx, a, B, backward);
+        case TA_WIDE: return train_attn_wide(cx, a, B, backward);
+        case TA_HD32: return train_attn_hd<32>(cx, a, B, backward);
+        case TA_HD64: return train_attn_hd<64>(cx, a, B, backward);
+        default: return fail(PARSEQ_E_INVALID, "training attention: head width %d not in {32, 64}", hd);
+    }
 }
 
 // The training step's encoder attention on its own (the kernels' unit test): the self-attention of `tokens` tokens, `heads` heads of 64,
@@ -380,8 +380,8 @@ extern "C" int parseq_op_train_attention(const float* qkv, float* o, float* lse,
     a.q = qkv; a.q_bstride = (long)tokens * 3 * E; a.ldq = 3 * E; a.k = qkv + E; a.v = qkv + 2 * E; a.ldkv = 3 * E;
     a.o = o; a.ldo = E; a.d_o = d_o; a.dq = dqkv; a.lddq = 3 * E; a.dk = dqkv ? dqkv + E : nullptr; a.dv = dqkv ? dqkv + 2 * E : nullptr;
     a.lddkv = 3 * E; a.Lq = tokens; a.Lk = tokens; a.H = heads; a.scale = 1.0f / sqrtf((float)TW_HD); a.lse = lse; a.dsum = dsum;
-    if (route) *route = train_attn_is_wide(a, TW_HD) ? 1 : 0;
     const TrainCtx cx{(hipStream_t)stream, nullptr, false, 0};
+    if (route) *route = train_attn_route(cx, a, TW_HD, backward != 0) == TA_WIDE ? 1 : 0;
     return train_attn(cx, a, batch, backward != 0, TW_HD);
 }
 
@@ -416,8 +416,8 @@ static TrainDecoderLayout train_decoder_layout(const parseq_model* m, int B, int
     o.d_kvc = take(MP * 2 * E); o.d_kvm = take(MS * 2 * E);
     // each pass's own d K | d V of the memory, folded into d_kvm after the batch — only where the cross-attention cannot walk the passes itself
     // (train_attn_dec_bf16_kernel's pass_loop: bf16-operand mode, head width 32, <= TD_Q queries, <= TD_K memory tokens)
-    o.ca_loop = o.KP > 1 && m->train_precision == PARSEQ_BF16 && E == (size_t)m->cfg.dec_heads * TD_HD && L <= TD_Q && (int)S <= TD_K && E % 4 == 0 &&
-                !getenv("PARSEQ_TRAIN_F32_ATTN") && !getenv("PARSEQ_TRAIN_NO_PASS_LOOP");
+    o.ca_loop = o.KP > 1 && E == (size_t)m->cfg.dec_heads * TD_HD && train_attn_dec_bf16_shape(m->train_precision == PARSEQ_BF16, TD_HD, L, (int)S) &&
+                E % 4 == 0 && !getenv("PARSEQ_TRAIN_NO_PASS_LOOP");
     o.d_kvm_p = (o.KP > 1 && !o.ca_loop) ? take(P * MS * 2 * E) : o.d_kvm;
     o.d_content = take(M * E); o.d_pq = take(L * E); o.d_qb = take(MP * E);
     o.row_loss = take(MP); o.tgt_all = take((size_t)K * M); o.losses = take(K + 1); o.counts = take(K + 1);
@@ -533,7 +533,7 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     // are staged once per batch instead of once per pass and d K | d V go straight into d_kvm, summed over the passes in the accumulators
     const bool ca_loop = o.ca_loop;      // decided by the layout (which then has no per-pass copies); the kernel's own preconditions must agree
     if (ca_loop) { ca.dk = d_kvm; ca.dv = d_kvm + E; }
-    if (ca_loop && !train_attn_is_dec_bf16(cx, ca, 32)) return fail(PARSEQ_E_STATE, "training decoder: the workspace was laid out for the pass-walking cross-attention, which this call cannot run (alignment or environment changed)");
+    if (ca_loop && train_attn_route(cx, ca, 32, true) != TA_DEC_BF16) return fail(PARSEQ_E_STATE, "training decoder: the workspace was laid out for the pass-walking cross-attention, which this call cannot run (its operands are not aligned for it)");
     enum { S_CONTENT, S_QUERY, S_SA_PROB, S_SA_OUT, S_CA_PROB, S_CA_OUT, S_FF_HIDDEN, S_FF_OUT };      // dropout sites of one pass
 
     for (int i0 = 0; i0 < K; i0 += KP) {
@@ -710,7 +710,7 @@ static int train_ln_fwd(hipStream_t s, const float* x, const float* w, const flo
 static bool train_enc_shadows(const parseq_model* m) {
     const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
     return m->train_precision == PARSEQ_BF16 && E % 64 == 0 && F % 64 == 0 && m->tokens == TB_N && E == m->cfg.enc_heads * TB_HD &&
-           !getenv("PARSEQ_TRAIN_F32_ATTN") && !getenv("PARSEQ_TRAIN_NO_SHADOWS");
+           !getenv("PARSEQ_TRAIN_NO_SHADOWS");
 }
 // Level 2 (the default with shadows on): tensors that exist ONLY to be rounded to bf16 by their consumers or to feed a GELU derivative are
 // stored as bf16 and nothing else — the fc1 pre-activation (its GELU derivative is taken at the bf16 value), the gradient of the fc1
@@ -956,7 +956,8 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
         side = m->train_sides[slot].side;
         side_ev = m->train_sides[slot].ev;
     }
-    const TrainCtx cxs{side, w + o.scratch2, m->train_precision == PARSEQ_BF16, o.scratch_floats};
+    // the context of the bf16 block's weight-gradient products: the side stream and its scratch, or with one stream the main context
+    const TrainCtx cxs = two_streams ? TrainCtx{side, w + o.scratch2, m->train_precision == PARSEQ_BF16, o.scratch_floats} : cx;
     m->grad_events_valid = false;
     if (segs) CHK(grad_event_record(m, 0, s));      // the decoder's gradients were written by parseq_train_decoder, earlier on this stream
     CHK(ln_bwd(cx, w + o.x_last, P("norm.weight"), dmemory, nullptr, d_x, G("norm.weight"), G("norm.bias"), tmp, MS, E, eps, d_x16));
@@ -966,72 +967,51 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
         const std::string p = "blocks." + std::to_string(i) + ".";
         float* x = w + o.x(i); float* qkv = x + o.qkv; float* ao = x + o.ao; float* x_mid = x + o.x_mid; float* hpre = x + o.hpre;
         if (shadows) {
-            const bf16_t* n1 = reinterpret_cast<const bf16_t*>(x + o.n1); const bf16_t* n2 = reinterpret_cast<const bf16_t*>(x + o.n2);
-            const bf16_t* ao16 = reinterpret_cast<const bf16_t*>(ao); const bf16_t* hact16 = reinterpret_cast<const bf16_t*>(x + o.hact_l);
-            if (two_streams) {
-                // The block's four weight-gradient products on the SECOND stream, beside the chain dX -> LayerNorm / attention backward -> dX that
-                // needs them for nothing: each starts when its dY exists (an event of the main stream) and is waited for only where the main
-                // stream is about to overwrite that dY (the residual-stream gradient's shadow d_x16) or closes the block.  Same kernels, same
-                // operands, same order inside every buffer: bit-identical to the one-stream schedule (PARSEQ_TRAIN_ONE_STREAM=1).
-                // (an error return inside the block must not leave weight-gradient kernels running on the hidden stream behind the caller's back:
-                // the block is a lambda and a failure joins the side stream before it is reported)
-                auto block = [&]() -> int {
-                hipEvent_t* ev = side_ev;
-                const bf16_t* hpre16 = reinterpret_cast<const bf16_t*>(hpre);
-                bf16_t* dqkv16 = reinterpret_cast<bf16_t*>(dqkv);
-                HIPCHK(hipEventRecord(ev[0], s)); HIPCHK(hipStreamWaitEvent(side, ev[0], 0));                    // d_x16 of this block exists
-                CHK(lin_bwd16_dw(cxs, hact16, nullptr, d_x16, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), MS, E, F));
-                HIPCHK(hipEventRecord(ev[4], side));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 3, E, F).wt, nullptr, d_x16, nullptr, d_h16, MS, E, F, nullptr, hpre16));
-                HIPCHK(hipEventRecord(ev[1], s)); HIPCHK(hipStreamWaitEvent(side, ev[1], 0));                    // d_h16 exists
-                CHK(lin_bwd16_dw(cxs, n2, nullptr, d_h16, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), MS, F, E));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 2, E, F).wt, nullptr, d_h16, d_a, nullptr, MS, F, E));
-                HIPCHK(hipStreamWaitEvent(s, ev[4], 0));                                                          // fc2's dW has read d_x16
+            // The block's four weight-gradient products run on the side context, beside the chain dX -> LayerNorm / attention backward -> dX that
+            // needs them for nothing.  With two streams each starts when its dY exists (an event of the main stream) and is waited for only where
+            // the main stream is about to overwrite that dY (the residual-stream gradient's shadow d_x16) or closes the block; with one stream
+            // (PARSEQ_TRAIN_ONE_STREAM=1, and always at level 1) the side context is the main one and the events are skipped.  Same kernels, same
+            // operands, same order inside every buffer either way: bit-identical.  The level decides only which gradients also exist in fp32
+            // (level 1) and which exist as bf16 only (level 2: the fc1 pre-activation, d q | k | v, and d_x as the dY of the dW products).
+            // (an error return inside the block must not leave weight-gradient kernels running on the side stream behind the caller's back:
+            // the block is a lambda and a failure joins the side stream before it is reported)
+            auto block = [&]() -> int {
+                const bf16_t* n1 = reinterpret_cast<const bf16_t*>(x + o.n1); const bf16_t* n2 = reinterpret_cast<const bf16_t*>(x + o.n2);
+                const bf16_t* ao16 = reinterpret_cast<const bf16_t*>(ao); const bf16_t* hact16 = reinterpret_cast<const bf16_t*>(x + o.hact_l);
+                const float* d_x32 = only16 ? nullptr : d_x; float* d_h32 = only16 ? nullptr : d_h; const float* dqkv32 = only16 ? nullptr : dqkv;
+                const float* hpre32 = only16 ? nullptr : hpre; const bf16_t* hpre16 = only16 ? reinterpret_cast<const bf16_t*>(hpre) : nullptr;
+                bf16_t* dqkv16 = only16 ? reinterpret_cast<bf16_t*>(dqkv) : nullptr;
+                auto fork = [&](int e) -> int { if (two_streams) { HIPCHK(hipEventRecord(side_ev[e], s)); HIPCHK(hipStreamWaitEvent(side, side_ev[e], 0)); } return 0; };
+                auto mark = [&](int e) -> int { if (two_streams) HIPCHK(hipEventRecord(side_ev[e], side)); return 0; };
+                auto join = [&](int e) -> int { if (two_streams) HIPCHK(hipStreamWaitEvent(s, side_ev[e], 0)); return 0; };
+                CHK(fork(0));                                                                                       // d_x16 of this block exists
+                CHK(lin_bwd16_dw(cxs, hact16, d_x32, d_x16, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), MS, E, F));
+                CHK(mark(4));
+                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 3, E, F).wt, d_x32, d_x16, d_h32, d_h16, MS, E, F, hpre32, hpre16));
+                CHK(fork(1));                                                                                       // d_h16 exists
+                CHK(lin_bwd16_dw(cxs, n2, d_h32, d_h16, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), MS, F, E));
+                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 2, E, F).wt, d_h32, d_h16, d_a, nullptr, MS, F, E));
+                CHK(join(4));                                                                                       // fc2's dW has read d_x16
                 CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), tmp, MS, E, eps, d_x16));
-                HIPCHK(hipEventRecord(ev[2], s)); HIPCHK(hipStreamWaitEvent(side, ev[2], 0));                    // the new d_x16 exists
-                CHK(lin_bwd16_dw(cxs, ao16, nullptr, d_x16, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), MS, E, E));
-                HIPCHK(hipEventRecord(ev[5], side));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 1, E, F).wt, nullptr, d_x16, d_a, nullptr, MS, E, E));
+                CHK(fork(2));                                                                                       // the new d_x16 exists
+                CHK(lin_bwd16_dw(cxs, ao16, d_x32, d_x16, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), MS, E, E));
+                CHK(mark(5));
+                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 1, E, F).wt, d_x32, d_x16, d_a, nullptr, MS, E, E));
                 TrainAttnArgs ab = enc_attn_args(m, qkv, ao, d_a, dqkv);
-                ab.dq16 = dqkv16; ab.dk16 = dqkv16 + E; ab.dv16 = dqkv16 + 2 * E;
+                if (dqkv16) { ab.dq16 = dqkv16; ab.dk16 = dqkv16 + E; ab.dv16 = dqkv16 + 2 * E; }
                 CHK(train_attn(cx, ab, batch, true, ATT_HD));
-                HIPCHK(hipEventRecord(ev[3], s)); HIPCHK(hipStreamWaitEvent(side, ev[3], 0));                    // dqkv16 exists
-                CHK(lin_bwd16_dw(cxs, n1, nullptr, dqkv16, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), MS, 3 * E, E));
-                HIPCHK(hipEventRecord(ev[6], side));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 0, E, F).wt, nullptr, dqkv16, d_a, nullptr, MS, 3 * E, E));
-                HIPCHK(hipStreamWaitEvent(s, ev[5], 0));                                                          // proj's dW has read d_x16
+                CHK(fork(3));                                                                                       // d q | k | v exists
+                CHK(lin_bwd16_dw(cxs, n1, dqkv32, dqkv16, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), MS, 3 * E, E));
+                CHK(mark(6));
+                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 0, E, F).wt, dqkv32, dqkv16, d_a, nullptr, MS, 3 * E, E));
+                CHK(join(5));                                                                                       // proj's dW has read d_x16
                 CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), tmp, MS, E, eps, d_x16));
-                HIPCHK(hipStreamWaitEvent(s, ev[6], 0));       // the block's gradients are final on the main stream too (the segment event that follows covers them)
-                return 0;
-                };
-                const int rc = block();
-                if (rc) {
-                    (void)hipStreamSynchronize(side);          // whatever was enqueued there has finished with `grads` and the workspace before the caller hears of the failure
-                    return rc;
-                }
-                continue;
+                return join(6);       // the block's gradients are final on the main stream too (the segment event that follows covers them)
+            };
+            if (const int rc = block()) {
+                if (two_streams) (void)hipStreamSynchronize(side);      // whatever was enqueued there has finished with `grads` and the workspace before the caller hears of the failure
+                return rc;
             }
-            if (only16) {
-                CHK(lin_bwd16(cx, hact16, enc_shadow_w(o, w, i, 3, E, F).wt, nullptr, d_x16, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), nullptr, d_h16, MS, E, F,
-                              nullptr, reinterpret_cast<const bf16_t*>(hpre)));
-                CHK(lin_bwd16(cx, n2, enc_shadow_w(o, w, i, 2, E, F).wt, nullptr, d_h16, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), d_a, nullptr, MS, F, E));
-            } else {
-                CHK(lin_bwd16(cx, hact16, enc_shadow_w(o, w, i, 3, E, F).wt, d_x, d_x16, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), d_h, d_h16, MS, E, F, hpre));
-                CHK(lin_bwd16(cx, n2, enc_shadow_w(o, w, i, 2, E, F).wt, d_h, d_h16, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), d_a, nullptr, MS, F, E));
-            }
-            CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), tmp, MS, E, eps, d_x16));
-            CHK(lin_bwd16(cx, ao16, enc_shadow_w(o, w, i, 1, E, F).wt, only16 ? nullptr : d_x, d_x16, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), d_a, nullptr, MS, E, E));
-            if (only16) {
-                TrainAttnArgs ab = enc_attn_args(m, qkv, ao, d_a, dqkv);
-                bf16_t* dqkv16 = reinterpret_cast<bf16_t*>(dqkv);
-                ab.dq16 = dqkv16; ab.dk16 = dqkv16 + E; ab.dv16 = dqkv16 + 2 * E;
-                CHK(train_attn(cx, ab, batch, true, ATT_HD));
-                CHK(lin_bwd16(cx, n1, enc_shadow_w(o, w, i, 0, E, F).wt, nullptr, dqkv16, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), d_a, nullptr, MS, 3 * E, E));
-            } else {
-                CHK(train_attn(cx, enc_attn_args(m, qkv, ao, d_a, dqkv), batch, true, ATT_HD));
-                CHK(lin_bwd16(cx, n1, enc_shadow_w(o, w, i, 0, E, F).wt, dqkv, nullptr, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), d_a, nullptr, MS, 3 * E, E));
-            }
-            CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), tmp, MS, E, eps, d_x16));
             continue;
         }
         // x_out = x_mid + fc2(gelu(fc1(norm2(x_mid))))        d_x = d x_out
