@@ -23,115 +23,124 @@ struct TrainCtx {
 };
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-// split-K: how many workgroups a product with few output tiles is cut into along the contraction
-constexpr int SPLIT_TARGET = 512;
+constexpr int SPLIT_TARGET = 512;      // split-K: how many workgroups a product with few output tiles is cut into along the contraction
 
-// asum (optional): [M] += row sums of A over k, folded into the product when it takes the bf16 matrix-core kernel; returns through
-// *asum_done whether it did (the caller runs the column-sum kernel otherwise)
-// bf16 shadow operands and outputs of a product (train_ops.h SgemmArgs a16 / b16 / c16 / gelu_out16): only on the matrix-core kernels of
-// the bf16-operand mode; a product that asks for them and cannot take those kernels is an error, never a silent fp32 read of bf16 data
-struct GemmExt {
-    bool a16 = false, b16 = false;
-    bf16_t* c16 = nullptr;
-    bf16_t* gelu_out16 = nullptr;
-    const bf16_t* gelu_pre16 = nullptr;
+// A product C[M, N] = A B is described by its parts, each of which carries its element type:
+// Operand: where an input matrix lives, its stride along the product's outer axis (m for A, n for B) and along the contraction, both in
+// ELEMENTS of its own type, and whether that type is fp32 or bf16 — constructible from a typed pointer only, so bf16 bytes cannot reach a
+// loader of floats by a cast at a call site.  bf16 operands are the SHADOWS of the bf16-operand mode (train_ops.h SgemmArgs a16 / b16).
+struct Operand {
+    const void* p; long so, sk; bool bf16;
+    Operand(const float* q, long outer, long k) : p(q), so(outer), sk(k), bf16(false) {}
+    Operand(const bf16_t* q, long outer, long k) : p(q), so(outer), sk(k), bf16(true) {}
 };
-static int sgemm(const TrainCtx& cx, const float* A, long sam, long sak, const float* B, long sbk, long sbn, const float* bias, const float* R,
-                 long ldr, int rper, float* C, long ldc, int M, int N, int K, float alpha, bool accumulate, float* asum = nullptr, bool* asum_done = nullptr,
-                 const float* gelu_pre = nullptr, float* gelu_out = nullptr,      // gelu_pre / gelu_out: same contract as asum (folded on the bf16 matrix-core kernel, reported through asum_done)
-                 const GemmExt* ext = nullptr) {
+// An [M, N] tensor the epilogue writes (Out) or reads (In), dense rows: as fp32, as bf16, or both
+template <typename F, typename H>
+struct Dual {
+    F* f32 = nullptr; H* b16 = nullptr;
+    Dual() = default;
+    Dual(F* p) : f32(p) {}
+    Dual(H* q) : b16(q) {}
+    Dual(F* p, H* q) : f32(p), b16(q) {}
+    explicit operator bool() const { return f32 || b16; }
+};
+using Out = Dual<float, bf16_t>;
+using In = Dual<const float, const bf16_t>;
+// The optional parts of a product: C (+)= alpha * A B + bias + R[m % rper], and what may ride on its epilogue
+struct GemmOpts {
+    const float* bias = nullptr;                          // [N]
+    const float* R = nullptr; long ldr = 0; int rper = 0; // residual rows
+    float alpha = 1.f; bool accumulate = false;
+    float* asum = nullptr;       // [M] += row sums of A over k (the bias gradient riding on a dW product)
+    In gelu_pre;                 // C is multiplied by gelu'(gelu_pre) (the GELU backward riding on a dX product)
+    Out gelu_out;                // gelu(C) as a second output
+};
+// Which of the optional epilogues the kernel sgemm chose has folded into the product; the caller launches the others itself
+struct GemmFolded { bool asum = false, gelu_pre = false, gelu_out = false; };
+
+// The matrix-core loaders read 16-byte pieces along the contraction (4 floats, 8 bf16) or, of an operand contiguous along its outer axis
+// (`outer` = M or N elements), whole groups of four
+static bool mc_readable(const Operand& x, int outer) {
+    return aligned16(x.p) && (x.sk == 1 ? x.so % (x.bf16 ? 8 : 4) == 0 : (x.so == 1 && x.sk % 4 == 0 && outer % 4 == 0));
+}
+// split-K: a product with few output tiles is cut along the contraction into `splits` workgroups per tile, k_chunk (whole stages of bk) each.
+// The 64-deep kernels of the bf16 shadows split as the 32-deep ones do: a product takes the same split whatever its operands are stored
+// as, which keeps the shadow path bit-identical to the fp32-in-memory one.
+struct GemmPlan { int gm, gn, tiles, bk, splits, k_chunk; };
+static GemmPlan gemm_plan(int M, int N, int K, int bk, size_t scratch_floats) {
+    GemmPlan p; p.gm = (M + MG_BM - 1) / MG_BM; p.gn = (N + MG_BN - 1) / MG_BN; p.tiles = p.gm * p.gn; p.bk = bk;
+    int splits = 1;
+    if (p.tiles < 256) {
+        splits = std::min((SPLIT_TARGET + p.tiles - 1) / p.tiles, K / (4 * std::min(bk, BG_BK)));
+        splits = (int)std::min<size_t>((size_t)std::max(splits, 1), scratch_floats / ((size_t)M * N + (size_t)M));      // + the row-sum slots
+        splits = std::max(splits, 1);
+    }
+    p.k_chunk = ((K + splits - 1) / splits + bk - 1) / bk * bk;
+    p.splits = (K + p.k_chunk - 1) / p.k_chunk;
+    return p;
+}
+// The matrix-core kernel of the bf16-operand mode for a product's operand types and contiguous axes (akf / bkf: contiguous along the
+// contraction); all of them take a one-dimensional tile index (they order the tiles XCD-aware) and the split in grid z.
+// whole: the four-workgroups-per-CU forms of the all-bf16 kernels; deep_t: both operands bf16, outer-contiguous, whole 64-deep stages
+using BgemmKernel = void (*)(const SgemmArgs, int, float*, int, int);
+static BgemmKernel bgemm_kernel(bool a16, bool b16, bool akf, bool bkf, bool whole, bool deep_t) {
+    if (a16 && akf) return whole ? mfma_bgemm16_kernel<true> : mfma_bgemm16_kernel<false>;
+    if (a16 && deep_t) return whole ? mfma_bgemm16t_kernel<true> : mfma_bgemm16t_kernel<false>;
+    if (a16) return mfma_bgemm_kernel<false, false, true, true>;
+    if (b16) return akf ? (bkf ? mfma_bgemm_kernel<true, true, true> : mfma_bgemm_kernel<true, false, true>)
+                        : (bkf ? mfma_bgemm_kernel<false, true, true> : mfma_bgemm_kernel<false, false, true>);
+    return akf ? (bkf ? mfma_bgemm_kernel<true, true> : mfma_bgemm_kernel<true, false>)
+               : (bkf ? mfma_bgemm_kernel<false, true> : mfma_bgemm_kernel<false, false>);
+}
+// Three routes, first match wins.  The bf16-operand mode's matrix-core kernels: edge tiles allowed (the 95-class head, the 96-wide patch
+// rows), every optional epilogue folded; a product with a bf16 part MUST take them — one that cannot is an error, never a silent fp32
+// read of bf16 data.  The fp32 matrix-core kernel: whole 128 x 128 tiles and 16-deep stages.  The VALU kernel: everything else.
+static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const Out& C, int M, int N, int K, const GemmOpts& o = GemmOpts(),
+                 GemmFolded* folded = nullptr) {
     hipStream_t s = cx.s;
     if (M <= 0 || N <= 0 || K <= 0) return fail(PARSEQ_E_INVALID, "sgemm: bad shape %d x %d x %d", M, N, K);
-    SgemmArgs a{A, sam, sak, B, sbk, sbn, bias, R, ldr, rper > 0 ? rper : 1, C, ldc, M, N, K, alpha, accumulate ? 1 : 0, nullptr, nullptr, nullptr};
-    if (asum_done) *asum_done = false;
-    if (ext && (ext->a16 || ext->b16 || ext->c16 || ext->gelu_out16 || ext->gelu_pre16)) {
-        if (!cx.bf16_ops || !cx.scratch || M < 16 || N < 16) return fail(PARSEQ_E_STATE, "sgemm: bf16 shadow operands outside the bf16-operand mode");
-        if (!C && !ext->c16) return fail(PARSEQ_E_INVALID, "sgemm: no output");
-        a.a16 = ext->a16; a.b16 = ext->b16; a.c16 = ext->c16; a.gelu_out16 = ext->gelu_out16; a.gelu_pre16 = ext->gelu_pre16;
-        const int gm_ = (M + MG_BM - 1) / MG_BM, gn_ = (N + MG_BN - 1) / MG_BN, tiles = gm_ * gn_;
-        const bool both = ext->a16 && ext->b16 && sak == 1 && sbk == 1;       // the 64-deep kernel
-        const bool both_t = ext->a16 && ext->b16 && sam == 1 && sbn == 1;     // dW with a bf16 dY: both operands outer-contiguous
-        const bool deep_t = both_t && K % BH_BK == 0;                       // ... at 64 rows of the contraction per stage
-        const int bk = (both || deep_t) ? BH_BK : BG_BK;
-        // alignment of the 16-byte (k-contiguous) / 8-byte (outer-contiguous) pieces the loaders read
-        const bool a_ok16 = !ext->a16 ? (aligned16(A) && (sak == 1 ? sam % 4 == 0 : (sam == 1 && sak % 4 == 0 && M % 4 == 0)))
-                                      : (aligned16(A) && (both ? sam % 8 == 0 : (both_t && sak % 4 == 0 && M % 4 == 0)));
-        const bool b_ok16 = !ext->b16 ? (aligned16(B) && (sbk == 1 ? sbn % 4 == 0 : (sbn == 1 && sbk % 4 == 0 && N % 4 == 0)))
-                                      : (aligned16(B) && (sbk == 1 ? sbn % 8 == 0 : (sbn == 1 && sbk % 4 == 0 && N % 4 == 0)));
-        if (!a_ok16 || !b_ok16 || K % bk != 0 || (ext->a16 && !both && !both_t))
-            return fail(PARSEQ_E_INVALID, "sgemm: shadow operands of a %d x %d x %d product are not laid out for the matrix-core kernels", M, N, K);
-        int splits = 1;
-        if (tiles < 256) {      // the same split as the fp32-in-memory path takes (32-deep stages), so that the two stay bit-identical
-            splits = std::min((SPLIT_TARGET + tiles - 1) / tiles, K / (4 * BG_BK));
-            splits = (int)std::min<size_t>((size_t)std::max(splits, 1), cx.scratch_floats / ((size_t)M * N + (size_t)M));
-            splits = std::max(splits, 1);
-        }
-        const int k_chunk = ((K + splits - 1) / splits + bk - 1) / bk * bk;
-        splits = (K + k_chunk - 1) / k_chunk;
-        if (asum) { if (both) return fail(PARSEQ_E_INVALID, "sgemm: row sums of a bf16 shadow"); a.asum = asum; }
-        a.gelu_pre = gelu_pre; a.gelu_out = gelu_out;
-        if (asum_done) *asum_done = true;
-        const dim3 grid_((unsigned)tiles, 1, splits);
-        void (*kern)(const SgemmArgs, int, float*, int, int);
-        // whole 128 x 128 tiles (every product of the PARSeq-S / ViTSTR encoders): the four-workgroups-per-CU forms (train_ops.h); the buffer
-        // loads' 32-bit byte offsets cover both operands with room to spare at any batch that fits the workspace
+    const bool shadow = A.bf16 || B.bf16 || C.b16 || o.gelu_out.b16 || o.gelu_pre.b16;
+    if (shadow && (!cx.bf16_ops || !cx.scratch || M < 16 || N < 16)) return fail(PARSEQ_E_STATE, "sgemm: bf16 shadow operands outside the bf16-operand mode");
+    if (!C) return fail(PARSEQ_E_INVALID, "sgemm: no output");
+    const bool akf = A.sk == 1, bkf = B.sk == 1, readable = mc_readable(A, M) && mc_readable(B, N);
+    const bool both = A.bf16 && B.bf16 && akf && bkf;                     // the 64-deep kernel
+    const bool both_t = A.bf16 && B.bf16 && A.so == 1 && B.so == 1;       // dW with a bf16 dY: both operands outer-contiguous
+    const bool deep_t = both_t && K % BH_BK == 0;                         // ... at 64 rows of the contraction per stage
+    const int bk16 = (both || deep_t) ? BH_BK : BG_BK;
+    if (shadow && (!readable || K % bk16 != 0 || (A.bf16 && !both && !both_t)))
+        return fail(PARSEQ_E_INVALID, "sgemm: shadow operands of a %d x %d x %d product are not laid out for the matrix-core kernels", M, N, K);
+    if (shadow && o.asum && both) return fail(PARSEQ_E_INVALID, "sgemm: row sums of a bf16 shadow");
+    const bool bf16 = shadow || (cx.bf16_ops && K % BG_BK == 0 && readable && cx.scratch && M >= 16 && N >= 16);
+    const bool mfma32 = !bf16 && M % MG_BM == 0 && N % MG_BN == 0 && K % MG_BK == 0 && readable && cx.scratch;
+
+    SgemmArgs a{};      // the one place where a typed operand becomes the kernels' pointer + flag
+    a.A = static_cast<const float*>(A.p); a.sam = A.so; a.sak = A.sk; a.a16 = A.bf16;
+    a.B = static_cast<const float*>(B.p); a.sbk = B.sk; a.sbn = B.so; a.b16 = B.bf16;
+    a.bias = o.bias; a.R = o.R; a.ldr = o.ldr; a.rper = o.rper > 0 ? o.rper : 1;
+    a.C = C.f32; a.c16 = C.b16; a.ldc = N; a.M = M; a.N = N; a.K = K; a.alpha = o.alpha; a.accumulate = o.accumulate ? 1 : 0;
+    if (bf16) { a.asum = o.asum; a.gelu_pre = o.gelu_pre.f32; a.gelu_pre16 = o.gelu_pre.b16; a.gelu_out = o.gelu_out.f32; a.gelu_out16 = o.gelu_out.b16; }
+    if (folded) folded->asum = folded->gelu_pre = folded->gelu_out = bf16;
+    if (!bf16 && !mfma32) {
+        hipLaunchKernelGGL(sgemm_kernel, dim3((N + SG_BN - 1) / SG_BN, (M + SG_BM - 1) / SG_BM), dim3(256), 0, s, a);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    const GemmPlan p = gemm_plan(M, N, K, bf16 ? bk16 : MG_BK, cx.scratch_floats);
+    if (bf16) {
+        // whole 128 x 128 tiles (every product of the PARSeq-S / ViTSTR encoders); the buffer loads' 32-bit byte offsets cover both operands
+        // with room to spare at any batch that fits the workspace
         const bool whole = M % MG_BM == 0 && N % MG_BN == 0 &&
-                           (size_t)M * (size_t)std::max(sam, sak) < ((size_t)1 << 29) && (size_t)N * (size_t)std::max(sbn, sbk) < ((size_t)1 << 29) &&
-                           (size_t)K * (size_t)std::max(sak, sbk) < ((size_t)1 << 29);
-        if (both) kern = whole ? mfma_bgemm16_kernel<true> : mfma_bgemm16_kernel<false>;
-        else if (deep_t) kern = whole ? mfma_bgemm16t_kernel<true> : mfma_bgemm16t_kernel<false>;
-        else if (both_t) kern = mfma_bgemm_kernel<false, false, true, true>;
-        else if (ext->b16) kern = sak == 1 ? (sbk == 1 ? mfma_bgemm_kernel<true, true, true> : mfma_bgemm_kernel<true, false, true>)
-                                           : (sbk == 1 ? mfma_bgemm_kernel<false, true, true> : mfma_bgemm_kernel<false, false, true>);
-        else kern = sak == 1 ? (sbk == 1 ? mfma_bgemm_kernel<true, true, false> : mfma_bgemm_kernel<true, false, false>)
-                             : (sbk == 1 ? mfma_bgemm_kernel<false, true, false> : mfma_bgemm_kernel<false, false, false>);
-        hipLaunchKernelGGL(kern, grid_, dim3(256), 0, s, a, k_chunk, cx.scratch, gn_, gm_);
-        HIPCHK(hipGetLastError());
-        if (splits > 1) {
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * N + (a.asum ? (size_t)M : 0) + 255) / 256)), dim3(256), 0, s, a, cx.scratch, splits);
-            HIPCHK(hipGetLastError());
-        }
-        return 0;
+                           (size_t)M * (size_t)std::max(A.so, A.sk) < ((size_t)1 << 29) && (size_t)N * (size_t)std::max(B.so, B.sk) < ((size_t)1 << 29) &&
+                           (size_t)K * (size_t)std::max(A.sk, B.sk) < ((size_t)1 << 29);
+        hipLaunchKernelGGL(bgemm_kernel(A.bf16, B.bf16, akf, bkf, whole, deep_t), dim3((unsigned)p.tiles, 1, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch, p.gn, p.gm);
+    } else {
+        hipLaunchKernelGGL(mfma_sgemm_kernel, dim3(p.gn, p.gm, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch);
     }
-    // matrix-core path: whole 128 x 128 tiles, whole 16-deep stages, 16-byte aligned rows along whichever axis is contiguous
-    const bool a_ok = aligned16(A) && (sak == 1 ? sam % 4 == 0 : (sam == 1 && sak % 4 == 0));
-    const bool b_ok = aligned16(B) && (sbk == 1 ? sbn % 4 == 0 : (sbn == 1 && sbk % 4 == 0));
-    // bf16-operand mode: edge tiles allowed (the 95-class head, the 96-wide patch rows) as long as an outer-contiguous operand has whole
-    // groups of four and at least one of them
-    const bool bf16 = cx.bf16_ops && K % BG_BK == 0 && a_ok && b_ok && cx.scratch && M >= 16 && N >= 16 &&
-                      (sak == 1 || M % 4 == 0) && (sbk == 1 || N % 4 == 0);
-    if (bf16 || (M % MG_BM == 0 && N % MG_BN == 0 && K % MG_BK == 0 && a_ok && b_ok && cx.scratch)) {
-        const int bk = bf16 ? BG_BK : MG_BK;
-        const int gm_ = (M + MG_BM - 1) / MG_BM, gn_ = (N + MG_BN - 1) / MG_BN;
-        const int tiles = gm_ * gn_;
-        int splits = 1;
-        if (tiles < 256) {
-            splits = std::min((SPLIT_TARGET + tiles - 1) / tiles, K / (4 * bk));
-            splits = (int)std::min<size_t>((size_t)std::max(splits, 1), cx.scratch_floats / ((size_t)M * N + (size_t)M));      // + the row-sum slots
-            splits = std::max(splits, 1);
-        }
-        const int k_chunk = ((K + splits - 1) / splits + bk - 1) / bk * bk;
-        splits = (K + k_chunk - 1) / k_chunk;
-        if (bf16) {
-            if (asum) { a.asum = asum; if (asum_done) *asum_done = true; }
-            if (gelu_pre) { a.gelu_pre = gelu_pre; if (asum_done) *asum_done = true; }
-            if (gelu_out) { a.gelu_out = gelu_out; if (asum_done) *asum_done = true; }
-            const dim3 grid_((unsigned)(gn_ * gm_), 1, splits);      // one-dimensional tile index: the kernel orders the tiles XCD-aware
-            if (sak == 1 && sbk == 1) hipLaunchKernelGGL((mfma_bgemm_kernel<true, true>), grid_, dim3(256), 0, s, a, k_chunk, cx.scratch, gn_, gm_);
-            else if (sak == 1) hipLaunchKernelGGL((mfma_bgemm_kernel<true, false>), grid_, dim3(256), 0, s, a, k_chunk, cx.scratch, gn_, gm_);
-            else if (sbk == 1) hipLaunchKernelGGL((mfma_bgemm_kernel<false, true>), grid_, dim3(256), 0, s, a, k_chunk, cx.scratch, gn_, gm_);
-            else hipLaunchKernelGGL((mfma_bgemm_kernel<false, false>), grid_, dim3(256), 0, s, a, k_chunk, cx.scratch, gn_, gm_);
-        } else
-        hipLaunchKernelGGL(mfma_sgemm_kernel, dim3(N / MG_BN, M / MG_BM, splits), dim3(256), 0, s, a, k_chunk, cx.scratch);
-        HIPCHK(hipGetLastError());
-        if (splits > 1) {
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * N + (a.asum ? (size_t)M : 0) + 255) / 256)), dim3(256), 0, s, a, cx.scratch, splits);
-            HIPCHK(hipGetLastError());
-        }
-        return 0;
-    }
-    hipLaunchKernelGGL(sgemm_kernel, dim3((N + SG_BN - 1) / SG_BN, (M + SG_BM - 1) / SG_BM), dim3(256), 0, s, a);
     HIPCHK(hipGetLastError());
+    if (p.splits > 1) {
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * N + (a.asum ? (size_t)M : 0) + 255) / 256)), dim3(256), 0, s, a, cx.scratch, p.splits);
+        HIPCHK(hipGetLastError());
+    }
     return 0;
 }
 static int colsum(const TrainCtx& cx, const float* A, long lda, int M, int N, float* out, bool accumulate) {
@@ -149,16 +158,22 @@ static int colsum(const TrainCtx& cx, const float* A, long lda, int M, int N, fl
     HIPCHK(hipGetLastError());
     return 0;
 }
-// y[M, N] = x[M, K] W[N, K]^T + bias + R[m % rper]
-// gelu_out (optional, [M, N]): gelu(y) as a second output — from the product's epilogue on the bf16 matrix-core kernel, by gelu_fwd_kernel otherwise
-static int lin_fwd(const TrainCtx& cx, const float* x, const float* W, const float* bias, const float* R, int rper, float* y, int M, int N, int K,
-                   float* gelu_out = nullptr) {
-    bool fused = false;
-    CHK(sgemm(cx, x, K, 1, W, 1, K, bias, R, N, rper, y, N, M, N, K, 1.f, false, nullptr, &fused, nullptr, gelu_out));
-    if (gelu_out && !fused) {
-        hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)(((size_t)M * N + 1023) / 1024)), dim3(256), 0, cx.s, y, gelu_out, (size_t)M * N);
+// y[M, N] = x[M, K] W[N, K]^T + bias + R[m % rper], x and W both fp32 or both bf16 shadows (x16 [M, K], W16 [N, K]; y as fp32, bf16 or both)
+// gelu_out (optional, [M, N]): gelu(y) as a second output — from the product's epilogue on the bf16 matrix-core kernels, by gelu_fwd_kernel otherwise
+template <typename T>
+static int lin_fwd(const TrainCtx& cx, const T* x, const T* W, const float* bias, const float* R, int rper, Out y, int M, int N, int K, Out gelu_out = Out()) {
+    GemmOpts g; g.bias = bias; g.R = R; g.ldr = N; g.rper = rper; g.gelu_out = gelu_out;
+    GemmFolded f;
+    CHK(sgemm(cx, Operand(x, K, 1), Operand(W, K, 1), y, M, N, K, g, &f));
+    if (gelu_out && !f.gelu_out) {
+        hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)(((size_t)M * N + 1023) / 1024)), dim3(256), 0, cx.s, y.f32, gelu_out.f32, (size_t)M * N);
         HIPCHK(hipGetLastError());
     }
+    return 0;
+}
+static int gelu_bwd(const TrainCtx& cx, const float* pre, float* d, size_t n) {      // d *= gelu'(pre)
+    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, cx.s, pre, d, d, n);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 // dW[N, K] += dy[M, N]^T x[M, K];  db[N] += column sums of dy;  dx[M, K] = dy W   (dx may be null)
@@ -179,63 +194,49 @@ static int lin_bwd(const TrainCtx& cx, const float* x, const float* W, const flo
         hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)(((size_t)M * Np + 255) / 256)), dim3(256), 0, s, dy, M, N, dyp, M, Np);
         hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)(((size_t)Np * K + 255) / 256)), dim3(256), 0, s, W, N, K, Wp, Np, K);
         HIPCHK(hipGetLastError());
-        CHK(sgemm(c2, dyp, 1, Np, x, K, 1, nullptr, nullptr, 0, 0, dWp, K, Np, K, M, 1.f, false));
+        CHK(sgemm(c2, Operand(dyp, 1, Np), Operand(x, 1, K), dWp, Np, K, M));
         hipLaunchKernelGGL(add_into_kernel, dim3((unsigned)(((size_t)N * K + 255) / 256)), dim3(256), 0, s, dWp, dW, (size_t)N * K);
         HIPCHK(hipGetLastError());
         CHK(colsum(c2, dy, N, M, N, db, true));
-        if (dx) CHK(sgemm(c2, dyp, Np, 1, Wp, K, 1, nullptr, nullptr, 0, 0, dx, K, M, K, Np, 1.f, false));
-        if (dx && dx_gelu_pre) { hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)(((size_t)M * K + 1023) / 1024)), dim3(256), 0, s, dx_gelu_pre, dx, dx, (size_t)M * K); HIPCHK(hipGetLastError()); }
+        if (dx) CHK(sgemm(c2, Operand(dyp, Np, 1), Operand(Wp, 1, K), dx, M, K, Np));
+        if (dx && dx_gelu_pre) CHK(gelu_bwd(cx, dx_gelu_pre, dx, (size_t)M * K));
         return 0;
     }
     // dW += dY^T X; the bias gradient (column sums of dY = row sums of the product's A operand) rides on it in the bf16-operand mode
-    bool db_done = false;
-    CHK(sgemm(cx, dy, 1, N, x, K, 1, nullptr, nullptr, 0, 0, dW, K, N, K, M, 1.f, true, db, &db_done));
-    if (!db_done) CHK(colsum(cx, dy, N, M, N, db, true));
+    GemmOpts gw; gw.accumulate = true; gw.asum = db;
+    GemmFolded f;
+    CHK(sgemm(cx, Operand(dy, 1, N), Operand(x, 1, K), dW, N, K, M, gw, &f));
+    if (!f.asum) CHK(colsum(cx, dy, N, M, N, db, true));
     if (dx) {
-        bool fused = false;
-        CHK(sgemm(cx, dy, N, 1, W, K, 1, nullptr, nullptr, 0, 0, dx, K, M, K, N, 1.f, false, nullptr, &fused, dx_gelu_pre));
-        if (dx_gelu_pre && !fused) {
-            hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)(((size_t)M * K + 1023) / 1024)), dim3(256), 0, cx.s, dx_gelu_pre, dx, dx, (size_t)M * K);
-            HIPCHK(hipGetLastError());
-        }
+        GemmOpts gx; gx.gelu_pre = dx_gelu_pre;
+        CHK(sgemm(cx, Operand(dy, N, 1), Operand(W, 1, K), dx, M, K, N, gx, &f));
+        if (dx_gelu_pre && !f.gelu_pre) CHK(gelu_bwd(cx, dx_gelu_pre, dx, (size_t)M * K));
     }
     return 0;
 }
-// The same three products on bf16 SHADOW operands (encoder, bf16-operand mode; train_ops.h SgemmArgs): x16 [M, K] and the weight shadows W16 [N, K] /
-// Wt16 [K, N] are bfloat16 in memory; dy stays fp32 where it is the A operand of the dW product (the bias gradient is summed from the
-// unrounded values there) and is read through its shadow dy16 (when the producer wrote one) by the dX product; dx16 / gelu_out16: the
-// result again as bf16 for the next product.  Bit-identical to lin_fwd / lin_bwd on the fp32 copies: the rounding moved, nothing else.
-// y may be nullptr when y16 is given (bf16-only storage of the result)
-static int lin_fwd16(const TrainCtx& cx, const bf16_t* x16, const bf16_t* W16, const float* bias, const float* R, int rper, float* y, int M, int N, int K,
-                     bf16_t* gelu_out16 = nullptr, bf16_t* y16 = nullptr) {
-    GemmExt e; e.a16 = e.b16 = true; e.gelu_out16 = gelu_out16; e.c16 = y16;
-    return sgemm(cx, reinterpret_cast<const float*>(x16), K, 1, reinterpret_cast<const float*>(W16), 1, K, bias, R, N, rper, y, N, M, N, K, 1.f, false,
-                 nullptr, nullptr, nullptr, nullptr, &e);
-}
-// dy may be nullptr when dy16 is given (the gradient exists as bf16 only: both products read it, the bias gradient sums the bf16 values);
-// dx may be nullptr when dx16 is given; dx_gelu_pre16: the pre-activation as bf16
+// The two backward products on bf16 SHADOW operands (encoder, bf16-operand mode; train_ops.h SgemmArgs): x16 [M, K] and the transposed weight
+// shadow Wt16 [K, N] are bfloat16 in memory; dy is read as fp32 where it exists (the bias gradient is then summed from the unrounded values) and
+// through its shadow dy16 otherwise — the dX product prefers the shadow; dx16: the result again as bf16 for the next product; dx_gelu_pre16: the
+// pre-activation as bf16.  Bit-identical to lin_bwd on the fp32 copies: the rounding moved, nothing else.
 static int lin_bwd16_dw(const TrainCtx& cx, const bf16_t* x16, const float* dy, const bf16_t* dy16, float* dW, float* db, int M, int N, int K) {
     if (!dy && !dy16) return fail(PARSEQ_E_INVALID, "lin_bwd16: no gradient");
-    GemmExt ew; ew.b16 = true; ew.a16 = dy == nullptr;
-    return sgemm(cx, dy ? dy : reinterpret_cast<const float*>(dy16), 1, N, reinterpret_cast<const float*>(x16), K, 1, nullptr, nullptr, 0, 0, dW, K, N, K, M, 1.f, true,
-                 db, nullptr, nullptr, nullptr, &ew);
+    GemmOpts g; g.accumulate = true; g.asum = db;
+    return sgemm(cx, dy ? Operand(dy, 1, N) : Operand(dy16, 1, N), Operand(x16, 1, K), dW, N, K, M, g);
 }
 static int lin_bwd16_dx(const TrainCtx& cx, const bf16_t* Wt16, const float* dy, const bf16_t* dy16, float* dx, bf16_t* dx16, int M, int N, int K,
-                        const float* dx_gelu_pre = nullptr, const bf16_t* dx_gelu_pre16 = nullptr) {
+                        In dx_gelu_pre = In()) {
     if (!dy && !dy16) return fail(PARSEQ_E_INVALID, "lin_bwd16: no gradient");
     if (!dx && !dx16) return 0;
-    GemmExt ex; ex.b16 = true; ex.a16 = dy16 != nullptr; ex.c16 = dx16; ex.gelu_pre16 = dx_gelu_pre16;
-    return sgemm(cx, dy16 ? reinterpret_cast<const float*>(dy16) : dy, N, 1, reinterpret_cast<const float*>(Wt16), 1, N, nullptr, nullptr, 0, 0, dx, K, M, K, N,
-                 1.f, false, nullptr, nullptr, dx_gelu_pre, nullptr, &ex);
+    GemmOpts g; g.gelu_pre = dx_gelu_pre;
+    return sgemm(cx, dy16 ? Operand(dy16, N, 1) : Operand(dy, N, 1), Operand(Wt16, N, 1), Out(dx, dx16), M, K, N, g);
 }
-// dx = add + LayerNorm backward; dgamma += column sums of dy * xhat; dbeta += column sums of dy.  `tmp` is [rows, E] scratch.
+// dx = add + LayerNorm backward; dgamma += column sums of dy * xhat; dbeta += column sums of dy.
 // dx16 (optional): dx again as bf16, the operand shadow of the dX product that follows.
 static int ln_bwd(const TrainCtx& cx, const float* x, const float* gamma, const float* dy, const float* add, float* dx, float* dgamma, float* dbeta,
-                  float* tmp, int rows, int E, float eps, bf16_t* dx16 = nullptr) {
+                  int rows, int E, float eps, bf16_t* dx16 = nullptr) {
     hipStream_t s = cx.s;
     if (E > 768) return fail(PARSEQ_E_INVALID, "layernorm backward: E=%d > 768", E);
-    // per-chunk partial sums of dy * xhat and dy land in the scratch ([chunks][2E]); two small column sums fold them (`tmp` is no longer used)
-    (void)tmp;
+    // per-chunk partial sums of dy * xhat and dy land in the scratch ([chunks][2E]); two small column sums fold them
     const int chunks = (rows + LNB_ROWS - 1) / LNB_ROWS;
     if (!cx.scratch || (size_t)chunks * 2 * E + (size_t)64 * E > cx.scratch_floats) return fail(PARSEQ_E_INVALID, "layernorm backward: %d rows do not fit the scratch", rows);
     float* part = cx.scratch + (cx.scratch_floats - (size_t)chunks * 2 * E);      // the END of the scratch: colsum's own partials use its start
@@ -255,64 +256,47 @@ static int ln_bwd(const TrainCtx& cx, const float* x, const float* gamma, const 
     HIPCHK(hipGetLastError());
     return 0;
 }
+// One attention launch of B * heads (or fewer) workgroups: the forward or the backward kernel, both allowed `cap_f` / `cap_b` bytes of dynamic
+// LDS once per device (one LdsAttr pair per pair of kernels)
+using AttnKernel = void (*)(const TrainAttnArgs);
+template <AttnKernel FWD, AttnKernel BWD>
+static int attn_launch(const TrainCtx& cx, const TrainAttnArgs& a, bool backward, int blocks, int threads, size_t cap_f, size_t cap_b, size_t lds) {
+    static LdsAttr attr_f, attr_b;
+    HIPCHK(attr_f.ensure(reinterpret_cast<const void*>(FWD), cap_f));
+    HIPCHK(attr_b.ensure(reinterpret_cast<const void*>(BWD), cap_b));
+    hipLaunchKernelGGL(backward ? BWD : FWD, dim3(blocks), dim3(threads), lds, cx.s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 template <int HD>
 static int train_attn_hd(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    hipStream_t s = cx.s;
     const size_t lds = train_attn_lds_floats(a.Lq, a.Lk, HD, backward) * sizeof(float);
     if (lds > 150 * 1024 || (size_t)a.Lk * HD > (size_t)TA_NACC * 256)
         return fail(PARSEQ_E_INVALID, "training attention: %d keys of width %d do not fit (LDS %zu bytes)", a.Lk, HD, lds);
-    static LdsAttr attr_f, attr_b;      // one pair per head width
-    HIPCHK(attr_f.ensure(reinterpret_cast<const void*>(train_attn_kernel<false, HD>), 150 * 1024));
-    HIPCHK(attr_b.ensure(reinterpret_cast<const void*>(train_attn_kernel<true, HD>), 150 * 1024));
-    if (backward) hipLaunchKernelGGL((train_attn_kernel<true, HD>), dim3(B * a.H), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((train_attn_kernel<false, HD>), dim3(B * a.H), dim3(256), lds, s, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return attn_launch<train_attn_kernel<false, HD>, train_attn_kernel<true, HD>>(cx, a, backward, B * a.H, 256, 150 * 1024, 150 * 1024, lds);
 }
 // encoder shape on the matrix cores (train_attn_mfma_kernel): head width 64, whole 32-row query blocks and 16-key tiles, no masks
 static int train_attn_mfma(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    hipStream_t s = cx.s;
     const size_t lds = ((size_t)2 * a.Lk * 65 + (size_t)(backward ? 2 : 1) * 32 * 65 + (size_t)(backward ? 2 : 1) * 32 * (a.Lk + 1)) * sizeof(float);
-    static LdsAttr attr_f, attr_b;
-    HIPCHK(attr_f.ensure(reinterpret_cast<const void*>(train_attn_mfma_kernel<false>), 150 * 1024));
-    HIPCHK(attr_b.ensure(reinterpret_cast<const void*>(train_attn_mfma_kernel<true>), 150 * 1024));
-    if (backward) hipLaunchKernelGGL((train_attn_mfma_kernel<true>), dim3(B * a.H), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((train_attn_mfma_kernel<false>), dim3(B * a.H), dim3(256), lds, s, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return attn_launch<train_attn_mfma_kernel<false>, train_attn_mfma_kernel<true>>(cx, a, backward, B * a.H, 256, 150 * 1024, 150 * 1024, lds);
 }
 // encoder shape in the bf16-operand mode (train_attn_bf16_kernel): 128 tokens, head width 64, per-image queries, no masks, no dropout
 static int train_attn_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    hipStream_t s = cx.s;
-    static LdsAttr attr_f, attr_b;
-    HIPCHK(attr_f.ensure(reinterpret_cast<const void*>(train_attn_bf16_kernel<false>), train_attn_bf16_lds(false)));
-    HIPCHK(attr_b.ensure(reinterpret_cast<const void*>(train_attn_bf16_kernel<true>), train_attn_bf16_lds(true)));
-    if (backward) hipLaunchKernelGGL((train_attn_bf16_kernel<true>), dim3(B * a.H), dim3(256), train_attn_bf16_lds(true), s, a);
-    else hipLaunchKernelGGL((train_attn_bf16_kernel<false>), dim3(B * a.H), dim3(256), train_attn_bf16_lds(false), s, a);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return attn_launch<train_attn_bf16_kernel<false>, train_attn_bf16_kernel<true>>(cx, a, backward, B * a.H, 256, train_attn_bf16_lds(false),
+                                                                                    train_attn_bf16_lds(true), train_attn_bf16_lds(backward));
 }
 // decoder shapes in the bf16-operand mode (train_attn_dec_bf16_kernel): head width 32, <= 32 queries, <= 128 keys, masks, dropout
+template <int KT>
+static int train_attn_dec_bf16_kt(const TrainCtx& cx, const TrainAttnArgs& a, int blocks, bool backward) {
+    return attn_launch<train_attn_dec_bf16_kernel<false, KT>, train_attn_dec_bf16_kernel<true, KT>>(cx, a, backward, blocks, 128, train_attn_dec_lds(false, KT),
+                                                                                                    train_attn_dec_lds(true, KT), train_attn_dec_lds(backward, KT));
+}
 static int train_attn_dec_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    hipStream_t s = cx.s;
-    static LdsAttr attr_f, attr_b, attr_f2, attr_b2;
-    HIPCHK(attr_f.ensure(reinterpret_cast<const void*>(train_attn_dec_bf16_kernel<false, 8>), train_attn_dec_lds(false, 8)));
-    HIPCHK(attr_b.ensure(reinterpret_cast<const void*>(train_attn_dec_bf16_kernel<true, 8>), train_attn_dec_lds(true, 8)));
-    HIPCHK(attr_f2.ensure(reinterpret_cast<const void*>(train_attn_dec_bf16_kernel<false, 2>), train_attn_dec_lds(false, 2)));
-    HIPCHK(attr_b2.ensure(reinterpret_cast<const void*>(train_attn_dec_bf16_kernel<true, 2>), train_attn_dec_lds(true, 2)));
     if (a.pass_loop > 1 && !(a.pass_B > 0 && a.kv_shared && B == a.pass_B * a.pass_loop))
         return fail(PARSEQ_E_INVALID, "training attention: pass_loop needs pass_B, shared K / V and a batch of pass_B * pass_loop images");
     const int blocks = (a.pass_loop > 1 ? a.pass_B : B) * a.H;      // pass_loop: one workgroup per (image, head) walks the passes
-    const bool small = a.Lk <= 32;      // the self-attention: the 32-key instantiation (a quarter of the LDS, a third of the registers)
-    if (small) {
-        if (backward) hipLaunchKernelGGL((train_attn_dec_bf16_kernel<true, 2>), dim3(blocks), dim3(128), train_attn_dec_lds(true, 2), s, a);
-        else hipLaunchKernelGGL((train_attn_dec_bf16_kernel<false, 2>), dim3(blocks), dim3(128), train_attn_dec_lds(false, 2), s, a);
-    } else {
-        if (backward) hipLaunchKernelGGL((train_attn_dec_bf16_kernel<true, 8>), dim3(blocks), dim3(128), train_attn_dec_lds(true, 8), s, a);
-        else hipLaunchKernelGGL((train_attn_dec_bf16_kernel<false, 8>), dim3(blocks), dim3(128), train_attn_dec_lds(false, 8), s, a);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    // up to 128 keys, or for the self-attention the 32-key instantiation (a quarter of the LDS, a third of the registers)
+    return a.Lk > 32 ? train_attn_dec_bf16_kt<8>(cx, a, blocks, backward) : train_attn_dec_bf16_kt<2>(cx, a, blocks, backward);
 }
 // the shapes train_attn_dec_bf16_kernel takes (bf16-operand mode, head width 32, <= TD_Q queries, <= TD_K keys); the decoder's workspace
 // layout asks the same question of its cross-attention (train_decoder_layout's ca_loop)
@@ -580,7 +564,7 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
         hipLaunchKernelGGL(ce_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, tgt, R, C, m->cfg.pad_id, 1.0f / (float)total_targets);
         HIPCHK(hipGetLastError());
         CHK(lin_bwd(cx, out, P("head.weight"), logits, G("head.weight"), G("head.bias"), d_a, R, C, E));                                    // d_a = d out
-        CHK(ln_bwd(cx, t3, P("decoder.norm.weight"), d_a, nullptr, d_b, G("decoder.norm.weight"), G("decoder.norm.bias"), nullptr, R, E, eps));  // d_b = d t3
+        CHK(ln_bwd(cx, t3, P("decoder.norm.weight"), d_a, nullptr, d_b, G("decoder.norm.weight"), G("decoder.norm.bias"), R, E, eps));  // d_b = d t3
         CHK(dropout_add(cx, d_b, false, nullptr, pm, ME, kp, drop, site(S_FF_OUT)));
         CHK(lin_bwd(cx, hact, P(p + "linear2.weight"), pm, G(p + "linear2.weight"), G(p + "linear2.bias"), d_h, R, E, F));                  // d_h = d hact
         if (drop.thresh && MF % 4 == 0)            // d_h = d hpre: the MLP's inner dropout and the GELU backward in one pass
@@ -591,7 +575,7 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
         }
         HIPCHK(hipGetLastError());
         CHK(lin_bwd(cx, n2, P(p + "linear1.weight"), d_h, G(p + "linear1.weight"), G(p + "linear1.bias"), d_a, R, F, E));                   // d_a = d n2
-        CHK(ln_bwd(cx, t2, P(p + "norm2.weight"), d_a, d_b, d_b, G(p + "norm2.weight"), G(p + "norm2.bias"), nullptr, R, E, eps));          // d_b = d t2
+        CHK(ln_bwd(cx, t2, P(p + "norm2.weight"), d_a, d_b, d_b, G(p + "norm2.weight"), G(p + "norm2.bias"), R, E, eps));          // d_b = d t2
         CHK(dropout_add(cx, d_b, false, nullptr, pm, ME, kp, drop, site(S_CA_OUT)));
         CHK(lin_bwd(cx, ca_o, P(p + "cross_attn.out_proj.weight"), pm, G(p + "cross_attn.out_proj.weight"), G(p + "cross_attn.out_proj.bias"),
                     d_c, R, E, E));                                                                                                        // d_c = d ca_o
@@ -602,18 +586,18 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
             HIPCHK(hipGetLastError());
         }
         CHK(lin_bwd(cx, n1, ca_w, d_a, G(p + "cross_attn.in_proj_weight"), G(p + "cross_attn.in_proj_bias"), d_c, R, E, E));                // d_c = d n1
-        CHK(ln_bwd(cx, t1, P(p + "norm1.weight"), d_c, d_b, d_a, G(p + "norm1.weight"), G(p + "norm1.bias"), nullptr, R, E, eps));          // d_a = d t1
+        CHK(ln_bwd(cx, t1, P(p + "norm1.weight"), d_c, d_b, d_a, G(p + "norm1.weight"), G(p + "norm1.bias"), R, E, eps));          // d_a = d t1
         CHK(dropout_add(cx, d_a, false, nullptr, pm, ME, kp, drop, site(S_SA_OUT)));
         CHK(lin_bwd(cx, sa_o, P(p + "self_attn.out_proj.weight"), pm, G(p + "self_attn.out_proj.weight"), G(p + "self_attn.out_proj.bias"),
                     d_b, R, E, E));                                                                                                        // d_b = d sa_o
         CHK(train_attn(cx, sa, kp * B, true, 32));                                                                                          // d_qb = d q; d_kvc =
         CHK(lin_bwd(cx, qn, sa_w, d_qb, G(p + "self_attn.in_proj_weight"), G(p + "self_attn.in_proj_bias"), d_c, R, E, E));                 // d_c = d qn
-        CHK(ln_bwd(cx, qd, P(p + "norm_q.weight"), d_c, d_a, d_b, G(p + "norm_q.weight"), G(p + "norm_q.bias"), nullptr, R, E, eps));       // d_b = d qd
+        CHK(ln_bwd(cx, qd, P(p + "norm_q.weight"), d_c, d_a, d_b, G(p + "norm_q.weight"), G(p + "norm_q.bias"), R, E, eps));       // d_b = d qd
         CHK(dropout_add(cx, d_b, false, nullptr, d_b, ME, kp, drop, site(S_QUERY)));
         CHK(colsum(cx, d_b, (long)L * E, kp * B, L * E, d_pq, true));                           // every image's query rows are pos_queries[l]
         CHK(lin_bwd(cx, cn, sa_w + (size_t)E * E, d_kvc, G(p + "self_attn.in_proj_weight") + (size_t)E * E, G(p + "self_attn.in_proj_bias") + E,
                     d_c, R, 2 * E, E));                                                                                                    // d_c = d cn
-        CHK(ln_bwd(cx, content, P(p + "norm_c.weight"), d_c, nullptr, d_b, G(p + "norm_c.weight"), G(p + "norm_c.bias"), nullptr, R, E, eps));  // d_b = d content
+        CHK(ln_bwd(cx, content, P(p + "norm_c.weight"), d_c, nullptr, d_b, G(p + "norm_c.weight"), G(p + "norm_c.bias"), R, E, eps));  // d_b = d content
         // d_content (+)= every pass's d content through that pass's mask (the passes in ascending order)
         hipLaunchKernelGGL(dropout_sum_passes_kernel, dim3((unsigned)((ME + 255) / 256)), dim3(256), 0, s, d_b, d_content, ME, kp, drop, site(S_CONTENT), i0 > 0 ? 1 : 0);
         HIPCHK(hipGetLastError());
@@ -646,7 +630,7 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
 
 // ---- training step, encoder side: forward that keeps what the backward needs, and the backward ------------------------------
 struct TrainEncoderLayout {          // offsets in floats
-    size_t patches, layer0, layer_stride, x_last, n, hact, d_x, d_a, d_h, dqkv, tmp, scratch, scratch2, scratch_floats, total;      // scratch2: the backward's second stream
+    size_t patches, layer0, layer_stride, x_last, d_x, d_a, d_h, dqkv, tmp, scratch, scratch2, scratch_floats, total;      // scratch2: the backward's second stream
     size_t w16, w16_layer, d_x16, d_h16;      // bf16 shadows (train_enc_shadows): the Linear weights and their transposes ([layer][qkv, proj, fc1, fc2][W16 | Wt16]),
                                               // the residual-stream gradient and the fc1-output gradient
     size_t x(int i) const { return layer0 + i * layer_stride; }
@@ -671,7 +655,7 @@ static TrainEncoderLayout train_encoder_layout(const parseq_model* m, int B) {
     if (wide) { o.lse = off - o.layer0; take(MS * m->cfg.enc_heads); }
     o.layer_stride = off - o.layer0;
     off = o.layer0 + o.layer_stride * (size_t)m->cfg.enc_depth;
-    o.x_last = take(MS * E); o.n = take(MS * E); o.hact = take(MS * F); o.d_x = take(MS * E); o.d_a = take(MS * E); o.d_h = take(MS * F);
+    o.x_last = take(MS * E); o.d_x = take(MS * E); o.d_a = take(MS * E); o.d_h = take(MS * F);
     o.dqkv = take(MS * 3 * E); o.tmp = take(MS * E);
     if (wide) o.dsum = take(MS * m->cfg.enc_heads);
     o.scratch_floats = train_scratch_floats(MS, E); o.scratch = take(o.scratch_floats);
@@ -730,11 +714,67 @@ static bool train_enc_one_launch(const parseq_model* m, const TrainEncoderLayout
            o.layer_stride * sizeof(float) < ((size_t)1 << 32) && !getenv("PARSEQ_TRAIN_ENC_PER_OP");
 }
 struct EncShadowW { bf16_t* w; bf16_t* wt; };
-// which: 0 attn.qkv [3E, E], 1 attn.proj [E, E], 2 mlp.fc1 [F, E], 3 mlp.fc2 [E, F]
+// which: 0 attn.qkv [3E, E], 1 attn.proj [E, E], 2 mlp.fc1 [F, E], 3 mlp.fc2 [E, F]; enc_shadow_at: where a block's W16 starts, in bf16
+// elements from the shadows' base (ws + o.w16); its Wt16 follows it
+static size_t enc_shadow_at(const TrainEncoderLayout& o, int layer, int which, size_t E, size_t F) {
+    const size_t at[4] = {0, 6 * E * E, 8 * E * E, 8 * E * E + 2 * E * F};
+    return 2 * o.w16_layer * (size_t)layer + at[which];
+}
 static EncShadowW enc_shadow_w(const TrainEncoderLayout& o, float* ws, int layer, int which, size_t E, size_t F) {
-    bf16_t* base = reinterpret_cast<bf16_t*>(ws + o.w16 + o.w16_layer * (size_t)layer);
-    const size_t at[4] = {0, 6 * E * E, 8 * E * E, 8 * E * E + 2 * E * F}, n[4] = {3 * E * E, E * E, E * F, E * F};
-    return EncShadowW{base + at[which], base + at[which] + n[which]};
+    bf16_t* w16 = reinterpret_cast<bf16_t*>(ws + o.w16) + enc_shadow_at(o, layer, which, E, F);
+    const size_t n[4] = {3 * E * E, E * E, E * F, E * F};
+    return EncShadowW{w16, w16 + n[which]};
+}
+
+// Two device tables, model constants built on first use (offsets only, relative to the master weights and to the shadows' base, so any
+// workspace of the same layout serves); each is published only when valid: a failed upload must not leave a non-null table of garbage
+// offsets behind for the next call
+template <typename T>
+static int upload_table(const std::vector<T>& tab, const char* what, T** out) {
+    void* dev = nullptr;
+    HIPCHK(hipMalloc(&dev, tab.size() * sizeof(T)));
+    if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(PARSEQ_E_HIP, "upload of the %s table failed: %s", what, hipGetErrorString(hipGetLastError()));
+    }
+    *out = static_cast<T*>(dev);
+    return 0;
+}
+// weight_shadows_kernel's table: the 4 * depth Linear weights, where each lies in the master and where its W16 | Wt16 pair goes
+static int enc_shadow_table(parseq_model* m, const TrainEncoderLayout& o) {
+    if (m->shadow_tab_dev) return 0;
+    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
+    const char* names[4] = {"attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"};
+    const int wn[4] = {3 * E, E, F, E}, wk[4] = {E, E, E, F};
+    std::vector<ShadowEntry> tab;
+    unsigned tile = 0;
+    for (int i = 0; i < m->cfg.enc_depth; ++i)
+        for (int j = 0; j < 4; ++j) {
+            tab.push_back(ShadowEntry{(unsigned)m->params[m->index.at(m->enc + "blocks." + std::to_string(i) + "." + names[j])].offset, (unsigned)wn[j], (unsigned)wk[j],
+                                      tile, (unsigned long long)enc_shadow_at(o, i, j, E, F)});
+            tile += (unsigned)((wn[j] / 32) * (wk[j] / 32));
+        }
+    ShadowEntry* dev = nullptr;
+    CHK(upload_table(tab, "weight-shadow", &dev));
+    m->shadow_tiles = (int)tile;
+    m->shadow_tab_dev = dev;
+    return 0;
+}
+// the one-launch forward's table: per block, the parameters' offsets into the master and the four W16 shadows' (bf16 elements from the shadows' base)
+static int enc_block_table(parseq_model* m, const TrainEncoderLayout& o) {
+    if (m->train_blocks_dev) return 0;
+    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
+    std::vector<EncBlockParams> tab(m->cfg.enc_depth);
+    auto off = [&](const std::string& key) { return (unsigned)m->params[m->index.at(m->enc + key)].offset; };
+    auto w16 = [&](int i, int which) { return (unsigned)enc_shadow_at(o, i, which, E, F); };
+    for (int i = 0; i < m->cfg.enc_depth; ++i) {
+        const std::string b = "blocks." + std::to_string(i) + ".";
+        EncBlockParams& e = tab[i];
+        e.ln1_w = off(b + "norm1.weight"); e.ln1_b = off(b + "norm1.bias"); e.bqkv = off(b + "attn.qkv.bias"); e.bproj = off(b + "attn.proj.bias");
+        e.ln2_w = off(b + "norm2.weight"); e.ln2_b = off(b + "norm2.bias"); e.b1 = off(b + "mlp.fc1.bias"); e.b2 = off(b + "mlp.fc2.bias");
+        e.wqkv = w16(i, 0); e.wproj = w16(i, 1); e.w1 = w16(i, 2); e.w2 = w16(i, 3);
+    }
+    return upload_table(tab, "training block", &m->train_blocks_dev);
 }
 
 static TrainAttnArgs enc_attn_args(const parseq_model* m, float* qkv, float* ao, const float* d_ao, float* dqkv, float* lse = nullptr, float* dsum = nullptr) {
@@ -772,35 +812,13 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
         HIPCHK(hipGetLastError());
         CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed"), S, w + o.x(0), MS, E, PK));
     }
-    const size_t elems = (size_t)MS * F;
     const bool shadows = train_enc_shadows(m), only16 = train_enc_bf16_only(m);
     m->enc_record_mode = (shadows ? 1 : 0) | (only16 ? 2 : 0);      // what the record's slots hold; the backward entry must read them the same way
     m->enc_record_ws = workspace;
     if (shadows) {
         // this step's weights as bf16, both ways round (the backward entry reads the transposes from the same workspace): one launch over
-        // the 4 * depth matrices (it was one launch per matrix: 48 launches of 2 - 7 us); the table is a model constant
-        if (!m->shadow_tab_dev) {
-            const char* names[4] = {"attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"};
-            const int wn[4] = {3 * E, E, F, E}, wk[4] = {E, E, E, F};
-            std::vector<ShadowEntry> tab;
-            unsigned tile = 0;
-            for (int i = 0; i < m->cfg.enc_depth; ++i)
-                for (int j = 0; j < 4; ++j) {
-                    const EncShadowW sw = enc_shadow_w(o, w, i, j, E, F);
-                    tab.push_back(ShadowEntry{(unsigned)m->params[m->index.at(m->enc + "blocks." + std::to_string(i) + "." + names[j])].offset, (unsigned)wn[j], (unsigned)wk[j],
-                                              tile, (unsigned long long)(sw.w - reinterpret_cast<bf16_t*>(w + o.w16))});
-                    tile += (unsigned)((wn[j] / 32) * (wk[j] / 32));
-                }
-            // published only when valid: a failed upload must not leave a non-null table of garbage offsets behind for the next call
-            void* dev = nullptr;
-            HIPCHK(hipMalloc(&dev, tab.size() * sizeof(ShadowEntry)));
-            if (hipMemcpy(dev, tab.data(), tab.size() * sizeof(ShadowEntry), hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(dev);
-                return fail(PARSEQ_E_HIP, "upload of the weight-shadow table failed: %s", hipGetErrorString(hipGetLastError()));
-            }
-            m->shadow_tiles = (int)tile;
-            m->shadow_tab_dev = dev;
-        }
+        // the 4 * depth matrices (it was one launch per matrix: 48 launches of 2 - 7 us)
+        CHK(enc_shadow_table(m, o));
         hipLaunchKernelGGL(weight_shadows_kernel, dim3(m->shadow_tiles), dim3(256), 0, s, m->master, reinterpret_cast<const ShadowEntry*>(m->shadow_tab_dev),
                            4 * m->cfg.enc_depth, reinterpret_cast<bf16_t*>(w + o.w16));
         HIPCHK(hipGetLastError());
@@ -810,30 +828,11 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
         // accumulators, the weights streamed from this step's bf16 shadows — writing the record on the way; 48 GEMM, 24 LayerNorm and
         // 12 attention launches and every re-read of an activation disappear, what is left is the record's own bytes.
         const int depth = m->cfg.enc_depth;
-        if (!m->train_blocks_dev) {      // a model constant: parameter offsets into the master, weight offsets relative to the shadows' base
-            std::vector<EncBlockParams> tab(depth);
-            auto off = [&](const std::string& key) { return (unsigned)m->params[m->index.at(m->enc + key)].offset; };
-            for (int i = 0; i < depth; ++i) {
-                const std::string b = "blocks." + std::to_string(i) + ".";
-                const unsigned w0 = (unsigned)(2 * o.w16_layer * (size_t)i), EE = (unsigned)(E * E), EF = (unsigned)(E * F);      // bf16 elements from the shadows' base
-                EncBlockParams& e = tab[i];
-                e.ln1_w = off(b + "norm1.weight"); e.ln1_b = off(b + "norm1.bias"); e.bqkv = off(b + "attn.qkv.bias"); e.bproj = off(b + "attn.proj.bias");
-                e.ln2_w = off(b + "norm2.weight"); e.ln2_b = off(b + "norm2.bias"); e.b1 = off(b + "mlp.fc1.bias"); e.b2 = off(b + "mlp.fc2.bias");
-                e.wqkv = w0; e.wproj = w0 + 6 * EE; e.w1 = w0 + 8 * EE; e.w2 = w0 + 8 * EE + 2 * EF;       // enc_shadow_w's W16 of each pair
-            }
-            EncBlockParams* dev = nullptr;
-            HIPCHK(hipMalloc(reinterpret_cast<void**>(&dev), depth * sizeof(EncBlockParams)));
-            if (hipMemcpy(dev, tab.data(), depth * sizeof(EncBlockParams), hipMemcpyHostToDevice) != hipSuccess) {
-                (void)hipFree(dev);
-                return fail(PARSEQ_E_HIP, "upload of the training block table failed: %s", hipGetErrorString(hipGetLastError()));
-            }
-            m->train_blocks_dev = dev;
-        }
-        const EncBlockParams* tab = m->train_blocks_dev;
+        CHK(enc_block_table(m, o));
         const EncRecordParams rec{w + o.layer0, o.layer_stride, (unsigned)(o.layer_stride * sizeof(float)), (unsigned)(o.qkv * 4), (unsigned)(o.ao * 4),
                                   (unsigned)(o.x_mid * 4), (unsigned)(o.hpre * 4), (unsigned)(o.hact_l * 4), (unsigned)(o.n1 * 4), (unsigned)(o.n2 * 4)};
         HIPCHK((launch_enc_blocks_record<384>(s, w + o.x_last, reinterpret_cast<const bf16_t*>(w + o.w16), o.w16_layer * (size_t)depth * sizeof(float),
-                                              m->master, tab, depth, eps, MS, rec)));
+                                              m->master, m->train_blocks_dev, depth, eps, MS, rec)));
         return run_layernorm<float>(s, w + o.x_last, P("norm.weight"), P("norm.bias"), memory_out, nullptr, MS, E, eps);
     }
     for (int i = 0; i < m->cfg.enc_depth; ++i) {
@@ -844,15 +843,15 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
             bf16_t* n1 = reinterpret_cast<bf16_t*>(x + o.n1); bf16_t* n2 = reinterpret_cast<bf16_t*>(x + o.n2);
             bf16_t* ao16 = reinterpret_cast<bf16_t*>(ao); bf16_t* hact16 = reinterpret_cast<bf16_t*>(x + o.hact_l);
             CHK(train_ln_fwd(s, x, P(p + "norm1.weight"), P(p + "norm1.bias"), n1, MS, E, eps));
-            CHK(lin_fwd16(cx, n1, enc_shadow_w(o, w, i, 0, E, F).w, P(p + "attn.qkv.bias"), nullptr, 0, qkv, MS, 3 * E, E));
+            CHK(lin_fwd(cx, n1, enc_shadow_w(o, w, i, 0, E, F).w, P(p + "attn.qkv.bias"), nullptr, 0, qkv, MS, 3 * E, E));
             TrainAttnArgs aa = enc_attn_args(m, qkv, ao, nullptr, nullptr);
             aa.o16 = ao16;
             CHK(train_attn(cx, aa, batch, false, ATT_HD));
-            CHK(lin_fwd16(cx, ao16, enc_shadow_w(o, w, i, 1, E, F).w, P(p + "attn.proj.bias"), x, MS, x_mid, MS, E, E));
+            CHK(lin_fwd(cx, ao16, enc_shadow_w(o, w, i, 1, E, F).w, P(p + "attn.proj.bias"), x, MS, x_mid, MS, E, E));
             CHK(train_ln_fwd(s, x_mid, P(p + "norm2.weight"), P(p + "norm2.bias"), n2, MS, E, eps));
-            if (only16) CHK(lin_fwd16(cx, n2, enc_shadow_w(o, w, i, 2, E, F).w, P(p + "mlp.fc1.bias"), nullptr, 0, nullptr, MS, F, E, hact16, reinterpret_cast<bf16_t*>(hpre)));
-            else CHK(lin_fwd16(cx, n2, enc_shadow_w(o, w, i, 2, E, F).w, P(p + "mlp.fc1.bias"), nullptr, 0, hpre, MS, F, E, hact16));
-            CHK(lin_fwd16(cx, hact16, enc_shadow_w(o, w, i, 3, E, F).w, P(p + "mlp.fc2.bias"), x_mid, MS, x_out, MS, E, F));
+            const Out pre = only16 ? Out(reinterpret_cast<bf16_t*>(hpre)) : Out(hpre);      // level 2: the pre-activation exists as bf16 only
+            CHK(lin_fwd(cx, n2, enc_shadow_w(o, w, i, 2, E, F).w, P(p + "mlp.fc1.bias"), nullptr, 0, pre, MS, F, E, hact16));
+            CHK(lin_fwd(cx, hact16, enc_shadow_w(o, w, i, 3, E, F).w, P(p + "mlp.fc2.bias"), x_mid, MS, x_out, MS, E, F));
             continue;
         }
         CHK(train_ln_fwd(s, x, P(p + "norm1.weight"), P(p + "norm1.bias"), x + o.n1, MS, E, eps));
@@ -928,7 +927,6 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
     auto G = [&](const std::string& key) { return grads + m->params[m->index.at(m->enc + key)].offset; };
     float* d_x = w + o.d_x; float* d_a = w + o.d_a; float* d_h = w + o.d_h; float* dqkv = w + o.dqkv;
     float* tmp = w + o.tmp;
-    const size_t elems = (size_t)MS * F;
     const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
     const bool shadows = train_enc_shadows(m), only16 = train_enc_bf16_only(m);
     if (m->enc_record_ws == workspace && m->enc_record_mode != ((shadows ? 1 : 0) | (only16 ? 2 : 0)))
@@ -960,7 +958,7 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
     const TrainCtx cxs = two_streams ? TrainCtx{side, w + o.scratch2, m->train_precision == PARSEQ_BF16, o.scratch_floats} : cx;
     m->grad_events_valid = false;
     if (segs) CHK(grad_event_record(m, 0, s));      // the decoder's gradients were written by parseq_train_decoder, earlier on this stream
-    CHK(ln_bwd(cx, w + o.x_last, P("norm.weight"), dmemory, nullptr, d_x, G("norm.weight"), G("norm.bias"), tmp, MS, E, eps, d_x16));
+    CHK(ln_bwd(cx, w + o.x_last, P("norm.weight"), dmemory, nullptr, d_x, G("norm.weight"), G("norm.bias"), MS, E, eps, d_x16));
     for (int i = m->cfg.enc_depth - 1; i >= 0; --i) {
         // block i + 1 (and, behind the last block, encoder.norm) is final: segment depth - 1 - i
         if (segs && i < m->cfg.enc_depth - 1 && i >= 0) CHK(grad_event_record(m, m->cfg.enc_depth - 1 - i, s));
@@ -987,12 +985,12 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
                 CHK(fork(0));                                                                                       // d_x16 of this block exists
                 CHK(lin_bwd16_dw(cxs, hact16, d_x32, d_x16, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), MS, E, F));
                 CHK(mark(4));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 3, E, F).wt, d_x32, d_x16, d_h32, d_h16, MS, E, F, hpre32, hpre16));
+                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 3, E, F).wt, d_x32, d_x16, d_h32, d_h16, MS, E, F, In(hpre32, hpre16)));
                 CHK(fork(1));                                                                                       // d_h16 exists
                 CHK(lin_bwd16_dw(cxs, n2, d_h32, d_h16, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), MS, F, E));
                 CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 2, E, F).wt, d_h32, d_h16, d_a, nullptr, MS, F, E));
                 CHK(join(4));                                                                                       // fc2's dW has read d_x16
-                CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), tmp, MS, E, eps, d_x16));
+                CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), MS, E, eps, d_x16));
                 CHK(fork(2));                                                                                       // the new d_x16 exists
                 CHK(lin_bwd16_dw(cxs, ao16, d_x32, d_x16, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), MS, E, E));
                 CHK(mark(5));
@@ -1005,7 +1003,7 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
                 CHK(mark(6));
                 CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 0, E, F).wt, dqkv32, dqkv16, d_a, nullptr, MS, 3 * E, E));
                 CHK(join(5));                                                                                       // proj's dW has read d_x16
-                CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), tmp, MS, E, eps, d_x16));
+                CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), MS, E, eps, d_x16));
                 return join(6);       // the block's gradients are final on the main stream too (the segment event that follows covers them)
             };
             if (const int rc = block()) {
@@ -1018,12 +1016,12 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
         const float* hact = x + o.hact_l;                        // kept by the forward
         CHK(lin_bwd(cx, hact, P(p + "mlp.fc2.weight"), d_x, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), d_h, MS, E, F, hpre));      // d_h = d hpre (GELU backward folded in)
         CHK(lin_bwd(cx, x + o.n2, P(p + "mlp.fc1.weight"), d_h, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), d_a, MS, F, E));
-        CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), tmp, MS, E, eps));   // d_x = d x_mid
+        CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), MS, E, eps));   // d_x = d x_mid
         // x_mid = x + proj(attention(qkv(norm1(x))))
         CHK(lin_bwd(cx, ao, P(p + "attn.proj.weight"), d_x, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), d_a, MS, E, E));        // d_a = d ao
         CHK(train_attn(cx, enc_attn_args(m, qkv, ao, d_a, dqkv, o.lse ? x + o.lse : nullptr, o.lse ? w + o.dsum : nullptr), batch, true, ATT_HD));
         CHK(lin_bwd(cx, x + o.n1, P(p + "attn.qkv.weight"), dqkv, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), d_a, MS, 3 * E, E));
-        CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), tmp, MS, E, eps));          // d_x = d x
+        CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), MS, E, eps));          // d_x = d x
     }
     CHK(colsum(cx, d_x, (long)S * E, batch, S * E, G("pos_embed"), true));
     if (m->vitstr) {
