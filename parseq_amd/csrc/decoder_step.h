@@ -18,7 +18,7 @@
 // register loads).  Each wave therefore owns a private ring of 1-KB LDS slots: `global_load_lds` copies the wave's next
 // W fragments (lane l's 16 bytes land at slot + 16 l, exactly where lane l reads its MFMA operand back) while the wave
 // multiplies — no block-level barrier inside a GEMM, only counted `s_waitcnt vmcnt`.
-// Rounding points are the generic path's (decode_pass_e): bf16 GEMM operands, fp32 accumulation, fp32 residual stream.
+// Rounding points are the generic path's (lib_decode.hip decoder_pass): bf16 GEMM operands, fp32 accumulation, fp32 residual stream.
 #pragma once
 #include "common.h"
 #include "decoder_attn.h"

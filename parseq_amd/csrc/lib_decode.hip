@@ -2,352 +2,390 @@
 #include "lib_internal.h"
 
 // -------------------------------------------------------------------------------------------------------------------
+// what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
+// -------------------------------------------------------------------------------------------------------------------
+// f(TE<T, E>{}) with the plan's storage type (bf16_t, or float for fp32 and bf16x3) and embed_dim as template arguments; dispatch_t
+// where only the type matters (E = 0).
+template <typename T_, int E_> struct TE { using T = T_; static constexpr int E = E_; };
+template <typename F>
+static int dispatch_t(const parseq_plan* p, F&& f) { return p->precision == PARSEQ_BF16 ? f(TE<bf16_t, 0>{}) : f(TE<float, 0>{}); }
+template <typename F>
+static int dispatch_te(const parseq_plan* p, F&& f) {
+    return dispatch_t(p, [&](auto t) {
+        using T = typename decltype(t)::T;
+        switch (p->m->cfg.embed_dim) {
+            case 192: return f(TE<T, 192>{});
+            case 384: return f(TE<T, 384>{});
+            default:  return f(TE<T, 768>{});
+        }
+    });
+}
+
+// The decoder's parameters, resolved once per call (on the stack: the master may be uploaded again between calls): GEMM weights in
+// the storage type, everything else fp32 from the master.
+struct LnW { const float *g, *b; };
+template <typename T> struct DecLayerW {
+    LnW norm_q, norm_c, norm1, norm2;
+    const T *sa_in, *sa_out, *ca_in, *ca_out, *lin1, *lin2;
+    const float *sa_in_b, *sa_out_b, *ca_in_b, *ca_out_b, *lin1_b, *lin2_b;
+};
+template <typename T> struct DecW {
+    DecLayerW<T> layer[PARSEQ_DEC_DEPTH_MAX];
+    LnW norm; const T* head; const float* head_b;      // decoder.norm, head
+    const float *pos_queries, *text_embed;
+};
+static std::string dec_layer_key(int l) { return "decoder.layers." + std::to_string(l) + "."; }
+// the cross-attention in-projection of the layer with key prefix d (rows 0 .. E: q; rows E .. 3E: k | v of memory) — all that parseq_set_memory reads
+template <typename T>
+static void ca_in_proj(const Weights<T>& W, const std::string& d, const T*& w, const float*& b) {
+    w = W.w(d + "cross_attn.in_proj_weight"); b = W.m->p(d + "cross_attn.in_proj_bias");
+}
+template <typename T>
+static DecW<T> dec_weights(const parseq_plan* p) {
+    const parseq_model* m = p->m;
+    const Weights<T> W = weights_of<T>(p);
+    DecW<T> w{};
+    for (int l = 0; l < m->cfg.dec_depth; ++l) {
+        const std::string d = dec_layer_key(l);
+        DecLayerW<T>& y = w.layer[l];
+        y.norm_q = {m->p(d + "norm_q.weight"), m->p(d + "norm_q.bias")}; y.norm_c = {m->p(d + "norm_c.weight"), m->p(d + "norm_c.bias")};
+        y.norm1 = {m->p(d + "norm1.weight"), m->p(d + "norm1.bias")}; y.norm2 = {m->p(d + "norm2.weight"), m->p(d + "norm2.bias")};
+        y.sa_in = W.w(d + "self_attn.in_proj_weight"); y.sa_in_b = m->p(d + "self_attn.in_proj_bias");
+        y.sa_out = W.w(d + "self_attn.out_proj.weight"); y.sa_out_b = m->p(d + "self_attn.out_proj.bias");
+        ca_in_proj(W, d, y.ca_in, y.ca_in_b);
+        y.ca_out = W.w(d + "cross_attn.out_proj.weight"); y.ca_out_b = m->p(d + "cross_attn.out_proj.bias");
+        y.lin1 = W.w(d + "linear1.weight"); y.lin1_b = m->p(d + "linear1.bias");
+        y.lin2 = W.w(d + "linear2.weight"); y.lin2_b = m->p(d + "linear2.bias");
+    }
+    w.norm = {m->p("decoder.norm.weight"), m->p("decoder.norm.bias")};
+    w.head = W.w("head.weight"); w.head_b = m->p("head.bias");
+    w.pos_queries = m->p("pos_queries"); w.text_embed = m->p("text_embed.embedding.weight");
+    return w;
+}
+
+// One pass of the decoder (model.decode + head, modules.py:55-124): queries pos_queries[i0 : i0 + Lq] of every image — or the caller's
+// `user_query` [B, Lq, E] — against the content tokens p->tok[:, :Lk].  Writes logits[b][i0 + qi][:] for qi < Lq into a [B][Ltot][C] tensor.
+struct DecPass {
+    int B = 0, Lk = 1, i0 = 0, Lq = 1;
+    int c0 = 0;      // dec_depth > 1: the first content row this pass computes (an AR step: Lk - 1, the rows before it are cached in kvself)
+    const unsigned char* qmask = nullptr;      // [npos][LDT] attention mask of the query stream, rows by absolute position; True = masked
+    const unsigned char* cmask = nullptr;      // the same for the content stream (read at dec_depth > 1 only)
+    const unsigned char* kpm = nullptr;        // [B][LDT] key padding of both streams
+    float* logits = nullptr; int Ltot = 0;
+    int argmax_mode = 0;      // Lq == 1: greedy pick of position i0 into tok[:, i0 + 1] with the EOS bookkeeping (2: testing, all rows run on)
+    const float* user_query = nullptr;
+    bool fused_step_allowed = false;      // a single unmasked query may take dec_step_pre / post, which leave no query stream in p->t
+};
+
+// The form a single-query (AR) step takes, decided once per parseq_forward / parseq_decode_* call:
+//   STEP_DEEP    dec_depth > 1: the layer walk with the per-layer content cache (decoder_step.h holds depth-1 kernels)
+//   STEP_FUSED   decoder_step.h.  parseq_forward's AR loop: mid / cross-attention / mlp launches, in bf16 or in the bf16x3 arithmetic on
+//                f32 storage (ar_loop_fused).  A single unmasked query of any other bf16 pass: the pre / post pair (step_pre_post).
+//   STEP_PER_OP  one launch per operation
+// p->wstep[0] is set only where the fragment-packed weights exist (step_ok, lib_model.hip parseq_plan_create_ex): a PARSeq model,
+// precision bf16 or bf16x3, embed_dim <= 384 and a multiple of 64, dec_mlp_ratio == 4 — none of which is asked again here.  Of the
+// widths parseq_model_create admits (192, 384, 768) that leaves 192 and 384, the two the step kernels are built for; forward_impl
+// and decoder_pass ask E <= 384 at compile time and keep the per-operation step otherwise.
+// The step kernels' head holds up to 128 classes.  `qsplit`: the mid kernel's start half on DS_QS workgroups per row tile, see ar_loop_fused.
+enum DecStep { STEP_DEEP, STEP_FUSED, STEP_PER_OP };
+struct DecRoute { DecStep step; bool qsplit; };
+static DecRoute dec_route(const parseq_plan* p, bool latency) {
+    const parseq_model* m = p->m;
+    if (m->cfg.dec_depth > 1) return {STEP_DEEP, false};
+    if (!(p->wstep[0] && p->fused_step && m->classes <= 128)) return {STEP_PER_OP, false};
+    return {STEP_FUSED, latency && p->qsplit && m->tokens == 128 && m->cfg.max_label_length + 1 >= DS_QS + 2};
+}
+
+static float dec_scale() { return sqrtf(1.0f / (float)DEC_HD); }
+
+// -------------------------------------------------------------------------------------------------------------------
 // decoder
 // -------------------------------------------------------------------------------------------------------------------
-// Cross-attention of Lq queries per image against the plan's cached memory K / V: tuned kernels for 128 memory tokens
-// (streaming AR kernel, MFMA multi-query kernel), the key-count-generic kernel otherwise.
+// Cross-attention of Lq queries per image against cached memory K / V: tuned kernels for 128 memory tokens (streaming AR kernels,
+// MFMA multi-query kernels), the key-count-generic kernels otherwise.  `half`: bf16 storage.
+enum CaKernel { CA_MFMA_N, CA_GENERIC, CA_AR24, CA_AR, CA_MULTI_MFMA, CA_MULTI_X3, CA_MULTI };
+static int ca_route(bool half, int E, int NK, int Lq, bool kv24, int nsplit, CaKernel& kern) {
+    if (nsplit && (nsplit != DS_QS || NK != 128 || Lq != 1)) return fail(PARSEQ_E_STATE, "cross-attention: split q-projection outside the AR step kernels");
+    if (NK != 128) kern = half && (NK + 15) / 16 <= 16 ? CA_MFMA_N : CA_GENERIC;
+    else if (Lq == 1) {
+        if (kv24 && (half || E != 384)) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows but no kernel for this geometry");
+        if (!kv24 && nsplit && E > 384) return fail(PARSEQ_E_STATE, "cross-attention: split q-projection at embed_dim %d", E);      // the split step exists for the fused AR loop's widths only
+        kern = kv24 ? CA_AR24 : CA_AR;
+    } else if (half) kern = CA_MULTI_MFMA;
+    else if (g_split) kern = CA_MULTI_X3;      // bf16x3: the matrix-core kernel on bf16 pairs
+    else if (kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows outside the bf16x3 mode");
+    else kern = CA_MULTI;
+    return 0;
+}
+
 template <typename T, int E>
-static int run_cross_attention(parseq_plan* p, hipStream_t s, int B, int Lq, float scale, T* ca, const QAsm qa = QAsm{}, int layer = 0) {
+static int run_cross_attention(parseq_plan* p, hipStream_t s, int layer, int B, int Lq, T* ca, const QAsm& qa) {
     const int H = p->m->cfg.dec_heads, NK = p->m->tokens;
     // decoder layer `layer`'s K / V of memory (layers >= 1: dec_depth > 1, f32 / bf16 rows of the generic GEMM, never 24-bit)
     const T* kmem = reinterpret_cast<const T*>(layer ? p->kmem_l[layer] : p->kmem); const T* vmem = reinterpret_cast<const T*>(layer ? p->vmem_l[layer] : p->vmem);
-    const bool kv24 = layer ? false : p->kv24;
+    const bool kv24 = layer ? false : p->kv24;      // the 24-bit rows come from the one-launch bf16x3 encoder's tail
     const float* qc_ = p->qc;
-    if (qa.nsplit && (qa.nsplit != DS_QS || NK != 128 || Lq != 1)) return fail(PARSEQ_E_STATE, "cross-attention: split q-projection outside the AR step kernels");
-    if (NK != 128) {
-        if constexpr (sizeof(T) == 2) {
-            const int nt16 = (NK + 15) / 16;
+    const float scale = dec_scale();
+    constexpr bool half = sizeof(T) == 2;
+    CaKernel kern;
+    CHK(ca_route(half, E, NK, Lq, kv24, qa.nsplit, kern));
+    // ca_route never picks a kernel that T, E or NK lacks; the `if constexpr` below only keep each kernel from being compiled for
+    // a type or width it does not exist for, and their other arms (unreachable) report instead of returning without a launch
+    const auto no_kernel = [&] { return fail(PARSEQ_E_STATE, "cross-attention: route %d has no kernel for this storage type, width or key count", (int)kern); };
+    ProfScope ps_(&p->prof, T_DEC_CA, s);
+    switch (kern) {
+        case CA_MFMA_N:
+            if constexpr (half) {
+                const int nt16 = (NK + 15) / 16;
 #define PQ_CAM_N(NT)                                                                                                                      \
-            if (nt16 > NT - 2 && nt16 <= NT) {                                                                                           \
-                static LdsAttr attr_;                                                                                                    \
-                HIPCHK(attr_.ensure(reinterpret_cast<const void*>(dec_cross_attn_mfma_n_kernel<NT>), dec_cross_attn_mfma_n_lds<NT>()));  \
-                hipLaunchKernelGGL((dec_cross_attn_mfma_n_kernel<NT>), dim3((B * H + 1) / 2), dim3(128), dec_cross_attn_mfma_n_lds<NT>(), s, \
-                                   qc_, kmem, vmem, H, Lq, NK, scale, ca, B * H);                                                      \
-                HIPCHK(hipGetLastError());                                                                                                \
-                return 0;                                                                                                                 \
-            }
-            PQ_CAM_N(2) PQ_CAM_N(4) PQ_CAM_N(6) PQ_CAM_N(8) PQ_CAM_N(10) PQ_CAM_N(12) PQ_CAM_N(14) PQ_CAM_N(16)
+                if (nt16 > NT - 2 && nt16 <= NT) {                                                                                       \
+                    static LdsAttr attr_;                                                                                                \
+                    HIPCHK(attr_.ensure(reinterpret_cast<const void*>(dec_cross_attn_mfma_n_kernel<NT>), dec_cross_attn_mfma_n_lds<NT>())); \
+                    hipLaunchKernelGGL((dec_cross_attn_mfma_n_kernel<NT>), dim3((B * H + 1) / 2), dim3(128), dec_cross_attn_mfma_n_lds<NT>(), s, \
+                                       qc_, kmem, vmem, H, Lq, NK, scale, ca, B * H);                                                  \
+                } else
+                PQ_CAM_N(2) PQ_CAM_N(4) PQ_CAM_N(6) PQ_CAM_N(8) PQ_CAM_N(10) PQ_CAM_N(12) PQ_CAM_N(14) PQ_CAM_N(16) return no_kernel();
 #undef PQ_CAM_N
+            } else return no_kernel();
+            break;
+        case CA_GENERIC: {
+            const size_t lds = dec_cross_attn_generic_lds(NK);
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(dec_cross_attn_generic_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL((dec_cross_attn_generic_kernel<T>), dim3(B * H), dim3(128), lds, s, qc_, kmem, vmem, H, Lq, NK, scale, ca);
+            break;
         }
-        const size_t lds = dec_cross_attn_generic_lds(NK);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(dec_cross_attn_generic_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((dec_cross_attn_generic_kernel<T>), dim3(B * H), dim3(128), lds, s, qc_, kmem, vmem, H, Lq, NK, scale, ca);
-    } else if (Lq == 1) {
-        if constexpr (sizeof(T) == 4 && E == 384) {
-            if (kv24) {
-                const auto kern = qa.nsplit ? dec_cross_attn_ar24_kernel<E, true> : dec_cross_attn_ar24_kernel<E, false>;
-                hipLaunchKernelGGL(kern, dim3(B), dim3(E), 0, s, qc_, qa, reinterpret_cast<const unsigned char*>(p->kmem),
+        case CA_AR24:
+            if constexpr (!half && E == 384) {
+                const auto k = qa.nsplit ? dec_cross_attn_ar24_kernel<E, true> : dec_cross_attn_ar24_kernel<E, false>;
+                hipLaunchKernelGGL(k, dim3(B), dim3(E), 0, s, qc_, qa, reinterpret_cast<const unsigned char*>(p->kmem),
                                    reinterpret_cast<const unsigned char*>(p->vmem), p->kv_plane_elems, scale, ca);
-                HIPCHK(hipGetLastError());
-                return 0;
-            }
+            } else return no_kernel();
+            break;
+        case CA_AR: {
+            auto k = dec_cross_attn_ar_kernel<T, E, false>;
+            if constexpr (E <= 384) { if (qa.nsplit) k = dec_cross_attn_ar_kernel<T, E, true>; }
+            hipLaunchKernelGGL(k, dim3(B), dim3(E), 0, s, qc_, qa, kmem, vmem, scale, ca);
+            break;
         }
-        if (kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows but no kernel for this geometry");
-        auto kern = dec_cross_attn_ar_kernel<T, E, false>;
-        if constexpr (E <= 384) { if (qa.nsplit) kern = dec_cross_attn_ar_kernel<T, E, true>; }      // the split step exists for the fused AR loop's widths only
-        else if (qa.nsplit) return fail(PARSEQ_E_STATE, "cross-attention: split q-projection at embed_dim %d", E);
-        hipLaunchKernelGGL(kern, dim3(B), dim3(E), 0, s, qc_, qa, kmem, vmem, scale, ca);
-    } else if constexpr (sizeof(T) == 2) {
-        hipLaunchKernelGGL(dec_cross_attn_multi_mfma_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H);
-    } else {
-        if (g_split && kv24)      // bf16x3: the matrix-core kernel on bf16 pairs, K / V from the 24-bit rows of the one-launch encoder's tail
-            hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<true>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, p->kv_plane_elems);
-        else if (g_split)
-            hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, (size_t)0);
-        else if (kv24) return fail(PARSEQ_E_STATE, "cross-attention: 24-bit K / V rows outside the bf16x3 mode");
-        else
-            hipLaunchKernelGGL((dec_cross_attn_multi_kernel<T>), dim3(B * H), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca);
+        case CA_MULTI_MFMA:
+            if constexpr (half) hipLaunchKernelGGL(dec_cross_attn_multi_mfma_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H);
+            else return no_kernel();
+            break;
+        case CA_MULTI_X3:      // K / V from the 24-bit rows, or from f32 rows
+            if constexpr (half) return no_kernel();
+            else if (kv24) hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<true>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, p->kv_plane_elems);
+            else hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, (size_t)0);
+            break;
+        case CA_MULTI:
+            if constexpr (half) return no_kernel();
+            else hipLaunchKernelGGL((dec_cross_attn_multi_kernel<T>), dim3(B * H), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca);
+            break;
     }
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// decoder.norm + head of the query stream in p->t (rows b * Lq + qi -> logits[b][i0 + qi] of a [B][Ltot][C] tensor), and for an AR
-// step (argmax_mode != 0, Lq == 1) the greedy pick of position i0 into tok[:, i0 + 1] with the EOS bookkeeping
+// decoder.norm + head of the query stream in p->t (rows b * Lq + qi -> logits[b][i0 + qi]), and for an AR step (argmax_mode != 0)
+// the greedy pick of position i0 into tok[:, i0 + 1] with the EOS bookkeeping
 template <typename T, int E>
-static int head_pass(parseq_plan* p, hipStream_t s, int B, int i0, int Lq, float* logits, int Ltot, int argmax_mode) {
-    const parseq_model* m = p->m;
-    const parseq_config& c = m->cfg;
-    const int M = B * Lq, C = m->classes;
-    const Weights<T> W = weights_of<T>(p);
-    int* eos_rows = p->counters; int* ar_len = p->counters + 1;
+static int head_pass(parseq_plan* p, hipStream_t s, const DecW<T>& w, const DecPass& a) {
+    const parseq_config& c = p->m->cfg;
+    const int M = a.B * a.Lq, C = p->m->classes;
     // decoder.norm fused into the head's A operand
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, m->p("decoder.norm.weight"), m->p("decoder.norm.bias"), c.dec_ln_eps,
-                     W.w("head.weight"), M, C, epi_store<float>(M, C, m->p("head.bias"), logits, C, 1.f, Lq, Ltot, i0), p->tn))); }
-    if (argmax_mode) {       // only meaningful for Lq == 1: greedy pick of position i0 into tok[:, i0 + 1]
-        hipLaunchKernelGGL(ar_argmax_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, Ltot, C, p->tok, LDT, i0, B, c.eos_id,
-                           p->eos_seen, eos_rows, ar_len, argmax_mode == 2 ? 1 : 0);
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, w.norm.g, w.norm.b, c.dec_ln_eps, w.head, M, C,
+                     epi_store<float>(M, C, w.head_b, a.logits, C, 1.f, a.Lq, a.Ltot, a.i0), p->tn))); }
+    if (a.argmax_mode) {
+        hipLaunchKernelGGL(ar_argmax_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.Ltot, C, p->tok, LDT, a.i0, a.B, c.eos_id,
+                           p->eos_seen, p->counters, p->counters + 1, a.argmax_mode == 2 ? 1 : 0);
         HIPCHK(hipGetLastError());
     }
     return 0;
 }
 
-template <typename T, int E>
-static int decode_pass_e(parseq_plan* p, hipStream_t s, int B, int Lk, int i0, int Lq, const unsigned char* qmask, const unsigned char* kpm,
-                         float* logits, int Ltot, int argmax_mode, bool keep_t = false, const float* user_query = nullptr, bool stream_only = false) {
-    // stream_only (dec_depth > 1): layer 0's query stream alone, left in p->t — the layer loop (deep_*) runs the deeper layers and the head
-    const parseq_model* m = p->m;
-    const parseq_config& c = m->cfg;
-    const int M = B * Lq, Fd = E * c.dec_mlp_ratio, C = m->classes, npos = c.max_label_length + 1, H = c.dec_heads;
-    const Weights<T> W = weights_of<T>(p);
-    const std::string d = "decoder.layers.0.";
-    T* sa = reinterpret_cast<T*>(p->sa); T* ca = reinterpret_cast<T*>(p->ca); T* hdn = reinterpret_cast<T*>(p->hdn);
-    const T* kmem = reinterpret_cast<const T*>(p->kmem); const T* vmem = reinterpret_cast<const T*>(p->vmem);
-    const float scale = sqrtf(1.0f / (float)DEC_HD);
-    int* eos_rows = p->counters; int* ar_len = p->counters + 1;
-    if constexpr (sizeof(T) == 2 && E <= 384) {
-        // AR step (one unmasked query per image): two fused row-block kernels around the cross-attention (decoder_step.h)
-        if (Lq == 1 && !qmask && !kpm && C <= 128 && p->fused_step && p->wstep[0] && !keep_t && !user_query && !stream_only) {
-            const dim3 grid((M + DS_ROWS - 1) / DS_ROWS), block(64 * DS_NW);
-            static LdsAttr attr_pre, attr_post;
-            HIPCHK(attr_pre.ensure(reinterpret_cast<const void*>(dec_step_pre_kernel<E>), dec_step_pre_lds<E>()));
-            HIPCHK(attr_post.ensure(reinterpret_cast<const void*>(dec_step_post_kernel<E>), dec_step_post_lds<E>()));
-            {
-                ProfScope ps_(&p->prof, T_DEC_PRE, s);
-                hipLaunchKernelGGL((dec_step_pre_kernel<E>), grid, block, dec_step_pre_lds<E>(), s, p->stab, reinterpret_cast<const bf16_t*>(p->kvtab),
-                                   p->tok, LDT, c.num_tokens, npos, Lk, i0, p->wstep[0], m->p(d + "self_attn.out_proj.bias"),
-                                   m->p("pos_queries") + (size_t)i0 * E, m->p(d + "norm1.weight"), m->p(d + "norm1.bias"), c.dec_ln_eps,
-                                   p->wstep[1], m->p(d + "cross_attn.in_proj_bias"), p->t, p->qc, M);
-                HIPCHK(hipGetLastError());
-            }
-            {
-                ProfScope ps_(&p->prof, T_DEC_CA, s);
-                CHK((run_cross_attention<T, E>(p, s, B, 1, scale, ca)));
-            }
-            {
-                ProfScope ps_(&p->prof, T_DEC_POST, s);
-                hipLaunchKernelGGL((dec_step_post_kernel<E>), grid, block, dec_step_post_lds<E>(), s, reinterpret_cast<const bf16_t*>(ca), p->t,
-                                   p->wstep[2], m->p(d + "cross_attn.out_proj.bias"), m->p(d + "norm2.weight"),
-                                   m->p(d + "norm2.bias"), p->wstep[3], m->p(d + "linear1.bias"), p->wstep[4],
-                                   m->p(d + "linear2.bias"), m->p("decoder.norm.weight"), m->p("decoder.norm.bias"), c.dec_ln_eps,
-                                   p->wstep[5], m->p("head.bias"), C, logits, Ltot, i0, M, argmax_mode, p->tok, LDT, c.eos_id,
-                                   p->eos_seen, eos_rows, ar_len);
-                HIPCHK(hipGetLastError());
-            }
-            return 0;
-        }
-    }
-    // self-attention from the tables, out-projection, residual onto the raw position queries
-    if (user_query) {
-        // model.py:100-102 with a caller-supplied tgt_query [B, Lq, E]: q-projection of norm_q(query) at run time (the position-query
-        // tables do not apply), scores against the content-key table, residual onto the caller's query itself
-        const float qscale = sqrtf(1.0f / (float)DEC_HD);
-        { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, user_query, m->p(d + "norm_q.weight"), m->p(d + "norm_q.bias"), c.dec_ln_eps,
-                         W.w(d + "self_attn.in_proj_weight"), M, E, epi_store<float>(M, E, m->p(d + "self_attn.in_proj_bias"), p->qc, E, qscale), p->tn))); }
-        {
-            ProfScope ps_(&p->prof, T_DEC_SA, s);
-            hipLaunchKernelGGL((dec_self_attn_kernel<T, E>), dim3(M), dim3(E), 0, s, p->stab, reinterpret_cast<const T*>(p->kvtab), p->tok, LDT,
-                               c.num_tokens, npos, qmask, LDT, kpm, LDT, Lk, i0, Lq, sa, p->qc);
-            HIPCHK(hipGetLastError());
-        }
-        HIPCHK(hipMemcpyAsync(p->t, user_query, (size_t)M * E * sizeof(float), hipMemcpyDeviceToDevice, s));
-        { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{sa, E}, W.w(d + "self_attn.out_proj.weight"), E, M, E, E,
-                         epi_resid(M, E, m->p(d + "self_attn.out_proj.bias"), p->t, E)))); }
-    } else {
+// A whole depth-1 pass of one unmasked query per image (bf16): two fused row-block kernels around the cross-attention
+// (decoder_step.h), head and greedy pick included.
+template <int E>
+static int step_pre_post(parseq_plan* p, hipStream_t s, const DecW<bf16_t>& w, const DecPass& a) {
+    const parseq_config& c = p->m->cfg;
+    const DecLayerW<bf16_t>& y = w.layer[0];
+    const int M = a.B, C = p->m->classes, npos = c.max_label_length + 1;
+    bf16_t* ca = reinterpret_cast<bf16_t*>(p->ca);
+    const dim3 grid((M + DS_ROWS - 1) / DS_ROWS), block(64 * DS_NW);
+    static LdsAttr attr_pre, attr_post;
+    HIPCHK(attr_pre.ensure(reinterpret_cast<const void*>(dec_step_pre_kernel<E>), dec_step_pre_lds<E>()));
+    HIPCHK(attr_post.ensure(reinterpret_cast<const void*>(dec_step_post_kernel<E>), dec_step_post_lds<E>()));
     {
-        ProfScope ps_(&p->prof, T_DEC_SA, s);
-        if constexpr (sizeof(T) == 2 && E <= 512)
-            hipLaunchKernelGGL((dec_self_attn_wave_kernel<E>), dim3((M + 3) / 4), dim3(256), 0, s, p->stab, reinterpret_cast<const bf16_t*>(p->kvtab),
-                               p->tok, LDT, c.num_tokens, npos, qmask, LDT, kpm, LDT, Lk, i0, Lq, reinterpret_cast<bf16_t*>(sa), M);
-        else {
-            bool wave_form = false;
-            if constexpr (sizeof(T) == 4 && E <= 512) wave_form = g_split;      // bf16x3: the same wave-per-row form on the f32 tables
-            if constexpr (sizeof(T) == 4 && E <= 512) {
-                if (wave_form)
-                    hipLaunchKernelGGL((dec_self_attn_wave_kernel<E, float>), dim3((M + 3) / 4), dim3(256), 0, s, p->stab, reinterpret_cast<const float*>(p->kvtab),
-                                       p->tok, LDT, c.num_tokens, npos, qmask, LDT, kpm, LDT, Lk, i0, Lq, reinterpret_cast<float*>(sa), M);
-            }
-            if (!wave_form)
-                hipLaunchKernelGGL((dec_self_attn_kernel<T, E>), dim3(M), dim3(E), 0, s, p->stab, reinterpret_cast<const T*>(p->kvtab), p->tok, LDT,
-                                   c.num_tokens, npos, qmask, LDT, kpm, LDT, Lk, i0, Lq, sa);
-        }
+        ProfScope ps_(&p->prof, T_DEC_PRE, s);
+        hipLaunchKernelGGL((dec_step_pre_kernel<E>), grid, block, dec_step_pre_lds<E>(), s, p->stab, reinterpret_cast<const bf16_t*>(p->kvtab),
+                           p->tok, LDT, c.num_tokens, npos, a.Lk, a.i0, p->wstep[0], y.sa_out_b, w.pos_queries + (size_t)a.i0 * E, y.norm1.g, y.norm1.b,
+                           c.dec_ln_eps, p->wstep[1], y.ca_in_b, p->t, p->qc, M);
         HIPCHK(hipGetLastError());
     }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{sa, E}, W.w(d + "self_attn.out_proj.weight"), E, M, E, E,
-                     epi_table(M, E, m->p(d + "self_attn.out_proj.bias"), p->t, E, m->p("pos_queries"), E, Lq, i0)))); }
-    }
-    // cross-attention against memory (head-split K / V^T cached in the plan); norm1 is fused into the q-projection's A operand
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, m->p(d + "norm1.weight"), m->p(d + "norm1.bias"), c.dec_ln_eps,
-                     W.w(d + "cross_attn.in_proj_weight"), M, E, epi_store<float>(M, E, m->p(d + "cross_attn.in_proj_bias"), p->qc, E), p->tn))); }
+    CHK((run_cross_attention<bf16_t, E>(p, s, 0, a.B, 1, ca, QAsm{})));
     {
-        ProfScope ps_(&p->prof, T_DEC_CA, s);
-        CHK((run_cross_attention<T, E>(p, s, B, Lq, scale, ca)));
+        ProfScope ps_(&p->prof, T_DEC_POST, s);
+        hipLaunchKernelGGL((dec_step_post_kernel<E>), grid, block, dec_step_post_lds<E>(), s, ca, p->t, p->wstep[2], y.ca_out_b, y.norm2.g, y.norm2.b,
+                           p->wstep[3], y.lin1_b, p->wstep[4], y.lin2_b, w.norm.g, w.norm.b, c.dec_ln_eps, p->wstep[5], w.head_b, C, a.logits, a.Ltot,
+                           a.i0, M, a.argmax_mode, p->tok, LDT, c.eos_id, p->eos_seen, p->counters, p->counters + 1);
+        HIPCHK(hipGetLastError());
     }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{ca, E}, W.w(d + "cross_attn.out_proj.weight"), E, M, E, E, epi_resid(M, E, m->p(d + "cross_attn.out_proj.bias"), p->t, E)))); }
-    // MLP (norm2 fused into linear1's A operand)
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, m->p(d + "norm2.weight"), m->p(d + "norm2.bias"), c.dec_ln_eps,
-                     W.w(d + "linear1.weight"), M, Fd, epi_gelu<T>(M, Fd, m->p(d + "linear1.bias"), hdn, Fd), p->tn))); }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{hdn, Fd}, W.w(d + "linear2.weight"), Fd, M, E, Fd, epi_resid(M, E, m->p(d + "linear2.bias"), p->t, E)))); }
-    if (stream_only) return 0;
-    return head_pass<T, E>(p, s, B, i0, Lq, logits, Ltot, argmax_mode);
+    return 0;
 }
 
-// One pass of the query stream (modules.py:55-98 with update_content=False, then decoder.norm and head) for queries
-// pos_queries[i0 : i0 + Lq] of every image against the content tokens p->tok[:, :Lk].  Writes
-// logits[b][i0 + qi][:] for qi < Lq into a [B][Ltot][C] tensor.
-template <typename T>
-static int decode_pass(parseq_plan* p, hipStream_t s, int B, int Lk, int i0, int Lq, const unsigned char* qmask, const unsigned char* kpm,
-                       float* logits, int Ltot, int argmax_mode = 0, bool keep_t = false, const float* user_query = nullptr) {
-    switch (p->m->cfg.embed_dim) {
-        case 192: return decode_pass_e<T, 192>(p, s, B, Lk, i0, Lq, qmask, kpm, logits, Ltot, argmax_mode, keep_t, user_query);
-        case 384: return decode_pass_e<T, 384>(p, s, B, Lk, i0, Lq, qmask, kpm, logits, Ltot, argmax_mode, keep_t, user_query);
-        default:  return decode_pass_e<T, 768>(p, s, B, Lk, i0, Lq, qmask, kpm, logits, Ltot, argmax_mode, keep_t, user_query);
+// The table self-attention launch of <T, E>: a wave per row up to 512 columns in bf16 and (on the f32 tables) in bf16x3; a thread per
+// column otherwise (fp32, embed_dim 768).
+template <typename T, int E>
+static void launch_self_attn_tables(parseq_plan* p, hipStream_t s, const DecPass& a, T* sa) {
+    const parseq_config& c = p->m->cfg;
+    const int M = a.B * a.Lq, npos = c.max_label_length + 1;
+    const T* kvtab = reinterpret_cast<const T*>(p->kvtab);
+    if constexpr (E <= 512) {
+        if (sizeof(T) == 2 || g_split) {
+            hipLaunchKernelGGL((dec_self_attn_wave_kernel<E, T>), dim3((M + 3) / 4), dim3(256), 0, s, p->stab, kvtab, p->tok, LDT, c.num_tokens, npos,
+                               a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, M);
+            return;
+        }
     }
+    hipLaunchKernelGGL((dec_self_attn_kernel<T, E>), dim3(M), dim3(E), 0, s, p->stab, kvtab, p->tok, LDT, c.num_tokens, npos,
+                       a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa);
+}
+
+// Layer 0's self-attention of the position queries, read from the tables (the keys are embeddings: a function of position and token id),
+// out-projection, residual onto the raw position queries -> p->t.
+template <typename T, int E>
+static int self_attn_tables(parseq_plan* p, hipStream_t s, const DecW<T>& w, const DecPass& a) {
+    const int M = a.B * a.Lq;
+    T* sa = reinterpret_cast<T*>(p->sa);
+    {
+        ProfScope ps_(&p->prof, T_DEC_SA, s);
+        launch_self_attn_tables<T, E>(p, s, a, sa);
+        HIPCHK(hipGetLastError());
+    }
+    ProfScope ps_(&p->prof, T_DEC_GEMM, s);
+    return run_gemm<T>(s, ARowMajor<T>{sa, E}, w.layer[0].sa_out, E, M, E, E, epi_table(M, E, w.layer[0].sa_out_b, p->t, E, w.pos_queries, E, a.Lq, a.i0));
+}
+
+// Self-attention of explicit queries (DecoderLayer.forward_stream, modules.py:55-65): x = xq + out_proj(attention(q_proj(norm(xq)))) over
+// the M = B * Lq rows of the pass, norm_c for the content stream and norm_q for the query stream, keys j < Lk.  The keys are the K | V
+// rows of the layer's content input (`kvself`, dec_depth > 1), or, without them, the content-key table: layer 0 with a caller's query
+// (model.py:100-102), whose residual lands on the caller's query itself.
+template <typename T, int E>
+static int self_attn_queries(parseq_plan* p, hipStream_t s, const DecLayerW<T>& y, const DecPass& a, bool content, const void* kvself, const float* xq, float* x) {
+    const parseq_config& c = p->m->cfg;
+    const int M = a.B * a.Lq, npos = c.max_label_length + 1;
+    const LnW& n = content ? y.norm_c : y.norm_q;
+    T* sa = reinterpret_cast<T*>(p->sa);
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, xq, n.g, n.b, c.dec_ln_eps, y.sa_in, M, E,
+                     epi_store<float>(M, E, y.sa_in_b, p->qc, E, dec_scale()), p->tn))); }
+    {
+        ProfScope ps_(&p->prof, T_DEC_SA, s);
+        if (kvself) hipLaunchKernelGGL((dec_self_attn_kv_kernel<T, E>), dim3(M), dim3(E), 0, s, p->qc, reinterpret_cast<const T*>(kvself), npos,
+                                       a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa);
+        else hipLaunchKernelGGL((dec_self_attn_kernel<T, E>), dim3(M), dim3(E), 0, s, p->stab, reinterpret_cast<const T*>(p->kvtab), p->tok, LDT,
+                                c.num_tokens, npos, a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, p->qc);
+        HIPCHK(hipGetLastError());
+    }
+    if (xq != x) HIPCHK(hipMemcpyAsync(x, xq, (size_t)M * E * sizeof(float), hipMemcpyDeviceToDevice, s));
+    ProfScope ps_(&p->prof, T_DEC_GEMM, s);
+    return run_gemm<T>(s, ARowMajor<T>{sa, E}, y.sa_out, E, M, E, E, epi_resid(M, E, y.sa_out_b, x, E));
+}
+
+// The rest of a stream of layer `l` (modules.py:66-76) over the M = B * Lq rows of x [M][E] f32, in place: cross-attention against the
+// layer's memory K / V (head-split, cached in the plan; norm1 rides in the q-projection's A operand), MLP (norm2 in linear1's).
+template <typename T, int E>
+static int cross_mlp(parseq_plan* p, hipStream_t s, const DecLayerW<T>& y, int l, int B, int Lq, float* x) {
+    const parseq_config& c = p->m->cfg;
+    const int M = B * Lq, Fd = E * c.dec_mlp_ratio;
+    T* ca = reinterpret_cast<T*>(p->ca); T* hdn = reinterpret_cast<T*>(p->hdn);
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, y.norm1.g, y.norm1.b, c.dec_ln_eps, y.ca_in, M, E,
+                     epi_store<float>(M, E, y.ca_in_b, p->qc, E), p->tn))); }
+    CHK((run_cross_attention<T, E>(p, s, l, B, Lq, ca, QAsm{})));
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{ca, E}, y.ca_out, E, M, E, E, epi_resid(M, E, y.ca_out_b, x, E)))); }
+    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, y.norm2.g, y.norm2.b, c.dec_ln_eps, y.lin1, M, Fd,
+                     epi_gelu<T>(M, Fd, y.lin1_b, hdn, Fd), p->tn))); }
+    ProfScope ps_(&p->prof, T_DEC_GEMM, s);
+    return run_gemm<T>(s, ARowMajor<T>{hdn, Fd}, y.lin2, Fd, M, E, Fd, epi_resid(M, E, y.lin2_b, x, E));
 }
 
 // -------------------------------------------------------------------------------------------------------------------
-// decoders deeper than one layer (dec_depth > 1): the reference's layer loop (modules.py:116-124)
+// the layer loop (modules.py:116-124)
 // -------------------------------------------------------------------------------------------------------------------
-// Layers 0 .. D-2 update the content stream (under the content mask), and layers 1 .. D-1 attend to that updated content, so from
-// layer 1 on nothing is a function of (position, token id) and the tables of the depth-1 path do not apply.  The plan holds the
-// content stream p->xc (f32, updated in place layer by layer) and, per layer l, the self-attention K | V rows of layer l's content
-// input, p->kvself[l][b][pos][2E] (T).  Layer 0's query stream keeps the depth-1 kernels (decode_pass_e, stream_only).
+// dec_depth > 1: layers 0 .. D-2 update the content stream (under the content mask), and layers 1 .. D-1 attend to that updated content,
+// so from layer 1 on nothing is a function of (position, token id) and the tables do not apply.  The plan holds the content stream
+// p->xc (f32, updated in place layer by layer) and, per layer l, the self-attention K | V rows of layer l's content input,
+// p->kvself[l][b][pos][2E] (T).  Layer 0's query stream keeps the table-driven kernels.
 
 // The content input of model.decode (model.py:95-97) for positions i0 .. i0 + Lc - 1 of every image into p->xc [B * Lc][E].
 template <int E>
-static int content_rows(parseq_plan* p, hipStream_t s, int B, int Lc, int i0) {
-    const parseq_model* m = p->m;
+static int content_rows(parseq_plan* p, hipStream_t s, const float* text_embed, const float* pos_queries, int B, int Lc, int i0) {
     const size_t n = (size_t)B * Lc * E;
-    hipLaunchKernelGGL((content_embed_kernel<E>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->p("text_embed.embedding.weight"),
-                       m->p("pos_queries"), p->tok, LDT, B, Lc, i0, p->xc);
+    hipLaunchKernelGGL((content_embed_kernel<E>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, text_embed, pos_queries, p->tok, LDT, B, Lc, i0, p->xc);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
-// K | V of norm_c(x) for layer l's self-attention (modules.py:115, 64): row r of x [M][E] is image r / period at position
+// K | V of norm_c(xc) for layer l's self-attention (modules.py:115, 64): row r of p->xc [M][E] is image r / period at position
 // offset + r % period, written to p->kvself[l][image][position][2E].
 template <typename T, int E>
-static int kv_rows(parseq_plan* p, hipStream_t s, int l, int M, const float* x, int period, int offset) {
-    const parseq_model* m = p->m;
-    const parseq_config& c = m->cfg;
-    const Weights<T> W = weights_of<T>(p);
-    const std::string d = "decoder.layers." + std::to_string(l) + ".";
+static int kv_rows(parseq_plan* p, hipStream_t s, const DecLayerW<T>& y, int l, int M, int period, int offset) {
+    const parseq_config& c = p->m->cfg;
     ProfScope ps_(&p->prof, T_DEC_GEMM, s);
-    return run_ln_gemm<T, E>(s, x, m->p(d + "norm_c.weight"), m->p(d + "norm_c.bias"), c.dec_ln_eps, W.w(d + "self_attn.in_proj_weight") + (size_t)E * E,
-                             M, 2 * E, epi_store<T>(M, 2 * E, m->p(d + "self_attn.in_proj_bias") + E, reinterpret_cast<T*>(p->kvself[l]), 2 * E, 1.f,
-                                                    period, c.max_label_length + 1, offset), p->tn);
+    return run_ln_gemm<T, E>(s, p->xc, y.norm_c.g, y.norm_c.b, c.dec_ln_eps, y.sa_in + (size_t)E * E, M, 2 * E,
+                             epi_store<T>(M, 2 * E, y.sa_in_b + E, reinterpret_cast<T*>(p->kvself[l]), 2 * E, 1.f, period, c.max_label_length + 1, offset), p->tn);
 }
 
-// One stream of layer l (DecoderLayer.forward_stream, modules.py:55-76) over the M = B * Lq rows of x [M][E] f32, updated in place:
-// self-attention of norm(x) — norm_c for the content stream, norm_q for the query stream — against the K | V rows of layer l's content
-// (keys j < Lk), cross-attention against layer l's memory K / V, MLP.  Row b * Lq + qi is absolute position i0 + qi (mask rows).
+// One pass (DecPass) through every layer, then decoder.norm and head.  At depth 1 that is the query stream of layer 0 alone.
+// Deeper, the content stream runs beside it: rows c0 .. Lk-1 of every image under `cmask`.  A whole context (NAR, refinement, the
+// decode entry points) has c0 = 0.  An AR step i (model.py:123-141) has c0 = i = Lk - 1: the AR loop's content mask is causal
+// (tgt_mask[:j, :j]), so the content rows of positions < i are those of the previous steps; only row i is computed per layer — its
+// K | V appended to kvself[l][:, i], its update carried to the next layer in xc [B][E] — and the query of position i runs through every
+// layer: 3 D + 1 row-block passes per step (content row of layers 0 .. D-2, query of layers 0 .. D-1, K | V rows of every layer), no host sync.
 template <typename T, int E>
-static int stream_layer(parseq_plan* p, hipStream_t s, int l, bool content, int B, int Lq, int i0, float* x, int Lk,
-                        const unsigned char* amask, const unsigned char* kpm) {
-    const parseq_model* m = p->m;
-    const parseq_config& c = m->cfg;
-    const int M = B * Lq, Fd = E * c.dec_mlp_ratio, npos = c.max_label_length + 1;
-    const Weights<T> W = weights_of<T>(p);
-    const std::string d = "decoder.layers." + std::to_string(l) + ".", nrm = d + (content ? "norm_c." : "norm_q.");
-    T* sa = reinterpret_cast<T*>(p->sa); T* ca = reinterpret_cast<T*>(p->ca); T* hdn = reinterpret_cast<T*>(p->hdn);
-    const float scale = sqrtf(1.0f / (float)DEC_HD);
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, m->p(nrm + "weight"), m->p(nrm + "bias"), c.dec_ln_eps,
-                     W.w(d + "self_attn.in_proj_weight"), M, E, epi_store<float>(M, E, m->p(d + "self_attn.in_proj_bias"), p->qc, E, scale), p->tn))); }
-    {
-        ProfScope ps_(&p->prof, T_DEC_SA, s);
-        hipLaunchKernelGGL((dec_self_attn_kv_kernel<T, E>), dim3(M), dim3(E), 0, s, p->qc, reinterpret_cast<const T*>(p->kvself[l]), npos,
-                           amask, LDT, kpm, LDT, Lk, i0, Lq, sa);
-        HIPCHK(hipGetLastError());
-    }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{sa, E}, W.w(d + "self_attn.out_proj.weight"), E, M, E, E,
-                     epi_resid(M, E, m->p(d + "self_attn.out_proj.bias"), x, E)))); }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, m->p(d + "norm1.weight"), m->p(d + "norm1.bias"), c.dec_ln_eps,
-                     W.w(d + "cross_attn.in_proj_weight"), M, E, epi_store<float>(M, E, m->p(d + "cross_attn.in_proj_bias"), p->qc, E), p->tn))); }
-    {
-        ProfScope ps_(&p->prof, T_DEC_CA, s);
-        CHK((run_cross_attention<T, E>(p, s, B, Lq, scale, ca, QAsm{}, l)));
-    }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{ca, E}, W.w(d + "cross_attn.out_proj.weight"), E, M, E, E,
-                     epi_resid(M, E, m->p(d + "cross_attn.out_proj.bias"), x, E)))); }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, x, m->p(d + "norm2.weight"), m->p(d + "norm2.bias"), c.dec_ln_eps,
-                     W.w(d + "linear1.weight"), M, Fd, epi_gelu<T>(M, Fd, m->p(d + "linear1.bias"), hdn, Fd), p->tn))); }
-    { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_gemm<T>(s, ARowMajor<T>{hdn, Fd}, W.w(d + "linear2.weight"), Fd, M, E, Fd,
-                     epi_resid(M, E, m->p(d + "linear2.bias"), x, E)))); }
-    return 0;
-}
-
-// model.decode + head over a whole context: content tokens p->tok[:, :Lc] under the content mask `cmask` ([npos][LDT], rows = content
-// positions), queries pos_queries[i0 : i0 + Lq] (or the caller's `user_query`) under `qmask`, key padding `kpm` for both streams.
-// NAR (Lc = 1, no masks), refinement (Lc = num_steps, cloze mask for both streams) and the decode entry points.
-template <typename T, int E>
-static int deep_pass_e(parseq_plan* p, hipStream_t s, int B, int Lc, int i0, int Lq, const unsigned char* qmask, const unsigned char* cmask,
-                       const unsigned char* kpm, float* logits, int Ltot, const float* user_query) {
+static int decoder_pass(parseq_plan* p, hipStream_t s, const DecW<T>& w, const DecPass& a) {
     const int D = p->m->cfg.dec_depth;
-    CHK(content_rows<E>(p, s, B, Lc, 0));
+    if constexpr (sizeof(T) == 2 && E <= 384) {
+        if (a.fused_step_allowed && a.Lq == 1 && !a.qmask && !a.kpm && !a.user_query) return step_pre_post<E>(p, s, w, a);
+    }
+    DecPass cs = a; cs.i0 = a.c0; cs.Lq = a.Lk - a.c0; cs.qmask = a.cmask;      // the content stream's rows
+    if (D > 1) CHK(content_rows<E>(p, s, w.text_embed, w.pos_queries, a.B, cs.Lq, cs.i0));
     for (int l = 0; l < D; ++l) {
-        CHK((kv_rows<T, E>(p, s, l, B * Lc, p->xc, Lc, 0)));      // before the content update below reads and overwrites xc
-        if (l < D - 1) CHK((stream_layer<T, E>(p, s, l, true, B, Lc, 0, p->xc, Lc, cmask, kpm)));
-        if (l == 0) CHK((decode_pass_e<T, E>(p, s, B, Lc, i0, Lq, qmask, kpm, logits, Ltot, 0, false, user_query, true)));
-        else CHK((stream_layer<T, E>(p, s, l, false, B, Lq, i0, p->t, Lc, qmask, kpm)));
+        const DecLayerW<T>& y = w.layer[l];
+        if (D > 1) CHK((kv_rows<T, E>(p, s, y, l, a.B * cs.Lq, cs.Lq, cs.i0)));      // K | V rows before the content update reads and overwrites xc
+        if (l < D - 1) {
+            CHK((self_attn_queries<T, E>(p, s, y, cs, true, p->kvself[l], p->xc, p->xc)));
+            CHK((cross_mlp<T, E>(p, s, y, l, a.B, cs.Lq, p->xc)));
+        }
+        if (l > 0) CHK((self_attn_queries<T, E>(p, s, y, a, false, p->kvself[l], p->t, p->t)));
+        else if (a.user_query) CHK((self_attn_queries<T, E>(p, s, y, a, false, nullptr, a.user_query, p->t)));
+        else CHK((self_attn_tables<T, E>(p, s, w, a)));
+        CHK((cross_mlp<T, E>(p, s, y, l, a.B, a.Lq, p->t)));
     }
-    return head_pass<T, E>(p, s, B, i0, Lq, logits, Ltot, 0);
-}
-
-// AR step i (model.py:123-141) with the per-layer content cache: the content mask of the AR loop is causal (tgt_mask[:j, :j]), so the
-// content rows of positions < i are those of the previous steps.  Only row i is computed per layer — its K | V appended to
-// kvself[l][:, i], its update carried to the next layer in xc [B][E] — and the query of position i runs through every layer.
-// 3 D + 1 row-block passes per step (content row of layers 0 .. D-2, query of layers 0 .. D-1, K | V rows of every layer), no host sync.
-template <typename T, int E>
-static int deep_ar_step_e(parseq_plan* p, hipStream_t s, int B, int i, float* logits, int Ltot, int argmax_mode) {
-    const int D = p->m->cfg.dec_depth;
-    CHK(content_rows<E>(p, s, B, 1, i));
-    for (int l = 0; l < D; ++l) {
-        CHK((kv_rows<T, E>(p, s, l, B, p->xc, 1, i)));
-        if (l < D - 1) CHK((stream_layer<T, E>(p, s, l, true, B, 1, i, p->xc, i + 1, nullptr, nullptr)));
-        if (l == 0) CHK((decode_pass_e<T, E>(p, s, B, i + 1, i, 1, nullptr, nullptr, logits, Ltot, 0, false, nullptr, true)));
-        else CHK((stream_layer<T, E>(p, s, l, false, B, 1, i, p->t, i + 1, nullptr, nullptr)));
-    }
-    return head_pass<T, E>(p, s, B, i, 1, logits, Ltot, argmax_mode);
-}
-
-template <typename T>
-static int deep_pass(parseq_plan* p, hipStream_t s, int B, int Lc, int i0, int Lq, const unsigned char* qmask, const unsigned char* cmask,
-                     const unsigned char* kpm, float* logits, int Ltot, const float* user_query = nullptr) {
-    switch (p->m->cfg.embed_dim) {
-        case 192: return deep_pass_e<T, 192>(p, s, B, Lc, i0, Lq, qmask, cmask, kpm, logits, Ltot, user_query);
-        case 384: return deep_pass_e<T, 384>(p, s, B, Lc, i0, Lq, qmask, cmask, kpm, logits, Ltot, user_query);
-        default:  return deep_pass_e<T, 768>(p, s, B, Lc, i0, Lq, qmask, cmask, kpm, logits, Ltot, user_query);
-    }
-}
-
-template <typename T>
-static int deep_ar_step(parseq_plan* p, hipStream_t s, int B, int i, float* logits, int Ltot, int argmax_mode) {
-    switch (p->m->cfg.embed_dim) {
-        case 192: return deep_ar_step_e<T, 192>(p, s, B, i, logits, Ltot, argmax_mode);
-        case 384: return deep_ar_step_e<T, 384>(p, s, B, i, logits, Ltot, argmax_mode);
-        default:  return deep_ar_step_e<T, 768>(p, s, B, i, logits, Ltot, argmax_mode);
-    }
+    return head_pass<T, E>(p, s, w, a);
 }
 
 // The whole AR loop with the mid / cross-attention / mlp arrangement of decoder_step.h (bf16 or, X3, the bf16x3 arithmetic on f32
 // storage; E <= 384): step i's logits are produced by the mid kernel of step i + 1 (and by one trailing finish-only launch after
 // the last step).
-template <int E, bool X3 = false>
-static int ar_loop_fused(parseq_plan* p, hipStream_t s, int B, int num_steps, float* logits, bool testing, bool latency) {
-    const parseq_model* m = p->m;
-    const parseq_config& c = m->cfg;
-    const int M = B, C = m->classes, npos = c.max_label_length + 1;
-    const std::string d = "decoder.layers.0.";
+template <int E, bool X3, typename TS = typename std::conditional<X3, float, bf16_t>::type>      // TS: storage type of kvtab, the memory K / V and ca
+static int ar_loop_fused(parseq_plan* p, hipStream_t s, const DecW<TS>& w, int B, int num_steps, float* logits, bool testing, bool qsplit) {
+    const parseq_config& c = p->m->cfg;
+    const DecLayerW<TS>& y = w.layer[0];
+    const int M = B, C = p->m->classes, npos = c.max_label_length + 1;
     int* eos_rows = p->counters; int* ar_len = p->counters + 1;
-    using TS = typename std::conditional<X3, float, bf16_t>::type;      // storage type of kvtab, the memory K / V and ca
     TS* ca = reinterpret_cast<TS*>(p->ca);
     float* partial = reinterpret_cast<float*>(p->hdn);                    // linear2 partial sums [ds_split][M][E] f32 (the generic path's MLP hidden buffer is idle here)
     float* tq = p->qc;                                                    // t' lives in the q-projection buffer once the cross-attention has consumed it
     float* t = p->t;
-    int* tok = p->tok;
-    unsigned char* eos_seen = p->eos_seen;
-    const float scale = sqrtf(1.0f / (float)DEC_HD);
     const dim3 grid((M + DS_ROWS - 1) / DS_ROWS), block(64 * DS_NW);
     static LdsAttr attr_mid, attr_midq, attr_mlp;
     HIPCHK(attr_mid.ensure(reinterpret_cast<const void*>(dec_step_mid_kernel<E, X3>), dec_step_mid_lds<E, X3>()));
     HIPCHK(attr_midq.ensure(reinterpret_cast<const void*>(dec_step_mid_kernel<E, X3, DS_QS>), dec_step_mid_lds<E, X3>()));
     HIPCHK(attr_mlp.ensure(reinterpret_cast<const void*>(dec_step_mlp_kernel<E, X3>), dec_step_mlp_lds<E, X3>()));
-    // The start half of the mid kernel split over DS_QS workgroups per row tile (decoder_step.h): the q-projection arrives at the
+    // qsplit (dec_route): the start half of the mid kernel split over DS_QS workgroups per row tile (decoder_step.h): the q-projection arrives at the
     // cross-attention as partial sums behind t' in the q buffer ([M][E] t' | [DS_QS][M][E] partials | [DS_QS][M][2] column sums; the buffer
     // holds npos rows per image).  Only the two AR cross-attention kernels know how to read that (128 memory tokens).
     // Taken when the caller says this forward is alone on the device (PARSEQ_FLAG_LATENCY): the wider step is a shorter chain but costs
     // about twice the compute-unit time, which batches in flight on other streams would rather have (profiles/r04_ar_step_timers.md).
-    const bool qsplit = latency && p->qsplit && m->tokens == 128 && npos >= DS_QS + 2;
     float* qp = tq + (size_t)M * E;
     float* qstats = qp + (size_t)DS_QS * M * E;
     QAsm qa;
@@ -360,66 +398,48 @@ static int ar_loop_fused(parseq_plan* p, hipStream_t s, int B, int num_steps, fl
             ProfScope ps_(&p->prof, T_DEC_PRE, s);
             const auto mid = qsplit ? dec_step_mid_kernel<E, X3, DS_QS> : dec_step_mid_kernel<E, X3, 1>;
             hipLaunchKernelGGL(mid, dim3(grid.x * (qsplit ? DS_QS : 1)), block, (dec_step_mid_lds<E, X3>()), s, do_finish, do_start, i, M,
-                               tq, partial, m->p(d + "linear2.bias"), m->p("decoder.norm.weight"), m->p("decoder.norm.bias"), c.dec_ln_eps,
-                               p->wstep[5], m->p("head.bias"), C, logits, num_steps, argmax_mode, c.eos_id, eos_seen, eos_rows, ar_len,
-                               p->stab, reinterpret_cast<const TS*>(p->kvtab), tok, LDT, c.num_tokens, npos, p->wstep[0],
-                               m->p(d + "self_attn.out_proj.bias"), m->p("pos_queries"), m->p(d + "norm1.weight"), m->p(d + "norm1.bias"),
-                               p->wstep[1], m->p(d + "cross_attn.in_proj_bias"), t, qsplit ? qp : tq, p->qfold, qstats);
+                               tq, partial, y.lin2_b, w.norm.g, w.norm.b, c.dec_ln_eps, p->wstep[5], w.head_b, C, logits, num_steps, argmax_mode,
+                               c.eos_id, p->eos_seen, eos_rows, ar_len, p->stab, reinterpret_cast<const TS*>(p->kvtab), p->tok, LDT, c.num_tokens, npos,
+                               p->wstep[0], y.sa_out_b, w.pos_queries, y.norm1.g, y.norm1.b, p->wstep[1], y.ca_in_b, t, qsplit ? qp : tq, p->qfold, qstats);
             HIPCHK(hipGetLastError());
         }
         if (!do_start) break;
-        {
-            ProfScope ps_(&p->prof, T_DEC_CA, s);
-            CHK((run_cross_attention<TS, E>(p, s, B, 1, scale, ca, qa)));
-        }
+        CHK((run_cross_attention<TS, E>(p, s, 0, B, 1, ca, qa)));
         {
             ProfScope ps_(&p->prof, T_DEC_POST, s);
             hipLaunchKernelGGL((dec_step_mlp_kernel<E, X3>), dim3(grid.x * ds_split<E>()), block, (dec_step_mlp_lds<E, X3>()), s, ca, t, p->wstep[2],
-                               m->p(d + "cross_attn.out_proj.bias"), m->p(d + "norm2.weight"), m->p(d + "norm2.bias"), c.dec_ln_eps,
-                               p->wstep[3], m->p(d + "linear1.bias"), p->wstep[4], tq, partial, M);
+                               y.ca_out_b, y.norm2.g, y.norm2.b, c.dec_ln_eps, p->wstep[3], y.lin1_b, p->wstep[4], tq, partial, M);
             HIPCHK(hipGetLastError());
         }
     }
     return 0;
 }
 
-template <typename T>
+template <typename T, int E>
 static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int num_steps, float* logits, int* out_len, hipStream_t s) {
-    const parseq_model* m = p->m;
-    const parseq_config& c = m->cfg;
-    const int C = m->classes;
-    const bool ar = flags & PARSEQ_FLAG_DECODE_AR, testing = flags & PARSEQ_FLAG_TESTING, latency = flags & PARSEQ_FLAG_LATENCY;
-    int* eos_rows = p->counters; int* ar_len = p->counters + 1;
+    const parseq_config& c = p->m->cfg;
+    const int C = p->m->classes;
+    const bool ar = flags & PARSEQ_FLAG_DECODE_AR, testing = flags & PARSEQ_FLAG_TESTING;
+    const DecW<T> w = dec_weights<T>(p);
+    const DecRoute route = dec_route(p, flags & PARSEQ_FLAG_LATENCY);
+    DecPass a; a.B = B; a.logits = logits; a.Ltot = num_steps; a.fused_step_allowed = route.step == STEP_FUSED;
     hipLaunchKernelGGL(ar_init_kernel, dim3((B * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, B, c.bos_id, c.pad_id, p->eos_seen, p->counters, 2, num_steps);
     HIPCHK(hipGetLastError());
-    if (ar) {
-        // model.py:119-147.  All num_steps steps are always run (no per-step host sync); the step at which the reference
-        // would have stopped is recorded on the device and only truncates the returned view.
-        const bool deep = c.dec_depth > 1;      // the fused step is a depth-1 kernel; deeper decoders run deep_ar_step
-        bool done = false;
-        if constexpr (sizeof(T) == 2) {
-            if (!deep && p->wstep[0] && p->fused_step && C <= 128 && c.dec_mlp_ratio == 4) {
-                if (c.embed_dim == 384) { CHK((ar_loop_fused<384>(p, s, B, num_steps, logits, testing, latency))); done = true; }
-                else if (c.embed_dim == 192) { CHK((ar_loop_fused<192>(p, s, B, num_steps, logits, testing, latency))); done = true; }
-            }
-        } else {
-            // bf16x3: the same fused step on bf16 pairs (f32 tables, f32 memory K / V); the fp32 mode keeps the per-op kernels
-            if (!deep && p->precision == PARSEQ_BF16X3 && p->wstep[0] && p->fused_step && C <= 128 && c.dec_mlp_ratio == 4) {
-                if (c.embed_dim == 384) { CHK((ar_loop_fused<384, true>(p, s, B, num_steps, logits, testing, latency))); done = true; }
-                else if (c.embed_dim == 192) { CHK((ar_loop_fused<192, true>(p, s, B, num_steps, logits, testing, latency))); done = true; }
-            }
-        }
-        for (int i = 0; !done && i < num_steps; ++i) {
-            // greedy pick of position i into tok[:, i + 1] (+ EOS bookkeeping) rides on the step; the last step needs none
-            const int argmax_mode = i + 1 < num_steps ? (testing ? 2 : 1) : 0;
-            if (deep) CHK((deep_ar_step<T>(p, s, B, i, logits, num_steps, argmax_mode)));
-            else CHK((decode_pass<T>(p, s, B, i + 1, i, 1, nullptr, nullptr, logits, num_steps, argmax_mode)));
-        }
-    } else if (c.dec_depth > 1) {
-        CHK((deep_pass<T>(p, s, B, 1, 0, num_steps, nullptr, nullptr, nullptr, logits, num_steps)));
-    } else {
+    // model.py:119-147.  All num_steps steps are always run (no per-step host sync); the step at which the reference
+    // would have stopped is recorded on the device and only truncates the returned view.
+    bool stepwise = ar;      // one decoder_pass per AR step, unless the fused loop runs them all
+    if constexpr (E <= 384) {
+        if (ar && route.step == STEP_FUSED) { CHK((ar_loop_fused<E, sizeof(T) == 4>(p, s, w, B, num_steps, logits, testing, route.qsplit))); stepwise = false; }
+    }
+    for (int i = 0; stepwise && i < num_steps; ++i) {
+        // greedy pick of position i into tok[:, i + 1] (+ EOS bookkeeping) rides on the step; the last step needs none
+        a.Lk = i + 1; a.i0 = a.c0 = i; a.Lq = 1; a.argmax_mode = i + 1 < num_steps ? (testing ? 2 : 1) : 0;
+        CHK((decoder_pass<T, E>(p, s, w, a)));
+    }
+    if (!ar) {
         // model.py:148-152: context is <bos> only, all positions queried at once
-        CHK((decode_pass<T>(p, s, B, 1, 0, num_steps, nullptr, nullptr, logits, num_steps)));
+        a.Lk = 1; a.Lq = num_steps;
+        CHK((decoder_pass<T, E>(p, s, w, a)));
     }
     for (int it = 0; it < refine_iters; ++it) {
         // model.py:154-167
@@ -431,8 +451,8 @@ static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int 
         // dec_depth > 1: the content stream under the same cloze-edited mask (model.py:117, 157: tgt_mask and query_mask are one tensor) over
         // all num_steps positions, those past a row's first EOS key-padded.  After an AR early exit at L < num_steps that is the reference
         // with tgt_mask[:L, :L] (it raises there: a [num_steps, num_steps] mask against L content tokens)
-        if (c.dec_depth > 1) CHK((deep_pass<T>(p, s, B, num_steps, 0, num_steps, p->cloze, p->cloze, p->kpm, logits, num_steps)));
-        else CHK((decode_pass<T>(p, s, B, num_steps, 0, num_steps, p->cloze, p->kpm, logits, num_steps)));
+        a.Lk = a.Lq = num_steps; a.i0 = a.c0 = 0; a.qmask = a.cmask = p->cloze; a.kpm = p->kpm; a.argmax_mode = 0;
+        CHK((decoder_pass<T, E>(p, s, w, a)));
     }
     int L = num_steps;
     if (ar && testing && refine_iters == 0) {
@@ -464,13 +484,10 @@ extern "C" int parseq_vitstr_forward(parseq_plan* p, const void* images, int ima
     // The head runs over every token row of the batch (one plain GEMM on the normalised features); the wanted rows are sliced out.
     float* all = reinterpret_cast<float*>(p->h);           // [batch * N][C] scratch (the MLP hidden buffer is idle here)
     const int M = batch * N;
-    if (p->precision == PARSEQ_BF16) {
-        const Weights<bf16_t> W = weights_of<bf16_t>(p);
-        CHK((run_gemm<bf16_t>(s, ARowMajor<bf16_t>{reinterpret_cast<const bf16_t*>(p->xn), E}, W.w("head.weight"), E, M, C, E, epi_store<float>(M, C, m->p("head.bias"), all, C))));
-    } else {
-        const Weights<float> W = weights_of<float>(p);
-        CHK((run_gemm<float>(s, ARowMajor<float>{reinterpret_cast<const float*>(p->xn), E}, W.w("head.weight"), E, M, C, E, epi_store<float>(M, C, m->p("head.bias"), all, C))));
-    }
+    CHK(dispatch_t(p, [&](auto te) {
+        using T = typename decltype(te)::T;
+        return run_gemm<T>(s, ARowMajor<T>{reinterpret_cast<const T*>(p->xn), E}, weights_of<T>(p).w("head.weight"), E, M, C, E, epi_store<float>(M, C, m->p("head.bias"), all, C));
+    }));
     HIPCHK(hipMemcpy2DAsync(logits_out, (size_t)num_steps * C * sizeof(float), all + (size_t)C, (size_t)N * C * sizeof(float),
                             (size_t)num_steps * C * sizeof(float), batch, hipMemcpyDeviceToDevice, s));
     return 0;
@@ -490,8 +507,7 @@ extern "C" int parseq_forward(parseq_plan* p, const void* images, int images_dty
     CHK(encode_dispatch(p, images, images_dtype, batch, nullptr, s));
     // (A decoder stream of its own with hipStreamCreateWithPriority(greatest), forked and joined by events, was measured and removed:
     // 121 -> 108 k img/s with two forwards in flight, 107 -> 58 k one at a time — profiles/r03_decoder_priority_stream_ab.md.)
-    if (p->precision == PARSEQ_BF16) return forward_impl<bf16_t>(p, batch, flags, refine_iters, num_steps, logits_out, out_len, s);
-    return forward_impl<float>(p, batch, flags, refine_iters, num_steps, logits_out, out_len, s);
+    return dispatch_te(p, [&](auto te) { return forward_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, flags, refine_iters, num_steps, logits_out, out_len, s); });
 }
 
 static int decode_entry(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len, const uint8_t* query_mask,
@@ -518,28 +534,26 @@ static int decode_entry(parseq_plan* p, const int32_t* tokens, int batch, int ct
         HIPCHK(hipMemcpy2DAsync(p->qmask_user + (size_t)q_start * LDT, LDT, query_mask, ctx_len, ctx_len, q_len, hipMemcpyDeviceToDevice, s));
         qm = p->qmask_user;
     }
-    const bool deep = p->m->cfg.dec_depth > 1;
     const unsigned char* cm = nullptr;
-    if (content_mask && deep) {      // depth 1 never updates the content stream, so the reference never reads its mask (modules.py:119-124)
+    if (content_mask && p->m->cfg.dec_depth > 1) {      // depth 1 never updates the content stream, so the reference never reads its mask (modules.py:119-124)
         HIPCHK(hipMemcpy2DAsync(p->cmask_user, LDT, content_mask, ctx_len, ctx_len, ctx_len, hipMemcpyDeviceToDevice, s));
         cm = p->cmask_user;
     }
-    const bool keep_t = hidden_out != nullptr;
-    // decode_pass writes logits[b][q_start + qi] of a [B][Ltot][C] tensor (the forward's layout).  Here the caller's tensor is
+    // A pass writes logits[b][q_start + qi] of a [B][Ltot][C] tensor (the forward's layout).  Here the caller's tensor is
     // [batch][q_len][C] with row qi: hand over the base shifted back by q_start rows, so that the rows written are exactly
     // [b * q_len + qi] (writing at b * q_len + q_start + qi ran q_start rows past the end of the buffer for q_start > 0).
-    float* lbase = logits_out - (size_t)q_start * p->m->classes;
-    if (deep) {
-        if (p->precision == PARSEQ_BF16) CHK((deep_pass<bf16_t>(p, s, batch, ctx_len, q_start, q_len, qm, cm, kpm, lbase, q_len, user_query)));
-        else CHK((deep_pass<float>(p, s, batch, ctx_len, q_start, q_len, qm, cm, kpm, lbase, q_len, user_query)));
-    } else if (p->precision == PARSEQ_BF16) CHK((decode_pass<bf16_t>(p, s, batch, ctx_len, q_start, q_len, qm, kpm, lbase, q_len, 0, keep_t, user_query)));
-    else CHK((decode_pass<float>(p, s, batch, ctx_len, q_start, q_len, qm, kpm, lbase, q_len, 0, keep_t, user_query)));
-    if (hidden_out) {      // model.decode's return value: decoder.norm of the query stream (modules.py:124), fp32
-        const parseq_model* m = p->m;
-        CHK((run_layernorm<float>(s, p->t, m->p("decoder.norm.weight"), m->p("decoder.norm.bias"), hidden_out, nullptr, batch * q_len,
-                                  m->cfg.embed_dim, m->cfg.dec_ln_eps)));
-    }
-    return 0;
+    DecPass a; a.B = batch; a.Lk = ctx_len; a.i0 = q_start; a.Lq = q_len; a.qmask = qm; a.cmask = cm; a.kpm = kpm;
+    a.logits = logits_out - (size_t)q_start * p->m->classes; a.Ltot = q_len; a.user_query = user_query;
+    a.fused_step_allowed = dec_route(p, false).step == STEP_FUSED && !hidden_out;      // hidden_out reads the query stream in p->t
+    return dispatch_te(p, [&](auto te) {
+        using T = typename decltype(te)::T;
+        constexpr int E = decltype(te)::E;
+        const DecW<T> w = dec_weights<T>(p);
+        CHK((decoder_pass<T, E>(p, s, w, a)));
+        // model.decode's return value: decoder.norm of the query stream (modules.py:124), fp32
+        if (hidden_out) CHK((run_layernorm<float>(s, p->t, w.norm.g, w.norm.b, hidden_out, nullptr, batch * q_len, E, p->m->cfg.dec_ln_eps)));
+        return 0;
+    });
 }
 
 extern "C" int parseq_decode_logits(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len,
@@ -590,12 +604,13 @@ static int set_memory_impl(parseq_plan* p, const float* memory, int B, hipStream
     }
     p->kv24 = false;      // rows in the storage type from the generic GEMM
     for (int l = 0; l < c.dec_depth; ++l) {      // every decoder layer's K / V
-        const std::string d = "decoder.layers." + std::to_string(l) + ".cross_attn.";
-        EpiHeads<T> ek; static_cast<EpiBase&>(ek) = epi_base(M, 2 * E, m->p(d + "in_proj_bias") + E);
+        const T* w_in; const float* b_in;
+        ca_in_proj(W, dec_layer_key(l), w_in, b_in);
+        EpiHeads<T> ek; static_cast<EpiBase&>(ek) = epi_base(M, 2 * E, b_in + E);
         ek.seg[0] = reinterpret_cast<T*>(l ? p->kmem_l[l] : p->kmem); ek.seg[1] = reinterpret_cast<T*>(l ? p->vmem_l[l] : p->vmem); ek.seg[2] = nullptr;
         ek.E = E; ek.heads = c.dec_heads; ek.hd = DEC_HD; ek.tokens = N; ek.tr_from = 2;
         ProfScope ps_(&p->prof, T_KVMEM, s);
-        CHK((run_gemm<T>(s, ARowMajor<T>{a, E}, W.w(d + "in_proj_weight") + (size_t)E * E, E, M, 2 * E, E, ek, E % 128 != 0)));
+        CHK((run_gemm<T>(s, ARowMajor<T>{a, E}, w_in + (size_t)E * E, E, M, 2 * E, E, ek, E % 128 != 0)));
     }
     p->last_batch = B;
     return 0;
@@ -608,6 +623,5 @@ extern "C" int parseq_set_memory(parseq_plan* p, const float* memory, int batch,
     if (p->packed_version != p->m->version) return fail(PARSEQ_E_STATE, "model parameters changed after the plan was packed; call parseq_plan_refresh");
     DevGuard dg(p->m->device);
     SplitScope ss(p->precision == PARSEQ_BF16X3);
-    if (p->precision == PARSEQ_BF16) return set_memory_impl<bf16_t>(p, memory, batch, (hipStream_t)stream);
-    return set_memory_impl<float>(p, memory, batch, (hipStream_t)stream);
+    return dispatch_t(p, [&](auto te) { return set_memory_impl<typename decltype(te)::T>(p, memory, batch, (hipStream_t)stream); });
 }

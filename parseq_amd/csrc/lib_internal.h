@@ -1,6 +1,6 @@
 // lib_internal.h — what the translation units of libparseq_hip.so share: error reporting, the device guard, the per-family
 // event profiler, the model / plan objects behind include/parseq_hip.h and the launch helpers of the generic kernels.
-// The library is split into lib_model.hip (model + plan objects), lib_infer.hip (encode / decode / forward),
+// The library is split into lib_model.hip (model + plan objects), lib_encode.hip / lib_decode.hip (encode; decode / forward),
 // lib_train.hip (training step) and lib_ops.hip (per-kernel test entry points, resize, post-process) so that build() compiles
 // them in parallel; kernels are templates or file-local (`static __global__`), so every unit carries the instantiations it launches.
 #pragma once
@@ -263,7 +263,7 @@ struct parseq_plan {
     void *xn = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *ao = nullptr, *h = nullptr;
     void *kmem = nullptr, *vmem = nullptr;   // cross-attention K and V of memory, head-split [B][H][N][32]
     float* stab = nullptr;         // [npos][npos][num_tokens][H] self-attention score table
-    void *sa = nullptr, *tn = nullptr, *ca = nullptr, *hdn = nullptr;   // tn: unused since LayerNorm moved into the GEMM A-loaders
+    void *sa = nullptr, *tn = nullptr, *ca = nullptr, *hdn = nullptr;   // tn: LayerNorm scratch of run_ln_gemm (bf16x3 at M >= 4096)
     float *t = nullptr, *qc = nullptr;
     int* tok = nullptr;            // [B][LDT]
     unsigned char* kpm = nullptr;  // [B][LDT]
