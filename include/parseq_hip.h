@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 10
+#define PARSEQ_ABI_VERSION 11
 
 /* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
 #define PARSEQ_DEC_DEPTH_MAX 4
@@ -250,6 +250,28 @@ int parseq_postprocess(const float* logits, int batch, int L, int C, int eos_id,
  * loss_out / numel_out: device scalars; workspace: device, `rows` floats.  Deterministic (fixed summation order). */
 int parseq_cross_entropy(const float* logits, const int32_t* targets, int rows, int C, int ignore_index, float* loss_out,
                          int32_t* numel_out, float* workspace, void* stream);
+
+/* (ABI 11) The per-sample loop of BaseSystem._eval_step (strhub/models/base.py:132-143) on the device: greedy decode, test-charset
+ * adapter, edit distance, exact match and the running totals the reference's test.py:115-126 sums on the host — nothing is copied back,
+ * nothing is allocated, the call does not synchronise.
+ *   logits         device fp32 [batch, L, C] contiguous, L <= 32 (max_label_length + 1)
+ *   adapter_table  device int32 [C]: the Unicode code point CharsetAdapter (strhub/data/utils.py:26-43) turns train token id into, or
+ *                  -1 for a token it drops (the entry of eos_id is never read)
+ *   gt, gt_len     device int32 [batch, gt_width] code points of the labels (any padding) and int32 [batch] their lengths;
+ *                  1 <= gt_width <= PARSEQ_EVAL_MAX_GT, a wider array is refused with PARSEQ_E_INVALID; lengths are clamped to gt_width
+ *   ids_out, lengths_out, confidence_out   int32 [batch, L], int32 [batch], fp32 [batch]: exactly what parseq_postprocess writes
+ *                  for these logits (the same kernel runs first)
+ *   rows_out       int32 [batch, 4]: length of the adapted prediction, length of the label, Levenshtein distance between them (unit
+ *                  costs, no transpositions: nltk.edit_distance's defaults, base.py:138), 1 if they are equal else 0
+ *   workspace      device, `batch` doubles (each row's distance / max(len(pred), len(gt), 1))
+ *   accum          device, PARSEQ_EVAL_ACCUM_BYTES: int64 num_samples, correct, label_length; double ned, confidence — ACCUMULATED
+ *                  into (zero it to start an evaluation).  The batch is summed in a fixed order by one workgroup, so equal inputs give
+ *                  bit-identical totals; calls that share an accumulator must be ordered (one stream). */
+#define PARSEQ_EVAL_MAX_GT 256
+#define PARSEQ_EVAL_ACCUM_BYTES 40
+int parseq_eval_metrics(const float* logits, int batch, int L, int C, int eos_id, const int32_t* adapter_table, const int32_t* gt,
+                        const int32_t* gt_len, int gt_width, int32_t* ids_out, int32_t* lengths_out, float* confidence_out,
+                        int32_t* rows_out, double* workspace, void* accum, void* stream);
 
 /* ---- "next" row N3: training step, decoder side (strhub/models/parseq/system.py:168-199 + loss.backward()) ---------- */
 

@@ -16,7 +16,7 @@ from . import build as _build
 PARSEQ_F32, PARSEQ_BF16, PARSEQ_U8, PARSEQ_BF16X3 = 0, 1, 2, 3
 ARCH_PARSEQ, ARCH_VITSTR = 0, 1
 FLAG_DECODE_AR, FLAG_TESTING, FLAG_LATENCY = 1, 2, 4
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class ParseqConfig(C.Structure):
@@ -54,6 +54,8 @@ SIGNATURES = {
     'parseq_resize_bicubic': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_cross_entropy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'parseq_eval_metrics': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_plan_set_profiling': (C.c_int, [C.c_void_p, C.c_int]),
     'parseq_plan_get_profile': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'parseq_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -210,7 +212,7 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def guard(device):
     """Context manager making `device` (torch.device or tensor) current: for the raw-pointer entry points (parseq_op_*,
-    parseq_postprocess, parseq_resize_bicubic, parseq_cross_entropy, parseq_grad_norm), which launch on the current device."""
+    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_cross_entropy, parseq_grad_norm), which launch on the current device."""
     import torch
     if hasattr(device, 'device'):
         device = device.device

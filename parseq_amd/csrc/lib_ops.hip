@@ -1,5 +1,6 @@
 // libparseq_hip.so — input resize, post-process, and the per-kernel entry points the parity tests call.
 #include "lib_internal.h"
+#include "eval_metrics.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 static int resize_taps(int in_size, int out_size) {
@@ -55,6 +56,28 @@ extern "C" int parseq_cross_entropy(const float* logits, const int32_t* targets,
     hipLaunchKernelGGL(ce_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, targets, rows, C, ignore_index, workspace);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, workspace, targets, rows, ignore_index, loss_out, numel_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// evaluation metrics (eval_metrics.h): replaces the per-sample host loop of strhub/models/base.py:132-143
+// -------------------------------------------------------------------------------------------------------------------
+extern "C" int parseq_eval_metrics(const float* logits, int batch, int L, int C, int eos_id, const int32_t* adapter_table, const int32_t* gt,
+                                   const int32_t* gt_len, int gt_width, int32_t* ids_out, int32_t* lengths_out, float* confidence_out,
+                                   int32_t* rows_out, double* workspace, void* accum, void* stream) {
+    static_assert(EVAL_MAX_GT == PARSEQ_EVAL_MAX_GT && sizeof(EvalAccum) == PARSEQ_EVAL_ACCUM_BYTES && EVAL_MAX_PRED == DEC_MAXL, "header and kernel limits must agree");
+    if (!logits || !adapter_table || !gt || !gt_len || !ids_out || !lengths_out || !confidence_out || !rows_out || !workspace || !accum)
+        return fail(PARSEQ_E_INVALID, "null argument");
+    if (batch <= 0 || L < 1 || L > EVAL_MAX_PRED || C < 1) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, L %d (1..%d), C %d", batch, L, EVAL_MAX_PRED, C);
+    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
+    if (gt_width < 1 || gt_width > EVAL_MAX_GT) return fail(PARSEQ_E_INVALID, "ground truth of %d code points per row: the limit is %d", gt_width, EVAL_MAX_GT);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(postprocess_kernel, dim3((batch + 3) / 4), dim3(256), 0, s, logits, batch, L, C, eos_id, ids_out, lengths_out, (float*)nullptr, confidence_out);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(eval_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, s, ids_out, lengths_out, batch, L, C, adapter_table, gt, gt_len, gt_width, rows_out, workspace);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(eval_reduce_kernel, dim3(1), dim3(256), 0, s, rows_out, workspace, confidence_out, batch, reinterpret_cast<EvalAccum*>(accum));
     HIPCHK(hipGetLastError());
     return 0;
 }
