@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 11
+#define PARSEQ_ABI_VERSION 12
 
 /* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
 #define PARSEQ_DEC_DEPTH_MAX 4
@@ -475,6 +475,63 @@ int parseq_op_encoder_attention(const void* q, const void* k, const void* vt, vo
  * fewer the step's resident kernels run and neither is touched.  *route (may be NULL): 1 for the key-streaming kernels, 0 otherwise. */
 int parseq_op_train_attention(const float* qkv, float* o, float* lse, const float* d_o, float* dqkv, float* dsum, int batch, int tokens,
                               int heads, int backward, int* route, void* stream);
+
+/* (ABI 12) The training step's products and row kernels one operator at a time (tests/test_train_gemm.py).  The three hooks build
+ * the step's context from their arguments and call the internal functions the step calls, unchanged.  bf16_ops: the bf16-operand
+ * mode (parseq_model_set_train_precision(PARSEQ_BF16)).  scratch / scratch_floats: the caller's, what the step carves out of its
+ * workspace (16 Mi floats there): split-K partials, partial column sums, the LayerNorm backward's chunk partials at its end; NULL / a small
+ * one are allowed and change the route. */
+enum parseq_gemm_kernel {          /* which kernel a product ran on; bf16-operand kernels: orientation of A, B (k = contiguous along the contraction, n = along the outer axis) */
+    PARSEQ_GEMM_NONE = -1,         /* refused */
+    PARSEQ_GEMM_VALU = 0,          /* sgemm_kernel */
+    PARSEQ_GEMM_MFMA_F32 = 1,      /* mfma_sgemm_kernel: exact fp32 products */
+    PARSEQ_GEMM_BF16_KK = 2, PARSEQ_GEMM_BF16_KN = 3, PARSEQ_GEMM_BF16_NK = 4, PARSEQ_GEMM_BF16_NN = 5,   /* mfma_bgemm_kernel, both operands fp32 in memory */
+    PARSEQ_GEMM_B16_KK = 6, PARSEQ_GEMM_B16_KN = 7, PARSEQ_GEMM_B16_NK = 8, PARSEQ_GEMM_B16_NN = 9,       /* ... B a bf16 shadow */
+    PARSEQ_GEMM_A16_NN = 10,       /* ... both shadows, both outer-contiguous, 32-deep stages */
+    PARSEQ_GEMM_BOTH16_K = 11,     /* mfma_bgemm16_kernel: both shadows k-contiguous */
+    PARSEQ_GEMM_BOTH16_T = 12      /* mfma_bgemm16t_kernel: both shadows outer-contiguous, 64-deep stages */
+};
+typedef struct parseq_gemm_operand {
+    const void* data;              /* device */
+    int32_t dtype;                 /* PARSEQ_F32, or PARSEQ_BF16: a shadow */
+    int64_t outer_stride, k_stride;/* in elements: along m (A) / n (B), and along the contraction */
+} parseq_gemm_operand;
+/* C[M, N] (+)= alpha * A B + bias[n] + R[m % rper][n], times gelu'(gelu_pre) if given; dense rows of N elements everywhere */
+typedef struct parseq_train_gemm_desc {
+    parseq_gemm_operand A, B;
+    int32_t M, N, K;
+    float* C;                      /* fp32 [M, N], may be NULL when c16 is given */
+    void* c16;                     /* bf16 [M, N] or NULL */
+    const float* bias;             /* [N] or NULL */
+    const float* R; int64_t ldr; int32_t rper;      /* residual rows or NULL */
+    float alpha;
+    int32_t accumulate;
+    float* asum;                   /* [M] += row sums of A, or NULL */
+    const float* gelu_pre; const void* gelu_pre16;  /* [M, N] fp32 / bf16 or NULL */
+    float* gelu_out; void* gelu_out16;              /* [M, N] fp32 / bf16 or NULL: gelu(C) as a second output */
+    int32_t bf16_ops;
+    float* scratch; size_t scratch_floats;
+} parseq_train_gemm_desc;
+typedef struct parseq_gemm_route {
+    int32_t kernel;                /* enum parseq_gemm_kernel */
+    int32_t whole;                 /* the four-workgroups-per-CU form of the all-bf16 kernels */
+    int32_t splits, k_chunk;       /* split-K: workgroups per tile along the contraction, and the contraction range of each */
+    int32_t folded_asum, folded_gelu_pre, folded_gelu_out;   /* riders the kernel's epilogue took (the others were not run: sgemm leaves them to its caller) */
+} parseq_gemm_route;
+/* One call of the training step's sgemm().  route may be NULL.  Riders the chosen kernel does not fold are NOT run (route->folded_*). */
+int parseq_op_train_gemm(const parseq_train_gemm_desc* desc, parseq_gemm_route* route, void* stream);
+/* lin_fwd (backward == 0): y[M, N] = x[M, K] W[N, K]^T + bias + R[m % rper] (R NULL: none), gelu_out (may be NULL) = gelu(y).
+ * lin_bwd (backward != 0): dW[N, K] += dy[M, N]^T x;  db[N] += column sums of dy;  dx[M, K] = dy W (dx may be NULL), times
+ * gelu'(dx_gelu_pre[M, K]) if given.  All fp32. */
+int parseq_op_train_linear(const float* x, const float* W, const float* bias, const float* R, int rper, float* y, float* gelu_out,
+                           const float* dy, float* dW, float* db, float* dx, const float* dx_gelu_pre, int M, int N, int K, int backward,
+                           int bf16_ops, float* scratch, size_t scratch_floats, void* stream);
+/* train_ln_fwd (backward == 0): y[rows, E] = LayerNorm(x; gamma, beta, eps) in y_dtype (PARSEQ_F32 / PARSEQ_BF16).
+ * ln_bwd (backward != 0): dx = add (may be NULL) + the LayerNorm backward of dy; dgamma, dbeta += their gradients; dx16 (may be NULL): dx
+ * again as bf16.  Refused when the chunk partials (rows / 4 rounded up, times 2 E floats, + 64 E) do not fit the scratch. */
+int parseq_op_train_layernorm(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, const float* dy, const float* add,
+                              float* dx, void* dx16, float* dgamma, float* dbeta, int rows, int E, float eps, int backward, float* scratch,
+                              size_t scratch_floats, void* stream);
 
 #ifdef __cplusplus
 }

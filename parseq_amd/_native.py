@@ -16,7 +16,7 @@ from . import build as _build
 PARSEQ_F32, PARSEQ_BF16, PARSEQ_U8, PARSEQ_BF16X3 = 0, 1, 2, 3
 ARCH_PARSEQ, ARCH_VITSTR = 0, 1
 FLAG_DECODE_AR, FLAG_TESTING, FLAG_LATENCY = 1, 2, 4
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class ParseqConfig(C.Structure):
@@ -28,6 +28,26 @@ class ParseqConfig(C.Structure):
 
 class ImageDesc(C.Structure):
     _fields_ = [('data', C.c_void_p), ('height', C.c_int32), ('width', C.c_int32), ('row_stride', C.c_int64)]
+
+
+class GemmOperand(C.Structure):
+    _fields_ = [('data', C.c_void_p), ('dtype', C.c_int32), ('outer_stride', C.c_int64), ('k_stride', C.c_int64)]
+
+
+class TrainGemmDesc(C.Structure):
+    """parseq_train_gemm_desc: one call of the training step's sgemm() (parseq_op_train_gemm)."""
+    _fields_ = [('A', GemmOperand), ('B', GemmOperand), ('M', C.c_int32), ('N', C.c_int32), ('K', C.c_int32), ('C', C.c_void_p), ('c16', C.c_void_p),
+                ('bias', C.c_void_p), ('R', C.c_void_p), ('ldr', C.c_int64), ('rper', C.c_int32), ('alpha', C.c_float), ('accumulate', C.c_int32),
+                ('asum', C.c_void_p), ('gelu_pre', C.c_void_p), ('gelu_pre16', C.c_void_p), ('gelu_out', C.c_void_p), ('gelu_out16', C.c_void_p),
+                ('bf16_ops', C.c_int32), ('scratch', C.c_void_p), ('scratch_floats', C.c_size_t)]
+
+
+class GemmRoute(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ('kernel', 'whole', 'splits', 'k_chunk', 'folded_asum', 'folded_gelu_pre', 'folded_gelu_out')]
+
+
+# enum parseq_gemm_kernel, by value
+GEMM_KERNELS = ('valu', 'mfma_f32', 'bf16_kk', 'bf16_kn', 'bf16_nk', 'bf16_nn', 'b16_kk', 'b16_kn', 'b16_nk', 'b16_nn', 'a16_nn', 'both16_k', 'both16_t')
 
 
 class NativeError(RuntimeError):
@@ -120,6 +140,11 @@ SIGNATURES = {
                                               C.c_void_p]),
     'parseq_op_train_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    'parseq_op_train_gemm': (C.c_int, [C.POINTER(TrainGemmDesc), C.POINTER(GemmRoute), C.c_void_p]),
+    'parseq_op_train_linear': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_op_train_layernorm': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 

@@ -64,8 +64,9 @@ static bool mc_readable(const Operand& x, int outer) {
     return aligned16(x.p) && (x.sk == 1 ? x.so % (x.bf16 ? 8 : 4) == 0 : (x.so == 1 && x.sk % 4 == 0 && outer % 4 == 0));
 }
 // split-K: a product with few output tiles is cut along the contraction into `splits` workgroups per tile, k_chunk (whole stages of bk) each.
-// The 64-deep kernels of the bf16 shadows split as the 32-deep ones do: a product takes the same split whatever its operands are stored
-// as, which keeps the shadow path bit-identical to the fp32-in-memory one.
+// The 64-deep kernels of the bf16 shadows ask for as many splits as the 32-deep ones do; k_chunk is then rounded up to whole stages of the
+// kernel's own depth.  Where K / splits rounds to the same chunk at 32 and at 64 the shadow path is
+// bit-identical to the fp32-in-memory one; elsewhere (K = 1472: 8 x 192 against 10 x 160) the two sum in a different order.
 struct GemmPlan { int gm, gn, tiles, bk, splits, k_chunk; };
 static GemmPlan gemm_plan(int M, int N, int K, int bk, size_t scratch_floats) {
     GemmPlan p; p.gm = (M + MG_BM - 1) / MG_BM; p.gn = (N + MG_BN - 1) / MG_BN; p.tiles = p.gm * p.gn; p.bk = bk;
@@ -82,21 +83,23 @@ static GemmPlan gemm_plan(int M, int N, int K, int bk, size_t scratch_floats) {
 // The matrix-core kernel of the bf16-operand mode for a product's operand types and contiguous axes (akf / bkf: contiguous along the
 // contraction); all of them take a one-dimensional tile index (they order the tiles XCD-aware) and the split in grid z.
 // whole: the four-workgroups-per-CU forms of the all-bf16 kernels; deep_t: both operands bf16, outer-contiguous, whole 64-deep stages
+// Each entry carries its name in the route report (parseq_gemm_kernel; parseq_op_train_gemm hands it to the operator tests).
 using BgemmKernel = void (*)(const SgemmArgs, int, float*, int, int);
-static BgemmKernel bgemm_kernel(bool a16, bool b16, bool akf, bool bkf, bool whole, bool deep_t) {
-    if (a16 && akf) return whole ? mfma_bgemm16_kernel<true> : mfma_bgemm16_kernel<false>;
-    if (a16 && deep_t) return whole ? mfma_bgemm16t_kernel<true> : mfma_bgemm16t_kernel<false>;
-    if (a16) return mfma_bgemm_kernel<false, false, true, true>;
-    if (b16) return akf ? (bkf ? mfma_bgemm_kernel<true, true, true> : mfma_bgemm_kernel<true, false, true>)
-                        : (bkf ? mfma_bgemm_kernel<false, true, true> : mfma_bgemm_kernel<false, false, true>);
-    return akf ? (bkf ? mfma_bgemm_kernel<true, true> : mfma_bgemm_kernel<true, false>)
-               : (bkf ? mfma_bgemm_kernel<false, true> : mfma_bgemm_kernel<false, false>);
+struct BgemmChoice { BgemmKernel fn; int id; };
+static BgemmChoice bgemm_kernel(bool a16, bool b16, bool akf, bool bkf, bool whole, bool deep_t) {
+    if (a16 && akf) return {whole ? mfma_bgemm16_kernel<true> : mfma_bgemm16_kernel<false>, PARSEQ_GEMM_BOTH16_K};
+    if (a16 && deep_t) return {whole ? mfma_bgemm16t_kernel<true> : mfma_bgemm16t_kernel<false>, PARSEQ_GEMM_BOTH16_T};
+    if (a16) return {mfma_bgemm_kernel<false, false, true, true>, PARSEQ_GEMM_A16_NN};
+    if (b16) return akf ? (bkf ? BgemmChoice{mfma_bgemm_kernel<true, true, true>, PARSEQ_GEMM_B16_KK} : BgemmChoice{mfma_bgemm_kernel<true, false, true>, PARSEQ_GEMM_B16_KN})
+                        : (bkf ? BgemmChoice{mfma_bgemm_kernel<false, true, true>, PARSEQ_GEMM_B16_NK} : BgemmChoice{mfma_bgemm_kernel<false, false, true>, PARSEQ_GEMM_B16_NN});
+    return akf ? (bkf ? BgemmChoice{mfma_bgemm_kernel<true, true>, PARSEQ_GEMM_BF16_KK} : BgemmChoice{mfma_bgemm_kernel<true, false>, PARSEQ_GEMM_BF16_KN})
+               : (bkf ? BgemmChoice{mfma_bgemm_kernel<false, true>, PARSEQ_GEMM_BF16_NK} : BgemmChoice{mfma_bgemm_kernel<false, false>, PARSEQ_GEMM_BF16_NN});
 }
 // Three routes, first match wins.  The bf16-operand mode's matrix-core kernels: edge tiles allowed (the 95-class head, the 96-wide patch
 // rows), every optional epilogue folded; a product with a bf16 part MUST take them — one that cannot is an error, never a silent fp32
 // read of bf16 data.  The fp32 matrix-core kernel: whole 128 x 128 tiles and 16-deep stages.  The VALU kernel: everything else.
 static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const Out& C, int M, int N, int K, const GemmOpts& o = GemmOpts(),
-                 GemmFolded* folded = nullptr) {
+                 GemmFolded* folded = nullptr, parseq_gemm_route* route = nullptr) {
     hipStream_t s = cx.s;
     if (M <= 0 || N <= 0 || K <= 0) return fail(PARSEQ_E_INVALID, "sgemm: bad shape %d x %d x %d", M, N, K);
     const bool shadow = A.bf16 || B.bf16 || C.b16 || o.gelu_out.b16 || o.gelu_pre.b16;
@@ -121,6 +124,7 @@ static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const O
     if (bf16) { a.asum = o.asum; a.gelu_pre = o.gelu_pre.f32; a.gelu_pre16 = o.gelu_pre.b16; a.gelu_out = o.gelu_out.f32; a.gelu_out16 = o.gelu_out.b16; }
     if (folded) folded->asum = folded->gelu_pre = folded->gelu_out = bf16;
     if (!bf16 && !mfma32) {
+        if (route) { route->kernel = PARSEQ_GEMM_VALU; route->whole = 0; route->splits = 1; route->k_chunk = K; }
         hipLaunchKernelGGL(sgemm_kernel, dim3((N + SG_BN - 1) / SG_BN, (M + SG_BM - 1) / SG_BM), dim3(256), 0, s, a);
         HIPCHK(hipGetLastError());
         return 0;
@@ -132,8 +136,11 @@ static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const O
         const bool whole = M % MG_BM == 0 && N % MG_BN == 0 &&
                            (size_t)M * (size_t)std::max(A.so, A.sk) < ((size_t)1 << 29) && (size_t)N * (size_t)std::max(B.so, B.sk) < ((size_t)1 << 29) &&
                            (size_t)K * (size_t)std::max(A.sk, B.sk) < ((size_t)1 << 29);
-        hipLaunchKernelGGL(bgemm_kernel(A.bf16, B.bf16, akf, bkf, whole, deep_t), dim3((unsigned)p.tiles, 1, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch, p.gn, p.gm);
+        const BgemmChoice k = bgemm_kernel(A.bf16, B.bf16, akf, bkf, whole, deep_t);
+        if (route) { route->kernel = k.id; route->whole = (whole && (k.id == PARSEQ_GEMM_BOTH16_K || k.id == PARSEQ_GEMM_BOTH16_T)) ? 1 : 0; route->splits = p.splits; route->k_chunk = p.k_chunk; }
+        hipLaunchKernelGGL(k.fn, dim3((unsigned)p.tiles, 1, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch, p.gn, p.gm);
     } else {
+        if (route) { route->kernel = PARSEQ_GEMM_MFMA_F32; route->whole = 0; route->splits = p.splits; route->k_chunk = p.k_chunk; }
         hipLaunchKernelGGL(mfma_sgemm_kernel, dim3(p.gn, p.gm, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch);
     }
     HIPCHK(hipGetLastError());
@@ -367,6 +374,40 @@ extern "C" int parseq_op_train_attention(const float* qkv, float* o, float* lse,
     const TrainCtx cx{(hipStream_t)stream, nullptr, false, 0};
     if (route) *route = train_attn_route(cx, a, TW_HD, backward != 0) == TA_WIDE ? 1 : 0;
     return train_attn(cx, a, batch, backward != 0, TW_HD);
+}
+
+
+// The step's products and row kernels one operator at a time (the kernels' unit tests): each hook builds the step's context from its
+// arguments and calls the function the step calls.
+static bool gemm_dtype_ok(int dtype) { return dtype == PARSEQ_F32 || dtype == PARSEQ_BF16; }
+static Operand gemm_operand(const parseq_gemm_operand& x) {
+    return x.dtype == PARSEQ_BF16 ? Operand(static_cast<const bf16_t*>(x.data), (long)x.outer_stride, (long)x.k_stride)
+                                  : Operand(static_cast<const float*>(x.data), (long)x.outer_stride, (long)x.k_stride);
+}
+extern "C" int parseq_op_train_gemm(const parseq_train_gemm_desc* d, parseq_gemm_route* route, void* stream) {
+    if (route) *route = parseq_gemm_route{PARSEQ_GEMM_NONE, 0, 0, 0, 0, 0, 0};
+    CHK(check_arch());
+    if (!d || !d->A.data || !d->B.data || !gemm_dtype_ok(d->A.dtype) || !gemm_dtype_ok(d->B.dtype)) return fail(PARSEQ_E_INVALID, "bad argument");
+    const TrainCtx cx{(hipStream_t)stream, d->scratch, d->bf16_ops != 0, d->scratch_floats};
+    GemmOpts g;
+    g.bias = d->bias; g.R = d->R; g.ldr = (long)d->ldr; g.rper = d->rper; g.alpha = d->alpha; g.accumulate = d->accumulate != 0; g.asum = d->asum;
+    g.gelu_pre = In(d->gelu_pre, static_cast<const bf16_t*>(d->gelu_pre16));
+    g.gelu_out = Out(d->gelu_out, static_cast<bf16_t*>(d->gelu_out16));
+    GemmFolded f;
+    parseq_gemm_route r{PARSEQ_GEMM_NONE, 0, 0, 0, 0, 0, 0};
+    const int rc = sgemm(cx, gemm_operand(d->A), gemm_operand(d->B), Out(d->C, static_cast<bf16_t*>(d->c16)), d->M, d->N, d->K, g, &f, &r);
+    if (rc == 0) { r.folded_asum = f.asum; r.folded_gelu_pre = f.gelu_pre; r.folded_gelu_out = f.gelu_out; }
+    if (route && rc == 0) *route = r;
+    return rc;
+}
+extern "C" int parseq_op_train_linear(const float* x, const float* W, const float* bias, const float* R, int rper, float* y, float* gelu_out,
+                                      const float* dy, float* dW, float* db, float* dx, const float* dx_gelu_pre, int M, int N, int K, int backward,
+                                      int bf16_ops, float* scratch, size_t scratch_floats, void* stream) {
+    CHK(check_arch());
+    if (!x || !W || M <= 0 || N <= 0 || K <= 0 || (backward ? (!dy || !dW || !db) : !y)) return fail(PARSEQ_E_INVALID, "bad argument");
+    const TrainCtx cx{(hipStream_t)stream, scratch, bf16_ops != 0, scratch_floats};
+    if (backward) return lin_bwd(cx, x, W, dy, dW, db, dx, M, N, K, dx_gelu_pre);
+    return lin_fwd<float>(cx, x, W, bias, R, rper, y, M, N, K, Out(gelu_out));
 }
 
 // The K permutation passes of a step share every weight and differ in their masks, dropout sites and (after two passes) targets only
@@ -687,6 +728,20 @@ static int train_ln_fwd(hipStream_t s, const float* x, const float* w, const flo
     hipLaunchKernelGGL((ln_fwd_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, out, rows, E, eps);
     HIPCHK(hipGetLastError());
     return 0;
+}
+extern "C" int parseq_op_train_layernorm(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, const float* dy, const float* add,
+                                         float* dx, void* dx16, float* dgamma, float* dbeta, int rows, int E, float eps, int backward, float* scratch,
+                                         size_t scratch_floats, void* stream) {
+    CHK(check_arch());
+    if (!x || !gamma || rows <= 0 || E <= 0) return fail(PARSEQ_E_INVALID, "bad argument");
+    if (backward) {
+        if (!dy || !dx || !dgamma || !dbeta) return fail(PARSEQ_E_INVALID, "bad argument");
+        const TrainCtx cx{(hipStream_t)stream, scratch, false, scratch_floats};
+        return ln_bwd(cx, x, gamma, dy, add, dx, dgamma, dbeta, rows, E, eps, static_cast<bf16_t*>(dx16));
+    }
+    if (!beta || !y || !gemm_dtype_ok(y_dtype)) return fail(PARSEQ_E_INVALID, "bad argument");
+    if (y_dtype == PARSEQ_BF16) return train_ln_fwd((hipStream_t)stream, x, gamma, beta, static_cast<bf16_t*>(y), rows, E, eps);
+    return train_ln_fwd((hipStream_t)stream, x, gamma, beta, static_cast<float*>(y), rows, E, eps);
 }
 // bf16 shadow operands for the encoder's products (train_ops.h SgemmArgs): the bf16-operand mode at the shapes the bf16 attention kernel
 // and the 64-deep GEMM take.  In that mode the record's n1 / n2 / ao / hact_l slots hold bf16 (in the first half of the fp32 slot).
