@@ -55,6 +55,15 @@ static int fail(int code, const char* fmt, ...) {
         int r_ = (expr);            \
         if (r_ != 0) return r_;     \
     } while (0)
+// One plain kernel launch and its check, answered in the library's status codes (a kernel chosen at run time among templates that need
+// their own dynamic-LDS attribute keeps its own launch site)
+template <typename... KArgs, typename... Args>
+static int launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(PARSEQ_E_HIP, "kernel launch failed: %s", hipGetErrorString(e));
+    return 0;
+}
 
 // Every entry point that takes a model or a plan runs on THAT object's device, whatever device is current in the calling
 // thread (a model moved to cuda:1 while cuda:0 is current must not launch on device 0 against device-1 pointers); the
@@ -130,6 +139,10 @@ struct ProfScope {
 // model
 // -------------------------------------------------------------------------------------------------------------------
 struct ParamSpec { std::string key; int64_t numel; size_t offset; bool set; };
+// How the training encoder's record stores what only feeds products: every slot fp32; the LayerNorm / attention / GELU outputs as bf16
+// shadows in the first half of their slots; or, beyond that, the fc1 pre-activation as bf16 alone.  The values are the mode numbers of
+// the backward's mismatch message.
+enum EncRecordMode { REC_F32 = 0, REC_SHADOWS = 1, REC_BF16_ONLY = 3 };
 
 struct parseq_model {
     parseq_config cfg;
@@ -150,8 +163,8 @@ struct parseq_model {
     std::vector<float*> out_ptrs;
     void* out_chunks = nullptr;
     int out_chunk_count = 0;
-    // parseq_train_encoder_forward: which storage mode (bit 0 bf16 shadows, bit 1 bf16-only slots) the record in `enc_record_ws` was written in
-    int enc_record_mode = 0;
+    // parseq_train_encoder_forward: what the slots of the record in `enc_record_ws` hold (lib_train.hip TrainEncRoute::record)
+    EncRecordMode enc_record_mode = REC_F32;
     const void* enc_record_ws = nullptr;
     // model constants of the training forward, built on first use: the one-launch encoder's block table (encoder_blocks.h; weight offsets relative
     // to the workspace's bf16 shadows, parameter offsets into the master) and the table of the one-launch weight-shadow kernel (train_ops.h)

@@ -42,6 +42,7 @@ struct Dual {
     Dual(F* p) : f32(p) {}
     Dual(H* q) : b16(q) {}
     Dual(F* p, H* q) : f32(p), b16(q) {}
+    template <typename F2, typename H2> Dual(const Dual<F2, H2>& o) : f32(o.f32), b16(o.b16) {}      // an Out read back as an In
     explicit operator bool() const { return f32 || b16; }
 };
 using Out = Dual<float, bf16_t>;
@@ -125,9 +126,7 @@ static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const O
     if (folded) folded->asum = folded->gelu_pre = folded->gelu_out = bf16;
     if (!bf16 && !mfma32) {
         if (route) { route->kernel = PARSEQ_GEMM_VALU; route->whole = 0; route->splits = 1; route->k_chunk = K; }
-        hipLaunchKernelGGL(sgemm_kernel, dim3((N + SG_BN - 1) / SG_BN, (M + SG_BM - 1) / SG_BM), dim3(256), 0, s, a);
-        HIPCHK(hipGetLastError());
-        return 0;
+        return launch(sgemm_kernel, dim3((N + SG_BN - 1) / SG_BN, (M + SG_BM - 1) / SG_BM), dim3(256), 0, s, a);
     }
     const GemmPlan p = gemm_plan(M, N, K, bf16 ? bk16 : MG_BK, cx.scratch_floats);
     if (bf16) {
@@ -139,15 +138,13 @@ static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const O
         const BgemmChoice k = bgemm_kernel(A.bf16, B.bf16, akf, bkf, whole, deep_t);
         if (route) { route->kernel = k.id; route->whole = (whole && (k.id == PARSEQ_GEMM_BOTH16_K || k.id == PARSEQ_GEMM_BOTH16_T)) ? 1 : 0; route->splits = p.splits; route->k_chunk = p.k_chunk; }
         hipLaunchKernelGGL(k.fn, dim3((unsigned)p.tiles, 1, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch, p.gn, p.gm);
+        HIPCHK(hipGetLastError());
     } else {
         if (route) { route->kernel = PARSEQ_GEMM_MFMA_F32; route->whole = 0; route->splits = p.splits; route->k_chunk = p.k_chunk; }
-        hipLaunchKernelGGL(mfma_sgemm_kernel, dim3(p.gn, p.gm, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch);
+        CHK(launch(mfma_sgemm_kernel, dim3(p.gn, p.gm, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch));
     }
-    HIPCHK(hipGetLastError());
-    if (p.splits > 1) {
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * N + (a.asum ? (size_t)M : 0) + 255) / 256)), dim3(256), 0, s, a, cx.scratch, p.splits);
-        HIPCHK(hipGetLastError());
-    }
+    if (p.splits > 1)
+        CHK(launch(splitk_reduce_kernel, dim3((unsigned)(((size_t)M * N + (a.asum ? (size_t)M : 0) + 255) / 256)), dim3(256), 0, s, a, cx.scratch, p.splits));
     return 0;
 }
 static int colsum(const TrainCtx& cx, const float* A, long lda, int M, int N, float* out, bool accumulate) {
@@ -155,33 +152,25 @@ static int colsum(const TrainCtx& cx, const float* A, long lda, int M, int N, fl
     constexpr int CHUNKS = 64;
     if (M >= 2048 && cx.scratch && (size_t)CHUNKS * N <= cx.scratch_floats) {
         const int rows_per = (M + CHUNKS - 1) / CHUNKS;
-        hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, CHUNKS), dim3(1024), 0, s, A, lda, M, N, cx.scratch, 0, rows_per, (float*)nullptr, 0);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, 1), dim3(1024), 0, s, cx.scratch, (long)N, CHUNKS, N, out, accumulate ? 1 : 0, CHUNKS, (float*)nullptr, 0);
-        HIPCHK(hipGetLastError());
-        return 0;
+        CHK(launch(colsum_kernel, dim3((N + 63) / 64, CHUNKS), dim3(1024), 0, s, A, lda, M, N, cx.scratch, 0, rows_per, (float*)nullptr, 0));
+        return launch(colsum_kernel, dim3((N + 63) / 64, 1), dim3(1024), 0, s, cx.scratch, (long)N, CHUNKS, N, out, accumulate ? 1 : 0, CHUNKS, (float*)nullptr, 0);
     }
-    hipLaunchKernelGGL(colsum_kernel, dim3((N + 63) / 64, 1), dim3(1024), 0, s, A, lda, M, N, out, accumulate ? 1 : 0, M, (float*)nullptr, 0);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(colsum_kernel, dim3((N + 63) / 64, 1), dim3(1024), 0, s, A, lda, M, N, out, accumulate ? 1 : 0, M, (float*)nullptr, 0);
 }
+// A dense row-major [rows, ld] tensor as a product's operand, in the type it is stored in (the bf16 shadow where there is one)
+static Operand rows_operand(In t, long ld) { return t.b16 ? Operand(t.b16, ld, 1) : Operand(t.f32, ld, 1); }
 // y[M, N] = x[M, K] W[N, K]^T + bias + R[m % rper], x and W both fp32 or both bf16 shadows (x16 [M, K], W16 [N, K]; y as fp32, bf16 or both)
 // gelu_out (optional, [M, N]): gelu(y) as a second output — from the product's epilogue on the bf16 matrix-core kernels, by gelu_fwd_kernel otherwise
-template <typename T>
-static int lin_fwd(const TrainCtx& cx, const T* x, const T* W, const float* bias, const float* R, int rper, Out y, int M, int N, int K, Out gelu_out = Out()) {
+static int lin_fwd(const TrainCtx& cx, In x, In W, const float* bias, const float* R, int rper, Out y, int M, int N, int K, Out gelu_out = Out()) {
     GemmOpts g; g.bias = bias; g.R = R; g.ldr = N; g.rper = rper; g.gelu_out = gelu_out;
     GemmFolded f;
-    CHK(sgemm(cx, Operand(x, K, 1), Operand(W, K, 1), y, M, N, K, g, &f));
-    if (gelu_out && !f.gelu_out) {
-        hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)(((size_t)M * N + 1023) / 1024)), dim3(256), 0, cx.s, y.f32, gelu_out.f32, (size_t)M * N);
-        HIPCHK(hipGetLastError());
-    }
+    CHK(sgemm(cx, rows_operand(x, K), rows_operand(W, K), y, M, N, K, g, &f));
+    if (gelu_out && !f.gelu_out)
+        CHK(launch(gelu_fwd_kernel, dim3((unsigned)(((size_t)M * N + 1023) / 1024)), dim3(256), 0, cx.s, y.f32, gelu_out.f32, (size_t)M * N));
     return 0;
 }
 static int gelu_bwd(const TrainCtx& cx, const float* pre, float* d, size_t n) {      // d *= gelu'(pre)
-    hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, cx.s, pre, d, d, n);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(gelu_bwd_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, cx.s, pre, d, d, n);
 }
 // dW[N, K] += dy[M, N]^T x[M, K];  db[N] += column sums of dy;  dx[M, K] = dy W   (dx may be null)
 // dx_gelu_pre (optional, [M, K]): dx is additionally multiplied by gelu'(dx_gelu_pre) — the GELU backward of the layer below, folded
@@ -198,12 +187,10 @@ static int lin_bwd(const TrainCtx& cx, const float* x, const float* W, const flo
         hipStream_t s = cx.s;
         TrainCtx c2 = cx; c2.scratch_floats = cx.scratch_floats - reserve;
         float* dyp = cx.scratch + c2.scratch_floats; float* Wp = dyp + (size_t)M * Np; float* dWp = Wp + (size_t)Np * K;
-        hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)(((size_t)M * Np + 255) / 256)), dim3(256), 0, s, dy, M, N, dyp, M, Np);
-        hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)(((size_t)Np * K + 255) / 256)), dim3(256), 0, s, W, N, K, Wp, Np, K);
-        HIPCHK(hipGetLastError());
+        CHK(launch(pad_copy_kernel, dim3((unsigned)(((size_t)M * Np + 255) / 256)), dim3(256), 0, s, dy, M, N, dyp, M, Np));
+        CHK(launch(pad_copy_kernel, dim3((unsigned)(((size_t)Np * K + 255) / 256)), dim3(256), 0, s, W, N, K, Wp, Np, K));
         CHK(sgemm(c2, Operand(dyp, 1, Np), Operand(x, 1, K), dWp, Np, K, M));
-        hipLaunchKernelGGL(add_into_kernel, dim3((unsigned)(((size_t)N * K + 255) / 256)), dim3(256), 0, s, dWp, dW, (size_t)N * K);
-        HIPCHK(hipGetLastError());
+        CHK(launch(add_into_kernel, dim3((unsigned)(((size_t)N * K + 255) / 256)), dim3(256), 0, s, dWp, dW, (size_t)N * K));
         CHK(colsum(c2, dy, N, M, N, db, true));
         if (dx) CHK(sgemm(c2, Operand(dyp, Np, 1), Operand(Wp, 1, K), dx, M, K, Np));
         if (dx && dx_gelu_pre) CHK(gelu_bwd(cx, dx_gelu_pre, dx, (size_t)M * K));
@@ -225,17 +212,16 @@ static int lin_bwd(const TrainCtx& cx, const float* x, const float* W, const flo
 // shadow Wt16 [K, N] are bfloat16 in memory; dy is read as fp32 where it exists (the bias gradient is then summed from the unrounded values) and
 // through its shadow dy16 otherwise — the dX product prefers the shadow; dx16: the result again as bf16 for the next product; dx_gelu_pre16: the
 // pre-activation as bf16.  Bit-identical to lin_bwd on the fp32 copies: the rounding moved, nothing else.
-static int lin_bwd16_dw(const TrainCtx& cx, const bf16_t* x16, const float* dy, const bf16_t* dy16, float* dW, float* db, int M, int N, int K) {
-    if (!dy && !dy16) return fail(PARSEQ_E_INVALID, "lin_bwd16: no gradient");
+static int lin_bwd16_dw(const TrainCtx& cx, const bf16_t* x16, In dy, float* dW, float* db, int M, int N, int K) {
+    if (!dy) return fail(PARSEQ_E_INVALID, "lin_bwd16: no gradient");
     GemmOpts g; g.accumulate = true; g.asum = db;
-    return sgemm(cx, dy ? Operand(dy, 1, N) : Operand(dy16, 1, N), Operand(x16, 1, K), dW, N, K, M, g);
+    return sgemm(cx, dy.f32 ? Operand(dy.f32, 1, N) : Operand(dy.b16, 1, N), Operand(x16, 1, K), dW, N, K, M, g);
 }
-static int lin_bwd16_dx(const TrainCtx& cx, const bf16_t* Wt16, const float* dy, const bf16_t* dy16, float* dx, bf16_t* dx16, int M, int N, int K,
-                        In dx_gelu_pre = In()) {
-    if (!dy && !dy16) return fail(PARSEQ_E_INVALID, "lin_bwd16: no gradient");
-    if (!dx && !dx16) return 0;
+static int lin_bwd16_dx(const TrainCtx& cx, const bf16_t* Wt16, In dy, Out dx, int M, int N, int K, In dx_gelu_pre = In()) {
+    if (!dy) return fail(PARSEQ_E_INVALID, "lin_bwd16: no gradient");
+    if (!dx) return 0;
     GemmOpts g; g.gelu_pre = dx_gelu_pre;
-    return sgemm(cx, dy16 ? Operand(dy16, N, 1) : Operand(dy, N, 1), Operand(Wt16, N, 1), Out(dx, dx16), M, K, N, g);
+    return sgemm(cx, rows_operand(dy, N), Operand(Wt16, N, 1), dx, M, K, N, g);
 }
 // dx = add + LayerNorm backward; dgamma += column sums of dy * xhat; dbeta += column sums of dy.
 // dx16 (optional): dx again as bf16, the operand shadow of the dX product that follows.
@@ -248,20 +234,15 @@ static int ln_bwd(const TrainCtx& cx, const float* x, const float* gamma, const 
     if (!cx.scratch || (size_t)chunks * 2 * E + (size_t)64 * E > cx.scratch_floats) return fail(PARSEQ_E_INVALID, "layernorm backward: %d rows do not fit the scratch", rows);
     float* part = cx.scratch + (cx.scratch_floats - (size_t)chunks * 2 * E);      // the END of the scratch: colsum's own partials use its start
     TrainCtx c2 = cx; c2.scratch_floats = cx.scratch_floats - (size_t)chunks * 2 * E;
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3(chunks), dim3(256), 0, s, x, gamma, dy, add, dx, part, rows, E, eps, dx16);
-    HIPCHK(hipGetLastError());
+    CHK(launch(ln_bwd_kernel, dim3(chunks), dim3(256), 0, s, x, gamma, dy, add, dx, part, rows, E, eps, dx16));
     // both column sums in one pair of launches: [chunks][2E] -> 64 row chunks -> dgamma (columns < E) and dbeta (the rest)
     constexpr int CHUNKS = 64;
     if (chunks >= 2048 && (size_t)CHUNKS * 2 * E <= c2.scratch_floats) {
         const int rows_per = (chunks + CHUNKS - 1) / CHUNKS;
-        hipLaunchKernelGGL(colsum_kernel, dim3((2 * E + 63) / 64, CHUNKS), dim3(1024), 0, s, part, 2L * E, chunks, 2 * E, c2.scratch, 0, rows_per, (float*)nullptr, 0);
-        hipLaunchKernelGGL(colsum_kernel, dim3((2 * E + 63) / 64, 1), dim3(1024), 0, s, c2.scratch, 2L * E, CHUNKS, 2 * E, dgamma, 1, CHUNKS, dbeta, E);
-        HIPCHK(hipGetLastError());
-        return 0;
+        CHK(launch(colsum_kernel, dim3((2 * E + 63) / 64, CHUNKS), dim3(1024), 0, s, part, 2L * E, chunks, 2 * E, c2.scratch, 0, rows_per, (float*)nullptr, 0));
+        return launch(colsum_kernel, dim3((2 * E + 63) / 64, 1), dim3(1024), 0, s, c2.scratch, 2L * E, CHUNKS, 2 * E, dgamma, 1, CHUNKS, dbeta, E);
     }
-    hipLaunchKernelGGL(colsum_kernel, dim3((2 * E + 63) / 64, 1), dim3(1024), 0, s, part, 2L * E, chunks, 2 * E, dgamma, 1, chunks, dbeta, E);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(colsum_kernel, dim3((2 * E + 63) / 64, 1), dim3(1024), 0, s, part, 2L * E, chunks, 2 * E, dgamma, 1, chunks, dbeta, E);
 }
 // One attention launch of B * heads (or fewer) workgroups: the forward or the backward kernel, both allowed `cap_f` / `cap_b` bytes of dynamic
 // LDS once per device (one LdsAttr pair per pair of kernels)
@@ -320,15 +301,9 @@ static int train_attn_wide(const TrainCtx& cx, const TrainAttnArgs& a, int B, bo
     if (backward) ok = ok && a.d_o && a.dq && a.dk && a.dv && aligned16(a.d_o);
     if (!ok) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: operands not laid out in 16-byte rows", a.Lk);
     const dim3 grid((unsigned)((a.Lk + TW_BLK - 1) / TW_BLK), (unsigned)(B * a.H));
-    if (backward) {
-        hipLaunchKernelGGL(train_attn_wide_dq_kernel, grid, dim3(256), 0, cx.s, a);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(train_attn_wide_dkv_kernel, grid, dim3(256), 0, cx.s, a);
-    } else {
-        hipLaunchKernelGGL(train_attn_wide_fwd_kernel, grid, dim3(256), 0, cx.s, a);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (!backward) return launch(train_attn_wide_fwd_kernel, grid, dim3(256), 0, cx.s, a);
+    CHK(launch(train_attn_wide_dq_kernel, grid, dim3(256), 0, cx.s, a));
+    return launch(train_attn_wide_dkv_kernel, grid, dim3(256), 0, cx.s, a);
 }
 // Which kernel a training attention call runs, first match wins: the two bf16-operand kernels (decoder shapes, the 128-token encoder), the
 // fp32 matrix-core kernel (head width 64, up to 128 keys), the key-streaming kernels past 128 tokens, the VALU kernels; TA_NONE: no kernel
@@ -407,48 +382,122 @@ extern "C" int parseq_op_train_linear(const float* x, const float* W, const floa
     if (!x || !W || M <= 0 || N <= 0 || K <= 0 || (backward ? (!dy || !dW || !db) : !y)) return fail(PARSEQ_E_INVALID, "bad argument");
     const TrainCtx cx{(hipStream_t)stream, scratch, bf16_ops != 0, scratch_floats};
     if (backward) return lin_bwd(cx, x, W, dy, dW, db, dx, M, N, K, dx_gelu_pre);
-    return lin_fwd<float>(cx, x, W, bias, R, rper, y, M, N, K, Out(gelu_out));
+    return lin_fwd(cx, x, W, bias, R, rper, y, M, N, K, Out(gelu_out));
 }
 
+// ---- what the step's entry points share ---------------------------------------------------------------------------------------------
+// Workspace layouts hand out their buffers in order, each on a 64-float boundary
+struct Take {
+    size_t off = 0;
+    size_t operator()(size_t n) { const size_t at = off; off += (n + 63) / 64 * 64; return at; }
+};
+static int require_params_set(const parseq_model* m) {
+    for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
+    return 0;
+}
+// A parameter resolved once per call (on the stack: the caller's gradient buffer may change between calls): where it lies in the master
+// (`at`, in floats) and its slot in the flat gradient buffer, which is laid out like the master (null where the call writes no gradients)
+struct ParamRef { const float* p; float* g; size_t at; };
+static ParamRef param_ref(const parseq_model* m, const std::string& key, float* grads) {
+    const size_t at = m->params[m->index.at(key)].offset;
+    return ParamRef{m->master + at, grads ? grads + at : nullptr, at};
+}
+template <int N> struct ParamSet {      // indexed by the enum of its key table: W(k) the parameter, W.g(k) its gradient
+    ParamRef v[N];
+    const float* operator()(int k) const { return v[k].p; }
+    float* g(int k) const { return v[k].g; }
+};
+// Cross-entropy of `passes` passes of M rows each over C classes (ignore_index = pad): each pass's own mean into loss[q] (system.py:189-190;
+// rows summed in the order its own launch would) with its kept targets in count[q], then logits <- d loss / d logits at 1 / total_targets per row
+static int ce_loss_and_grad(hipStream_t s, float* logits, const int32_t* tgt, int passes, int M, int C, int pad, float* row_loss, float* loss, int* count,
+                            int total_targets) {
+    const int R = passes * M;
+    CHK(launch(ce_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, tgt, R, C, pad, row_loss));
+    for (int q = 0; q < passes; ++q)
+        CHK(launch(ce_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss + (size_t)q * M, tgt + (size_t)q * M, M, pad, loss + q, count + q));
+    return launch(ce_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, tgt, R, C, pad, 1.0f / (float)total_targets);
+}
+
+// ---- decoder side ---------------------------------------------------------------------------------------------------------------------
 // The K permutation passes of a step share every weight and differ in their masks, dropout sites and (after two passes) targets only
 // (system.py:175-196), so the decoder runs them as ONE batch of KP * B images (KP = K by default): every Linear product, LayerNorm,
 // attention launch and column sum once per step instead of once per pass — 6 x the rows per launch, a sixth of the launches and of the
 // split-K folds, the dW products contracted over all passes at once.  PARSEQ_TRAIN_PERM_GROUP=g runs the passes g at a time (1 = one after
 // the other, the arrangement of rounds 1-2: same masks, same per-pass losses, gradients equal up to fp32 summation order).
-static int train_perm_group(int K) {
+// ca_loop: the cross-attention walks the passes of a batch inside one workgroup (train_attn_dec_bf16_kernel's pass_loop: bf16-operand mode,
+// head width 32, <= TD_Q queries, <= TD_K memory tokens), so no pass keeps its own d K | d V of the memory; PARSEQ_TRAIN_NO_PASS_LOOP=1
+// turns it off.  Decided here, once per call, for the layout (which then has no per-pass copies) and for parseq_train_decoder alike.
+struct TrainDecRoute { int KP; bool ca_loop; };
+static TrainDecRoute train_dec_route(const parseq_model* m, int L, int K) {
+    TrainDecRoute r;
     int g = K;
     if (const char* e = getenv("PARSEQ_TRAIN_PERM_GROUP")) { const int v = atoi(e); if (v >= 1) g = v; }
-    return std::min(std::max(g, 1), K);
-}
-struct TrainDecoderLayout {          // offsets in floats into the caller's workspace
-    size_t content0, content, cn, kvc, qd, qn, qsa, kvm, sa_o, t1, n1, q2, ca_o, t2, n2, hpre, hact, t3, out, logits;
-    size_t d_a, d_b, d_c, d_h, pm, d_kvc, d_kvm, d_kvm_p, d_content, d_pq, d_qb, row_loss, tgt_all, losses, counts, scratch, scratch_floats, total;
-    int KP;                          // passes per batch
-    bool ca_loop;                    // the cross-attention walks the passes of a batch inside one workgroup (no per-pass d K | d V copies)
-};
-static TrainDecoderLayout train_decoder_layout(const parseq_model* m, int B, int L, int K) {
-    const size_t E = m->cfg.embed_dim, F = E * m->cfg.dec_mlp_ratio, S = m->tokens, C = m->classes, M = (size_t)B * L, MS = (size_t)B * S;
-    TrainDecoderLayout o;
-    o.KP = train_perm_group(K);
-    const size_t P = (size_t)o.KP, MP = P * M;      // rows of a per-pass buffer
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t at = off; off += (n + 63) / 64 * 64; return at; };
-    o.content0 = take(M * E); o.content = take(MP * E); o.cn = take(MP * E); o.kvc = take(MP * 2 * E); o.qd = take(MP * E); o.qn = take(MP * E);
-    o.qsa = take(MP * E); o.kvm = take(MS * 2 * E);
-    o.sa_o = take(MP * E); o.t1 = take(MP * E); o.n1 = take(MP * E); o.q2 = take(MP * E); o.ca_o = take(MP * E); o.t2 = take(MP * E); o.n2 = take(MP * E);
-    o.hpre = take(MP * F); o.hact = take(MP * F); o.t3 = take(MP * E); o.out = take(MP * E); o.logits = take(MP * C);
-    o.d_a = take(MP * E); o.d_b = take(MP * E); o.d_c = take(MP * E); o.d_h = take(MP * F); o.pm = take(MP * E);
-    o.d_kvc = take(MP * 2 * E); o.d_kvm = take(MS * 2 * E);
-    // each pass's own d K | d V of the memory, folded into d_kvm after the batch — only where the cross-attention cannot walk the passes itself
-    // (train_attn_dec_bf16_kernel's pass_loop: bf16-operand mode, head width 32, <= TD_Q queries, <= TD_K memory tokens)
-    o.ca_loop = o.KP > 1 && E == (size_t)m->cfg.dec_heads * TD_HD && train_attn_dec_bf16_shape(m->train_precision == PARSEQ_BF16, TD_HD, L, (int)S) &&
+    r.KP = std::min(std::max(g, 1), K);
+    const int E = m->cfg.embed_dim;
+    r.ca_loop = r.KP > 1 && E == m->cfg.dec_heads * TD_HD && train_attn_dec_bf16_shape(m->train_precision == PARSEQ_BF16, TD_HD, L, m->tokens) &&
                 E % 4 == 0 && !getenv("PARSEQ_TRAIN_NO_PASS_LOOP");
-    o.d_kvm_p = (o.KP > 1 && !o.ca_loop) ? take(P * MS * 2 * E) : o.d_kvm;
-    o.d_content = take(M * E); o.d_pq = take(L * E); o.d_qb = take(MP * E);
-    o.row_loss = take(MP); o.tgt_all = take((size_t)K * M); o.losses = take(K + 1); o.counts = take(K + 1);
-    o.scratch_floats = train_scratch_floats(MP, E); o.scratch = take(o.scratch_floats);
-    o.total = off;
+    return r;
+}
+
+// The decoder's workspace: offsets in floats into the caller's buffer, one member and one row of kDecBufs per buffer.  A row names the
+// buffer (parseq_train_decoder_workspace_offset answers by that name), its rows and its width; the layout hands the buffers out in table order.
+struct TrainDecoderLayout {
+    size_t content0, content, cn, kvc, qd, qn, qsa, kvm, sa_o, t1, n1, q2, ca_o, t2, n2, hpre, hact, t3, out, logits;
+    size_t d_a, d_b, d_c, d_h, pm, d_kvc, d_kvm, d_kvm_p, d_content, d_pq, d_qb, row_loss, tgt_all, losses, counts, scratch, total;
+    size_t scratch_floats;
+};
+enum DecRows { ROWS_PASSES, ROWS_ONCE, ROWS_MEMORY, ROWS_MEMORY_PASSES, ROWS_POS, ROWS_PERMS, ROWS_PERMS_1, ROWS_SCRATCH };
+enum DecWidth { W_E, W_2E, W_F, W_C, W_1 };
+struct DecBuf { const char* name; size_t TrainDecoderLayout::* at; DecRows rows; DecWidth width; };
+#define DEC_BUF(member, rows, width) {#member, &TrainDecoderLayout::member, rows, width}
+static const DecBuf kDecBufs[] = {
+    DEC_BUF(content0, ROWS_ONCE, W_E), DEC_BUF(content, ROWS_PASSES, W_E), DEC_BUF(cn, ROWS_PASSES, W_E), DEC_BUF(kvc, ROWS_PASSES, W_2E),
+    DEC_BUF(qd, ROWS_PASSES, W_E), DEC_BUF(qn, ROWS_PASSES, W_E), DEC_BUF(qsa, ROWS_PASSES, W_E), DEC_BUF(kvm, ROWS_MEMORY, W_2E),
+    DEC_BUF(sa_o, ROWS_PASSES, W_E), DEC_BUF(t1, ROWS_PASSES, W_E), DEC_BUF(n1, ROWS_PASSES, W_E), DEC_BUF(q2, ROWS_PASSES, W_E),
+    DEC_BUF(ca_o, ROWS_PASSES, W_E), DEC_BUF(t2, ROWS_PASSES, W_E), DEC_BUF(n2, ROWS_PASSES, W_E), DEC_BUF(hpre, ROWS_PASSES, W_F),
+    DEC_BUF(hact, ROWS_PASSES, W_F), DEC_BUF(t3, ROWS_PASSES, W_E), DEC_BUF(out, ROWS_PASSES, W_E),
+    {"dlogits", &TrainDecoderLayout::logits, ROWS_PASSES, W_C},      // the logits, then their gradient in place: the name callers ask for
+    DEC_BUF(d_a, ROWS_PASSES, W_E), DEC_BUF(d_b, ROWS_PASSES, W_E), DEC_BUF(d_c, ROWS_PASSES, W_E), DEC_BUF(d_h, ROWS_PASSES, W_F),
+    DEC_BUF(pm, ROWS_PASSES, W_E), DEC_BUF(d_kvc, ROWS_PASSES, W_2E), DEC_BUF(d_kvm, ROWS_MEMORY, W_2E),
+    // each pass's own d K | d V of the memory, folded into d_kvm after the batch — only where the cross-attention cannot walk the passes
+    // itself; otherwise the name stands for d_kvm
+    DEC_BUF(d_kvm_p, ROWS_MEMORY_PASSES, W_2E),
+    DEC_BUF(d_content, ROWS_ONCE, W_E), DEC_BUF(d_pq, ROWS_POS, W_E), DEC_BUF(d_qb, ROWS_PASSES, W_E), DEC_BUF(row_loss, ROWS_PASSES, W_1),
+    DEC_BUF(tgt_all, ROWS_PERMS, W_1), DEC_BUF(losses, ROWS_PERMS_1, W_1), DEC_BUF(counts, ROWS_PERMS_1, W_1), DEC_BUF(scratch, ROWS_SCRATCH, W_1)};
+#undef DEC_BUF
+static TrainDecoderLayout train_decoder_layout(const parseq_model* m, int B, int L, int K, const TrainDecRoute& r) {
+    const size_t E = m->cfg.embed_dim, M = (size_t)B * L, MS = (size_t)B * m->tokens, P = (size_t)r.KP;
+    TrainDecoderLayout o;
+    o.scratch_floats = train_scratch_floats(P * M, E);
+    // DecRows: a row per token of every pass of a batch / of one pass / per memory token / per memory token and pass / per position /
+    // per token of all K permutations / K + 1 scalars / the scratch
+    const size_t rows[] = {P * M, M, MS, P * MS, (size_t)L, (size_t)K * M, (size_t)K + 1, o.scratch_floats};
+    const size_t width[] = {E, 2 * E, E * m->cfg.dec_mlp_ratio, (size_t)m->classes, 1};
+    Take take;
+    for (const DecBuf& b : kDecBufs) {
+        const bool alias = b.at == &TrainDecoderLayout::d_kvm_p && !(r.KP > 1 && !r.ca_loop);
+        o.*b.at = alias ? o.d_kvm : take(rows[b.rows] * width[b.width]);
+    }
+    o.total = take.off;
     return o;
+}
+
+// The decoder's parameters and their gradient slots, resolved once per call; the training step has depth-1 decoder kernels only
+enum TrainDecParam { D_NORM_C_W, D_NORM_C_B, D_NORM_Q_W, D_NORM_Q_B, D_NORM1_W, D_NORM1_B, D_NORM2_W, D_NORM2_B, D_SA_IN_W, D_SA_IN_B, D_SA_OUT_W, D_SA_OUT_B,
+                     D_CA_IN_W, D_CA_IN_B, D_CA_OUT_W, D_CA_OUT_B, D_LIN1_W, D_LIN1_B, D_LIN2_W, D_LIN2_B, D_LAYER_PARAMS,
+                     D_NORM_W = D_LAYER_PARAMS, D_NORM_B, D_HEAD_W, D_HEAD_B, D_TEXT_EMBED, D_POS_QUERIES, D_PARAMS };
+static const char* const kDecKeys[D_PARAMS] = {
+    "norm_c.weight", "norm_c.bias", "norm_q.weight", "norm_q.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias",
+    "self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+    "cross_attn.in_proj_weight", "cross_attn.in_proj_bias", "cross_attn.out_proj.weight", "cross_attn.out_proj.bias",
+    "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias",
+    "decoder.norm.weight", "decoder.norm.bias", "head.weight", "head.bias", "text_embed.embedding.weight", "pos_queries"};
+static std::string train_dec_key(int k) { return k < D_LAYER_PARAMS ? std::string("decoder.layers.0.") + kDecKeys[k] : std::string(kDecKeys[k]); }
+using TrainDecW = ParamSet<D_PARAMS>;
+static TrainDecW train_dec_weights(const parseq_model* m, float* grads) {
+    TrainDecW W;
+    for (int k = 0; k < D_PARAMS; ++k) W.v[k] = param_ref(m, train_dec_key(k), grads);
+    return W;
 }
 
 extern "C" int64_t parseq_model_param_offset(const parseq_model* m, int index) {
@@ -463,34 +512,28 @@ extern "C" int parseq_model_set_train_precision(parseq_model* m, int precision) 
     return 0;
 }
 
-// Where a named intermediate of the LAST permutation (or an accumulator) lives in the workspace, in floats; -1 if unknown.  For tests.
+// Where a named buffer lives in the workspace, in floats — of a per-pass buffer, the slot of the LAST permutation; -1 if unknown.  For tests.
 extern "C" int64_t parseq_train_decoder_workspace_offset(const parseq_model* m, int batch, int ctx_len, int num_perms, const char* name) {
     if (!m || !name || batch <= 0 || ctx_len <= 0 || num_perms <= 0) return -1;
-    const TrainDecoderLayout o = train_decoder_layout(m, batch, ctx_len, num_perms);
-    const size_t E = m->cfg.embed_dim, F = E * m->cfg.dec_mlp_ratio, C = m->classes, M = (size_t)batch * ctx_len;
-    const size_t last = (size_t)((num_perms - 1) % o.KP);      // the last pass's slot in its batch of KP passes
-    struct Entry { const char* name; size_t off, width; };      // width: floats per row of a per-pass buffer; 0 = shared by the passes
-    const Entry table[] = {
-        {"content", o.content, E}, {"cn", o.cn, E}, {"kvc", o.kvc, 2 * E}, {"qd", o.qd, E}, {"qn", o.qn, E}, {"qsa", o.qsa, E}, {"kvm", o.kvm, 0},
-        {"sa_o", o.sa_o, E}, {"t1", o.t1, E}, {"n1", o.n1, E}, {"q2", o.q2, E}, {"ca_o", o.ca_o, E}, {"t2", o.t2, E}, {"n2", o.n2, E},
-        {"hpre", o.hpre, F}, {"hact", o.hact, F}, {"t3", o.t3, E}, {"out", o.out, E}, {"dlogits", o.logits, C}, {"d_kvc", o.d_kvc, 2 * E},
-        {"d_kvm", o.d_kvm, 0}, {"d_content", o.d_content, 0}, {"d_pq", o.d_pq, 0}};
-    for (const Entry& e : table) if (!strcmp(e.name, name)) return (int64_t)(e.off + last * M * e.width);
+    const TrainDecRoute r = train_dec_route(m, ctx_len, num_perms);
+    const TrainDecoderLayout o = train_decoder_layout(m, batch, ctx_len, num_perms, r);
+    const size_t E = m->cfg.embed_dim, M = (size_t)batch * ctx_len;
+    const size_t width[] = {E, 2 * E, E * m->cfg.dec_mlp_ratio, (size_t)m->classes, 1};
+    const size_t last = (size_t)((num_perms - 1) % r.KP);      // the last pass's slot in its batch of KP passes
+    for (const DecBuf& b : kDecBufs)
+        if (!strcmp(b.name, name)) return (int64_t)(o.*b.at + (b.rows == ROWS_PASSES ? last * M * width[b.width] : 0));
     return -1;
 }
 
 extern "C" size_t parseq_train_decoder_workspace_bytes(const parseq_model* m, int batch, int ctx_len, int num_perms) {
     if (!m || batch <= 0 || ctx_len <= 0 || num_perms <= 0) return 0;
-    return train_decoder_layout(m, batch, ctx_len, num_perms).total * sizeof(float);
+    return train_decoder_layout(m, batch, ctx_len, num_perms, train_dec_route(m, ctx_len, num_perms)).total * sizeof(float);
 }
 
 // y = R + dropout(x) over `passes` passes of n_pass elements each (train_ops.h dropout_passes_kernel: R may be null, x == y allowed,
 // x_shared: one pass of x read by every pass); with dropout off a plain add / copy
 static int dropout_add(const TrainCtx& cx, const float* x, bool x_shared, const float* R, float* y, size_t n_pass, int passes, const DropSpec& d, unsigned site) {
-    hipStream_t s = cx.s;
-    hipLaunchKernelGGL(dropout_passes_kernel, dim3((unsigned)((n_pass + 255) / 256), (unsigned)passes), dim3(256), 0, s, x, x_shared ? 1 : 0, R, y, n_pass, d, site);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(dropout_passes_kernel, dim3((unsigned)((n_pass + 255) / 256), (unsigned)passes), dim3(256), 0, cx.s, x, x_shared ? 1 : 0, R, y, n_pass, d, site);
 }
 
 extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const int32_t* tokens, const int32_t* targets, const uint8_t* key_padding_mask,
@@ -500,14 +543,15 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
         return fail(PARSEQ_E_INVALID, "null argument");
     if (m->vitstr) return fail(PARSEQ_E_INVALID, "ViTSTR has no decoder");
     if (m->cfg.dec_depth != 1) return fail(PARSEQ_E_INVALID, "dec_depth=%d: the training step has depth-1 decoder kernels only", m->cfg.dec_depth);
-    for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
+    CHK(require_params_set(m));
     m->grad_events_valid = false;      // a new step starts writing the flat gradient buffer: the previous step's segment events say nothing about it
     DevGuard dg(m->device);
     const int B = batch, L = ctx_len, K = num_perms;
     if (B <= 0 || L < 2 || L > m->cfg.max_label_length + 1 || K <= 0 || total_targets <= 0)
         return fail(PARSEQ_E_INVALID, "bad shape: batch %d, ctx_len %d (2..%d), %d permutations, %d targets", B, L, m->cfg.max_label_length + 1, K, total_targets);
     if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(PARSEQ_E_INVALID, "dropout_p %g outside [0, 1)", dropout_p);
-    const TrainDecoderLayout o = train_decoder_layout(m, B, L, K);
+    const TrainDecRoute route = train_dec_route(m, L, K);
+    const TrainDecoderLayout o = train_decoder_layout(m, B, L, K, route);
     if (workspace_bytes < o.total * sizeof(float)) return fail(PARSEQ_E_INVALID, "workspace: %zu bytes given, %zu needed", workspace_bytes, o.total * sizeof(float));
     hipStream_t s = (hipStream_t)stream;
     const int E = m->cfg.embed_dim, F = E * m->cfg.dec_mlp_ratio, S = m->tokens, C = m->classes, H = m->cfg.dec_heads, M = B * L, MS = B * S;
@@ -515,49 +559,40 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     DropSpec drop{(unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), 0u, 1.0f};
     if (dropout_p > 0.f) { drop.thresh = (unsigned)((double)dropout_p * 4294967296.0); drop.scale = 1.0f / (1.0f - dropout_p); }
     float* w = reinterpret_cast<float*>(workspace);
-    const std::string p = "decoder.layers.0.";
-    auto P = [&](const std::string& key) { return m->p(key); };
-    auto G = [&](const std::string& key) { return grads + m->params[m->index.at(key)].offset; };
-    const float* pq = P("pos_queries");
-    const float* sa_w = P(p + "self_attn.in_proj_weight"); const float* sa_b = P(p + "self_attn.in_proj_bias");
-    const float* ca_w = P(p + "cross_attn.in_proj_weight"); const float* ca_b = P(p + "cross_attn.in_proj_bias");
-    float* content0 = w + o.content0; float* content = w + o.content; float* cn = w + o.cn; float* kvc = w + o.kvc; float* qd = w + o.qd;
-    float* qn = w + o.qn; float* qsa = w + o.qsa; float* kvm = w + o.kvm;
-    float* sa_o = w + o.sa_o; float* t1 = w + o.t1; float* n1 = w + o.n1; float* q2 = w + o.q2; float* ca_o = w + o.ca_o; float* t2 = w + o.t2;
-    float* n2 = w + o.n2; float* hpre = w + o.hpre; float* hact = w + o.hact; float* t3 = w + o.t3; float* out = w + o.out; float* logits = w + o.logits;
-    float* d_a = w + o.d_a; float* d_b = w + o.d_b; float* d_c = w + o.d_c; float* d_h = w + o.d_h; float* pm = w + o.pm;
-    float* d_kvc = w + o.d_kvc; float* d_kvm = w + o.d_kvm; float* d_kvm_p = w + o.d_kvm_p; float* d_content = w + o.d_content; float* d_pq = w + o.d_pq;
-    float* d_qb = w + o.d_qb;
-    float* row_loss = w + o.row_loss; int* tgt_all = reinterpret_cast<int*>(w + o.tgt_all); float* losses = w + o.losses; int* counts = reinterpret_cast<int*>(w + o.counts);
-    const size_t ME = (size_t)M * E, MF = (size_t)M * F;
-    const int KP = o.KP;                           // passes per batch (train_perm_group)
+    const TrainDecW W = train_dec_weights(m, grads);
+    // the in-projections by their rows: [0, E) the queries, [E, 3E) k | v
+    const float* sa_w = W(D_SA_IN_W); const float* sa_b = W(D_SA_IN_B); const float* ca_w = W(D_CA_IN_W); const float* ca_b = W(D_CA_IN_B);
+    const float* pq = W(D_POS_QUERIES);
+    int* tgt_all = reinterpret_cast<int*>(w + o.tgt_all); float* losses = w + o.losses; int* counts = reinterpret_cast<int*>(w + o.counts);
+    const size_t ME = (size_t)M * E, MF = (size_t)M * F, EE = (size_t)E * E;
+    const int KP = route.KP; const bool ca_loop = route.ca_loop;      // passes per batch; the pass-walking cross-attention
     const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
 
     // ---- shared by all permutations: the content rows before dropout, and the memory's K / V (model.py:95-98, modules.py:74) ----
-    hipLaunchKernelGGL(train_content_kernel, dim3(M), dim3(256), 0, s, P("text_embed.embedding.weight"), pq, tokens, L, L, E, sqrtE, content0);
-    HIPCHK(hipGetLastError());
-    CHK(lin_fwd(cx, memory, ca_w + (size_t)E * E, ca_b + E, nullptr, 0, kvm, MS, 2 * E, E));
-    if (KP == 1) HIPCHK(hipMemsetAsync(d_kvm, 0, (size_t)MS * 2 * E * sizeof(float), s));      // the passes accumulate into it one after the other
-    HIPCHK(hipMemsetAsync(d_pq, 0, (size_t)L * E * sizeof(float), s));
+    CHK(launch(train_content_kernel, dim3(M), dim3(256), 0, s, W(D_TEXT_EMBED), pq, tokens, L, L, E, sqrtE, w + o.content0));
+    CHK(lin_fwd(cx, memory, ca_w + EE, ca_b + E, nullptr, 0, w + o.kvm, MS, 2 * E, E));
+    if (KP == 1) HIPCHK(hipMemsetAsync(w + o.d_kvm, 0, (size_t)MS * 2 * E * sizeof(float), s));      // the passes accumulate into it one after the other
+    HIPCHK(hipMemsetAsync(w + o.d_pq, 0, (size_t)L * E * sizeof(float), s));
     // the targets of pass i, one row per pass: <eos> targets are dropped after two permutations (system.py:191-195)
     for (int i = 0; i < K; ++i)
         HIPCHK(hipMemcpyAsync(tgt_all + (size_t)i * M, targets + (size_t)(i < 2 ? 0 : 1) * M, (size_t)M * sizeof(int), hipMemcpyDeviceToDevice, s));
 
     TrainAttnArgs sa{};      // self-attention of the query stream over the content stream (modules.py:70-72)
-    sa.q = qsa; sa.q_bstride = (long)L * E; sa.ldq = E; sa.k = kvc; sa.v = kvc + E; sa.ldkv = 2 * E; sa.kmask = key_padding_mask; sa.ldkm = L;
-    sa.o = sa_o; sa.ldo = E; sa.d_o = d_b; sa.dq = d_qb; sa.lddq = E; sa.dk = d_kvc; sa.dv = d_kvc + E; sa.lddkv = 2 * E;
+    sa.q = w + o.qsa; sa.q_bstride = (long)L * E; sa.ldq = E; sa.k = w + o.kvc; sa.v = w + o.kvc + E; sa.ldkv = 2 * E; sa.kmask = key_padding_mask; sa.ldkm = L;
+    sa.o = w + o.sa_o; sa.ldo = E; sa.d_o = w + o.d_b; sa.dq = w + o.d_qb; sa.lddq = E; sa.dk = w + o.d_kvc; sa.dv = w + o.d_kvc + E; sa.lddkv = 2 * E;
     sa.Lq = L; sa.Lk = L; sa.H = H; sa.scale = scale; sa.kv_accumulate = 0; sa.drop = drop;
     sa.pass_B = B; sa.qmask_pstride = (long)L * L; sa.site_pstride = 8; sa.kv_shared = 0;
     TrainAttnArgs ca{};      // cross-attention over the encoder memory (modules.py:74-75)
-    ca.q = q2; ca.q_bstride = (long)L * E; ca.ldq = E; ca.k = kvm; ca.v = kvm + E; ca.ldkv = 2 * E; ca.o = ca_o; ca.ldo = E; ca.d_o = d_c;
-    ca.dq = d_a; ca.lddq = E; ca.dk = d_kvm_p; ca.dv = d_kvm_p + E; ca.lddkv = 2 * E; ca.Lq = L; ca.Lk = S; ca.H = H; ca.scale = scale;
-    ca.kv_accumulate = KP == 1 ? 1 : 0;      // KP == 1: d_kvm_p IS d_kvm; otherwise each pass of the batch writes its own copy
+    ca.q = w + o.q2; ca.q_bstride = (long)L * E; ca.ldq = E; ca.k = w + o.kvm; ca.v = w + o.kvm + E; ca.ldkv = 2 * E; ca.o = w + o.ca_o; ca.ldo = E;
+    ca.d_o = w + o.d_c; ca.dq = w + o.d_a; ca.lddq = E; ca.lddkv = 2 * E; ca.Lq = L; ca.Lk = S; ca.H = H; ca.scale = scale;
+    // d K | d V: KP == 1: d_kvm_p IS d_kvm and the passes accumulate; otherwise each pass of the batch writes its own copy — or, in the
+    // bf16-operand mode, one workgroup per (image, head) walks the batch's passes (train_ops.h TrainAttnArgs::pass_loop): the memory's K | V are
+    // staged once per batch instead of once per pass and d K | d V go straight into d_kvm (which d_kvm_p then names too), summed over the
+    // passes in the accumulators
+    ca.dk = w + o.d_kvm_p; ca.dv = w + o.d_kvm_p + E; ca.kv_accumulate = KP == 1 ? 1 : 0;
     ca.drop = drop;
     ca.pass_B = B; ca.qmask_pstride = 0; ca.site_pstride = 8; ca.kv_shared = 1;
-    // bf16-operand mode: one workgroup per (image, head) walks the batch's passes (train_ops.h TrainAttnArgs::pass_loop) — the memory's K | V
-    // are staged once per batch instead of once per pass and d K | d V go straight into d_kvm, summed over the passes in the accumulators
-    const bool ca_loop = o.ca_loop;      // decided by the layout (which then has no per-pass copies); the kernel's own preconditions must agree
-    if (ca_loop) { ca.dk = d_kvm; ca.dv = d_kvm + E; }
+    // the route (and with it the layout, which then has no per-pass copies) chose the pass-walking kernel; the kernel's own preconditions must agree
     if (ca_loop && train_attn_route(cx, ca, 32, true) != TA_DEC_BF16) return fail(PARSEQ_E_STATE, "training decoder: the workspace was laid out for the pass-walking cross-attention, which this call cannot run (its operands are not aligned for it)");
     enum { S_CONTENT, S_QUERY, S_SA_PROB, S_SA_OUT, S_CA_PROB, S_CA_OUT, S_FF_HIDDEN, S_FF_OUT };      // dropout sites of one pass
 
@@ -568,111 +603,88 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
         const int32_t* tgt = tgt_all + (size_t)i0 * M;
         auto site = [&](int k) { return (unsigned)(8 * i0 + k); };      // of the batch's first pass; pass p draws site + 8 p
         // ---- forward: model.decode (model.py:86-103) — the embeddings and the queries are dropped afresh in every pass -----------
-        CHK(dropout_add(cx, content0, true, nullptr, content, ME, kp, drop, site(S_CONTENT)));
-        CHK((run_layernorm<float>(s, content, P(p + "norm_c.weight"), P(p + "norm_c.bias"), cn, nullptr, R, E, eps)));
-        CHK(lin_fwd(cx, cn, sa_w + (size_t)E * E, sa_b + E, nullptr, 0, kvc, R, 2 * E, E));
-        hipLaunchKernelGGL(dropout_rows_passes_kernel, dim3((unsigned)((ME + 255) / 256), (unsigned)kp), dim3(256), 0, s, pq, L, E, qd, ME, drop, site(S_QUERY));
-        HIPCHK(hipGetLastError());
-        CHK((run_layernorm<float>(s, qd, P(p + "norm_q.weight"), P(p + "norm_q.bias"), qn, nullptr, R, E, eps)));
-        CHK(lin_fwd(cx, qn, sa_w, sa_b, nullptr, 0, qsa, R, E, E));
+        CHK(dropout_add(cx, w + o.content0, true, nullptr, w + o.content, ME, kp, drop, site(S_CONTENT)));
+        CHK((run_layernorm<float>(s, w + o.content, W(D_NORM_C_W), W(D_NORM_C_B), w + o.cn, nullptr, R, E, eps)));
+        CHK(lin_fwd(cx, w + o.cn, sa_w + EE, sa_b + E, nullptr, 0, w + o.kvc, R, 2 * E, E));
+        CHK(launch(dropout_rows_passes_kernel, dim3((unsigned)((ME + 255) / 256), (unsigned)kp), dim3(256), 0, s, pq, L, E, w + o.qd, ME, drop, site(S_QUERY)));
+        CHK((run_layernorm<float>(s, w + o.qd, W(D_NORM_Q_W), W(D_NORM_Q_B), w + o.qn, nullptr, R, E, eps)));
+        CHK(lin_fwd(cx, w + o.qn, sa_w, sa_b, nullptr, 0, w + o.qsa, R, E, E));
         // ---- DecoderLayer.forward_stream (modules.py:55-79), Decoder.norm (:124), head (model.py:63) -----------------------------
         sa.qmask = query_masks + (size_t)i0 * L * L; sa.drop_site = site(S_SA_PROB);
         CHK(train_attn(cx, sa, kp * B, false, 32));
-        CHK(lin_fwd(cx, sa_o, P(p + "self_attn.out_proj.weight"), P(p + "self_attn.out_proj.bias"), nullptr, 0, pm, R, E, E));
-        CHK(dropout_add(cx, pm, false, qd, t1, ME, kp, drop, site(S_SA_OUT)));
-        CHK((run_layernorm<float>(s, t1, P(p + "norm1.weight"), P(p + "norm1.bias"), n1, nullptr, R, E, eps)));
-        CHK(lin_fwd(cx, n1, ca_w, ca_b, nullptr, 0, q2, R, E, E));
+        CHK(lin_fwd(cx, w + o.sa_o, W(D_SA_OUT_W), W(D_SA_OUT_B), nullptr, 0, w + o.pm, R, E, E));
+        CHK(dropout_add(cx, w + o.pm, false, w + o.qd, w + o.t1, ME, kp, drop, site(S_SA_OUT)));
+        CHK((run_layernorm<float>(s, w + o.t1, W(D_NORM1_W), W(D_NORM1_B), w + o.n1, nullptr, R, E, eps)));
+        CHK(lin_fwd(cx, w + o.n1, ca_w, ca_b, nullptr, 0, w + o.q2, R, E, E));
         ca.drop_site = site(S_CA_PROB);
         if (ca_loop) { ca.pass_loop = kp; ca.kv_accumulate = i0 > 0 ? 1 : 0; }
         CHK(train_attn(cx, ca, kp * B, false, 32));
-        CHK(lin_fwd(cx, ca_o, P(p + "cross_attn.out_proj.weight"), P(p + "cross_attn.out_proj.bias"), nullptr, 0, pm, R, E, E));
-        CHK(dropout_add(cx, pm, false, t1, t2, ME, kp, drop, site(S_CA_OUT)));
-        CHK((run_layernorm<float>(s, t2, P(p + "norm2.weight"), P(p + "norm2.bias"), n2, nullptr, R, E, eps)));
-        CHK(lin_fwd(cx, n2, P(p + "linear1.weight"), P(p + "linear1.bias"), nullptr, 0, hpre, R, F, E, hact));      // hact = gelu(hpre): the product's epilogue (bf16-operand mode) or gelu_fwd_kernel
-        if (drop.thresh) CHK(dropout_add(cx, hact, false, nullptr, hact, MF, kp, drop, site(S_FF_HIDDEN)));
-        CHK(lin_fwd(cx, hact, P(p + "linear2.weight"), P(p + "linear2.bias"), nullptr, 0, pm, R, E, F));
-        CHK(dropout_add(cx, pm, false, t2, t3, ME, kp, drop, site(S_FF_OUT)));
-        CHK((run_layernorm<float>(s, t3, P("decoder.norm.weight"), P("decoder.norm.bias"), out, nullptr, R, E, eps)));
-        CHK(lin_fwd(cx, out, P("head.weight"), P("head.bias"), nullptr, 0, logits, R, C, E));
-        hipLaunchKernelGGL(ce_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, tgt, R, C, m->cfg.pad_id, row_loss);
-        HIPCHK(hipGetLastError());
-        for (int q = 0; q < kp; ++q) {             // each pass's own mean (system.py:189-190), rows summed in the order its own launch would
-            hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, row_loss + (size_t)q * M, tgt + (size_t)q * M, M, m->cfg.pad_id, losses + i0 + q,
-                               counts + i0 + q);
-            HIPCHK(hipGetLastError());
-        }
-        // ---- backward ------------------------------------------------------------------------------------------------------------
-        hipLaunchKernelGGL(ce_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, tgt, R, C, m->cfg.pad_id, 1.0f / (float)total_targets);
-        HIPCHK(hipGetLastError());
-        CHK(lin_bwd(cx, out, P("head.weight"), logits, G("head.weight"), G("head.bias"), d_a, R, C, E));                                    // d_a = d out
-        CHK(ln_bwd(cx, t3, P("decoder.norm.weight"), d_a, nullptr, d_b, G("decoder.norm.weight"), G("decoder.norm.bias"), R, E, eps));  // d_b = d t3
-        CHK(dropout_add(cx, d_b, false, nullptr, pm, ME, kp, drop, site(S_FF_OUT)));
-        CHK(lin_bwd(cx, hact, P(p + "linear2.weight"), pm, G(p + "linear2.weight"), G(p + "linear2.bias"), d_h, R, E, F));                  // d_h = d hact
+        CHK(lin_fwd(cx, w + o.ca_o, W(D_CA_OUT_W), W(D_CA_OUT_B), nullptr, 0, w + o.pm, R, E, E));
+        CHK(dropout_add(cx, w + o.pm, false, w + o.t1, w + o.t2, ME, kp, drop, site(S_CA_OUT)));
+        CHK((run_layernorm<float>(s, w + o.t2, W(D_NORM2_W), W(D_NORM2_B), w + o.n2, nullptr, R, E, eps)));
+        CHK(lin_fwd(cx, w + o.n2, W(D_LIN1_W), W(D_LIN1_B), nullptr, 0, w + o.hpre, R, F, E, w + o.hact));      // hact = gelu(hpre): the product's epilogue (bf16-operand mode) or gelu_fwd_kernel
+        if (drop.thresh) CHK(dropout_add(cx, w + o.hact, false, nullptr, w + o.hact, MF, kp, drop, site(S_FF_HIDDEN)));
+        CHK(lin_fwd(cx, w + o.hact, W(D_LIN2_W), W(D_LIN2_B), nullptr, 0, w + o.pm, R, E, F));
+        CHK(dropout_add(cx, w + o.pm, false, w + o.t2, w + o.t3, ME, kp, drop, site(S_FF_OUT)));
+        CHK((run_layernorm<float>(s, w + o.t3, W(D_NORM_W), W(D_NORM_B), w + o.out, nullptr, R, E, eps)));
+        CHK(lin_fwd(cx, w + o.out, W(D_HEAD_W), W(D_HEAD_B), nullptr, 0, w + o.logits, R, C, E));
+        CHK(ce_loss_and_grad(s, w + o.logits, tgt, kp, M, C, m->cfg.pad_id, w + o.row_loss, losses + i0, counts + i0, total_targets));
+        // ---- backward (o.logits now holds d logits) ------------------------------------------------------------------------------
+        CHK(lin_bwd(cx, w + o.out, W(D_HEAD_W), w + o.logits, W.g(D_HEAD_W), W.g(D_HEAD_B), w + o.d_a, R, C, E));                              // d_a = d out
+        CHK(ln_bwd(cx, w + o.t3, W(D_NORM_W), w + o.d_a, nullptr, w + o.d_b, W.g(D_NORM_W), W.g(D_NORM_B), R, E, eps));                        // d_b = d t3
+        CHK(dropout_add(cx, w + o.d_b, false, nullptr, w + o.pm, ME, kp, drop, site(S_FF_OUT)));
+        CHK(lin_bwd(cx, w + o.hact, W(D_LIN2_W), w + o.pm, W.g(D_LIN2_W), W.g(D_LIN2_B), w + o.d_h, R, E, F));                                 // d_h = d hact
         if (drop.thresh && MF % 4 == 0)            // d_h = d hpre: the MLP's inner dropout and the GELU backward in one pass
-            hipLaunchKernelGGL(gelu_bwd_drop_passes_kernel, dim3((unsigned)((MF + 1023) / 1024), (unsigned)kp), dim3(256), 0, s, hpre, d_h, d_h, MF, drop, site(S_FF_HIDDEN));
+            CHK(launch(gelu_bwd_drop_passes_kernel, dim3((unsigned)((MF + 1023) / 1024), (unsigned)kp), dim3(256), 0, s, w + o.hpre, w + o.d_h, w + o.d_h, MF, drop, site(S_FF_HIDDEN)));
         else {
-            if (drop.thresh) CHK(dropout_add(cx, d_h, false, nullptr, d_h, MF, kp, drop, site(S_FF_HIDDEN)));
-            hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)((RF + 1023) / 1024)), dim3(256), 0, s, hpre, d_h, d_h, RF);
+            if (drop.thresh) CHK(dropout_add(cx, w + o.d_h, false, nullptr, w + o.d_h, MF, kp, drop, site(S_FF_HIDDEN)));
+            CHK(gelu_bwd(cx, w + o.hpre, w + o.d_h, RF));
         }
-        HIPCHK(hipGetLastError());
-        CHK(lin_bwd(cx, n2, P(p + "linear1.weight"), d_h, G(p + "linear1.weight"), G(p + "linear1.bias"), d_a, R, F, E));                   // d_a = d n2
-        CHK(ln_bwd(cx, t2, P(p + "norm2.weight"), d_a, d_b, d_b, G(p + "norm2.weight"), G(p + "norm2.bias"), R, E, eps));          // d_b = d t2
-        CHK(dropout_add(cx, d_b, false, nullptr, pm, ME, kp, drop, site(S_CA_OUT)));
-        CHK(lin_bwd(cx, ca_o, P(p + "cross_attn.out_proj.weight"), pm, G(p + "cross_attn.out_proj.weight"), G(p + "cross_attn.out_proj.bias"),
-                    d_c, R, E, E));                                                                                                        // d_c = d ca_o
-        CHK(train_attn(cx, ca, kp * B, true, 32));                                                                                          // d_a = d q2; d_kvm_p[pass] = (KP == 1: d_kvm +=)
-        if (KP > 1 && !ca_loop) {                  // d_kvm (+)= the batch's passes, in ascending order
-            hipLaunchKernelGGL(sum_passes_kernel, dim3((unsigned)(((size_t)MS * 2 * E / 4 + 255) / 256)), dim3(256), 0, s, d_kvm_p, d_kvm, (size_t)MS * 2 * E, kp,
-                               i0 > 0 ? 1 : 0);
-            HIPCHK(hipGetLastError());
-        }
-        CHK(lin_bwd(cx, n1, ca_w, d_a, G(p + "cross_attn.in_proj_weight"), G(p + "cross_attn.in_proj_bias"), d_c, R, E, E));                // d_c = d n1
-        CHK(ln_bwd(cx, t1, P(p + "norm1.weight"), d_c, d_b, d_a, G(p + "norm1.weight"), G(p + "norm1.bias"), R, E, eps));          // d_a = d t1
-        CHK(dropout_add(cx, d_a, false, nullptr, pm, ME, kp, drop, site(S_SA_OUT)));
-        CHK(lin_bwd(cx, sa_o, P(p + "self_attn.out_proj.weight"), pm, G(p + "self_attn.out_proj.weight"), G(p + "self_attn.out_proj.bias"),
-                    d_b, R, E, E));                                                                                                        // d_b = d sa_o
-        CHK(train_attn(cx, sa, kp * B, true, 32));                                                                                          // d_qb = d q; d_kvc =
-        CHK(lin_bwd(cx, qn, sa_w, d_qb, G(p + "self_attn.in_proj_weight"), G(p + "self_attn.in_proj_bias"), d_c, R, E, E));                 // d_c = d qn
-        CHK(ln_bwd(cx, qd, P(p + "norm_q.weight"), d_c, d_a, d_b, G(p + "norm_q.weight"), G(p + "norm_q.bias"), R, E, eps));       // d_b = d qd
-        CHK(dropout_add(cx, d_b, false, nullptr, d_b, ME, kp, drop, site(S_QUERY)));
-        CHK(colsum(cx, d_b, (long)L * E, kp * B, L * E, d_pq, true));                           // every image's query rows are pos_queries[l]
-        CHK(lin_bwd(cx, cn, sa_w + (size_t)E * E, d_kvc, G(p + "self_attn.in_proj_weight") + (size_t)E * E, G(p + "self_attn.in_proj_bias") + E,
-                    d_c, R, 2 * E, E));                                                                                                    // d_c = d cn
-        CHK(ln_bwd(cx, content, P(p + "norm_c.weight"), d_c, nullptr, d_b, G(p + "norm_c.weight"), G(p + "norm_c.bias"), R, E, eps));  // d_b = d content
+        CHK(lin_bwd(cx, w + o.n2, W(D_LIN1_W), w + o.d_h, W.g(D_LIN1_W), W.g(D_LIN1_B), w + o.d_a, R, F, E));                                  // d_a = d n2
+        CHK(ln_bwd(cx, w + o.t2, W(D_NORM2_W), w + o.d_a, w + o.d_b, w + o.d_b, W.g(D_NORM2_W), W.g(D_NORM2_B), R, E, eps));                   // d_b = d t2
+        CHK(dropout_add(cx, w + o.d_b, false, nullptr, w + o.pm, ME, kp, drop, site(S_CA_OUT)));
+        CHK(lin_bwd(cx, w + o.ca_o, W(D_CA_OUT_W), w + o.pm, W.g(D_CA_OUT_W), W.g(D_CA_OUT_B), w + o.d_c, R, E, E));                           // d_c = d ca_o
+        CHK(train_attn(cx, ca, kp * B, true, 32));                                                                                              // d_a = d q2; d_kvm_p[pass] = (KP == 1: d_kvm +=)
+        if (KP > 1 && !ca_loop)                    // d_kvm (+)= the batch's passes, in ascending order
+            CHK(launch(sum_passes_kernel, dim3((unsigned)(((size_t)MS * 2 * E / 4 + 255) / 256)), dim3(256), 0, s, w + o.d_kvm_p, w + o.d_kvm, (size_t)MS * 2 * E, kp,
+                       i0 > 0 ? 1 : 0));
+        CHK(lin_bwd(cx, w + o.n1, ca_w, w + o.d_a, W.g(D_CA_IN_W), W.g(D_CA_IN_B), w + o.d_c, R, E, E));                                        // d_c = d n1
+        CHK(ln_bwd(cx, w + o.t1, W(D_NORM1_W), w + o.d_c, w + o.d_b, w + o.d_a, W.g(D_NORM1_W), W.g(D_NORM1_B), R, E, eps));                   // d_a = d t1
+        CHK(dropout_add(cx, w + o.d_a, false, nullptr, w + o.pm, ME, kp, drop, site(S_SA_OUT)));
+        CHK(lin_bwd(cx, w + o.sa_o, W(D_SA_OUT_W), w + o.pm, W.g(D_SA_OUT_W), W.g(D_SA_OUT_B), w + o.d_b, R, E, E));                           // d_b = d sa_o
+        CHK(train_attn(cx, sa, kp * B, true, 32));                                                                                              // d_qb = d q; d_kvc =
+        CHK(lin_bwd(cx, w + o.qn, sa_w, w + o.d_qb, W.g(D_SA_IN_W), W.g(D_SA_IN_B), w + o.d_c, R, E, E));                                       // d_c = d qn
+        CHK(ln_bwd(cx, w + o.qd, W(D_NORM_Q_W), w + o.d_c, w + o.d_a, w + o.d_b, W.g(D_NORM_Q_W), W.g(D_NORM_Q_B), R, E, eps));                // d_b = d qd
+        CHK(dropout_add(cx, w + o.d_b, false, nullptr, w + o.d_b, ME, kp, drop, site(S_QUERY)));
+        CHK(colsum(cx, w + o.d_b, (long)L * E, kp * B, L * E, w + o.d_pq, true));               // every image's query rows are pos_queries[l]
+        CHK(lin_bwd(cx, w + o.cn, sa_w + EE, w + o.d_kvc, W.g(D_SA_IN_W) + EE, W.g(D_SA_IN_B) + E, w + o.d_c, R, 2 * E, E));                    // d_c = d cn
+        CHK(ln_bwd(cx, w + o.content, W(D_NORM_C_W), w + o.d_c, nullptr, w + o.d_b, W.g(D_NORM_C_W), W.g(D_NORM_C_B), R, E, eps));             // d_b = d content
         // d_content (+)= every pass's d content through that pass's mask (the passes in ascending order)
-        hipLaunchKernelGGL(dropout_sum_passes_kernel, dim3((unsigned)((ME + 255) / 256)), dim3(256), 0, s, d_b, d_content, ME, kp, drop, site(S_CONTENT), i0 > 0 ? 1 : 0);
-        HIPCHK(hipGetLastError());
+        CHK(launch(dropout_sum_passes_kernel, dim3((unsigned)((ME + 255) / 256)), dim3(256), 0, s, w + o.d_b, w + o.d_content, ME, kp, drop, site(S_CONTENT), i0 > 0 ? 1 : 0));
     }
-    hipLaunchKernelGGL(loss_combine_kernel, dim3(1), dim3(64), 0, s, losses, counts, K, losses + K);
-    HIPCHK(hipGetLastError());
+    CHK(launch(loss_combine_kernel, dim3(1), dim3(64), 0, s, losses, counts, K, losses + K));
     HIPCHK(hipMemcpyAsync(loss_out, losses + K, sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(loss_out + 1, losses, (size_t)K * sizeof(float), hipMemcpyDeviceToDevice, s));
 
     // ---- what every permutation shares, once ---------------------------------------------------------------------------------------
-    if (L > 1) CHK(colsum(cx, d_content + E, (long)L * E, B, (L - 1) * E, d_pq, true));       // content row j carries pos_queries[j - 1]
+    if (L > 1) CHK(colsum(cx, w + o.d_content + E, (long)L * E, B, (L - 1) * E, w + o.d_pq, true));       // content row j carries pos_queries[j - 1]
     {   // token-embedding gradient: the B * L rows in chunks of 768, one workgroup per (token id, chunk), then the chunks folded in order
         const int rows_per = 768, chunks = (M + rows_per - 1) / rows_per;
         if (chunks > 1 && (size_t)m->cfg.num_tokens * chunks * E <= cx.scratch_floats) {
-            hipLaunchKernelGGL(embed_bwd_kernel, dim3(m->cfg.num_tokens, chunks), dim3(256), 0, s, d_content, tokens, L, B, L, E, sqrtE,
-                               G("text_embed.embedding.weight"), cx.scratch, rows_per);
-            hipLaunchKernelGGL(embed_bwd_fold_kernel, dim3(m->cfg.num_tokens), dim3(256), 0, s, cx.scratch, chunks, E, sqrtE, G("text_embed.embedding.weight"));
+            CHK(launch(embed_bwd_kernel, dim3(m->cfg.num_tokens, chunks), dim3(256), 0, s, w + o.d_content, tokens, L, B, L, E, sqrtE, W.g(D_TEXT_EMBED), cx.scratch, rows_per));
+            CHK(launch(embed_bwd_fold_kernel, dim3(m->cfg.num_tokens), dim3(256), 0, s, cx.scratch, chunks, E, sqrtE, W.g(D_TEXT_EMBED)));
         } else {
-            hipLaunchKernelGGL(embed_bwd_kernel, dim3(m->cfg.num_tokens, 1), dim3(256), 0, s, d_content, tokens, L, B, L, E, sqrtE,
-                               G("text_embed.embedding.weight"), (float*)nullptr, M);
+            CHK(launch(embed_bwd_kernel, dim3(m->cfg.num_tokens, 1), dim3(256), 0, s, w + o.d_content, tokens, L, B, L, E, sqrtE, W.g(D_TEXT_EMBED), (float*)nullptr, M));
         }
-        HIPCHK(hipGetLastError());
     }
-    CHK(lin_bwd(cx, memory, ca_w + (size_t)E * E, d_kvm, G(p + "cross_attn.in_proj_weight") + (size_t)E * E, G(p + "cross_attn.in_proj_bias") + E,
-                dmemory, MS, 2 * E, E));
-    hipLaunchKernelGGL(add_kernel, dim3((unsigned)(((size_t)L * E + 255) / 256)), dim3(256), 0, s, G("pos_queries"), d_pq, G("pos_queries"), (size_t)L * E);
-    HIPCHK(hipGetLastError());
-    return 0;
+    CHK(lin_bwd(cx, memory, ca_w + EE, w + o.d_kvm, W.g(D_CA_IN_W) + EE, W.g(D_CA_IN_B) + E, dmemory, MS, 2 * E, E));
+    return launch(add_kernel, dim3((unsigned)(((size_t)L * E + 255) / 256)), dim3(256), 0, s, W.g(D_POS_QUERIES), w + o.d_pq, W.g(D_POS_QUERIES), (size_t)L * E);
 }
 
 // ---- training step, encoder side: forward that keeps what the backward needs, and the backward ------------------------------
 struct TrainEncoderLayout {          // offsets in floats
     size_t patches, layer0, layer_stride, x_last, d_x, d_a, d_h, dqkv, tmp, scratch, scratch2, scratch_floats, total;      // scratch2: the backward's second stream
-    size_t w16, w16_layer, d_x16, d_h16;      // bf16 shadows (train_enc_shadows): the Linear weights and their transposes ([layer][qkv, proj, fc1, fc2][W16 | Wt16]),
+    size_t w16, w16_layer, d_x16, d_h16;      // bf16 shadows (TrainEncRoute::shadows): the Linear weights and their transposes ([layer][qkv, proj, fc1, fc2][W16 | Wt16]),
                                               // the residual-stream gradient and the fc1-output gradient
     size_t x(int i) const { return layer0 + i * layer_stride; }
     size_t lse = 0, dsum = 0;        // past 128 tokens only (train_attn_wide.h): the attention's log-sum-exp [B, H, tokens] inside each layer's
@@ -681,30 +693,65 @@ struct TrainEncoderLayout {          // offsets in floats
                                              // LayerNorm outputs, kept for the backward (round 3: they used to be recomputed there — a 600 MB and two
                                              // 150 MB passes per block; the record grows from 10 E to 16 E floats per token per block)
 };
+// How a training encoder call runs, decided once per call (on every call: the switches may change between two steps of one process):
+//   shadows      bf16 shadow operands for the encoder's products (train_ops.h SgemmArgs): the bf16-operand mode at the shapes the bf16
+//                attention kernel and the 64-deep GEMM take.  The record's n1 / n2 / ao / hact_l slots then hold bf16 (in the first half of
+//                the fp32 slot).  PARSEQ_TRAIN_NO_SHADOWS=1 keeps every operand fp32 in memory (the A/B and the bit-identity test).
+//   bf16_only    level 2 (the default with shadows on): tensors that exist ONLY to be rounded to bf16 by their consumers or to feed a GELU
+//                derivative are stored as bf16 and nothing else — the fc1 pre-activation (its GELU derivative is taken at the bf16 value),
+//                the gradient of the fc1 output and the gradient of q | k | v (the dW products read them as bf16 too; the bias gradients are
+//                sums of the bf16 values) — and the fc2 / proj dW products read the residual-stream gradient through its bf16 shadow (the
+//                fp32 copy stays: LayerNorm backward adds to it).  That is what bf16-mixed autocast keeps of these tensors (BASELINE
+//                configs[4]); it is no longer bit-identical to the fp32-in-memory path — the oracle gates of the bf16-operand mode hold
+//                it.  PARSEQ_TRAIN_SHADOW_LEVEL=1: shadows beside the fp32 copies only (bit-identical).
+//   one_launch   the forward as one launch: the bf16-only record at the geometry encoder_blocks.h is written for (E = 384, six 64-wide
+//                heads, 128 tokens, hidden = 4 E) with a block's record inside one 32-bit buffer descriptor.  PARSEQ_TRAIN_ENC_PER_OP=1:
+//                the per-operation launches (the A/B; also what every other geometry and record mode runs).
+//   two_streams  the backward's weight-gradient products on a side stream (enc_block_bwd_shadow); PARSEQ_TRAIN_ONE_STREAM=1 and level 1: one stream.
+//   wide         more than 128 tokens: the key-streaming attention (train_attn_wide.h) with its lse / dsum slots; the record at 128 tokens
+//                stays as it was, slot for slot.
+// The layout's sizes depend on `wide` (the lse / dsum slots; train_enc_wide, which the route repeats) and on whether a second stream can
+// exist at all (scratch2: the precision, not the switch, so a workspace serves either setting) — facts of the model alone; everything
+// else of the route needs the layout's record stride first.
+struct TrainEncRoute {
+    bool shadows, bf16_only, one_launch, two_streams, wide;
+    EncRecordMode record() const { return bf16_only ? REC_BF16_ONLY : shadows ? REC_SHADOWS : REC_F32; }      // what the record's slots hold
+};
+static bool train_enc_wide(const parseq_model* m) { return m->tokens > 128; }
+static TrainEncRoute train_enc_route(const parseq_model* m, const TrainEncoderLayout& o) {
+    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
+    TrainEncRoute r;
+    r.wide = train_enc_wide(m);
+    r.shadows = m->train_precision == PARSEQ_BF16 && E % 64 == 0 && F % 64 == 0 && m->tokens == TB_N && E == m->cfg.enc_heads * TB_HD &&
+                !getenv("PARSEQ_TRAIN_NO_SHADOWS");
+    const char* lv = getenv("PARSEQ_TRAIN_SHADOW_LEVEL");
+    r.bf16_only = r.shadows && !(lv && lv[0] == '1');
+    r.one_launch = r.bf16_only && E == 384 && m->cfg.enc_mlp_ratio == 4 && m->tokens == 128 && o.layer_stride * sizeof(float) < ((size_t)1 << 32) &&
+                   !getenv("PARSEQ_TRAIN_ENC_PER_OP");
+    r.two_streams = r.bf16_only && !getenv("PARSEQ_TRAIN_ONE_STREAM");
+    return r;
+}
 static TrainEncoderLayout train_encoder_layout(const parseq_model* m, int B) {
     const size_t E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio, MS = (size_t)B * m->tokens, PK = m->patch_k;
     TrainEncoderLayout o;
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t at = off; off += (n + 63) / 64 * 64; return at; };
+    Take take;
     o.patches = take(MS * PK);
-    o.layer0 = off;
-    take(MS * E); o.qkv = off - o.layer0; take(MS * 3 * E); o.ao = off - o.layer0; take(MS * E); o.x_mid = off - o.layer0; take(MS * E);
-    o.hpre = off - o.layer0; take(MS * F);
-    o.hact_l = off - o.layer0; take(MS * F);
-    o.n1 = off - o.layer0; take(MS * E); o.n2 = off - o.layer0; take(MS * E);
-    const bool wide = m->tokens > 128;          // the record at 128 tokens stays as it was, slot for slot
-    if (wide) { o.lse = off - o.layer0; take(MS * m->cfg.enc_heads); }
-    o.layer_stride = off - o.layer0;
-    off = o.layer0 + o.layer_stride * (size_t)m->cfg.enc_depth;
+    o.layer0 = take.off;
+    auto slot = [&](size_t n) { return take(n) - o.layer0; };      // inside the first block's record; every block's is laid out alike
+    slot(MS * E); o.qkv = slot(MS * 3 * E); o.ao = slot(MS * E); o.x_mid = slot(MS * E); o.hpre = slot(MS * F); o.hact_l = slot(MS * F);
+    o.n1 = slot(MS * E); o.n2 = slot(MS * E);
+    if (train_enc_wide(m)) o.lse = slot(MS * m->cfg.enc_heads);
+    o.layer_stride = take.off - o.layer0;
+    take.off = o.layer0 + o.layer_stride * (size_t)m->cfg.enc_depth;
     o.x_last = take(MS * E); o.d_x = take(MS * E); o.d_a = take(MS * E); o.d_h = take(MS * F);
     o.dqkv = take(MS * 3 * E); o.tmp = take(MS * E);
-    if (wide) o.dsum = take(MS * m->cfg.enc_heads);
+    if (train_enc_wide(m)) o.dsum = take(MS * m->cfg.enc_heads);
     o.scratch_floats = train_scratch_floats(MS, E); o.scratch = take(o.scratch_floats);
     // the second scratch belongs to the backward's second stream, which only the bf16-operand mode has (the fp32 mode carves nothing for it)
     o.scratch2 = m->train_precision == PARSEQ_BF16 ? take(o.scratch_floats) : o.scratch;
     o.w16_layer = 4 * E * E + 2 * E * F;      // floats = 2 bf16 each: W16 and Wt16 of the block's four Linear weights
     o.w16 = take(o.w16_layer * (size_t)m->cfg.enc_depth); o.d_x16 = take(MS * E / 2 + 8); o.d_h16 = take(MS * F / 2 + 8);
-    o.total = off;
+    o.total = take.off;
     return o;
 }
 
@@ -716,18 +763,17 @@ extern "C" size_t parseq_train_encoder_workspace_bytes(const parseq_model* m, in
 static int train_encoder_check(const parseq_model* m, int batch, const void* workspace, size_t workspace_bytes) {
     if (!m || !workspace) return fail(PARSEQ_E_INVALID, "null argument");
     if (batch <= 0) return fail(PARSEQ_E_INVALID, "batch %d", batch);
-    for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
+    CHK(require_params_set(m));
     const size_t need = train_encoder_layout(m, batch).total * sizeof(float);
     if (workspace_bytes < need) return fail(PARSEQ_E_INVALID, "workspace: %zu bytes given, %zu needed", workspace_bytes, need);
     return 0;
 }
 
-template <typename TO>
-static int train_ln_fwd(hipStream_t s, const float* x, const float* w, const float* b, TO* out, int rows, int E, float eps) {
+// LayerNorm of the training encoder, written in the type its consumer reads: fp32, or the bf16 shadow
+static int train_ln_fwd(hipStream_t s, const float* x, const float* w, const float* b, Out out, int rows, int E, float eps) {
     if (E > 768 || E % 2) return fail(PARSEQ_E_INVALID, "training layernorm: E=%d", E);
-    hipLaunchKernelGGL((ln_fwd_kernel<TO>), dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, out, rows, E, eps);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (out.b16) return launch(ln_fwd_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, out.b16, rows, E, eps);
+    return launch(ln_fwd_kernel<float>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, out.f32, rows, E, eps);
 }
 extern "C" int parseq_op_train_layernorm(const float* x, const float* gamma, const float* beta, void* y, int y_dtype, const float* dy, const float* add,
                                          float* dx, void* dx16, float* dgamma, float* dbeta, int rows, int E, float eps, int backward, float* scratch,
@@ -740,45 +786,40 @@ extern "C" int parseq_op_train_layernorm(const float* x, const float* gamma, con
         return ln_bwd(cx, x, gamma, dy, add, dx, dgamma, dbeta, rows, E, eps, static_cast<bf16_t*>(dx16));
     }
     if (!beta || !y || !gemm_dtype_ok(y_dtype)) return fail(PARSEQ_E_INVALID, "bad argument");
-    if (y_dtype == PARSEQ_BF16) return train_ln_fwd((hipStream_t)stream, x, gamma, beta, static_cast<bf16_t*>(y), rows, E, eps);
-    return train_ln_fwd((hipStream_t)stream, x, gamma, beta, static_cast<float*>(y), rows, E, eps);
+    return train_ln_fwd((hipStream_t)stream, x, gamma, beta, y_dtype == PARSEQ_BF16 ? Out(static_cast<bf16_t*>(y)) : Out(static_cast<float*>(y)), rows, E, eps);
 }
-// bf16 shadow operands for the encoder's products (train_ops.h SgemmArgs): the bf16-operand mode at the shapes the bf16 attention kernel
-// and the 64-deep GEMM take.  In that mode the record's n1 / n2 / ao / hact_l slots hold bf16 (in the first half of the fp32 slot).
-// PARSEQ_TRAIN_NO_SHADOWS=1 keeps every operand fp32 in memory (the A/B and the bit-identity test).
-static bool train_enc_shadows(const parseq_model* m) {
+
+// A block's twelve parameters with their gradient slots, its four Linear weights' bf16 shadows in the workspace (W16 [N, K] and the
+// transpose Wt16 [K, N] behind it; `at`: where W16 starts, in bf16 elements from the shadows' base ws + o.w16) and the forward's weight
+// operands in the route's type, resolved once per call for all blocks
+enum EncBlockParam { E_LN1_W, E_LN1_B, E_QKV_W, E_QKV_B, E_PROJ_W, E_PROJ_B, E_LN2_W, E_LN2_B, E_FC1_W, E_FC1_B, E_FC2_W, E_FC2_B, E_PARAMS };
+static const char* const kEncBlockKeys[E_PARAMS] = {"norm1.weight", "norm1.bias", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight", "attn.proj.bias",
+                                                    "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias"};
+static std::string enc_block_key(const parseq_model* m, int i, int k) { return m->enc + "blocks." + std::to_string(i) + "." + kEncBlockKeys[k]; }
+enum EncLinear { LIN_QKV, LIN_PROJ, LIN_FC1, LIN_FC2, ENC_LINEARS };      // [3E, E], [E, E], [F, E], [E, F]
+static const EncBlockParam kEncLinearW[ENC_LINEARS] = {E_QKV_W, E_PROJ_W, E_FC1_W, E_FC2_W};
+struct EncShadowW { bf16_t* w; bf16_t* wt; size_t at; int n, k; };      // n, k: the weight's shape [n, k]
+struct EncBlockW : ParamSet<E_PARAMS> {
+    EncShadowW s16[ENC_LINEARS];
+    In lin[ENC_LINEARS];      // the forward's weight operand: the W16 shadow on the shadow route, the master's fp32 otherwise
+};
+// grads, ws: null where the caller wants the offsets alone (the device tables below)
+static std::vector<EncBlockW> enc_block_weights(const parseq_model* m, const TrainEncoderLayout& o, bool shadows, float* grads, float* ws) {
     const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
-    return m->train_precision == PARSEQ_BF16 && E % 64 == 0 && F % 64 == 0 && m->tokens == TB_N && E == m->cfg.enc_heads * TB_HD &&
-           !getenv("PARSEQ_TRAIN_NO_SHADOWS");
-}
-// Level 2 (the default with shadows on): tensors that exist ONLY to be rounded to bf16 by their consumers or to feed a GELU derivative are
-// stored as bf16 and nothing else — the fc1 pre-activation (its GELU derivative is taken at the bf16 value), the gradient of the fc1
-// output and the gradient of q | k | v (the dW products read them as bf16 too; the bias gradients are sums of the bf16 values) — and the
-// fc2 / proj dW products read the residual-stream gradient through its bf16 shadow (the fp32 copy stays: LayerNorm backward adds to it).  That is
-// what bf16-mixed autocast keeps of these tensors (BASELINE configs[4]); it is no longer bit-identical to the fp32-in-memory path — the
-// oracle gates of the bf16-operand mode hold it.  PARSEQ_TRAIN_SHADOW_LEVEL=1: shadows beside the fp32 copies only (bit-identical).
-static bool train_enc_bf16_only(const parseq_model* m) {
-    const char* lv = getenv("PARSEQ_TRAIN_SHADOW_LEVEL");
-    return train_enc_shadows(m) && !(lv && lv[0] == '1');
-}
-// The forward as one launch: the bf16-only record (level 2) at the geometry encoder_blocks.h is written for (E = 384, six 64-wide heads,
-// 128 tokens, hidden = 4 E) with a block's record inside one 32-bit buffer descriptor.  PARSEQ_TRAIN_ENC_PER_OP=1: the per-operation
-// launches (the A/B; also what every other geometry and record mode runs).
-static bool train_enc_one_launch(const parseq_model* m, const TrainEncoderLayout& o) {
-    return train_enc_bf16_only(m) && m->cfg.embed_dim == 384 && m->cfg.enc_mlp_ratio == 4 && m->tokens == 128 &&
-           o.layer_stride * sizeof(float) < ((size_t)1 << 32) && !getenv("PARSEQ_TRAIN_ENC_PER_OP");
-}
-struct EncShadowW { bf16_t* w; bf16_t* wt; };
-// which: 0 attn.qkv [3E, E], 1 attn.proj [E, E], 2 mlp.fc1 [F, E], 3 mlp.fc2 [E, F]; enc_shadow_at: where a block's W16 starts, in bf16
-// elements from the shadows' base (ws + o.w16); its Wt16 follows it
-static size_t enc_shadow_at(const TrainEncoderLayout& o, int layer, int which, size_t E, size_t F) {
-    const size_t at[4] = {0, 6 * E * E, 8 * E * E, 8 * E * E + 2 * E * F};
-    return 2 * o.w16_layer * (size_t)layer + at[which];
-}
-static EncShadowW enc_shadow_w(const TrainEncoderLayout& o, float* ws, int layer, int which, size_t E, size_t F) {
-    bf16_t* w16 = reinterpret_cast<bf16_t*>(ws + o.w16) + enc_shadow_at(o, layer, which, E, F);
-    const size_t n[4] = {3 * E * E, E * E, E * F, E * F};
-    return EncShadowW{w16, w16 + n[which]};
+    const int wn[ENC_LINEARS] = {3 * E, E, F, E}, wk[ENC_LINEARS] = {E, E, E, F};
+    bf16_t* base = ws ? reinterpret_cast<bf16_t*>(ws + o.w16) : nullptr;
+    std::vector<EncBlockW> W(m->cfg.enc_depth);
+    for (int i = 0; i < m->cfg.enc_depth; ++i) {
+        for (int k = 0; k < E_PARAMS; ++k) W[i].v[k] = param_ref(m, enc_block_key(m, i, k), grads);
+        size_t at = 2 * o.w16_layer * (size_t)i;
+        for (int j = 0; j < ENC_LINEARS; ++j) {
+            const size_t nk = (size_t)wn[j] * wk[j];
+            W[i].s16[j] = EncShadowW{base ? base + at : nullptr, base ? base + at + nk : nullptr, at, wn[j], wk[j]};
+            W[i].lin[j] = shadows ? In(W[i].s16[j].w) : In(W[i](kEncLinearW[j]));
+            at += 2 * nk;
+        }
+    }
+    return W;
 }
 
 // Two device tables, model constants built on first use (offsets only, relative to the master weights and to the shadows' base, so any
@@ -798,16 +839,13 @@ static int upload_table(const std::vector<T>& tab, const char* what, T** out) {
 // weight_shadows_kernel's table: the 4 * depth Linear weights, where each lies in the master and where its W16 | Wt16 pair goes
 static int enc_shadow_table(parseq_model* m, const TrainEncoderLayout& o) {
     if (m->shadow_tab_dev) return 0;
-    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
-    const char* names[4] = {"attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight"};
-    const int wn[4] = {3 * E, E, F, E}, wk[4] = {E, E, E, F};
     std::vector<ShadowEntry> tab;
     unsigned tile = 0;
-    for (int i = 0; i < m->cfg.enc_depth; ++i)
-        for (int j = 0; j < 4; ++j) {
-            tab.push_back(ShadowEntry{(unsigned)m->params[m->index.at(m->enc + "blocks." + std::to_string(i) + "." + names[j])].offset, (unsigned)wn[j], (unsigned)wk[j],
-                                      tile, (unsigned long long)enc_shadow_at(o, i, j, E, F)});
-            tile += (unsigned)((wn[j] / 32) * (wk[j] / 32));
+    for (const EncBlockW& W : enc_block_weights(m, o, true, nullptr, nullptr))
+        for (int j = 0; j < ENC_LINEARS; ++j) {
+            const EncShadowW& sh = W.s16[j];
+            tab.push_back(ShadowEntry{(unsigned)W.v[kEncLinearW[j]].at, (unsigned)sh.n, (unsigned)sh.k, tile, (unsigned long long)sh.at});
+            tile += (unsigned)((sh.n / 32) * (sh.k / 32));
         }
     ShadowEntry* dev = nullptr;
     CHK(upload_table(tab, "weight-shadow", &dev));
@@ -818,18 +856,34 @@ static int enc_shadow_table(parseq_model* m, const TrainEncoderLayout& o) {
 // the one-launch forward's table: per block, the parameters' offsets into the master and the four W16 shadows' (bf16 elements from the shadows' base)
 static int enc_block_table(parseq_model* m, const TrainEncoderLayout& o) {
     if (m->train_blocks_dev) return 0;
-    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio;
-    std::vector<EncBlockParams> tab(m->cfg.enc_depth);
-    auto off = [&](const std::string& key) { return (unsigned)m->params[m->index.at(m->enc + key)].offset; };
-    auto w16 = [&](int i, int which) { return (unsigned)enc_shadow_at(o, i, which, E, F); };
-    for (int i = 0; i < m->cfg.enc_depth; ++i) {
-        const std::string b = "blocks." + std::to_string(i) + ".";
-        EncBlockParams& e = tab[i];
-        e.ln1_w = off(b + "norm1.weight"); e.ln1_b = off(b + "norm1.bias"); e.bqkv = off(b + "attn.qkv.bias"); e.bproj = off(b + "attn.proj.bias");
-        e.ln2_w = off(b + "norm2.weight"); e.ln2_b = off(b + "norm2.bias"); e.b1 = off(b + "mlp.fc1.bias"); e.b2 = off(b + "mlp.fc2.bias");
-        e.wqkv = w16(i, 0); e.wproj = w16(i, 1); e.w1 = w16(i, 2); e.w2 = w16(i, 3);
+    std::vector<EncBlockParams> tab;
+    for (const EncBlockW& W : enc_block_weights(m, o, true, nullptr, nullptr)) {
+        auto off = [&](int k) { return (unsigned)W.v[k].at; };
+        auto w16 = [&](int j) { return (unsigned)W.s16[j].at; };
+        EncBlockParams e{};
+        e.ln1_w = off(E_LN1_W); e.ln1_b = off(E_LN1_B); e.bqkv = off(E_QKV_B); e.bproj = off(E_PROJ_B);
+        e.ln2_w = off(E_LN2_W); e.ln2_b = off(E_LN2_B); e.b1 = off(E_FC1_B); e.b2 = off(E_FC2_B);
+        e.wqkv = w16(LIN_QKV); e.wproj = w16(LIN_PROJ); e.w1 = w16(LIN_FC1); e.w2 = w16(LIN_FC2);
+        tab.push_back(e);
     }
     return upload_table(tab, "training block", &m->train_blocks_dev);
+}
+
+// A block's record, slot by slot in the type the route stores it in — the one place where a record slot is read as bf16.  On the shadow
+// route n1 / n2 / the attention output / the GELU output hold bf16 in the first half of their slots, at level 2 the fc1 pre-activation too.
+//   x, qkv, x_mid, x_out   the block's input, q | k | v, the residual stream after the attention branch, the block's output: fp32 always
+//   ao, ao_v               the attention output's slot as the attention kernels address it (rows of E floats, whatever it holds), and its values
+//   lse                    past 128 tokens only
+struct EncBlockRec { float *x, *qkv, *x_mid, *x_out, *ao, *lse; Out n1, n2, ao_v, hpre, hact; };
+static EncBlockRec enc_block_rec(const TrainEncoderLayout& o, float* w, int i, int depth, const TrainEncRoute& r) {
+    float* x = w + o.x(i);
+    auto slot = [&](size_t at, bool bf16) { return bf16 ? Out(reinterpret_cast<bf16_t*>(x + at)) : Out(x + at); };
+    EncBlockRec c;
+    c.x = x; c.qkv = x + o.qkv; c.x_mid = x + o.x_mid; c.x_out = w + (i + 1 < depth ? o.x(i + 1) : o.x_last);
+    c.ao = x + o.ao; c.lse = r.wide ? x + o.lse : nullptr;
+    c.n1 = slot(o.n1, r.shadows); c.n2 = slot(o.n2, r.shadows); c.ao_v = slot(o.ao, r.shadows); c.hact = slot(o.hact_l, r.shadows);
+    c.hpre = slot(o.hpre, r.bf16_only);
+    return c;
 }
 
 static TrainAttnArgs enc_attn_args(const parseq_model* m, float* qkv, float* ao, const float* d_ao, float* dqkv, float* lse = nullptr, float* dsum = nullptr) {
@@ -842,81 +896,66 @@ static TrainAttnArgs enc_attn_args(const parseq_model* m, float* qkv, float* ao,
     return a;
 }
 
+// One block of the per-operation forward: x_mid = x + proj(attention(qkv(norm1(x)))), x_out = x_mid + fc2(gelu(fc1(norm2(x_mid)))), every
+// intermediate into the record.  The operands carry their type: the same seven operations run on fp32 slots and weights or on bf16 shadows.
+static int enc_block_fwd(const TrainCtx& cx, const parseq_model* m, int batch, const EncBlockRec& rec, const EncBlockW& W) {
+    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio, MS = batch * m->tokens;
+    const float eps = m->cfg.enc_ln_eps;
+    CHK(train_ln_fwd(cx.s, rec.x, W(E_LN1_W), W(E_LN1_B), rec.n1, MS, E, eps));
+    CHK(lin_fwd(cx, rec.n1, W.lin[LIN_QKV], W(E_QKV_B), nullptr, 0, rec.qkv, MS, 3 * E, E));
+    TrainAttnArgs aa = enc_attn_args(m, rec.qkv, rec.ao, nullptr, nullptr, rec.lse);
+    aa.o16 = rec.ao_v.b16;
+    CHK(train_attn(cx, aa, batch, false, ATT_HD));
+    CHK(lin_fwd(cx, rec.ao_v, W.lin[LIN_PROJ], W(E_PROJ_B), rec.x, MS, rec.x_mid, MS, E, E));
+    CHK(train_ln_fwd(cx.s, rec.x_mid, W(E_LN2_W), W(E_LN2_B), rec.n2, MS, E, eps));
+    CHK(lin_fwd(cx, rec.n2, W.lin[LIN_FC1], W(E_FC1_B), nullptr, 0, rec.hpre, MS, F, E, rec.hact));      // hpre and gelu(hpre), one epilogue
+    return lin_fwd(cx, rec.hact, W.lin[LIN_FC2], W(E_FC2_B), rec.x_mid, MS, rec.x_out, MS, E, F);
+}
+
 extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images, int batch, float* memory_out, void* workspace,
                                             size_t workspace_bytes, void* stream) {
     if (!images || !memory_out) return fail(PARSEQ_E_INVALID, "null argument");
     CHK(train_encoder_check(m, batch, workspace, workspace_bytes));
     DevGuard dg(m->device);
     const TrainEncoderLayout o = train_encoder_layout(m, batch);
+    const TrainEncRoute r = train_enc_route(m, o);
     hipStream_t s = (hipStream_t)stream;
-    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio, S = m->tokens, MS = batch * S, PK = m->patch_k;
+    const int E = m->cfg.embed_dim, S = m->tokens, MS = batch * S, PK = m->patch_k, depth = m->cfg.enc_depth;
     const float eps = m->cfg.enc_ln_eps;
     float* w = reinterpret_cast<float*>(workspace);
-    auto P = [&](const std::string& key) { return m->p(m->enc + key); };
+    auto P = [&](const char* key) { return m->p(m->enc + key); };
     const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
     if (m->vitstr) {
         // S - 1 patch rows per image, S token rows: the class token in front (timm _pos_embed), assembled from the patch product in `tmp`
         const int MP = batch * (S - 1);
-        hipLaunchKernelGGL(patches_kernel, dim3(MP), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches);
-        HIPCHK(hipGetLastError());
+        CHK(launch(patches_kernel, dim3(MP), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches));
         CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), nullptr, 0, w + o.tmp, MP, E, PK));
-        hipLaunchKernelGGL(vitstr_tokens_kernel, dim3(MS), dim3(256), 0, s, w + o.tmp, P("cls_token"), P("pos_embed"), w + o.x(0), S, E);
-        HIPCHK(hipGetLastError());
+        CHK(launch(vitstr_tokens_kernel, dim3(MS), dim3(256), 0, s, w + o.tmp, P("cls_token"), P("pos_embed"), w + o.x(0), S, E));
     } else {
-        hipLaunchKernelGGL(patches_kernel, dim3(MS), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches);
-        HIPCHK(hipGetLastError());
+        CHK(launch(patches_kernel, dim3(MS), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches));
         CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed"), S, w + o.x(0), MS, E, PK));
     }
-    const bool shadows = train_enc_shadows(m), only16 = train_enc_bf16_only(m);
-    m->enc_record_mode = (shadows ? 1 : 0) | (only16 ? 2 : 0);      // what the record's slots hold; the backward entry must read them the same way
+    m->enc_record_mode = r.record();      // what the record's slots hold; the backward entry must read them the same way
     m->enc_record_ws = workspace;
-    if (shadows) {
+    if (r.shadows) {
         // this step's weights as bf16, both ways round (the backward entry reads the transposes from the same workspace): one launch over
         // the 4 * depth matrices (it was one launch per matrix: 48 launches of 2 - 7 us)
         CHK(enc_shadow_table(m, o));
-        hipLaunchKernelGGL(weight_shadows_kernel, dim3(m->shadow_tiles), dim3(256), 0, s, m->master, reinterpret_cast<const ShadowEntry*>(m->shadow_tab_dev),
-                           4 * m->cfg.enc_depth, reinterpret_cast<bf16_t*>(w + o.w16));
-        HIPCHK(hipGetLastError());
+        CHK(launch(weight_shadows_kernel, dim3(m->shadow_tiles), dim3(256), 0, s, m->master, reinterpret_cast<const ShadowEntry*>(m->shadow_tab_dev), 4 * depth,
+                   reinterpret_cast<bf16_t*>(w + o.w16)));
     }
-    if (train_enc_one_launch(m, o)) {
+    if (r.one_launch) {
         // The twelve blocks as ONE launch (encoder_blocks.h record mode): the inference throughput kernel's walk — x resident in the
         // accumulators, the weights streamed from this step's bf16 shadows — writing the record on the way; 48 GEMM, 24 LayerNorm and
         // 12 attention launches and every re-read of an activation disappear, what is left is the record's own bytes.
-        const int depth = m->cfg.enc_depth;
         CHK(enc_block_table(m, o));
         const EncRecordParams rec{w + o.layer0, o.layer_stride, (unsigned)(o.layer_stride * sizeof(float)), (unsigned)(o.qkv * 4), (unsigned)(o.ao * 4),
                                   (unsigned)(o.x_mid * 4), (unsigned)(o.hpre * 4), (unsigned)(o.hact_l * 4), (unsigned)(o.n1 * 4), (unsigned)(o.n2 * 4)};
         HIPCHK((launch_enc_blocks_record<384>(s, w + o.x_last, reinterpret_cast<const bf16_t*>(w + o.w16), o.w16_layer * (size_t)depth * sizeof(float),
                                               m->master, m->train_blocks_dev, depth, eps, MS, rec)));
-        return run_layernorm<float>(s, w + o.x_last, P("norm.weight"), P("norm.bias"), memory_out, nullptr, MS, E, eps);
-    }
-    for (int i = 0; i < m->cfg.enc_depth; ++i) {
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        float* x = w + o.x(i); float* qkv = x + o.qkv; float* ao = x + o.ao; float* x_mid = x + o.x_mid; float* hpre = x + o.hpre;
-        float* x_out = i + 1 < m->cfg.enc_depth ? w + o.x(i + 1) : w + o.x_last;
-        if (shadows) {
-            bf16_t* n1 = reinterpret_cast<bf16_t*>(x + o.n1); bf16_t* n2 = reinterpret_cast<bf16_t*>(x + o.n2);
-            bf16_t* ao16 = reinterpret_cast<bf16_t*>(ao); bf16_t* hact16 = reinterpret_cast<bf16_t*>(x + o.hact_l);
-            CHK(train_ln_fwd(s, x, P(p + "norm1.weight"), P(p + "norm1.bias"), n1, MS, E, eps));
-            CHK(lin_fwd(cx, n1, enc_shadow_w(o, w, i, 0, E, F).w, P(p + "attn.qkv.bias"), nullptr, 0, qkv, MS, 3 * E, E));
-            TrainAttnArgs aa = enc_attn_args(m, qkv, ao, nullptr, nullptr);
-            aa.o16 = ao16;
-            CHK(train_attn(cx, aa, batch, false, ATT_HD));
-            CHK(lin_fwd(cx, ao16, enc_shadow_w(o, w, i, 1, E, F).w, P(p + "attn.proj.bias"), x, MS, x_mid, MS, E, E));
-            CHK(train_ln_fwd(s, x_mid, P(p + "norm2.weight"), P(p + "norm2.bias"), n2, MS, E, eps));
-            const Out pre = only16 ? Out(reinterpret_cast<bf16_t*>(hpre)) : Out(hpre);      // level 2: the pre-activation exists as bf16 only
-            CHK(lin_fwd(cx, n2, enc_shadow_w(o, w, i, 2, E, F).w, P(p + "mlp.fc1.bias"), nullptr, 0, pre, MS, F, E, hact16));
-            CHK(lin_fwd(cx, hact16, enc_shadow_w(o, w, i, 3, E, F).w, P(p + "mlp.fc2.bias"), x_mid, MS, x_out, MS, E, F));
-            continue;
-        }
-        CHK(train_ln_fwd(s, x, P(p + "norm1.weight"), P(p + "norm1.bias"), x + o.n1, MS, E, eps));
-        CHK(lin_fwd(cx, x + o.n1, P(p + "attn.qkv.weight"), P(p + "attn.qkv.bias"), nullptr, 0, qkv, MS, 3 * E, E));
-        CHK(train_attn(cx, enc_attn_args(m, qkv, ao, nullptr, nullptr, o.lse ? x + o.lse : nullptr), batch, false, ATT_HD));
-        CHK(lin_fwd(cx, ao, P(p + "attn.proj.weight"), P(p + "attn.proj.bias"), x, MS, x_mid, MS, E, E));
-        CHK(train_ln_fwd(s, x_mid, P(p + "norm2.weight"), P(p + "norm2.bias"), x + o.n2, MS, E, eps));
-        float* hact_l = x + o.hact_l;
-        CHK(lin_fwd(cx, x + o.n2, P(p + "mlp.fc1.weight"), P(p + "mlp.fc1.bias"), nullptr, 0, hpre, MS, F, E, hact_l));      // hpre and gelu(hpre), one epilogue
-        CHK(lin_fwd(cx, hact_l, P(p + "mlp.fc2.weight"), P(p + "mlp.fc2.bias"), x_mid, MS, x_out, MS, E, F));
+    } else {
+        const std::vector<EncBlockW> W = enc_block_weights(m, o, r.shadows, nullptr, w);
+        for (int i = 0; i < depth; ++i) CHK(enc_block_fwd(cx, m, batch, enc_block_rec(o, w, i, depth, r), W[i]));
     }
     return run_layernorm<float>(s, w + o.x_last, P("norm.weight"), P("norm.bias"), memory_out, nullptr, MS, E, eps);
 }
@@ -930,12 +969,12 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
 // stream right after the last kernel that writes into it:
 //   0: [decoder begin, end)            1: [block depth-1 begin, decoder begin)  (with encoder.norm)
 //   1 + j: block depth-1-j, j = 1 .. depth-2          depth: [0, block 0 end)   (pos_queries, pos_embed, patch_embed, block 0)
-static int64_t grad_block_begin(const parseq_model* m, int i) { return (int64_t)m->params[m->index.at(m->enc + "blocks." + std::to_string(i) + ".norm1.weight")].offset; }
+static int64_t grad_block_begin(const parseq_model* m, int i) { return (int64_t)m->params[m->index.at(enc_block_key(m, i, E_LN1_W))].offset; }
 static int grad_segment_range(const parseq_model* m, int k, int64_t* begin, int64_t* end) {
     const int depth = m->cfg.enc_depth;
     if (m->vitstr || depth < 2) return fail(PARSEQ_E_INVALID, "gradient segments are defined for the PARSeq training step (depth >= 2)");
     if (k < 0 || k > depth) return fail(PARSEQ_E_INVALID, "gradient segment %d outside [0, %d]", k, depth);
-    const int64_t dec = (int64_t)m->params[m->index.at("decoder.layers.0.self_attn.in_proj_weight")].offset;
+    const int64_t dec = (int64_t)m->params[m->index.at(train_dec_key(D_SA_IN_W))].offset;
     if (k == 0) { *begin = dec; *end = (int64_t)m->master_elems; }
     else if (k == 1) { *begin = grad_block_begin(m, depth - 1); *end = dec; }
     else if (k < depth) { *begin = grad_block_begin(m, depth - k); *end = grad_block_begin(m, depth - k + 1); }
@@ -968,128 +1007,147 @@ extern "C" int parseq_stream_wait_event(void* stream, void* event) {
     return 0;
 }
 
+// The backward's gradient buffers in the type the route keeps them in.  Level 2 keeps the gradient of the fc1 output and of q | k | v as
+// bf16 alone, and its dW products read the residual-stream gradient through the shadow d_x16 (the fp32 d_x stays: LayerNorm backward adds to it).
+//   d_x, d_x16    the residual-stream gradient and its shadow (shadow route); d_x_dy: ... as the dY of a product
+//   d_h           the gradient of the fc1 output, then of its pre-activation
+//   dqkv, dqkv16  the gradient of q | k | v as the attention kernels address it, and where level 2 has them write bf16; dqkv_dy: as a dY
+//   dsum          past 128 tokens only
+struct EncBwdBufs { float *d_x, *d_a, *dqkv, *dsum; bf16_t *d_x16, *dqkv16; In d_x_dy, dqkv_dy; Out d_h; };
+static EncBwdBufs enc_bwd_bufs(const TrainEncoderLayout& o, float* w, const TrainEncRoute& r) {
+    EncBwdBufs g;
+    g.d_x = w + o.d_x; g.d_a = w + o.d_a; g.dqkv = w + o.dqkv; g.dsum = r.wide ? w + o.dsum : nullptr;
+    g.d_x16 = r.shadows ? reinterpret_cast<bf16_t*>(w + o.d_x16) : nullptr; g.dqkv16 = r.bf16_only ? reinterpret_cast<bf16_t*>(g.dqkv) : nullptr;
+    g.d_x_dy = In(r.bf16_only ? nullptr : g.d_x, g.d_x16); g.dqkv_dy = In(r.bf16_only ? nullptr : g.dqkv, g.dqkv16);
+    g.d_h = Out(r.bf16_only ? nullptr : w + o.d_h, r.shadows ? reinterpret_cast<bf16_t*>(w + o.d_h16) : nullptr);
+    return g;
+}
+
+// The caller stream's own side stream and events, created on first use (a step split into micro-batches runs several backwards at once,
+// each on its own stream), and the three ways the shadow block orders the two; with `on` false everything runs on the caller's stream
+struct SideFork {
+    bool on = false; hipStream_t s = nullptr, side = nullptr; hipEvent_t* ev = nullptr;
+    int fork(int e) const { if (on) { HIPCHK(hipEventRecord(ev[e], s)); HIPCHK(hipStreamWaitEvent(side, ev[e], 0)); } return 0; }      // the side stream waits for the main one
+    int mark(int e) const { if (on) HIPCHK(hipEventRecord(ev[e], side)); return 0; }                                                  // a point on the side stream ...
+    int join(int e) const { if (on) HIPCHK(hipStreamWaitEvent(s, ev[e], 0)); return 0; }                                              // ... that the main stream waits for
+};
+static int train_side_for(parseq_model* m, hipStream_t s, SideFork* out) {
+    size_t slot = 0;
+    while (slot < m->train_sides.size() && m->train_sides[slot].key != s) ++slot;
+    if (slot == m->train_sides.size()) {
+        if (slot >= 8) return fail(PARSEQ_E_STATE, "training encoder backward: more than 8 distinct caller streams on one model");
+        parseq_model::TrainSide ts;
+        ts.key = s;
+        HIPCHK(hipStreamCreateWithFlags(&ts.side, hipStreamNonBlocking));
+        for (hipEvent_t& e : ts.ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        m->train_sides.push_back(ts);
+    }
+    out->on = true; out->s = s; out->side = m->train_sides[slot].side; out->ev = m->train_sides[slot].ev;
+    return 0;
+}
+
+// One block of the backward on bf16 shadow operands.  The block's four weight-gradient products run on the side context `cxs`, beside the
+// chain dX -> LayerNorm / attention backward -> dX that needs them for nothing.  With two streams each starts when its dY exists (an event
+// of the main stream) and is waited for only where the main stream is about to overwrite that dY (the residual-stream gradient's shadow
+// d_x16) or closes the block; with one stream (PARSEQ_TRAIN_ONE_STREAM=1, and always at level 1) the side context is the main one and the
+// events are skipped.  Same kernels, same operands, same order inside every buffer either way: bit-identical.  The level decides only which
+// gradients also exist in fp32 (level 1) and which exist as bf16 only (level 2: the fc1 pre-activation, d q | k | v, and d_x as the dY of
+// the dW products).  An error return must not leave weight-gradient kernels running on the side stream behind the caller's back: the
+// caller joins the side stream before it reports a failure of this function.
+static int enc_block_bwd_shadow(const TrainCtx& cx, const TrainCtx& cxs, const SideFork& fk, const parseq_model* m, int batch, const EncBlockRec& rec,
+                                const EncBlockW& W, const EncBwdBufs& g) {
+    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio, MS = batch * m->tokens;
+    const float eps = m->cfg.enc_ln_eps;
+    CHK(fk.fork(0));                                                                                    // d_x16 of this block exists
+    CHK(lin_bwd16_dw(cxs, rec.hact.b16, g.d_x_dy, W.g(E_FC2_W), W.g(E_FC2_B), MS, E, F));
+    CHK(fk.mark(4));
+    CHK(lin_bwd16_dx(cx, W.s16[LIN_FC2].wt, g.d_x_dy, g.d_h, MS, E, F, rec.hpre));
+    CHK(fk.fork(1));                                                                                    // d_h16 exists
+    CHK(lin_bwd16_dw(cxs, rec.n2.b16, g.d_h, W.g(E_FC1_W), W.g(E_FC1_B), MS, F, E));
+    CHK(lin_bwd16_dx(cx, W.s16[LIN_FC1].wt, g.d_h, g.d_a, MS, F, E));
+    CHK(fk.join(4));                                                                                    // fc2's dW has read d_x16
+    CHK(ln_bwd(cx, rec.x_mid, W(E_LN2_W), g.d_a, g.d_x, g.d_x, W.g(E_LN2_W), W.g(E_LN2_B), MS, E, eps, g.d_x16));
+    CHK(fk.fork(2));                                                                                    // the new d_x16 exists
+    CHK(lin_bwd16_dw(cxs, rec.ao_v.b16, g.d_x_dy, W.g(E_PROJ_W), W.g(E_PROJ_B), MS, E, E));
+    CHK(fk.mark(5));
+    CHK(lin_bwd16_dx(cx, W.s16[LIN_PROJ].wt, g.d_x_dy, g.d_a, MS, E, E));
+    TrainAttnArgs ab = enc_attn_args(m, rec.qkv, rec.ao, g.d_a, g.dqkv);
+    if (g.dqkv16) { ab.dq16 = g.dqkv16; ab.dk16 = g.dqkv16 + E; ab.dv16 = g.dqkv16 + 2 * E; }
+    CHK(train_attn(cx, ab, batch, true, ATT_HD));
+    CHK(fk.fork(3));                                                                                    // d q | k | v exists
+    CHK(lin_bwd16_dw(cxs, rec.n1.b16, g.dqkv_dy, W.g(E_QKV_W), W.g(E_QKV_B), MS, 3 * E, E));
+    CHK(fk.mark(6));
+    CHK(lin_bwd16_dx(cx, W.s16[LIN_QKV].wt, g.dqkv_dy, g.d_a, MS, 3 * E, E));
+    CHK(fk.join(5));                                                                                    // proj's dW has read d_x16
+    CHK(ln_bwd(cx, rec.x, W(E_LN1_W), g.d_a, g.d_x, g.d_x, W.g(E_LN1_W), W.g(E_LN1_B), MS, E, eps, g.d_x16));
+    return fk.join(6);        // the block's gradients are final on the main stream too (the segment event that follows covers them)
+}
+// One block of the backward with every operand fp32 in memory (lin_bwd: its padded path and folded epilogues), one stream
+static int enc_block_bwd_f32(const TrainCtx& cx, const parseq_model* m, int batch, const EncBlockRec& rec, const EncBlockW& W, const EncBwdBufs& g) {
+    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio, MS = batch * m->tokens;
+    const float eps = m->cfg.enc_ln_eps;
+    // x_out = x_mid + fc2(gelu(fc1(norm2(x_mid))))        d_x = d x_out
+    CHK(lin_bwd(cx, rec.hact.f32, W(E_FC2_W), g.d_x, W.g(E_FC2_W), W.g(E_FC2_B), g.d_h.f32, MS, E, F, rec.hpre.f32));      // d_h = d hpre (GELU backward folded in)
+    CHK(lin_bwd(cx, rec.n2.f32, W(E_FC1_W), g.d_h.f32, W.g(E_FC1_W), W.g(E_FC1_B), g.d_a, MS, F, E));
+    CHK(ln_bwd(cx, rec.x_mid, W(E_LN2_W), g.d_a, g.d_x, g.d_x, W.g(E_LN2_W), W.g(E_LN2_B), MS, E, eps));                   // d_x = d x_mid
+    // x_mid = x + proj(attention(qkv(norm1(x))))
+    CHK(lin_bwd(cx, rec.ao_v.f32, W(E_PROJ_W), g.d_x, W.g(E_PROJ_W), W.g(E_PROJ_B), g.d_a, MS, E, E));                     // d_a = d ao
+    CHK(train_attn(cx, enc_attn_args(m, rec.qkv, rec.ao, g.d_a, g.dqkv, rec.lse, rec.lse ? g.dsum : nullptr), batch, true, ATT_HD));
+    CHK(lin_bwd(cx, rec.n1.f32, W(E_QKV_W), g.dqkv, W.g(E_QKV_W), W.g(E_QKV_B), g.d_a, MS, 3 * E, E));
+    return ln_bwd(cx, rec.x, W(E_LN1_W), g.d_a, g.d_x, g.d_x, W.g(E_LN1_W), W.g(E_LN1_B), MS, E, eps);                     // d_x = d x
+}
+
 extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemory, int batch, float* grads, void* workspace, size_t workspace_bytes,
                                              void* stream) {
     if (!dmemory || !grads) return fail(PARSEQ_E_INVALID, "null argument");
     CHK(train_encoder_check(m, batch, workspace, workspace_bytes));
     DevGuard dg(m->device);
     const TrainEncoderLayout o = train_encoder_layout(m, batch);
+    const TrainEncRoute r = train_enc_route(m, o);
+    if (m->enc_record_ws == workspace && m->enc_record_mode != r.record())
+        return fail(PARSEQ_E_STATE, "training encoder backward: the record in this workspace was written in mode %d, this call would read it in mode %d "
+                    "(PARSEQ_TRAIN_NO_SHADOWS / PARSEQ_TRAIN_SHADOW_LEVEL / train precision changed between forward and backward)", (int)m->enc_record_mode,
+                    (int)r.record());
     hipStream_t s = (hipStream_t)stream;
-    const int E = m->cfg.embed_dim, F = E * m->cfg.enc_mlp_ratio, S = m->tokens, MS = batch * S, PK = m->patch_k;
+    const int E = m->cfg.embed_dim, S = m->tokens, MS = batch * S, PK = m->patch_k, depth = m->cfg.enc_depth;
     const float eps = m->cfg.enc_ln_eps;
     float* w = reinterpret_cast<float*>(workspace);
-    auto P = [&](const std::string& key) { return m->p(m->enc + key); };
-    auto G = [&](const std::string& key) { return grads + m->params[m->index.at(m->enc + key)].offset; };
-    float* d_x = w + o.d_x; float* d_a = w + o.d_a; float* d_h = w + o.d_h; float* dqkv = w + o.dqkv;
-    float* tmp = w + o.tmp;
+    auto top = [&](const char* key) { return param_ref(m, m->enc + key, grads); };      // the encoder's parameters outside the blocks
     const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
-    const bool shadows = train_enc_shadows(m), only16 = train_enc_bf16_only(m);
-    if (m->enc_record_ws == workspace && m->enc_record_mode != ((shadows ? 1 : 0) | (only16 ? 2 : 0)))
-        return fail(PARSEQ_E_STATE, "training encoder backward: the record in this workspace was written in mode %d, this call would read it in mode %d "
-                    "(PARSEQ_TRAIN_NO_SHADOWS / PARSEQ_TRAIN_SHADOW_LEVEL / train precision changed between forward and backward)", m->enc_record_mode,
-                    (shadows ? 1 : 0) | (only16 ? 2 : 0));
-    bf16_t* d_x16 = shadows ? reinterpret_cast<bf16_t*>(w + o.d_x16) : nullptr;
-    bf16_t* d_h16 = shadows ? reinterpret_cast<bf16_t*>(w + o.d_h16) : nullptr;
-    const bool segs = !m->vitstr && m->cfg.enc_depth >= 2;
-    const bool two_streams = only16 && !getenv("PARSEQ_TRAIN_ONE_STREAM");
-    hipStream_t side = nullptr;
-    hipEvent_t* side_ev = nullptr;
-    if (two_streams) {
-        // the caller stream's own side stream and events (a step split into micro-batches runs several backwards at once, each on its own stream)
-        size_t slot = 0;
-        while (slot < m->train_sides.size() && m->train_sides[slot].key != s) ++slot;
-        if (slot == m->train_sides.size()) {
-            if (slot >= 8) return fail(PARSEQ_E_STATE, "training encoder backward: more than 8 distinct caller streams on one model");
-            parseq_model::TrainSide ts;
-            ts.key = s;
-            HIPCHK(hipStreamCreateWithFlags(&ts.side, hipStreamNonBlocking));
-            for (hipEvent_t& e : ts.ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            m->train_sides.push_back(ts);
-        }
-        side = m->train_sides[slot].side;
-        side_ev = m->train_sides[slot].ev;
-    }
-    // the context of the bf16 block's weight-gradient products: the side stream and its scratch, or with one stream the main context
-    const TrainCtx cxs = two_streams ? TrainCtx{side, w + o.scratch2, m->train_precision == PARSEQ_BF16, o.scratch_floats} : cx;
+    const EncBwdBufs g = enc_bwd_bufs(o, w, r);
+    const bool segs = !m->vitstr && depth >= 2;
+    SideFork fk;
+    if (r.two_streams) CHK(train_side_for(m, s, &fk));
+    // the context of the shadow block's weight-gradient products: the side stream and its scratch, or with one stream the main context
+    const TrainCtx cxs = r.two_streams ? TrainCtx{fk.side, w + o.scratch2, cx.bf16_ops, o.scratch_floats} : cx;
+    const std::vector<EncBlockW> W = enc_block_weights(m, o, r.shadows, grads, w);
     m->grad_events_valid = false;
     if (segs) CHK(grad_event_record(m, 0, s));      // the decoder's gradients were written by parseq_train_decoder, earlier on this stream
-    CHK(ln_bwd(cx, w + o.x_last, P("norm.weight"), dmemory, nullptr, d_x, G("norm.weight"), G("norm.bias"), MS, E, eps, d_x16));
-    for (int i = m->cfg.enc_depth - 1; i >= 0; --i) {
+    const ParamRef norm_w = top("norm.weight");
+    CHK(ln_bwd(cx, w + o.x_last, norm_w.p, dmemory, nullptr, g.d_x, norm_w.g, top("norm.bias").g, MS, E, eps, g.d_x16));
+    for (int i = depth - 1; i >= 0; --i) {
         // block i + 1 (and, behind the last block, encoder.norm) is final: segment depth - 1 - i
-        if (segs && i < m->cfg.enc_depth - 1 && i >= 0) CHK(grad_event_record(m, m->cfg.enc_depth - 1 - i, s));
-        const std::string p = "blocks." + std::to_string(i) + ".";
-        float* x = w + o.x(i); float* qkv = x + o.qkv; float* ao = x + o.ao; float* x_mid = x + o.x_mid; float* hpre = x + o.hpre;
-        if (shadows) {
-            // The block's four weight-gradient products run on the side context, beside the chain dX -> LayerNorm / attention backward -> dX that
-            // needs them for nothing.  With two streams each starts when its dY exists (an event of the main stream) and is waited for only where
-            // the main stream is about to overwrite that dY (the residual-stream gradient's shadow d_x16) or closes the block; with one stream
-            // (PARSEQ_TRAIN_ONE_STREAM=1, and always at level 1) the side context is the main one and the events are skipped.  Same kernels, same
-            // operands, same order inside every buffer either way: bit-identical.  The level decides only which gradients also exist in fp32
-            // (level 1) and which exist as bf16 only (level 2: the fc1 pre-activation, d q | k | v, and d_x as the dY of the dW products).
-            // (an error return inside the block must not leave weight-gradient kernels running on the side stream behind the caller's back:
-            // the block is a lambda and a failure joins the side stream before it is reported)
-            auto block = [&]() -> int {
-                const bf16_t* n1 = reinterpret_cast<const bf16_t*>(x + o.n1); const bf16_t* n2 = reinterpret_cast<const bf16_t*>(x + o.n2);
-                const bf16_t* ao16 = reinterpret_cast<const bf16_t*>(ao); const bf16_t* hact16 = reinterpret_cast<const bf16_t*>(x + o.hact_l);
-                const float* d_x32 = only16 ? nullptr : d_x; float* d_h32 = only16 ? nullptr : d_h; const float* dqkv32 = only16 ? nullptr : dqkv;
-                const float* hpre32 = only16 ? nullptr : hpre; const bf16_t* hpre16 = only16 ? reinterpret_cast<const bf16_t*>(hpre) : nullptr;
-                bf16_t* dqkv16 = only16 ? reinterpret_cast<bf16_t*>(dqkv) : nullptr;
-                auto fork = [&](int e) -> int { if (two_streams) { HIPCHK(hipEventRecord(side_ev[e], s)); HIPCHK(hipStreamWaitEvent(side, side_ev[e], 0)); } return 0; };
-                auto mark = [&](int e) -> int { if (two_streams) HIPCHK(hipEventRecord(side_ev[e], side)); return 0; };
-                auto join = [&](int e) -> int { if (two_streams) HIPCHK(hipStreamWaitEvent(s, side_ev[e], 0)); return 0; };
-                CHK(fork(0));                                                                                       // d_x16 of this block exists
-                CHK(lin_bwd16_dw(cxs, hact16, d_x32, d_x16, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), MS, E, F));
-                CHK(mark(4));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 3, E, F).wt, d_x32, d_x16, d_h32, d_h16, MS, E, F, In(hpre32, hpre16)));
-                CHK(fork(1));                                                                                       // d_h16 exists
-                CHK(lin_bwd16_dw(cxs, n2, d_h32, d_h16, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), MS, F, E));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 2, E, F).wt, d_h32, d_h16, d_a, nullptr, MS, F, E));
-                CHK(join(4));                                                                                       // fc2's dW has read d_x16
-                CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), MS, E, eps, d_x16));
-                CHK(fork(2));                                                                                       // the new d_x16 exists
-                CHK(lin_bwd16_dw(cxs, ao16, d_x32, d_x16, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), MS, E, E));
-                CHK(mark(5));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 1, E, F).wt, d_x32, d_x16, d_a, nullptr, MS, E, E));
-                TrainAttnArgs ab = enc_attn_args(m, qkv, ao, d_a, dqkv);
-                if (dqkv16) { ab.dq16 = dqkv16; ab.dk16 = dqkv16 + E; ab.dv16 = dqkv16 + 2 * E; }
-                CHK(train_attn(cx, ab, batch, true, ATT_HD));
-                CHK(fork(3));                                                                                       // d q | k | v exists
-                CHK(lin_bwd16_dw(cxs, n1, dqkv32, dqkv16, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), MS, 3 * E, E));
-                CHK(mark(6));
-                CHK(lin_bwd16_dx(cx, enc_shadow_w(o, w, i, 0, E, F).wt, dqkv32, dqkv16, d_a, nullptr, MS, 3 * E, E));
-                CHK(join(5));                                                                                       // proj's dW has read d_x16
-                CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), MS, E, eps, d_x16));
-                return join(6);       // the block's gradients are final on the main stream too (the segment event that follows covers them)
-            };
-            if (const int rc = block()) {
-                if (two_streams) (void)hipStreamSynchronize(side);      // whatever was enqueued there has finished with `grads` and the workspace before the caller hears of the failure
-                return rc;
-            }
-            continue;
+        if (segs && i < depth - 1) CHK(grad_event_record(m, depth - 1 - i, s));
+        const EncBlockRec rec = enc_block_rec(o, w, i, depth, r);
+        if (!r.shadows) { CHK(enc_block_bwd_f32(cx, m, batch, rec, W[i], g)); continue; }
+        if (const int rc = enc_block_bwd_shadow(cx, cxs, fk, m, batch, rec, W[i], g)) {
+            if (fk.on) (void)hipStreamSynchronize(fk.side);      // whatever was enqueued there has finished with `grads` and the workspace before the caller hears of the failure
+            return rc;
         }
-        // x_out = x_mid + fc2(gelu(fc1(norm2(x_mid))))        d_x = d x_out
-        const float* hact = x + o.hact_l;                        // kept by the forward
-        CHK(lin_bwd(cx, hact, P(p + "mlp.fc2.weight"), d_x, G(p + "mlp.fc2.weight"), G(p + "mlp.fc2.bias"), d_h, MS, E, F, hpre));      // d_h = d hpre (GELU backward folded in)
-        CHK(lin_bwd(cx, x + o.n2, P(p + "mlp.fc1.weight"), d_h, G(p + "mlp.fc1.weight"), G(p + "mlp.fc1.bias"), d_a, MS, F, E));
-        CHK(ln_bwd(cx, x_mid, P(p + "norm2.weight"), d_a, d_x, d_x, G(p + "norm2.weight"), G(p + "norm2.bias"), MS, E, eps));   // d_x = d x_mid
-        // x_mid = x + proj(attention(qkv(norm1(x))))
-        CHK(lin_bwd(cx, ao, P(p + "attn.proj.weight"), d_x, G(p + "attn.proj.weight"), G(p + "attn.proj.bias"), d_a, MS, E, E));        // d_a = d ao
-        CHK(train_attn(cx, enc_attn_args(m, qkv, ao, d_a, dqkv, o.lse ? x + o.lse : nullptr, o.lse ? w + o.dsum : nullptr), batch, true, ATT_HD));
-        CHK(lin_bwd(cx, x + o.n1, P(p + "attn.qkv.weight"), dqkv, G(p + "attn.qkv.weight"), G(p + "attn.qkv.bias"), d_a, MS, 3 * E, E));
-        CHK(ln_bwd(cx, x, P(p + "norm1.weight"), d_a, d_x, d_x, G(p + "norm1.weight"), G(p + "norm1.bias"), MS, E, eps));          // d_x = d x
     }
-    CHK(colsum(cx, d_x, (long)S * E, batch, S * E, G("pos_embed"), true));
+    CHK(colsum(cx, g.d_x, (long)S * E, batch, S * E, top("pos_embed").g, true));
+    const ParamRef pe_w = top("patch_embed.proj.weight");
+    float* pe_db = top("patch_embed.proj.bias").g;
     if (m->vitstr) {
         // d cls_token = sum over the images of row 0; the patch embedding sees rows 1 .. S - 1 only (gathered into `tmp`)
         const int MP = batch * (S - 1);
-        CHK(colsum(cx, d_x, (long)S * E, batch, E, G("cls_token"), true));
-        hipLaunchKernelGGL(gather_image_rows_kernel, dim3(MP), dim3(256), 0, s, d_x, S, 1, tmp, S - 1, E);
-        HIPCHK(hipGetLastError());
-        CHK(lin_bwd(cx, w + o.patches, P("patch_embed.proj.weight"), tmp, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), nullptr, MP, E, PK));
+        CHK(colsum(cx, g.d_x, (long)S * E, batch, E, top("cls_token").g, true));
+        CHK(launch(gather_image_rows_kernel, dim3(MP), dim3(256), 0, s, g.d_x, S, 1, w + o.tmp, S - 1, E));
+        CHK(lin_bwd(cx, w + o.patches, pe_w.p, w + o.tmp, pe_w.g, pe_db, nullptr, MP, E, PK));
     } else {
-        CHK(lin_bwd(cx, w + o.patches, P("patch_embed.proj.weight"), d_x, G("patch_embed.proj.weight"), G("patch_embed.proj.bias"), nullptr, MS, E, PK));
+        CHK(lin_bwd(cx, w + o.patches, pe_w.p, g.d_x, pe_w.g, pe_db, nullptr, MS, E, PK));
     }
-    if (segs) CHK(grad_event_record(m, m->cfg.enc_depth, s));      // block 0, patch_embed, pos_embed (and pos_queries): everything is final
+    if (segs) CHK(grad_event_record(m, depth, s));      // block 0, patch_embed, pos_embed (and pos_queries): everything is final
     m->grad_events_valid = segs;
     return 0;
 }
@@ -1101,11 +1159,10 @@ struct VitstrHeadLayout { size_t hin, logits, dh, row_loss, counts, scratch, scr
 static VitstrHeadLayout vitstr_head_layout(const parseq_model* m, int B, int T) {
     const size_t E = m->cfg.embed_dim, C = m->classes, R = (size_t)B * T;
     VitstrHeadLayout o;
-    size_t off = 0;
-    auto take = [&](size_t n) { const size_t at = off; off += (n + 63) / 64 * 64; return at; };
+    Take take;
     o.hin = take(R * E); o.logits = take(R * C); o.dh = take(R * E); o.row_loss = take(R); o.counts = take(1);
     o.scratch_floats = train_scratch_floats(R, E); o.scratch = take(o.scratch_floats);
-    o.total = off;
+    o.total = take.off;
     return o;
 }
 extern "C" size_t parseq_train_vitstr_head_workspace_bytes(const parseq_model* m, int batch, int T) {
@@ -1119,40 +1176,28 @@ extern "C" int parseq_train_vitstr_head(parseq_model* m, const float* memory, co
     const int S = m->tokens;
     if (batch <= 0 || T < 1 || T > m->cfg.max_label_length + 1 || T + 1 > S || total_targets <= 0)
         return fail(PARSEQ_E_INVALID, "bad shape: batch %d, %d target positions (1..%d), %d targets", batch, T, m->cfg.max_label_length + 1, total_targets);
-    for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
+    CHK(require_params_set(m));
     const VitstrHeadLayout o = vitstr_head_layout(m, batch, T);
     if (workspace_bytes < o.total * sizeof(float)) return fail(PARSEQ_E_INVALID, "workspace: %zu bytes given, %zu needed", workspace_bytes, o.total * sizeof(float));
     DevGuard dg(m->device);
     hipStream_t s = (hipStream_t)stream;
     const int E = m->cfg.embed_dim, C = m->classes, R = batch * T;
     float* w = reinterpret_cast<float*>(workspace);
-    auto G = [&](const std::string& key) { return grads + m->params[m->index.at(key)].offset; };
+    const ParamRef head_w = param_ref(m, "head.weight", grads), head_b = param_ref(m, "head.bias", grads);
     const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
-    float* hin = w + o.hin; float* logits = w + o.logits; float* dh = w + o.dh;
-    hipLaunchKernelGGL(gather_image_rows_kernel, dim3(R), dim3(256), 0, s, memory, S, 1, hin, T, E);
-    HIPCHK(hipGetLastError());
-    CHK(lin_fwd(cx, hin, m->p("head.weight"), m->p("head.bias"), nullptr, 0, logits, R, C, E));
-    hipLaunchKernelGGL(ce_rows_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, targets, R, C, m->cfg.pad_id, w + o.row_loss);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, s, w + o.row_loss, targets, R, m->cfg.pad_id, loss_out, reinterpret_cast<int*>(w + o.counts));
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3((R + 3) / 4), dim3(256), 0, s, logits, targets, R, C, m->cfg.pad_id, 1.0f / (float)total_targets);
-    HIPCHK(hipGetLastError());
-    CHK(lin_bwd(cx, hin, m->p("head.weight"), logits, G("head.weight"), G("head.bias"), dh, R, C, E));
-    hipLaunchKernelGGL(scatter_image_rows_kernel, dim3(batch * S), dim3(256), 0, s, dh, T, 1, dmemory, S, E);
-    HIPCHK(hipGetLastError());
-    return 0;
+    CHK(launch(gather_image_rows_kernel, dim3(R), dim3(256), 0, s, memory, S, 1, w + o.hin, T, E));
+    CHK(lin_fwd(cx, w + o.hin, head_w.p, head_b.p, nullptr, 0, w + o.logits, R, C, E));
+    CHK(ce_loss_and_grad(s, w + o.logits, targets, 1, R, C, m->cfg.pad_id, w + o.row_loss, loss_out, reinterpret_cast<int*>(w + o.counts), total_targets));
+    CHK(lin_bwd(cx, w + o.hin, head_w.p, w + o.logits, head_w.g, head_b.g, w + o.dh, R, C, E));
+    return launch(scatter_image_rows_kernel, dim3(batch * S), dim3(256), 0, s, w + o.dh, T, 1, dmemory, S, E);
 }
 
 // ---- training step, optimiser ---------------------------------------------------------------------------------------------
 extern "C" int parseq_grad_norm(const float* grads, int64_t n, float* norm_out, float* workspace, void* stream) {
     if (!grads || !norm_out || !workspace || n <= 0) return fail(PARSEQ_E_INVALID, "null / empty argument");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(SUMSQ_BLOCKS), dim3(256), 0, s, grads, (size_t)n, workspace);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, s, workspace, norm_out);
-    HIPCHK(hipGetLastError());
-    return 0;
+    CHK(launch(sumsq_partial_kernel, dim3(SUMSQ_BLOCKS), dim3(256), 0, s, grads, (size_t)n, workspace));
+    return launch(sumsq_final_kernel, dim3(1), dim3(256), 0, s, workspace, norm_out);
 }
 
 extern "C" int parseq_adamw_step(parseq_model* m, const float* grads, float* exp_avg, float* exp_avg_sq, const int32_t* decay_flags, float lr,
@@ -1161,7 +1206,7 @@ extern "C" int parseq_adamw_step(parseq_model* m, const float* grads, float* exp
     if (!m || !grads || !exp_avg || !exp_avg_sq) return fail(PARSEQ_E_INVALID, "null argument");
     if (step < 1) return fail(PARSEQ_E_INVALID, "step %d: steps count from 1", step);
     DevGuard dg(m->device);
-    for (const ParamSpec& ps : m->params) if (!ps.set) return fail(PARSEQ_E_STATE, "parameter %s was never set", ps.key.c_str());
+    CHK(require_params_set(m));
     hipStream_t s = (hipStream_t)stream;
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
     // runs of consecutive tensors with the same weight-decay flag are one launch (with weight_decay == 0, the reference's
@@ -1173,9 +1218,8 @@ extern "C" int parseq_adamw_step(parseq_model* m, const float* grads, float* exp
         int j = i + 1;
         while (j < np && (decay_flags && weight_decay != 0.f && decay_flags[j]) == decay) ++j;
         const size_t lo = m->params[i].offset, hi = j < np ? m->params[j].offset : m->master_elems;
-        hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, s, m->master + lo, grads + lo, exp_avg + lo,
-                           exp_avg_sq + lo, hi - lo, lr, beta1, beta2, eps, decay ? weight_decay : 0.f, bc1, bc2_sqrt, grad_norm, max_norm);
-        HIPCHK(hipGetLastError());
+        CHK(launch(adamw_kernel, dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, s, m->master + lo, grads + lo, exp_avg + lo, exp_avg_sq + lo, hi - lo, lr,
+                   beta1, beta2, eps, decay ? weight_decay : 0.f, bc1, bc2_sqrt, grad_norm, max_norm));
         i = j;
     }
     m->version++;
@@ -1215,9 +1259,7 @@ extern "C" int parseq_model_get_params(parseq_model* m, float* const* device_ptr
         m->out_chunk_count = (int)pieces.size();
         m->out_ptrs.assign(device_ptrs, device_ptrs + count);
     }
-    hipLaunchKernelGGL(copy_pieces_kernel, dim3((unsigned)m->out_chunk_count), dim3(256), 0, s, reinterpret_cast<const CopyPiece*>(m->out_chunks));
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(copy_pieces_kernel, dim3((unsigned)m->out_chunk_count), dim3(256), 0, s, reinterpret_cast<const CopyPiece*>(m->out_chunks));
 }
 
 // -------------------------------------------------------------------------------------------------------------------

@@ -1171,3 +1171,47 @@ def test_micro_batched_step_equals_the_one_piece_step(parts):
             w = one.grads[k].double()
             if float(w.norm()) > 1e-9:
                 assert float((g.double() - w).norm() / w.norm()) <= 1e-4, k
+
+
+@pytest.mark.gpu
+def test_encoder_backward_refuses_a_record_written_in_another_mode(monkeypatch):
+    """parseq_train_encoder_forward notes on the model how the record in its workspace stores what only feeds products (fp32, bf16 shadows,
+    bf16 alone); parseq_train_encoder_backward decides its own route afresh and must refuse to read the record another way — a switch
+    flipped between the two calls would otherwise have bf16 bytes read as floats.  PARSeq-Ti (E = 192: three heads of 64, 128 tokens) at
+    batch 2 in the bf16-operand mode is the smallest configuration with a shadow route: the forward writes mode 3 (bf16 alone), the
+    backward under PARSEQ_TRAIN_NO_SHADOWS=1 would read mode 0.  The refusal is the library's argument check (PARSEQ_E_STATE = -3), made
+    before anything is enqueued: the gradient buffer keeps its sentinel.  With the variable cleared the same call succeeds."""
+    from gpu_util import DEV, make_model
+    from parseq_amd import _native
+    from parseq_amd.train import _set_train_precision
+    cfg = CONFIGS['parseq-tiny']
+    m = make_model('parseq-tiny', 'bf16')
+    m.train_precision = 'bf16'
+    B, S, E = 2, 128, 192
+    for var in ('PARSEQ_TRAIN_NO_SHADOWS', 'PARSEQ_TRAIN_SHADOW_LEVEL'):
+        monkeypatch.delenv(var, raising=False)
+    images = synth_images(B, cfg, seed=3).to(DEV)
+    lib = _native.lib()
+    native = m.model._sync_native().model
+    _set_train_precision(m, native)
+    nbytes = lib.parseq_train_encoder_workspace_bytes(native, B)
+    ws = torch.zeros(nbytes // 4, dtype=torch.float32, device=DEV)
+    mem = torch.empty(B, S, E, dtype=torch.float32, device=DEV)
+    dmem = torch.randn(B, S, E, generator=torch.Generator().manual_seed(4)).to(DEV)
+    grads = torch.full((lib.parseq_model_grad_elems(native),), -7.0, dtype=torch.float32, device=DEV)
+    stream = _native.stream_ptr(images)
+    _native.check(lib.parseq_train_encoder_forward(native, _native.ptr(images), B, _native.ptr(mem), _native.ptr(ws), nbytes, stream))
+    torch.cuda.synchronize()
+
+    def backward():
+        _native.check(lib.parseq_train_encoder_backward(native, _native.ptr(dmem), B, _native.ptr(grads), _native.ptr(ws), nbytes, stream))
+        torch.cuda.synchronize()
+    monkeypatch.setenv('PARSEQ_TRAIN_NO_SHADOWS', '1')
+    with pytest.raises(_native.NativeError, match=r'error -3: .*written in mode 3, this call would read it in mode 0'):
+        backward()
+    torch.cuda.synchronize()
+    assert bool((grads == -7.0).all())                               # nothing was enqueued
+    monkeypatch.delenv('PARSEQ_TRAIN_NO_SHADOWS')
+    grads.zero_()
+    backward()
+    assert bool(torch.isfinite(grads).all()) and float(grads.abs().sum()) > 0.0      # the encoder's gradients were written
