@@ -21,7 +21,7 @@
  *   - devices: a model lives on the device that was current at parseq_model_create; every entry point that takes a model or
  *     a plan makes that device current for the duration of the call and restores the caller's (so `stream` must be a stream
  *     of the model's device).  The raw-pointer entry points (parseq_op_*, parseq_postprocess, parseq_resize_bicubic,
- *     parseq_cross_entropy, parseq_grad_norm) launch on the CURRENT device.  Per-kernel launch attributes are tracked per
+ *     parseq_rotate_resize_bicubic, parseq_cross_entropy, parseq_grad_norm) launch on the CURRENT device.  Per-kernel launch attributes are tracked per
  *     device, so one process may drive several GPUs / host threads (one plan each).
  *   - memory: the caller owns every tensor it passes; each plan owns ONE device arena (packed weights, decoder tables and all
  *     intermediates, about 0.9 GB at max_batch 512 in bf16) taken from hipMalloc (parseq_plan_create) or from the caller's
@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 12
+#define PARSEQ_ABI_VERSION 13
 
 /* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
 #define PARSEQ_DEC_DEPTH_MAX 4
@@ -229,6 +229,35 @@ typedef struct {
  * parseq_resize_workspace_bytes(batch) bytes (the descriptors are copied there on `stream`). */
 size_t parseq_resize_workspace_bytes(int batch);
 int parseq_resize_bicubic(const parseq_image_desc* images, int batch, int out_h, int out_w, uint8_t* out, void* workspace, void* stream);
+
+/* (ABI 13) The rotation ahead of the resize: `img.rotate(rotation, expand=True)` of the same transform (strhub/data/module.py:72-73, the
+ * reference's test.py --rotation), i.e. Pillow's Image.rotate with nearest resampling and black fill, bit-exact.  A descriptor holds the
+ * MAP, not an angle — the library does no trigonometry: the caller evaluates Pillow's float64 expressions on the host
+ * (parseq_amd/preprocess.py rotation_map; INTEGRATION.md spells them out) and the kernels do 32-bit integer arithmetic only.
+ *   mode                    PARSEQ_ROTATE_NONE (a copy), _90 / _180 / _270 (Pillow's exact transposes for those angles; a[] unused), or
+ *                           PARSEQ_ROTATE_AFFINE
+ *   rot_height, rot_width   size of the rotated image: the source's for NONE / 180, swapped for 90 / 270 (anything else is refused),
+ *                           Pillow's expanded canvas for AFFINE
+ *   a[6]                    AFFINE: Pillow's 16.16 fixed-point inverse map; pixel (x, y) of the rotated image is source pixel
+ *                           ((a[2] + a[0] x + a[1] y) >> 16, (a[5] + a[3] x + a[4] y) >> 16), arithmetic shift, black outside the source
+ * No side, source or rotated, may exceed PARSEQ_ROTATE_MAX_SIDE (the sums then fit 32 bits; PARSEQ_E_INVALID otherwise). */
+enum { PARSEQ_ROTATE_NONE = 0, PARSEQ_ROTATE_90 = 1, PARSEQ_ROTATE_180 = 2, PARSEQ_ROTATE_270 = 3, PARSEQ_ROTATE_AFFINE = 4 };
+#define PARSEQ_ROTATE_MAX_SIDE 16384
+typedef struct {
+    const uint8_t* data;            /* DEVICE pointer, RGB HWC uint8 */
+    int32_t height, width;          /* of the source */
+    int64_t row_stride;             /* in bytes, >= 3 * width */
+    int32_t mode;
+    int32_t rot_height, rot_width;
+    int32_t a[6];
+} parseq_rotated_image_desc;
+
+/* parseq_resize_bicubic of the ROTATED images, in one launch whatever the batch: the horizontal pass gathers each tap through the image's
+ * map straight from the source, so no rotated copy is ever written.  Arguments as parseq_resize_bicubic; workspace of
+ * parseq_rotate_resize_workspace_bytes(batch) bytes.  An image in mode PARSEQ_ROTATE_NONE gives parseq_resize_bicubic's bytes. */
+size_t parseq_rotate_resize_workspace_bytes(int batch);
+int parseq_rotate_resize_bicubic(const parseq_rotated_image_desc* images, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
+                                 void* stream);
 
 /* ---- post-processing --------------------------------------------------------------- */
 
@@ -475,6 +504,10 @@ int parseq_op_encoder_attention(const void* q, const void* k, const void* vt, vo
  * fewer the step's resident kernels run and neither is touched.  *route (may be NULL): 1 for the key-streaming kernels, 0 otherwise. */
 int parseq_op_train_attention(const float* qkv, float* o, float* lse, const float* d_o, float* dqkv, float* dsum, int batch, int tokens,
                               int heads, int backward, int* route, void* stream);
+
+/* (ABI 13) The rotation alone, for one image (tests/test_rotate.py compares it with Pillow): out = device uint8
+ * [rot_height, rot_width, 3], dense.  image: HOST descriptor, read before the call returns. */
+int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t* out, void* stream);
 
 /* (ABI 12) The training step's products and row kernels one operator at a time (tests/test_train_gemm.py).  The three hooks build
  * the step's context from their arguments and call the internal functions the step calls, unchanged.  bf16_ops: the bf16-operand

@@ -34,6 +34,64 @@ extern "C" int parseq_resize_bicubic(const parseq_image_desc* images, int batch,
     return 0;
 }
 
+// rotate, then resize: the first two steps of the reference's evaluation transform (strhub/data/module.py:72-77) in one launch
+static int check_rotated(const parseq_rotated_image_desc& d, int i) {
+    if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
+        return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
+    const bool turned = d.mode == PARSEQ_ROTATE_90 || d.mode == PARSEQ_ROTATE_270;
+    switch (d.mode) {
+        case PARSEQ_ROTATE_NONE: case PARSEQ_ROTATE_90: case PARSEQ_ROTATE_180: case PARSEQ_ROTATE_270:
+            if (d.rot_height != (turned ? d.width : d.height) || d.rot_width != (turned ? d.height : d.width))
+                return fail(PARSEQ_E_INVALID, "image %d: mode %d turns %dx%d into %dx%d, not %dx%d", i, d.mode, d.height, d.width,
+                            turned ? d.width : d.height, turned ? d.height : d.width, d.rot_height, d.rot_width);
+            break;
+        case PARSEQ_ROTATE_AFFINE:
+            if (d.rot_height <= 0 || d.rot_width <= 0) return fail(PARSEQ_E_INVALID, "image %d: rotated size %dx%d", i, d.rot_height, d.rot_width);
+            break;
+        default: return fail(PARSEQ_E_INVALID, "image %d: unknown rotation mode %d", i, d.mode);
+    }
+    if (std::max(std::max(d.height, d.width), std::max(d.rot_height, d.rot_width)) > PARSEQ_ROTATE_MAX_SIDE)
+        return fail(PARSEQ_E_INVALID, "image %d: %dx%d rotated to %dx%d, a side is above %d (the map is 32-bit fixed point)", i, d.height, d.width,
+                    d.rot_height, d.rot_width, PARSEQ_ROTATE_MAX_SIDE);
+    return 0;
+}
+
+extern "C" size_t parseq_rotate_resize_workspace_bytes(int batch) { return batch > 0 ? (size_t)batch * sizeof(RotatedImageDesc) : 0; }
+
+extern "C" int parseq_rotate_resize_bicubic(const parseq_rotated_image_desc* images, int batch, int out_h, int out_w, uint8_t* out,
+                                            void* workspace, void* stream) {
+    static_assert(sizeof(parseq_rotated_image_desc) == sizeof(RotatedImageDesc) && offsetof(parseq_rotated_image_desc, a) == offsetof(RotatedImageDesc, a) &&
+                  PARSEQ_ROTATE_AFFINE == ROT_AFFINE && PARSEQ_ROTATE_MAX_SIDE == ROT_MAX_SIDE, "descriptor layouts must match");
+    if (!images || !out || !workspace) return fail(PARSEQ_E_INVALID, "null images / out / workspace");
+    if (batch <= 0 || out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, output %dx%d", batch, out_h, out_w);
+    int ksh = 1, ksv = 1;
+    for (int i = 0; i < batch; ++i) {
+        CHK(check_rotated(images[i], i));
+        ksh = std::max(ksh, resize_taps(images[i].rot_width, out_w));
+        ksv = std::max(ksv, resize_taps(images[i].rot_height, out_h));
+    }
+    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
+    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "a rotated image is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemcpyAsync(workspace, images, (size_t)batch * sizeof(RotatedImageDesc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(rotate_resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(rotate_resize_bicubic_kernel, dim3(batch), dim3(256), lds, s, reinterpret_cast<const RotatedImageDesc*>(workspace), out_h, out_w, ksh,
+                       ksv, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t* out, void* stream) {
+    if (!image || !out) return fail(PARSEQ_E_INVALID, "null image / out");
+    CHK(check_rotated(*image, 0));
+    RotatedImageDesc im;
+    memcpy(&im, image, sizeof(im));
+    const long long pixels = (long long)im.rot_height * im.rot_width;
+    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)std::min<long long>((pixels + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, im, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // -------------------------------------------------------------------------------------------------------------------
 // post-processing
 // -------------------------------------------------------------------------------------------------------------------

@@ -13,8 +13,9 @@ sub-directory is evaluated, in name order, and one table with a `Combined` row i
 
 Labels go through the reference dataset's filter (`strhub/data/dataset.py:105-117`): whitespace removed, NFKD-normalised to ASCII,
 dropped if longer than `max_label_length`, mapped into the test charset, dropped if nothing is left.  Images are decoded on the
-host (PIL; `--rotation` rotates there, as the reference transform does, `strhub/data/module.py:72-73`); the bicubic resize, the model
-and the metrics (parseq_amd.evaluate.Evaluator, one per dataset) run on the device with no copy back until a dataset is done.
+host (PIL) and uploaded as they are; the rotation of `--rotation` (`img.rotate(rotation, expand=True)` of the reference transform,
+`strhub/data/module.py:72-73`), the bicubic resize, the model and the metrics (parseq_amd.evaluate.Evaluator, one per dataset) run on
+the device with no copy back until a dataset is done.
 """
 import argparse
 import os
@@ -79,14 +80,8 @@ def find_datasets(root: str) -> List[str]:
     return sorted(d for d in os.listdir(root) if os.path.isfile(os.path.join(root, d, 'gt.txt')))
 
 
-def load_crops(files, rotation: int, device):
-    crops = []
-    for f in files:
-        img = Image.open(f).convert('RGB')
-        if rotation:
-            img = img.rotate(rotation, expand=True)
-        crops.append(torch.from_numpy(np.asarray(img).copy()).to(device))
-    return crops
+def load_crops(files, device):
+    return [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
 
 
 def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0) -> Result:
@@ -95,7 +90,7 @@ def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotatio
     evaluator = Evaluator(model)
     for at in range(0, len(samples), batch_size):
         chunk = samples[at:at + batch_size]
-        images = resize_batch(load_crops([f for f, _ in chunk], rotation, model.device), tuple(hp.img_size))      # uint8 [N, 3, H, W]
+        images = resize_batch(load_crops([f for f, _ in chunk], model.device), tuple(hp.img_size), rotation=rotation)      # uint8 [N, 3, H, W]
         evaluator.update(images, [label for _, label in chunk])
     r = evaluator.result()
     n = r.num_samples
