@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 13
+#define PARSEQ_ABI_VERSION 14
 
 /* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
 #define PARSEQ_DEC_DEPTH_MAX 4
@@ -258,6 +258,56 @@ typedef struct {
 size_t parseq_rotate_resize_workspace_bytes(int batch);
 int parseq_rotate_resize_bicubic(const parseq_rotated_image_desc* images, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
                                  void* stream);
+
+/* ---- (ABI 14) training augmentation: the reference's RandAugment operators ----------------------------------------- */
+
+/* The operators of rand_augment_transform() (strhub/data/augment.py, aa_overrides.py: timm's auto_augment calls into Pillow) on a ragged
+ * batch of RGB uint8 HWC images in device memory, bit-exact with Pillow.  An image carries a chain of up to PARSEQ_AUGMENT_MAX_OPS
+ * operators; the chains run stage by stage, one launch per stage for the whole batch, between two per-image regions of the workspace.
+ *   PARSEQ_AUG_TABLE         arg.table: a 256-entry table applied to every channel (Invert, Posterize, Solarize, SolarizeAdd, Brightness;
+ *                            parseq_amd/augment.py lut_for builds it from Pillow's own steps)
+ *   PARSEQ_AUG_AUTOCONTRAST  ImageOps.autocontrast(img)                      (per-channel histogram, table built on the device)
+ *   PARSEQ_AUG_EQUALIZE      ImageOps.equalize(img)                          (the same)
+ *   PARSEQ_AUG_CONTRAST      ImageEnhance.Contrast(img).enhance(arg.factor)  (rounded mean of convert('L'), table built on the device)
+ *   PARSEQ_AUG_COLOR         ImageEnhance.Color(img).enhance(arg.factor)
+ *   PARSEQ_AUG_AFFINE        img.transform((out_width, out_height), AFFINE, arg.coef, resample=mode, fillcolor=(128, 128, 128)); mode is
+ *                            PARSEQ_AUG_BILINEAR or PARSEQ_AUG_BICUBIC.  ShearX / ShearY / TranslateXRel / TranslateYRel keep the size,
+ *                            Rotate (expand=True) carries its expanded size (augment.py rotate_expand_map)
+ *   PARSEQ_AUG_TURN          Pillow's exact rotation by 90 / 180 / 270 degrees: mode is PARSEQ_ROTATE_90 / _180 / _270
+ * out_height / out_width: the image after the operator; every operator but AFFINE and TURN must repeat its input's size.  Factors are
+ * finite and >= 0.1, coefficients finite, no side (source or any stage) outside 1 .. PARSEQ_ROTATE_MAX_SIDE.  Every descriptor is checked
+ * on the host before anything is launched (PARSEQ_E_INVALID, parseq_last_error names the image and the field). */
+enum { PARSEQ_AUG_NONE = 0, PARSEQ_AUG_TABLE = 1, PARSEQ_AUG_AUTOCONTRAST = 2, PARSEQ_AUG_EQUALIZE = 3, PARSEQ_AUG_CONTRAST = 4,
+       PARSEQ_AUG_COLOR = 5, PARSEQ_AUG_AFFINE = 6, PARSEQ_AUG_TURN = 7 };
+enum { PARSEQ_AUG_BILINEAR = 2, PARSEQ_AUG_BICUBIC = 3 };      /* Pillow's Image.Resampling values */
+#define PARSEQ_AUGMENT_MAX_OPS 3
+
+typedef struct {
+    int32_t op;                       /* PARSEQ_AUG_* (never NONE inside a chain) */
+    int32_t mode;                     /* AFFINE: the resampling filter; TURN: the quarter turn; otherwise 0 */
+    int32_t out_height, out_width;
+    union { uint8_t table[256]; float factor; double coef[6]; } arg;
+} parseq_augment_op;
+
+typedef struct {
+    const uint8_t* data;              /* DEVICE pointer, RGB, HWC */
+    int32_t height, width;
+    int64_t row_stride;               /* bytes between rows (>= 3 * width) */
+    int32_t num_ops;                  /* 0 .. PARSEQ_AUGMENT_MAX_OPS; 0 = the image passes unchanged */
+    int32_t reserved;
+    parseq_augment_op ops[PARSEQ_AUGMENT_MAX_OPS];
+} parseq_augment_desc;
+
+/* Bytes of workspace the two calls below need for these descriptors (HOST array): the descriptors' device copy, the plan, and two regions per
+ * image of its largest stage.  0 if a descriptor is invalid (parseq_last_error says why). */
+size_t parseq_augment_workspace_bytes(const parseq_augment_desc* descs, int batch);
+
+/* Runs every chain, then parseq_resize_bicubic's arithmetic (the same kernel) on the augmented images: out = device uint8
+ * [batch, 3, out_h, out_w], no host round trip, no synchronisation inside.  descs: HOST array, copied on `stream` — keep it alive until the
+ * stream has passed.  workspace: device memory of at least parseq_augment_workspace_bytes(descs, batch) bytes; workspace_bytes says how
+ * much there is (less is refused). */
+int parseq_augment_resize_bicubic(const parseq_augment_desc* descs, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
+                                  size_t workspace_bytes, void* stream);
 
 /* ---- post-processing --------------------------------------------------------------- */
 
@@ -508,6 +558,10 @@ int parseq_op_train_attention(const float* qkv, float* o, float* lse, const floa
 /* (ABI 13) The rotation alone, for one image (tests/test_rotate.py compares it with Pillow): out = device uint8
  * [rot_height, rot_width, 3], dense.  image: HOST descriptor, read before the call returns. */
 int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t* out, void* stream);
+
+/* (ABI 14) One image's augmentation chain alone (tests/test_augment.py compares it with Pillow): out = device uint8 [h, w, 3], dense, of the
+ * last operator's size.  desc: HOST descriptor, alive until the stream has passed; workspace as for parseq_augment_resize_bicubic with batch 1. */
+int parseq_op_augment(const parseq_augment_desc* desc, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (ABI 12) The training step's products and row kernels one operator at a time (tests/test_train_gemm.py).  The three hooks build
  * the step's context from their arguments and call the internal functions the step calls, unchanged.  bf16_ops: the bf16-operand

@@ -16,7 +16,7 @@ from . import build as _build
 PARSEQ_F32, PARSEQ_BF16, PARSEQ_U8, PARSEQ_BF16X3 = 0, 1, 2, 3
 ARCH_PARSEQ, ARCH_VITSTR = 0, 1
 FLAG_DECODE_AR, FLAG_TESTING, FLAG_LATENCY = 1, 2, 4
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 class ParseqConfig(C.Structure):
@@ -34,6 +34,21 @@ class RotatedImageDesc(C.Structure):
     """parseq_rotated_image_desc: an image and the map of its rotation (parseq_amd/preprocess.py rotation_map fills it)."""
     _fields_ = [('data', C.c_void_p), ('height', C.c_int32), ('width', C.c_int32), ('row_stride', C.c_int64), ('mode', C.c_int32),
                 ('rot_height', C.c_int32), ('rot_width', C.c_int32), ('a', C.c_int32 * 6)]
+
+
+class AugmentArg(C.Union):
+    _fields_ = [('table', C.c_uint8 * 256), ('factor', C.c_float), ('coef', C.c_double * 6)]
+
+
+class AugmentOp(C.Structure):
+    """parseq_augment_op: one operator of a chain (parseq_amd/augment.py fills it)."""
+    _fields_ = [('op', C.c_int32), ('mode', C.c_int32), ('out_height', C.c_int32), ('out_width', C.c_int32), ('arg', AugmentArg)]
+
+
+class AugmentDesc(C.Structure):
+    """parseq_augment_desc: an image and its chain of at most three operators."""
+    _fields_ = [('data', C.c_void_p), ('height', C.c_int32), ('width', C.c_int32), ('row_stride', C.c_int64), ('num_ops', C.c_int32),
+                ('reserved', C.c_int32), ('ops', AugmentOp * 3)]
 
 
 class GemmOperand(C.Structure):
@@ -81,6 +96,9 @@ SIGNATURES = {
     'parseq_rotate_resize_workspace_bytes': (C.c_size_t, [C.c_int]),
     'parseq_rotate_resize_bicubic': (C.c_int, [C.POINTER(RotatedImageDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_op_rotate': (C.c_int, [C.POINTER(RotatedImageDesc), C.c_void_p, C.c_void_p]),
+    'parseq_augment_workspace_bytes': (C.c_size_t, [C.POINTER(AugmentDesc), C.c_int]),
+    'parseq_augment_resize_bicubic': (C.c_int, [C.POINTER(AugmentDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_op_augment': (C.c_int, [C.POINTER(AugmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_cross_entropy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_eval_metrics': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -246,7 +264,7 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def guard(device):
     """Context manager making `device` (torch.device or tensor) current: for the raw-pointer entry points (parseq_op_*,
-    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_cross_entropy, parseq_grad_norm), which launch on the current device."""
+    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_cross_entropy, parseq_grad_norm), which launch on the current device."""
     import torch
     if hasattr(device, 'device'):
         device = device.device

@@ -1,0 +1,296 @@
+"""Training augmentation on the device: the RandAugment operators of the reference's training transform, bit-exact with Pillow.
+
+The reference trains on `rand_augment_transform()` -> Resize(img_size, BICUBIC) -> ToTensor -> Normalize (strhub/data/module.py:69-82;
+strhub/data/augment.py, aa_overrides.py: timm's auto_augment operators, i.e. calls into Pillow).  `augment_resize_batch` is the first
+two steps on a ragged batch of uint8 HWC crops that already live in device memory: every image's chain of up to three operators runs
+stage by stage (one launch per stage for the whole batch, csrc/augment.h), and the augmented crops go straight into the bicubic resize
+of `preprocess.resize_batch` — the same kernel — so uint8 [N, 3, H, W] comes out with no host round trip.  `apply_batch` returns the
+augmented crops themselves (parseq_op_augment, the kernel tests' view).
+
+A chain is a list of at most three `(name, *args)` tuples:
+    ('AutoContrast',)  ('Equalize',)  ('Invert',)                       ImageOps.autocontrast / equalize / invert
+    ('Posterize', bits)  ('Solarize', thresh)  ('SolarizeAdd', add)     ImageOps.posterize (identity for bits >= 8) / solarize, timm's solarize_add
+    ('Color', f)  ('Contrast', f)  ('Brightness', f)                    ImageEnhance.<Name>(img).enhance(f), f >= 0.1
+    ('ShearX', f, r)  ('ShearY', f, r)                                  img.transform(img.size, AFFINE, ..., resample=r, fillcolor=(128,) * 3)
+    ('TranslateXRel', pct, r)  ('TranslateYRel', pct, r)                the same, by pct of the width / height
+    ('Rotate', deg, r)                                                  img.rotate(deg, resample=r, expand=True, fillcolor=(128,) * 3)
+with r = BILINEAR or BICUBIC.  The host halves are public: `lut_for` (the 256-entry tables, from Pillow's own integer and single-precision
+steps), `affine_coeffs` and `rotate_expand_map` (the six float64 coefficients, from the Python expressions Pillow evaluates).
+`RandAugment` is the policy.  Not covered: GaussianBlur and PoissonNoise (`RandAugment.missing`).
+"""
+from __future__ import annotations
+
+import math
+from typing import Sequence
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from . import _native
+from .preprocess import MAX_SIDE, ROTATE_90, ROTATE_180, ROTATE_270, _checked
+
+BILINEAR, BICUBIC = 2, 3                                 # Pillow's Image.Resampling values (PARSEQ_AUG_BILINEAR / _BICUBIC)
+OP_TABLE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_CONTRAST, OP_COLOR, OP_AFFINE, OP_TURN = range(1, 8)      # PARSEQ_AUG_*
+MAX_OPS = 3                                              # PARSEQ_AUGMENT_MAX_OPS
+TABLE_OPS = ('Invert', 'Posterize', 'Solarize', 'SolarizeAdd', 'Brightness')
+GEOMETRIC_OPS = ('ShearX', 'ShearY', 'TranslateXRel', 'TranslateYRel', 'Rotate')
+_ARITY = {'AutoContrast': 0, 'Equalize': 0, 'Invert': 0, 'Posterize': 1, 'Solarize': 1, 'SolarizeAdd': 1, 'Color': 1, 'Contrast': 1,
+          'Brightness': 1, 'ShearX': 2, 'ShearY': 2, 'TranslateXRel': 2, 'TranslateYRel': 2, 'Rotate': 2}
+
+
+def _factor(name: str, factor) -> np.float32:
+    f = np.float32(factor)                               # Image.blend takes a C float
+    if not (np.isfinite(f) and f >= np.float32(0.1)):
+        raise ValueError(f'{name}: factor {factor} must be finite and at least 0.1')
+    return f
+
+
+def _int_arg(name: str, arg, lo: int, hi: int) -> int:
+    if int(arg) != arg or not lo <= arg <= hi:
+        raise ValueError(f'{name}: argument {arg} must be an integer in {lo} .. {hi}')
+    return int(arg)
+
+
+def lut_for(name: str, arg=None) -> np.ndarray:
+    """The uint8 [256] table of a statistics-free operator, as Pillow builds it (Brightness: ImagingBlend's single-precision
+    0 + f * (i - 0), truncated for f <= 1, clipped first above)."""
+    i = np.arange(256, dtype=np.int32)
+    if name == 'Invert':
+        return (255 - i).astype(np.uint8)
+    if name == 'Posterize':
+        bits = _int_arg(name, arg, 0, 8)
+        return (i & ~(2 ** (8 - bits) - 1) & 255).astype(np.uint8)       # bits = 8: the mask is ~0, the identity timm returns early
+    if name == 'Solarize':
+        thresh = _int_arg(name, arg, 0, 256)
+        return np.where(i < thresh, i, 255 - i).astype(np.uint8)
+    if name == 'SolarizeAdd':
+        add = _int_arg(name, arg, 0, 128)
+        return np.where(i < 128, np.minimum(255, i + add), i).astype(np.uint8)
+    if name == 'Brightness':
+        f = _factor(name, arg)
+        if f == np.float32(1.0):
+            return i.astype(np.uint8)
+        t = np.float32(0.0) + f * i.astype(np.float32)
+        if f > np.float32(1.0):
+            t = np.clip(t, np.float32(0.0), np.float32(255.0))
+        return t.astype(np.int32).astype(np.uint8)
+    raise ValueError(f'{name} is not a table operator (one of {TABLE_OPS})')
+
+
+def affine_coeffs(name: str, h: int, w: int, arg) -> tuple:
+    """The six coefficients timm hands Image.transform(img.size, AFFINE, ...) for a shear or a relative translation of an h x w image:
+    output pixel centre (x, y) samples the source at (a0 x + a1 y + a2, a3 x + a4 y + a5)."""
+    arg = float(arg)
+    if not math.isfinite(arg):
+        raise ValueError(f'{name}: argument {arg} must be finite')
+    if name == 'ShearX':
+        return (1.0, arg, 0.0, 0.0, 1.0, 0.0)
+    if name == 'ShearY':
+        return (1.0, 0.0, 0.0, arg, 1.0, 0.0)
+    if name == 'TranslateXRel':
+        return (1.0, 0.0, arg * w, 0.0, 1.0, 0.0)
+    if name == 'TranslateYRel':
+        return (1.0, 0.0, 0.0, 0.0, 1.0, arg * h)
+    raise ValueError(f'{name} is not a shear or a translation')
+
+
+def rotate_expand_map(h: int, w: int, deg) -> tuple:
+    """(turn, nh, nw, (a0 .. a5)) of PIL's Image.rotate(deg, resample, expand=True) with a BILINEAR or BICUBIC filter on an image of height
+    h and width w.  Multiples of 90 degrees are Pillow's exact copies / transposes whatever the filter: turn is ROTATE_NONE (0),
+    ROTATE_90, ROTATE_180 or ROTATE_270 and the coefficients are unused.  Any other angle gives turn = None and the float64 inverse map
+    on the expanded nh x nw canvas, from the expressions Image.rotate evaluates."""
+    if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError(f'image of {h} x {w}: each side must be in 1 .. {MAX_SIDE}')
+    deg = float(deg)
+    if not math.isfinite(deg):
+        raise ValueError(f'Rotate: angle {deg} must be finite')
+    angle = deg % 360.0
+    if angle == 0:
+        return 0, h, w, (0.0,) * 6
+    if angle == 180:
+        return ROTATE_180, h, w, (0.0,) * 6
+    if angle in (90, 270):
+        return (ROTATE_90 if angle == 90 else ROTATE_270), w, h, (0.0,) * 6
+    a = -math.radians(angle)
+    m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
+
+    def transform(x, y):
+        return m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2], m[5] = transform(-w / 2.0, -h / 2.0)
+    m[2] += w / 2.0
+    m[5] += h / 2.0
+    xs, ys = zip(*(transform(x, y) for x, y in ((0, 0), (w, 0), (w, h), (0, h))))
+    nw = math.ceil(max(xs)) - math.floor(min(xs))
+    nh = math.ceil(max(ys)) - math.floor(min(ys))
+    if nh > MAX_SIDE or nw > MAX_SIDE:
+        raise ValueError(f'image of {h} x {w} rotated by {deg} degrees is {nh} x {nw}: each side must be at most {MAX_SIDE}')
+    m[2], m[5] = transform(-(nw - w) / 2.0, -(nh - h) / 2.0)
+    return None, nh, nw, tuple(m)
+
+
+def _fill_op(op, h: int, w: int, name: str, args) -> tuple:
+    """Writes one chain entry into `op` (an _native.AugmentOp); returns (used, nh, nw): used is False where the entry is the identity."""
+    if name not in _ARITY:
+        raise ValueError(f'unknown operator {name!r} (one of {tuple(_ARITY)})')
+    if len(args) != _ARITY[name]:
+        raise ValueError(f'{name} takes {_ARITY[name]} argument(s), got {len(args)}')
+    op.mode, op.out_height, op.out_width = 0, h, w
+    if name in TABLE_OPS:
+        op.op = OP_TABLE
+        op.arg.table[:] = lut_for(name, *args).tolist()
+    elif name in ('AutoContrast', 'Equalize'):
+        op.op = OP_AUTOCONTRAST if name == 'AutoContrast' else OP_EQUALIZE
+    elif name in ('Color', 'Contrast'):
+        op.op = OP_COLOR if name == 'Color' else OP_CONTRAST
+        op.arg.factor = float(_factor(name, args[0]))
+    else:
+        resample = args[1]
+        if resample not in (BILINEAR, BICUBIC):
+            raise ValueError(f'{name}: resample {resample} must be BILINEAR ({BILINEAR}) or BICUBIC ({BICUBIC})')
+        if name == 'Rotate':
+            turn, nh, nw, coef = rotate_expand_map(h, w, args[0])
+            if turn == 0:
+                return False, h, w
+            op.out_height, op.out_width = nh, nw
+            if turn is not None:
+                op.op, op.mode = OP_TURN, turn
+                return True, nh, nw
+        else:
+            coef = affine_coeffs(name, h, w, args[0])
+        op.op, op.mode = OP_AFFINE, int(resample)
+        op.arg.coef[:] = coef
+    return True, op.out_height, op.out_width
+
+
+def _descs(images, chains):
+    """The descriptor array of `images` (checked) under `chains`, and every image's size after its chain."""
+    chains = list(chains)
+    if len(chains) != len(images):
+        raise ValueError(f'{len(chains)} chains for {len(images)} images')
+    descs = (_native.AugmentDesc * len(images))()
+    sizes = []
+    for i, (d, im, chain) in enumerate(zip(descs, images, chains)):
+        chain = list(chain)
+        if len(chain) > MAX_OPS:
+            raise ValueError(f'image {i}: a chain holds at most {MAX_OPS} operators, got {len(chain)}')
+        h, w = im.shape[0], im.shape[1]
+        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+            raise ValueError(f'image {i} of {h} x {w}: each side must be in 1 .. {MAX_SIDE}')
+        d.data = im.data_ptr()
+        d.height, d.width, d.row_stride = h, w, im.stride(0)
+        n = 0
+        for entry in chain:
+            used, h, w = _fill_op(d.ops[n], h, w, entry[0], tuple(entry[1:]))
+            n += used
+        d.num_ops = n
+        sizes.append((h, w))
+    return descs, sizes
+
+
+def _workspace(lib, descs, n, dev):
+    need = lib.parseq_augment_workspace_bytes(descs, n)
+    if not need:
+        _native.check(-1)
+    return torch.empty((need,), dtype=torch.uint8, device=dev), need
+
+
+def _checked_gpu(images, what):
+    for im in images:
+        if not im.is_cuda:
+            raise RuntimeError(f'{what} runs on the GPU (no CPU fallback); move the decoded images to the device first')
+    return _checked(images)
+
+
+def apply_batch(images: Sequence[Tensor], chains) -> list:
+    """images: CUDA uint8 tensors [H_i, W_i, 3]; chains[i]: at most three (name, *args) tuples.  Returns the augmented uint8
+    [H'_i, W'_i, 3] tensors, each bit for bit what the Pillow calls of the module docstring give (parseq_op_augment, one chain per call)."""
+    keep = _checked_gpu(images, 'apply_batch')
+    dev = keep[0].device
+    lib = _native.lib()
+    outs, hold = [], []
+    with _native.guard(dev):
+        chains = list(chains)
+        if len(chains) != len(keep):
+            raise ValueError(f'{len(chains)} chains for {len(keep)} images')
+        for im, chain in zip(keep, chains):
+            descs, sizes = _descs([im], [chain])
+            ws, need = _workspace(lib, descs, 1, dev)
+            out = torch.empty(sizes[0] + (3,), dtype=torch.uint8, device=dev)
+            _native.check(lib.parseq_op_augment(descs, _native.ptr(out), _native.ptr(ws), need, _native.stream_ptr(dev)))
+            outs.append(out)
+            hold.append((descs, ws))
+    torch.cuda.current_stream(dev).synchronize()         # the descriptors are host memory read by asynchronous copies
+    return outs
+
+
+def augment_resize_batch(images: Sequence[Tensor], chains, size=(32, 128)) -> Tensor:
+    """images: CUDA uint8 tensors [H_i, W_i, 3] (sizes may differ); chains as for `apply_batch`.  Returns uint8 [N, 3, size[0], size[1]]:
+    every image augmented, then resized as `resize_batch` resizes it, in one call (one launch per chain stage, then the resize kernel)."""
+    keep = _checked_gpu(images, 'augment_resize_batch')
+    dev = keep[0].device
+    n = len(keep)
+    descs, _ = _descs(keep, chains)
+    lib = _native.lib()
+    out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
+    with _native.guard(dev):
+        ws, need = _workspace(lib, descs, n, dev)
+        _native.check(lib.parseq_augment_resize_bicubic(descs, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), need, _native.stream_ptr(dev)))
+    torch.cuda.current_stream(dev).synchronize()         # the descriptor array is host memory read by an asynchronous copy
+    return out
+
+
+class RandAugment:
+    """The policy of the reference's rand_augment_transform(magnitude, num_layers): per image, `num_layers` DISTINCT operators drawn
+    uniformly (timm's RandAugment with choice weights, i.e. without replacement) from timm's increasing set minus SharpnessIncreasing,
+    each applied with probability 0.5, signed arguments negated with probability 0.5, geometric operators with BILINEAR or BICUBIC at
+    random (timm's _RANDOM_INTERPOLATION), fill colour (128, 128, 128).  The reference's set has two more operators, GaussianBlur and
+    PoissonNoise (`missing`): until they exist the draw is among the fourteen of `ops`.
+    The generator is numpy's, seeded by `seed`; it makes no claim to reproduce the stream of timm's `random` / `np.random` calls."""
+
+    ops = ('AutoContrast', 'Equalize', 'Invert', 'Rotate', 'Posterize', 'Solarize', 'SolarizeAdd', 'Color', 'Contrast', 'Brightness',
+           'ShearX', 'ShearY', 'TranslateXRel', 'TranslateYRel')
+    missing = ('GaussianBlur', 'PoissonNoise')
+    _LEVEL_DENOM = 10.0
+    # strhub/data/augment.py:102-108
+    _SIGNED_MAX = {'Rotate': 30, 'ShearX': 0.9, 'ShearY': 0.2, 'TranslateXRel': 0.10, 'TranslateYRel': 0.30}
+
+    def __init__(self, magnitude: float = 5, num_layers: int = 3, seed=None):
+        if not 0 <= magnitude <= self._LEVEL_DENOM:
+            raise ValueError(f'magnitude {magnitude} must be in 0 .. 10')
+        if not 1 <= num_layers <= MAX_OPS:
+            raise ValueError(f'num_layers {num_layers} must be in 1 .. {MAX_OPS}')
+        self.magnitude, self.num_layers = magnitude, num_layers
+        self.rng = np.random.default_rng(seed)
+
+    def _negate(self, v):
+        return -v if self.rng.random() > 0.5 else v
+
+    def _args(self, name: str) -> tuple:
+        level = self.magnitude / self._LEVEL_DENOM
+        if name in self._SIGNED_MAX:                       # aa_overrides.py _level_to_arg: (level / _LEVEL_DENOM) * max, randomly negated
+            arg = self._negate(level * self._SIGNED_MAX[name])
+            return (arg, BILINEAR if self.rng.random() < 0.5 else BICUBIC)
+        if name == 'Posterize':                            # timm _posterize_increasing_level_to_arg
+            return (4 - int(level * 4),)
+        if name == 'Solarize':                             # timm _solarize_increasing_level_to_arg
+            return (256 - min(256, int(level * 256)),)
+        if name == 'SolarizeAdd':                          # timm _solarize_add_level_to_arg
+            return (min(128, int(level * 110)),)
+        if name in ('Color', 'Contrast', 'Brightness'):    # timm _enhance_increasing_level_to_arg
+            return (max(0.1, 1.0 + self._negate(level * 0.9)),)
+        return ()
+
+    def sample(self, sizes) -> list:
+        """One chain per entry of `sizes` (the sizes are not needed to draw a chain — every argument is relative — only counted)."""
+        pool = self.ops
+        chains = []
+        for _ in range(len(sizes)):
+            chain = []
+            for j in self.rng.choice(len(pool), self.num_layers, replace=False):
+                name = pool[j]
+                if self.rng.random() > 0.5:                # timm AugmentOp: prob = 0.5
+                    continue
+                chain.append((name,) + self._args(name))
+            chains.append(chain)
+        return chains

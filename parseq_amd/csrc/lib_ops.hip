@@ -1,6 +1,7 @@
 // libparseq_hip.so — input resize, post-process, and the per-kernel entry points the parity tests call.
 #include "lib_internal.h"
 #include "eval_metrics.h"
+#include "augment.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 static int resize_taps(int in_size, int out_size) {
@@ -89,6 +90,146 @@ extern "C" int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t*
     const long long pixels = (long long)im.rot_height * im.rot_width;
     hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)std::min<long long>((pixels + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, im, out);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// training augmentation (augment.h): chains of Pillow-exact RandAugment operators, then the resize above
+// -------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(parseq_augment_op) == sizeof(AugOp) && offsetof(parseq_augment_op, arg) == offsetof(AugOp, arg) &&
+              sizeof(parseq_augment_desc) == sizeof(AugDesc) && offsetof(parseq_augment_desc, ops) == offsetof(AugDesc, ops) &&
+              PARSEQ_AUGMENT_MAX_OPS == AUG_MAX_OPS && PARSEQ_AUG_TURN == AUG_TURN && PARSEQ_AUG_TABLE == AUG_TABLE &&
+              PARSEQ_AUG_BICUBIC == AUG_BICUBIC, "descriptor layouts must match");
+
+static bool aug_side_ok(int v) { return v >= 1 && v <= PARSEQ_ROTATE_MAX_SIDE; }
+
+static int check_augment(const parseq_augment_desc& d, int i) {
+    if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
+        return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
+    if (!aug_side_ok(d.height) || !aug_side_ok(d.width))
+        return fail(PARSEQ_E_INVALID, "image %d: %dx%d, a side is above %d", i, d.height, d.width, PARSEQ_ROTATE_MAX_SIDE);
+    if (d.num_ops < 0 || d.num_ops > PARSEQ_AUGMENT_MAX_OPS)
+        return fail(PARSEQ_E_INVALID, "image %d: %d operators, a chain holds at most %d", i, d.num_ops, PARSEQ_AUGMENT_MAX_OPS);
+    int h = d.height, w = d.width;
+    for (int k = 0; k < d.num_ops; ++k) {
+        const parseq_augment_op& op = d.ops[k];
+        if (!aug_side_ok(op.out_height) || !aug_side_ok(op.out_width))
+            return fail(PARSEQ_E_INVALID, "image %d, operator %d: output of %dx%d, each side must be in 1 .. %d", i, k, op.out_height, op.out_width,
+                        PARSEQ_ROTATE_MAX_SIDE);
+        const bool same = op.out_height == h && op.out_width == w;
+        switch (op.op) {
+            case PARSEQ_AUG_TABLE: case PARSEQ_AUG_AUTOCONTRAST: case PARSEQ_AUG_EQUALIZE: break;
+            case PARSEQ_AUG_CONTRAST: case PARSEQ_AUG_COLOR:
+                if (!(std::isfinite(op.arg.factor) && op.arg.factor >= 0.1f))
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: factor %g is out of range (finite, >= 0.1)", i, k, (double)op.arg.factor);
+                break;
+            case PARSEQ_AUG_AFFINE:
+                if (op.mode != PARSEQ_AUG_BILINEAR && op.mode != PARSEQ_AUG_BICUBIC)
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: resample %d is out of range (2 bilinear, 3 bicubic)", i, k, op.mode);
+                for (int t = 0; t < 6; ++t)
+                    if (!std::isfinite(op.arg.coef[t]))
+                        return fail(PARSEQ_E_INVALID, "image %d, operator %d: coefficient %d is out of range (not finite)", i, k, t);
+                break;
+            case PARSEQ_AUG_TURN: {
+                if (op.mode != PARSEQ_ROTATE_90 && op.mode != PARSEQ_ROTATE_180 && op.mode != PARSEQ_ROTATE_270)
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: turn %d is out of range (1, 2 or 3 quarter turns)", i, k, op.mode);
+                const bool swap = op.mode != PARSEQ_ROTATE_180;
+                if (op.out_height != (swap ? w : h) || op.out_width != (swap ? h : w))
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: turn %d makes %dx%d of %dx%d, not %dx%d", i, k, op.mode, swap ? w : h, swap ? h : w,
+                                h, w, op.out_height, op.out_width);
+                break;
+            }
+            default: return fail(PARSEQ_E_INVALID, "image %d, operator %d: unknown operator %d", i, k, op.op);
+        }
+        if (op.op != PARSEQ_AUG_AFFINE && op.op != PARSEQ_AUG_TURN && !same)
+            return fail(PARSEQ_E_INVALID, "image %d, operator %d: operator %d keeps the size, %dx%d stated for %dx%d", i, k, op.op, op.out_height,
+                        op.out_width, h, w);
+        h = op.out_height; w = op.out_width;
+    }
+    return 0;
+}
+
+struct AugLayout { size_t descs, offsets, finals, regions, total; };
+
+static size_t aug_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+static AugLayout aug_layout(const parseq_augment_desc* descs, int batch) {
+    AugLayout l;
+    l.descs = 0;
+    l.offsets = aug_align((size_t)batch * sizeof(AugDesc));
+    l.finals = l.offsets + aug_align((size_t)batch * sizeof(size_t));
+    l.regions = l.finals + aug_align((size_t)batch * sizeof(ImageDesc));
+    l.total = l.regions;
+    for (int i = 0; i < batch; ++i) l.total += 2 * aug_region_bytes(descs[i]);
+    return l;
+}
+
+extern "C" size_t parseq_augment_workspace_bytes(const parseq_augment_desc* descs, int batch) {
+    if (!descs || batch <= 0) { fail(PARSEQ_E_INVALID, "null descriptors / batch %d", batch); return 0; }
+    for (int i = 0; i < batch; ++i)
+        if (check_augment(descs[i], i)) return 0;
+    return aug_layout(descs, batch).total;
+}
+
+// validates, copies the descriptors, plans the regions and runs every stage on `s`
+static int augment_run(const parseq_augment_desc* descs, int batch, void* workspace, size_t workspace_bytes, hipStream_t s, AugLayout* layout) {
+    if (!descs || !workspace) return fail(PARSEQ_E_INVALID, "null descriptors / workspace");
+    if (batch <= 0) return fail(PARSEQ_E_INVALID, "bad shape: batch %d", batch);
+    for (int i = 0; i < batch; ++i) CHK(check_augment(descs[i], i));
+    const AugLayout l = aug_layout(descs, batch);
+    if (workspace_bytes < l.total)
+        return fail(PARSEQ_E_INVALID, "workspace of %zu bytes, %zu needed (parseq_augment_workspace_bytes)", workspace_bytes, l.total);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    const AugDesc* dd = reinterpret_cast<const AugDesc*>(ws + l.descs);
+    size_t* offsets = reinterpret_cast<size_t*>(ws + l.offsets);
+    HIPCHK(hipMemcpyAsync(ws + l.descs, descs, (size_t)batch * sizeof(AugDesc), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(augment_plan_kernel, dim3(1), dim3(256), 0, s, dd, batch, ws + l.regions, offsets, reinterpret_cast<ImageDesc*>(ws + l.finals));
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < PARSEQ_AUGMENT_MAX_OPS; ++k) {
+        int tiles = 0;
+        for (int i = 0; i < batch; ++i)
+            if (descs[i].num_ops > k) tiles = std::max(tiles, aug_tiles((long long)descs[i].ops[k].out_height * descs[i].ops[k].out_width));
+        if (!tiles) break;                                   // chains are dense: no image has an operator k + 1 without an operator k
+        hipLaunchKernelGGL(augment_stage_kernel, dim3(batch, tiles), dim3(256), 0, s, dd, offsets, ws + l.regions, k);
+        HIPCHK(hipGetLastError());
+    }
+    *layout = l;
+    return 0;
+}
+
+extern "C" int parseq_augment_resize_bicubic(const parseq_augment_desc* descs, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
+                                             size_t workspace_bytes, void* stream) {
+    if (!out) return fail(PARSEQ_E_INVALID, "null out");
+    if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
+    if (!descs || batch <= 0) return fail(PARSEQ_E_INVALID, "null descriptors / batch %d", batch);
+    int ksh = 1, ksv = 1;
+    for (int i = 0; i < batch; ++i) {
+        CHK(check_augment(descs[i], i));
+        const parseq_augment_desc& d = descs[i];
+        ksh = std::max(ksh, resize_taps(d.num_ops ? d.ops[d.num_ops - 1].out_width : d.width, out_w));
+        ksv = std::max(ksv, resize_taps(d.num_ops ? d.ops[d.num_ops - 1].out_height : d.height, out_h));
+    }
+    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
+    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "an augmented image is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
+    hipStream_t s = (hipStream_t)stream;
+    AugLayout l;
+    CHK(augment_run(descs, batch, workspace, workspace_bytes, s, &l));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(batch), dim3(256), lds, s,
+                       reinterpret_cast<const ImageDesc*>(static_cast<unsigned char*>(workspace) + l.finals), out_h, out_w, ksh, ksv, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int parseq_op_augment(const parseq_augment_desc* desc, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!desc || !out) return fail(PARSEQ_E_INVALID, "null descriptor / out");
+    hipStream_t s = (hipStream_t)stream;
+    AugLayout l;
+    CHK(augment_run(desc, 1, workspace, workspace_bytes, s, &l));
+    const int n = desc->num_ops;
+    const int h = n ? desc->ops[n - 1].out_height : desc->height, w = n ? desc->ops[n - 1].out_width : desc->width;
+    const unsigned char* last = n ? static_cast<unsigned char*>(workspace) + l.regions + (size_t)((n - 1) & 1) * aug_region_bytes(*desc) : desc->data;
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)w * 3, last, n ? (size_t)w * 3 : (size_t)desc->row_stride, (size_t)w * 3, (size_t)h, hipMemcpyDeviceToDevice, s));
     return 0;
 }
 
