@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define PARSEQ_ABI_VERSION 14
+#define PARSEQ_ABI_VERSION 15
 
 /* (ABI 9) deepest decoder a model may have: parseq_config.dec_depth in [1, PARSEQ_DEC_DEPTH_MAX] */
 #define PARSEQ_DEC_DEPTH_MAX 4
@@ -361,7 +361,10 @@ int64_t parseq_model_grad_elems(const parseq_model* m);
 /* Arithmetic of the training step's matrix products (reference: `precision: bf16-mixed`, /root/reference/train.py:62-64):
  * PARSEQ_F32 (default) = exact fp32 products on v_mfma_f32_16x16x4_f32; PARSEQ_BF16 = both operands of every aligned Linear
  * product (forward, dX, dW) rounded to bfloat16 on their way into LDS, fp32 accumulate, fp32 master weights / activations /
- * gradients in memory.  Attention products, LayerNorm, soft-max, loss and the optimiser stay fp32 in both modes. */
+ * gradients in memory.  Attention products, LayerNorm, soft-max, loss and the optimiser stay fp32 in both modes.
+ * (ABI 15) PARSEQ_BF16X3 = the same Linear products with both operands SPLIT into bf16 pairs hi = bf16(v), lo = bf16(v - hi) on their
+ * way into LDS and evaluated as lo*hi + hi*lo + hi*hi (three bf16 MFMAs, fp32 accumulate): within 3 * 2^-16 sum |a||b| of the exact
+ * product.  Everything else — attention, workspace layout and sizes, kernel routes — is the PARSEQ_F32 mode's. */
 int parseq_model_set_train_precision(parseq_model* m, int precision);
 
 /* Loss of the K-permutation training objective (system.py:168-199, dropout off) for a batch whose encoder output is
@@ -564,8 +567,9 @@ int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t* out, void*
 int parseq_op_augment(const parseq_augment_desc* desc, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (ABI 12) The training step's products and row kernels one operator at a time (tests/test_train_gemm.py).  The three hooks build
- * the step's context from their arguments and call the internal functions the step calls, unchanged.  bf16_ops: the bf16-operand
- * mode (parseq_model_set_train_precision(PARSEQ_BF16)).  scratch / scratch_floats: the caller's, what the step carves out of its
+ * the step's context from their arguments and call the internal functions the step calls, unchanged.  bf16_ops: the operand
+ * mode as a precision constant (parseq_model_set_train_precision): PARSEQ_F32 (0), PARSEQ_BF16 (1) or, from ABI 15, PARSEQ_BF16X3 (3);
+ * any other value is refused with PARSEQ_E_INVALID.  scratch / scratch_floats: the caller's, what the step carves out of its
  * workspace (16 Mi floats there): split-K partials, partial column sums, the LayerNorm backward's chunk partials at its end; NULL / a small
  * one are allowed and change the route. */
 enum parseq_gemm_kernel {          /* which kernel a product ran on; bf16-operand kernels: orientation of A, B (k = contiguous along the contraction, n = along the outer axis) */
@@ -576,7 +580,8 @@ enum parseq_gemm_kernel {          /* which kernel a product ran on; bf16-operan
     PARSEQ_GEMM_B16_KK = 6, PARSEQ_GEMM_B16_KN = 7, PARSEQ_GEMM_B16_NK = 8, PARSEQ_GEMM_B16_NN = 9,       /* ... B a bf16 shadow */
     PARSEQ_GEMM_A16_NN = 10,       /* ... both shadows, both outer-contiguous, 32-deep stages */
     PARSEQ_GEMM_BOTH16_K = 11,     /* mfma_bgemm16_kernel: both shadows k-contiguous */
-    PARSEQ_GEMM_BOTH16_T = 12      /* mfma_bgemm16t_kernel: both shadows outer-contiguous, 64-deep stages */
+    PARSEQ_GEMM_BOTH16_T = 12,     /* mfma_bgemm16t_kernel: both shadows outer-contiguous, 64-deep stages */
+    PARSEQ_GEMM_X3_KK = 13, PARSEQ_GEMM_X3_KN = 14, PARSEQ_GEMM_X3_NK = 15, PARSEQ_GEMM_X3_NN = 16         /* (ABI 15) mfma_x3gemm_kernel: split-bf16 operands, both fp32 in memory */
 };
 typedef struct parseq_gemm_operand {
     const void* data;              /* device */

@@ -16,7 +16,7 @@ from . import build as _build
 PARSEQ_F32, PARSEQ_BF16, PARSEQ_U8, PARSEQ_BF16X3 = 0, 1, 2, 3
 ARCH_PARSEQ, ARCH_VITSTR = 0, 1
 FLAG_DECODE_AR, FLAG_TESTING, FLAG_LATENCY = 1, 2, 4
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 class ParseqConfig(C.Structure):
@@ -69,6 +69,8 @@ class GemmRoute(C.Structure):
 
 # enum parseq_gemm_kernel, by value
 GEMM_KERNELS = ('valu', 'mfma_f32', 'bf16_kk', 'bf16_kn', 'bf16_nk', 'bf16_nn', 'b16_kk', 'b16_kn', 'b16_nk', 'b16_nn', 'a16_nn', 'both16_k', 'both16_t')
+# the split-bf16 kernels of the bf16x3 training mode (ABI 15), by their value in the same enum
+GEMM_KERNELS_X3 = {13: 'x3_kk', 14: 'x3_kn', 15: 'x3_nk', 16: 'x3_nn'}
 
 
 class NativeError(RuntimeError):

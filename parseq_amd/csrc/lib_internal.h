@@ -153,7 +153,7 @@ struct parseq_model {
     std::string enc;          // key prefix of the encoder parameters: "encoder." (PARSeq) or "" (ViTSTR)
     int patch_k = 0;          // 3 * patch_h * patch_w
     int classes = 0;          // num_tokens - 2
-    int train_precision = PARSEQ_F32;     // training step: PARSEQ_F32 (exact products) or PARSEQ_BF16 (GEMM operands rounded to bf16)
+    int train_precision = PARSEQ_F32;     // training step: PARSEQ_F32 (exact products), PARSEQ_BF16 (GEMM operands rounded to bf16) or PARSEQ_BF16X3 (split into bf16 pairs)
     std::vector<ParamSpec> params;
     std::unordered_map<std::string, int> index;
     float* master = nullptr;  // device, all parameters fp32 back to back (each 16-byte aligned)

@@ -18,9 +18,13 @@ static size_t train_scratch_floats(size_t ln_rows, size_t E) {
 struct TrainCtx {
     hipStream_t s;
     float* scratch;      // scratch_floats floats (train_scratch_floats)
-    bool bf16_ops = false;      // GEMM operands rounded to bf16 (parseq_model_set_train_precision), fp32 accumulate and everything else
+    int ops = PARSEQ_F32;       // the operand mode of the products (parseq_model_set_train_precision): PARSEQ_F32 exact, PARSEQ_BF16 GEMM operands
+                                // rounded to bf16, PARSEQ_BF16X3 split into bf16 (hi, lo) pairs; fp32 accumulate and everything else in all three
     size_t scratch_floats = TRAIN_SCRATCH_FLOATS;      // what of `scratch` the split-K partials / column sums may use (lin_bwd carves its padded copies off the end)
+    bool bf16_ops() const { return ops == PARSEQ_BF16; }
+    bool x3_ops() const { return ops == PARSEQ_BF16X3; }
 };
+static bool train_ops_ok(int ops) { return ops == PARSEQ_F32 || ops == PARSEQ_BF16 || ops == PARSEQ_BF16X3; }
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 constexpr int SPLIT_TARGET = 512;      // split-K: how many workgroups a product with few output tiles is cut into along the contraction
@@ -96,7 +100,13 @@ static BgemmChoice bgemm_kernel(bool a16, bool b16, bool akf, bool bkf, bool who
     return akf ? (bkf ? BgemmChoice{mfma_bgemm_kernel<true, true>, PARSEQ_GEMM_BF16_KK} : BgemmChoice{mfma_bgemm_kernel<true, false>, PARSEQ_GEMM_BF16_KN})
                : (bkf ? BgemmChoice{mfma_bgemm_kernel<false, true>, PARSEQ_GEMM_BF16_NK} : BgemmChoice{mfma_bgemm_kernel<false, false>, PARSEQ_GEMM_BF16_NN});
 }
-// Three routes, first match wins.  The bf16-operand mode's matrix-core kernels: edge tiles allowed (the 95-class head, the 96-wide patch
+// The split-bf16 kernel of the bf16x3 mode (fp32 operands in memory only): same arguments, same grid
+static BgemmChoice x3gemm_kernel(bool akf, bool bkf) {
+    return akf ? (bkf ? BgemmChoice{mfma_x3gemm_kernel<true, true>, PARSEQ_GEMM_X3_KK} : BgemmChoice{mfma_x3gemm_kernel<true, false>, PARSEQ_GEMM_X3_KN})
+               : (bkf ? BgemmChoice{mfma_x3gemm_kernel<false, true>, PARSEQ_GEMM_X3_NK} : BgemmChoice{mfma_x3gemm_kernel<false, false>, PARSEQ_GEMM_X3_NN});
+}
+// Routes, first match wins.  The bf16x3 mode's split-bf16 kernel takes what the bf16-operand mode's fp32-in-memory kernels take and
+// falls through to the fp32 routes otherwise.  The bf16-operand mode's matrix-core kernels: edge tiles allowed (the 95-class head, the 96-wide patch
 // rows), every optional epilogue folded; a product with a bf16 part MUST take them — one that cannot is an error, never a silent fp32
 // read of bf16 data.  The fp32 matrix-core kernel: whole 128 x 128 tiles and 16-deep stages.  The VALU kernel: everything else.
 static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const Out& C, int M, int N, int K, const GemmOpts& o = GemmOpts(),
@@ -104,7 +114,7 @@ static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const O
     hipStream_t s = cx.s;
     if (M <= 0 || N <= 0 || K <= 0) return fail(PARSEQ_E_INVALID, "sgemm: bad shape %d x %d x %d", M, N, K);
     const bool shadow = A.bf16 || B.bf16 || C.b16 || o.gelu_out.b16 || o.gelu_pre.b16;
-    if (shadow && (!cx.bf16_ops || !cx.scratch || M < 16 || N < 16)) return fail(PARSEQ_E_STATE, "sgemm: bf16 shadow operands outside the bf16-operand mode");
+    if (shadow && (!cx.bf16_ops() || !cx.scratch || M < 16 || N < 16)) return fail(PARSEQ_E_STATE, "sgemm: bf16 shadow operands outside the bf16-operand mode");
     if (!C) return fail(PARSEQ_E_INVALID, "sgemm: no output");
     const bool akf = A.sk == 1, bkf = B.sk == 1, readable = mc_readable(A, M) && mc_readable(B, N);
     const bool both = A.bf16 && B.bf16 && akf && bkf;                     // the 64-deep kernel
@@ -114,22 +124,29 @@ static int sgemm(const TrainCtx& cx, const Operand& A, const Operand& B, const O
     if (shadow && (!readable || K % bk16 != 0 || (A.bf16 && !both && !both_t)))
         return fail(PARSEQ_E_INVALID, "sgemm: shadow operands of a %d x %d x %d product are not laid out for the matrix-core kernels", M, N, K);
     if (shadow && o.asum && both) return fail(PARSEQ_E_INVALID, "sgemm: row sums of a bf16 shadow");
-    const bool bf16 = shadow || (cx.bf16_ops && K % BG_BK == 0 && readable && cx.scratch && M >= 16 && N >= 16);
-    const bool mfma32 = !bf16 && M % MG_BM == 0 && N % MG_BN == 0 && K % MG_BK == 0 && readable && cx.scratch;
+    const bool mc16 = K % BG_BK == 0 && readable && cx.scratch && M >= 16 && N >= 16;      // what the fp32-in-memory bf16 kernels take
+    const bool x3 = cx.x3_ops() && mc16;
+    const bool bf16 = shadow || (cx.bf16_ops() && mc16);
+    const bool mfma32 = !bf16 && !x3 && M % MG_BM == 0 && N % MG_BN == 0 && K % MG_BK == 0 && readable && cx.scratch;
 
     SgemmArgs a{};      // the one place where a typed operand becomes the kernels' pointer + flag
     a.A = static_cast<const float*>(A.p); a.sam = A.so; a.sak = A.sk; a.a16 = A.bf16;
     a.B = static_cast<const float*>(B.p); a.sbk = B.sk; a.sbn = B.so; a.b16 = B.bf16;
     a.bias = o.bias; a.R = o.R; a.ldr = o.ldr; a.rper = o.rper > 0 ? o.rper : 1;
     a.C = C.f32; a.c16 = C.b16; a.ldc = N; a.M = M; a.N = N; a.K = K; a.alpha = o.alpha; a.accumulate = o.accumulate ? 1 : 0;
-    if (bf16) { a.asum = o.asum; a.gelu_pre = o.gelu_pre.f32; a.gelu_pre16 = o.gelu_pre.b16; a.gelu_out = o.gelu_out.f32; a.gelu_out16 = o.gelu_out.b16; }
-    if (folded) folded->asum = folded->gelu_pre = folded->gelu_out = bf16;
-    if (!bf16 && !mfma32) {
+    if (bf16 || x3) { a.asum = o.asum; a.gelu_pre = o.gelu_pre.f32; a.gelu_pre16 = o.gelu_pre.b16; a.gelu_out = o.gelu_out.f32; a.gelu_out16 = o.gelu_out.b16; }
+    if (folded) folded->asum = folded->gelu_pre = folded->gelu_out = bf16 || x3;
+    if (!bf16 && !x3 && !mfma32) {
         if (route) { route->kernel = PARSEQ_GEMM_VALU; route->whole = 0; route->splits = 1; route->k_chunk = K; }
         return launch(sgemm_kernel, dim3((N + SG_BN - 1) / SG_BN, (M + SG_BM - 1) / SG_BM), dim3(256), 0, s, a);
     }
-    const GemmPlan p = gemm_plan(M, N, K, bf16 ? bk16 : MG_BK, cx.scratch_floats);
-    if (bf16) {
+    const GemmPlan p = gemm_plan(M, N, K, (bf16 || x3) ? bk16 : MG_BK, cx.scratch_floats);
+    if (x3) {
+        const BgemmChoice k = x3gemm_kernel(akf, bkf);
+        if (route) { route->kernel = k.id; route->whole = 0; route->splits = p.splits; route->k_chunk = p.k_chunk; }
+        hipLaunchKernelGGL(k.fn, dim3((unsigned)p.tiles, 1, p.splits), dim3(256), 0, s, a, p.k_chunk, cx.scratch, p.gn, p.gm);
+        HIPCHK(hipGetLastError());
+    } else if (bf16) {
         // whole 128 x 128 tiles (every product of the PARSeq-S / ViTSTR encoders); the buffer loads' 32-bit byte offsets cover both operands
         // with room to spare at any batch that fits the workspace
         const bool whole = M % MG_BM == 0 && N % MG_BN == 0 &&
@@ -183,7 +200,7 @@ static int lin_bwd(const TrainCtx& cx, const float* x, const float* W, const flo
     // first N rows of the padded dW are added to the gradient.
     const int Np = (N + 31) / 32 * 32;
     const size_t reserve = (size_t)M * Np + 2 * (size_t)Np * K;
-    if (cx.bf16_ops && N % 4 != 0 && cx.scratch && M % 4 == 0 && K % 4 == 0 && reserve + ((size_t)4 << 20) <= cx.scratch_floats) {
+    if ((cx.bf16_ops() || cx.x3_ops()) && N % 4 != 0 && cx.scratch && M % 4 == 0 && K % 4 == 0 && reserve + ((size_t)4 << 20) <= cx.scratch_floats) {
         hipStream_t s = cx.s;
         TrainCtx c2 = cx; c2.scratch_floats = cx.scratch_floats - reserve;
         float* dyp = cx.scratch + c2.scratch_floats; float* Wp = dyp + (size_t)M * Np; float* dWp = Wp + (size_t)Np * K;
@@ -310,8 +327,8 @@ static int train_attn_wide(const TrainCtx& cx, const TrainAttnArgs& a, int B, bo
 enum TrainAttnRoute { TA_DEC_BF16, TA_ENC_BF16, TA_MFMA, TA_WIDE, TA_HD32, TA_HD64, TA_NONE };
 static TrainAttnRoute train_attn_route(const TrainCtx& cx, const TrainAttnArgs& a, int hd, bool backward) {
     const bool rows4 = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv)));
-    if (train_attn_dec_bf16_shape(cx.bf16_ops, hd, a.Lq, a.Lk) && rows4 && a.q_bstride % 4 == 0) return TA_DEC_BF16;
-    if (cx.bf16_ops && hd == TB_HD && a.Lq == TB_N && a.Lk == TB_N && !a.qmask && !a.kmask && !a.drop.thresh && a.q_bstride == (long)a.Lq * a.ldq && rows4)
+    if (train_attn_dec_bf16_shape(cx.bf16_ops(), hd, a.Lq, a.Lk) && rows4 && a.q_bstride % 4 == 0) return TA_DEC_BF16;
+    if (cx.bf16_ops() && hd == TB_HD && a.Lq == TB_N && a.Lk == TB_N && !a.qmask && !a.kmask && !a.drop.thresh && a.q_bstride == (long)a.Lq * a.ldq && rows4)
         return TA_ENC_BF16;
     if (hd == 64 && a.Lq % 32 == 0 && a.Lk % 16 == 0 && a.Lk <= 128 && !a.qmask && !a.kmask && !a.drop.thresh) return TA_MFMA;
     if (train_attn_is_wide(a, hd)) return TA_WIDE;
@@ -346,7 +363,7 @@ extern "C" int parseq_op_train_attention(const float* qkv, float* o, float* lse,
     a.q = qkv; a.q_bstride = (long)tokens * 3 * E; a.ldq = 3 * E; a.k = qkv + E; a.v = qkv + 2 * E; a.ldkv = 3 * E;
     a.o = o; a.ldo = E; a.d_o = d_o; a.dq = dqkv; a.lddq = 3 * E; a.dk = dqkv ? dqkv + E : nullptr; a.dv = dqkv ? dqkv + 2 * E : nullptr;
     a.lddkv = 3 * E; a.Lq = tokens; a.Lk = tokens; a.H = heads; a.scale = 1.0f / sqrtf((float)TW_HD); a.lse = lse; a.dsum = dsum;
-    const TrainCtx cx{(hipStream_t)stream, nullptr, false, 0};
+    const TrainCtx cx{(hipStream_t)stream, nullptr, PARSEQ_F32, 0};
     if (route) *route = train_attn_route(cx, a, TW_HD, backward != 0) == TA_WIDE ? 1 : 0;
     return train_attn(cx, a, batch, backward != 0, TW_HD);
 }
@@ -363,7 +380,8 @@ extern "C" int parseq_op_train_gemm(const parseq_train_gemm_desc* d, parseq_gemm
     if (route) *route = parseq_gemm_route{PARSEQ_GEMM_NONE, 0, 0, 0, 0, 0, 0};
     CHK(check_arch());
     if (!d || !d->A.data || !d->B.data || !gemm_dtype_ok(d->A.dtype) || !gemm_dtype_ok(d->B.dtype)) return fail(PARSEQ_E_INVALID, "bad argument");
-    const TrainCtx cx{(hipStream_t)stream, d->scratch, d->bf16_ops != 0, d->scratch_floats};
+    if (!train_ops_ok(d->bf16_ops)) return fail(PARSEQ_E_INVALID, "operand mode %d", d->bf16_ops);
+    const TrainCtx cx{(hipStream_t)stream, d->scratch, d->bf16_ops, d->scratch_floats};
     GemmOpts g;
     g.bias = d->bias; g.R = d->R; g.ldr = (long)d->ldr; g.rper = d->rper; g.alpha = d->alpha; g.accumulate = d->accumulate != 0; g.asum = d->asum;
     g.gelu_pre = In(d->gelu_pre, static_cast<const bf16_t*>(d->gelu_pre16));
@@ -380,7 +398,8 @@ extern "C" int parseq_op_train_linear(const float* x, const float* W, const floa
                                       int bf16_ops, float* scratch, size_t scratch_floats, void* stream) {
     CHK(check_arch());
     if (!x || !W || M <= 0 || N <= 0 || K <= 0 || (backward ? (!dy || !dW || !db) : !y)) return fail(PARSEQ_E_INVALID, "bad argument");
-    const TrainCtx cx{(hipStream_t)stream, scratch, bf16_ops != 0, scratch_floats};
+    if (!train_ops_ok(bf16_ops)) return fail(PARSEQ_E_INVALID, "operand mode %d", bf16_ops);
+    const TrainCtx cx{(hipStream_t)stream, scratch, bf16_ops, scratch_floats};
     if (backward) return lin_bwd(cx, x, W, dy, dW, db, dx, M, N, K, dx_gelu_pre);
     return lin_fwd(cx, x, W, bias, R, rper, y, M, N, K, Out(gelu_out));
 }
@@ -507,7 +526,7 @@ extern "C" int64_t parseq_model_param_offset(const parseq_model* m, int index) {
 extern "C" int64_t parseq_model_grad_elems(const parseq_model* m) { return m ? (int64_t)m->master_elems : 0; }
 extern "C" int parseq_model_set_train_precision(parseq_model* m, int precision) {
     if (!m) return fail(PARSEQ_E_INVALID, "null model");
-    if (precision != PARSEQ_F32 && precision != PARSEQ_BF16) return fail(PARSEQ_E_INVALID, "training precision %d (PARSEQ_F32 or PARSEQ_BF16)", precision);
+    if (!train_ops_ok(precision)) return fail(PARSEQ_E_INVALID, "training precision %d (PARSEQ_F32, PARSEQ_BF16 or PARSEQ_BF16X3)", precision);
     m->train_precision = precision;
     return 0;
 }
@@ -566,7 +585,7 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     int* tgt_all = reinterpret_cast<int*>(w + o.tgt_all); float* losses = w + o.losses; int* counts = reinterpret_cast<int*>(w + o.counts);
     const size_t ME = (size_t)M * E, MF = (size_t)M * F, EE = (size_t)E * E;
     const int KP = route.KP; const bool ca_loop = route.ca_loop;      // passes per batch; the pass-walking cross-attention
-    const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
+    const TrainCtx cx{s, w + o.scratch, m->train_precision, o.scratch_floats};
 
     // ---- shared by all permutations: the content rows before dropout, and the memory's K / V (model.py:95-98, modules.py:74) ----
     CHK(launch(train_content_kernel, dim3(M), dim3(256), 0, s, W(D_TEXT_EMBED), pq, tokens, L, L, E, sqrtE, w + o.content0));
@@ -782,7 +801,7 @@ extern "C" int parseq_op_train_layernorm(const float* x, const float* gamma, con
     if (!x || !gamma || rows <= 0 || E <= 0) return fail(PARSEQ_E_INVALID, "bad argument");
     if (backward) {
         if (!dy || !dx || !dgamma || !dbeta) return fail(PARSEQ_E_INVALID, "bad argument");
-        const TrainCtx cx{(hipStream_t)stream, scratch, false, scratch_floats};
+        const TrainCtx cx{(hipStream_t)stream, scratch, PARSEQ_F32, scratch_floats};
         return ln_bwd(cx, x, gamma, dy, add, dx, dgamma, dbeta, rows, E, eps, static_cast<bf16_t*>(dx16));
     }
     if (!beta || !y || !gemm_dtype_ok(y_dtype)) return fail(PARSEQ_E_INVALID, "bad argument");
@@ -924,7 +943,7 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
     const float eps = m->cfg.enc_ln_eps;
     float* w = reinterpret_cast<float*>(workspace);
     auto P = [&](const char* key) { return m->p(m->enc + key); };
-    const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
+    const TrainCtx cx{s, w + o.scratch, m->train_precision, o.scratch_floats};
     if (m->vitstr) {
         // S - 1 patch rows per image, S token rows: the class token in front (timm _pos_embed), assembled from the patch product in `tmp`
         const int MP = batch * (S - 1);
@@ -1113,13 +1132,13 @@ extern "C" int parseq_train_encoder_backward(parseq_model* m, const float* dmemo
     const float eps = m->cfg.enc_ln_eps;
     float* w = reinterpret_cast<float*>(workspace);
     auto top = [&](const char* key) { return param_ref(m, m->enc + key, grads); };      // the encoder's parameters outside the blocks
-    const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
+    const TrainCtx cx{s, w + o.scratch, m->train_precision, o.scratch_floats};
     const EncBwdBufs g = enc_bwd_bufs(o, w, r);
     const bool segs = !m->vitstr && depth >= 2;
     SideFork fk;
     if (r.two_streams) CHK(train_side_for(m, s, &fk));
     // the context of the shadow block's weight-gradient products: the side stream and its scratch, or with one stream the main context
-    const TrainCtx cxs = r.two_streams ? TrainCtx{fk.side, w + o.scratch2, cx.bf16_ops, o.scratch_floats} : cx;
+    const TrainCtx cxs = r.two_streams ? TrainCtx{fk.side, w + o.scratch2, cx.ops, o.scratch_floats} : cx;
     const std::vector<EncBlockW> W = enc_block_weights(m, o, r.shadows, grads, w);
     m->grad_events_valid = false;
     if (segs) CHK(grad_event_record(m, 0, s));      // the decoder's gradients were written by parseq_train_decoder, earlier on this stream
@@ -1184,7 +1203,7 @@ extern "C" int parseq_train_vitstr_head(parseq_model* m, const float* memory, co
     const int E = m->cfg.embed_dim, C = m->classes, R = batch * T;
     float* w = reinterpret_cast<float*>(workspace);
     const ParamRef head_w = param_ref(m, "head.weight", grads), head_b = param_ref(m, "head.bias", grads);
-    const TrainCtx cx{s, w + o.scratch, m->train_precision == PARSEQ_BF16, o.scratch_floats};
+    const TrainCtx cx{s, w + o.scratch, m->train_precision, o.scratch_floats};
     CHK(launch(gather_image_rows_kernel, dim3(R), dim3(256), 0, s, memory, S, 1, w + o.hin, T, E));
     CHK(lin_fwd(cx, w + o.hin, head_w.p, head_b.p, nullptr, 0, w + o.logits, R, C, E));
     CHK(ce_loss_and_grad(s, w + o.logits, targets, 1, R, C, m->cfg.pad_id, w + o.row_loss, loss_out, reinterpret_cast<int*>(w + o.counts), total_targets));

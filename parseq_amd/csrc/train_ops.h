@@ -574,6 +574,178 @@ void mfma_bgemm_kernel(const SgemmArgs a, int k_chunk, float* __restrict__ parti
     bg_epilogue(a, acc, partial, reinterpret_cast<float*>(smem), m0, n0, tid, zsplit);
 }
 
+// The same contraction with SPLIT-bf16 operands (the training step's "bf16x3" mode; gemm.h SPLIT is the inference form): every fp32
+// element v of A and B goes into LDS as a PAIR of bf16, hi = bf16(v) and lo = bf16(v - hi) (the subtraction is exact in fp32), and every
+// product is evaluated as lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x32_bf16 — three MFMAs per fragment pair into the same accumulator,
+// small terms first.  The three bf16 products are exact in fp32; what is dropped is lo*lo and the second rounding of lo, under
+// 3 * 2^-16 relative to sum |a||b|.  Geometry, tile order, split-K, row sums (of the unsplit fp32 values) and epilogue are
+// mfma_bgemm_kernel's; each operand parks two planes per stage, so the LDS block is 80 KiB and two workgroups share a CU.
+//
+// x3_split keeps the residual a scalar-f32 subtraction pinned to its own register (the empty asm): see the note above ln_apply4 in
+// gemm.h — packed-f32 arithmetic next to this convert / subtract / convert sequence once produced wrong values in lanes 48-63.
+__device__ __forceinline__ void x3_split(float v, bf16_t& hi, bf16_t& lo) {
+    hi = static_cast<bf16_t>(v);                     // round to nearest even
+    float d = v - static_cast<float>(hi);            // exact
+    asm volatile("" : "+v"(d));
+    lo = static_cast<bf16_t>(d);
+}
+// BgOperand<KFAST, float>::park with the split: the same threads, rows and 8-byte stores, once into each plane
+template <bool KFAST>
+__device__ __forceinline__ void x3_park(bf16_t (*hi)[BG_LD], bf16_t (*lo)[BG_LD], const float4 (&r)[4], int tid) {
+    if constexpr (KFAST) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            const int idx = tid + 256 * it, o = idx >> 3, k4 = idx & 7;
+            union { uint2 u; bf16_t e[4]; } h, l;
+            x3_split(r[it].x, h.e[0], l.e[0]); x3_split(r[it].y, h.e[1], l.e[1]); x3_split(r[it].z, h.e[2], l.e[2]); x3_split(r[it].w, h.e[3], l.e[3]);
+            *reinterpret_cast<uint2*>(&hi[o][4 * k4]) = h.u;
+            *reinterpret_cast<uint2*>(&lo[o][4 * k4]) = l.u;
+        }
+    } else {
+        const int kq = tid >> 5, o4 = tid & 31;
+        const float v[4][4] = {{r[0].x, r[0].y, r[0].z, r[0].w}, {r[1].x, r[1].y, r[1].z, r[1].w}, {r[2].x, r[2].y, r[2].z, r[2].w}, {r[3].x, r[3].y, r[3].z, r[3].w}};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            union { uint2 u; bf16_t e[4]; } h, l;
+#pragma unroll
+            for (int it = 0; it < 4; ++it) x3_split(v[it][i], h.e[it], l.e[it]);
+            *reinterpret_cast<uint2*>(&hi[4 * o4 + i][4 * kq]) = h.u;
+            *reinterpret_cast<uint2*>(&lo[4 * o4 + i][4 * kq]) = l.u;
+        }
+    }
+}
+
+// The row-sum rider's tail as in mfma_bgemm_kernel (which keeps its own inline copy: calling this helper there changes the register
+// allocation of those tuned kernels, 150 -> 166 VGPRs in the k-contiguous forms): the threads' partial row sums of A over
+// this workgroup's k range — rs[i] belongs to outer index 4 (tid & 31) + i (outer-contiguous A) or to row (tid >> 3) + 32 i (k-contiguous A:
+// eight lanes per row) — folded in a fixed order through LDS (`red`, [8][128] floats: the operand tiles are dead) and added to a.asum
+// (split-K: to this split's slot behind the product's partials; splitk_reduce_kernel adds the slots up)
+template <bool AKF>
+__device__ __forceinline__ void bg_fold_row_sums(const SgemmArgs& a, const float (&rs)[4], float* red, float* partial,
+                                                 int m0, int zsplit, int tid) {
+    if constexpr (AKF) {
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+            float v = rs[it];
+            v += __shfl_xor(v, 1, 64); v += __shfl_xor(v, 2, 64); v += __shfl_xor(v, 4, 64);
+            if ((tid & 7) == 0) red[(tid >> 3) + 32 * it] = v;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) red[(tid >> 5) * 128 + 4 * (tid & 31) + i] = rs[i];
+    }
+    __syncthreads();
+    if (tid < 128 && m0 + tid < a.M) {
+        float v;
+        if constexpr (AKF) v = red[tid];
+        else v = ((red[tid] + red[128 + tid]) + (red[256 + tid] + red[384 + tid])) + ((red[512 + tid] + red[640 + tid]) + (red[768 + tid] + red[896 + tid]));
+        if (gridDim.z == 1) a.asum[m0 + tid] += v;
+        else partial[(size_t)gridDim.z * a.M * a.N + (size_t)zsplit * a.M + m0 + tid] = v;
+    }
+    __syncthreads();
+}
+
+template <bool AKF, bool BKF>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void mfma_x3gemm_kernel(const SgemmArgs a, int k_chunk, float* __restrict__ partial, int gn, int gm) {
+    using OpA = BgOperand<AKF, float>;
+    using OpB = BgOperand<BKF, float>;
+    // one LDS block: per stage the hi and lo planes of A, then of B; two stages; then (all of it) the epilogue's staging tile
+    constexpr int PLANE_BYTES = MG_BM * BG_LD * 2, STAGE_BYTES = 4 * PLANE_BYTES;
+    static_assert(MG_BM == MG_BN, "one plane size for both operands");
+    static_assert(2 * STAGE_BYTES >= EP_STAGE_BYTES && 2 * STAGE_BYTES >= 8 * 128 * 4, "LDS block too small for the epilogue");
+    static_assert(2 * (2 * STAGE_BYTES) <= 160 * 1024, "two workgroups per CU");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE_BYTES];
+    using Plane = bf16_t (*)[BG_LD];
+    auto plane = [&](int stage, int which) { return reinterpret_cast<Plane>(smem + stage * STAGE_BYTES + which * PLANE_BYTES); };      // which: A hi, A lo, B hi, B lo
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const BgTile bt = bg_tile<true>(gn, gm);
+    const int tn_ = bt.tn, tm_ = bt.tm, zsplit = bt.z;
+    const int m0 = tm_ * MG_BM, n0 = tn_ * MG_BN;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    const int r16 = lane & 15, g = lane >> 4;
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int kbeg = zsplit * k_chunk, kend = min(a.K, kbeg + k_chunk);
+    OpA oa; OpB ob;
+    oa.init(a.A, a.sam, a.sak, m0, a.M, kbeg, tid);
+    ob.init(a.B, a.sbn, a.sbk, n0, a.N, kbeg, tid);
+    float4 ra[4], rb[4];
+    // row sums of A over this workgroup's k range, of the fp32 values before the split, in mfma_bgemm_kernel's order.  They read the
+    // registers x3_park splits next, so every addition is a scalar-f32 one pinned to its register like x3_split's residual (unpinned,
+    // the compiler packs them into v_pk_add_f32 right in front of the convert / subtract / convert sequence)
+    const bool do_sum = a.asum != nullptr && tn_ == 0;
+    float rs[4] = {0.f, 0.f, 0.f, 0.f};
+    auto add_rows = [&]() {
+        if constexpr (AKF) {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                float s0 = ra[it].x + ra[it].y, s1 = ra[it].z + ra[it].w;
+                asm volatile("" : "+v"(s0)); asm volatile("" : "+v"(s1));
+                s0 += s1; asm volatile("" : "+v"(s0));
+                rs[it] += s0; asm volatile("" : "+v"(rs[it]));
+            }
+        } else {
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                // (a pin behind each sum alone left the first two additions of a call packed: the addends are pinned as well)
+                float x = ra[it].x, y = ra[it].y, z = ra[it].z, w = ra[it].w;
+                asm volatile("" : "+v"(x)); rs[0] += x; asm volatile("" : "+v"(rs[0]));
+                asm volatile("" : "+v"(y)); rs[1] += y; asm volatile("" : "+v"(rs[1]));
+                asm volatile("" : "+v"(z)); rs[2] += z; asm volatile("" : "+v"(rs[2]));
+                asm volatile("" : "+v"(w)); rs[3] += w; asm volatile("" : "+v"(rs[3]));
+            }
+        }
+    };
+    if (kbeg < kend) {
+        oa.fetch(ra); ob.fetch(rb);
+        if (do_sum) add_rows();
+        x3_park<AKF>(plane(0, 0), plane(0, 1), ra, tid);
+        x3_park<BKF>(plane(0, 2), plane(0, 3), rb, tid);
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int k0 = kbeg; k0 < kend; k0 += BG_BK) {
+        const bool more = k0 + BG_BK < kend;
+        if (more) { oa.fetch(ra); ob.fetch(rb); }       // in flight under this stage's MFMAs; first touched by x3_park() below
+        const Plane Ah = plane(cur, 0), Al = plane(cur, 1), Bh = plane(cur, 2), Bl = plane(cur, 3);
+        bf16x8 ah[4], al[4], bh[4], bl[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            ah[i] = *reinterpret_cast<const bf16x8*>(&Ah[wm + 16 * i + r16][8 * g]);
+            al[i] = *reinterpret_cast<const bf16x8*>(&Al[wm + 16 * i + r16][8 * g]);
+            bh[i] = *reinterpret_cast<const bf16x8*>(&Bh[wn + 16 * i + r16][8 * g]);
+            bl[i] = *reinterpret_cast<const bf16x8*>(&Bl[wn + 16 * i + r16][8 * g]);
+        }
+        // per accumulator lo*hi, then hi*lo, then hi*hi; the sixteen accumulators of one term are independent
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);              // nothing of x3_park() (its waits for the loads) moves above the MFMAs
+        if (more) {
+            if (do_sum) add_rows();
+            x3_park<AKF>(plane(cur ^ 1, 0), plane(cur ^ 1, 1), ra, tid);
+            x3_park<BKF>(plane(cur ^ 1, 2), plane(cur ^ 1, 3), rb, tid);
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    if (do_sum) bg_fold_row_sums<AKF>(a, rs, reinterpret_cast<float*>(smem), partial, m0, zsplit, tid);
+    bg_epilogue(a, acc, partial, reinterpret_cast<float*>(smem), m0, n0, tid, zsplit);
+}
+
 // Both operands bf16 shadows with k contiguous (the forward products x W^T of the encoder, and dX = dY W through the transposed
 // weight shadow): 64 of K per stage — a row of a stage is 128 bytes, one whole cache line per row and request, where a 32-deep stage of
 // bf16 would use half of every line it pulls into the CU's L1 — loaded as 16-byte pieces and parked in LDS as they are (no conversion,

@@ -89,13 +89,18 @@ def loss_denominator(labels, num_perms: int) -> int:
     return (chars + len(labels)) * min(num_perms, 2) + chars * max(num_perms - 2, 0)
 
 
+_TRAIN_PRECISIONS = {'fp32': _native.PARSEQ_F32, 'bf16': _native.PARSEQ_BF16, 'bf16x3': _native.PARSEQ_BF16X3}
+
+
 def _set_train_precision(system, native):
-    """`system.train_precision`: 'fp32' (default; exact products, the gradient-parity gate) or 'bf16' (GEMM operands rounded to
-    bfloat16, fp32 accumulate and master weights — the reference trains `bf16-mixed`, train.py:62-64)."""
+    """`system.train_precision`: 'fp32' (default; exact products, the gradient-parity gate), 'bf16' (GEMM operands rounded to
+    bfloat16, fp32 accumulate and master weights — the reference trains `bf16-mixed`, train.py:62-64) or 'bf16x3' (the operands of
+    every Linear product split into bf16 pairs hi = bf16(v), lo = bf16(v - hi) and multiplied as lo*hi + hi*lo + hi*hi on the bf16
+    matrix cores: the fp32 mode's gradients to within its own gate; attention and everything else exactly as in 'fp32')."""
     mode = getattr(system, 'train_precision', 'fp32')
-    if mode not in ('fp32', 'bf16'):
-        raise ValueError(f"train_precision must be 'fp32' or 'bf16', got {mode!r}")
-    _native.check(_native.lib().parseq_model_set_train_precision(native, _native.PARSEQ_BF16 if mode == 'bf16' else _native.PARSEQ_F32))
+    if mode not in _TRAIN_PRECISIONS:
+        raise ValueError(f"train_precision must be 'fp32', 'bf16' or 'bf16x3', got {mode!r}")
+    _native.check(_native.lib().parseq_model_set_train_precision(native, _TRAIN_PRECISIONS[mode]))
 
 
 class _PinnedStaging:
@@ -276,7 +281,9 @@ def loss_and_grads(system, images: Tensor, labels, perms: Optional[Tensor] = Non
     """Loss and the gradient of EVERY parameter for one batch — the state `loss.backward()` leaves after the reference's
     `training_step` (system.py:168-199), dropout off.  `images`: fp32 [B, 3, H, W] on the device, normalised.  Everything is enqueued on
     the CURRENT stream (`inputs`: prepared ahead by the caller — loss_and_grads_micro).  A ViTSTR system takes its own step
-    (_vitstr_loss_and_grads: no permutations, no dropout)."""
+    (_vitstr_loss_and_grads: no permutations, no dropout).  `system.train_precision` picks the arithmetic of the Linear products:
+    'fp32' exact, 'bf16' operands rounded to bfloat16, 'bf16x3' operands split into bf16 (hi, lo) pairs and three bf16 MFMAs per
+    product — the fp32 mode's gradients within its own gate, on the bf16 matrix cores (_set_train_precision)."""
     if is_vitstr(system):
         if perms is not None or inputs is not None or dropout:
             raise ValueError('ViTSTR has no permutations, decoder inputs or dropout')
@@ -372,7 +379,8 @@ class TrainStep:
     """The per-batch work of `Trainer.fit` on the reference's configuration (base.py:98-110, configs/main.yaml:33-41): forward and
     backward of `training_step`, gradient averaging across ranks (what DDP does), gradient-norm clipping, one AdamW update under
     the OneCycle schedule — all on the device, no host synchronisation inside a step.  Epoch loops, checkpoints, logging and
-    SWA are the framework's business and stay outside."""
+    SWA are the framework's business and stay outside.  The arithmetic of the step's Linear products is `system.train_precision`
+    ('fp32', 'bf16' or 'bf16x3': _set_train_precision), read at every step."""
 
     def __init__(self, system, total_steps: int, lr: Optional[float] = None, weight_decay: Optional[float] = None,
                  warmup_pct: Optional[float] = None, clip_val: float = 20.0, betas=(0.9, 0.999), eps: float = 1e-8,

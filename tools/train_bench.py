@@ -4,7 +4,8 @@ forward + backward + gradient averaging across ranks + clip + AdamW, synthetic c
 
 Not the headline metric (bench.py measures that); same protocol: W warm-up steps, K timed steps bracketed by a barrier and a
 device synchronise, max over ranks, one JSON line from rank 0.  `--train-precision bf16` (default) rounds the operands of the
-Linear products to bfloat16 (fp32 accumulate, fp32 master weights); `fp32` is the exact-product gate mode.
+Linear products to bfloat16 (fp32 accumulate, fp32 master weights; DESIGN.md section 9); `fp32` is the exact-product gate mode;
+`bf16x3` splits the operands of the Linear products into bf16 pairs (three bf16 MFMAs per product).
 
     python tools/train_bench.py [--batch 384] [--steps 3] [--warmup 1] [--model {parseq,vitstr,parseq-patch16-224}]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/train_bench.py --gpus 8
@@ -23,6 +24,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+DTYPES = {'fp32': 'f32', 'bf16': 'bf16', 'bf16x3': 'split-bf16 products (three bf16 MFMAs), fp32 everywhere else'}
+PRODUCTS = {'fp32': 'exact fp32 on the f32 matrix cores', 'bf16': 'with bf16 operands / fp32 accumulate / fp32 master weights',
+            'bf16x3': 'as split-bf16 products (three bf16 MFMAs), fp32 everywhere else'}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -31,7 +37,8 @@ def main():
     ap.add_argument('--batch', type=int, default=384, help='crops per GPU per step (configs/main.yaml:15)')
     ap.add_argument('--model', default='parseq', choices=['parseq', 'vitstr', 'parseq-patch16-224'],
                     help='vitstr / parseq-patch16-224: 129 / 196 encoder tokens (the key-streaming training attention)')
-    ap.add_argument('--train-precision', default='bf16', choices=['fp32', 'bf16'], help="GEMM operands of the step: exact fp32 products, or rounded to bf16 (fp32 accumulate / master weights)")
+    ap.add_argument('--train-precision', default='bf16', choices=['fp32', 'bf16', 'bf16x3'],
+                    help="GEMM operands of the step: exact fp32 products, rounded to bf16 (fp32 accumulate / master weights), or split into bf16 pairs (three bf16 MFMAs per product)")
     args = ap.parse_args()
     world, rank, local_rank = (int(os.environ.get(k, d)) for k, d in (('WORLD_SIZE', '1'), ('RANK', '0'), ('LOCAL_RANK', '0')))
     dev = torch.device('cuda', local_rank)
@@ -82,11 +89,11 @@ def main():
         print(json.dumps({
             'metric': f'training images/sec ({ih}x{iw} crops) {args.model}' + (', K=6 permutations' if args.model != 'vitstr' else '') + ', AdamW', 'value': round(world * B * args.steps / el, 1),
             'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(1e3 * el / args.steps, 2),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32' if args.train_precision == 'fp32' else 'bf16', 'data': 'synthetic',
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': DTYPES[args.train_precision], 'data': 'synthetic',
             'final_loss': round(float(loss), 4),
             'config': {'workload': f'{args.model} training step, batch={B}/GPU, labels of 1..25 characters (sequence length 26), 6 permutations, '
                                    f'dropout {dict(system.hparams).get("dropout", 0) if system.training else 0} (decoder, 8 sites per pass), Linear products '
-                                   f'{"exact fp32 on the f32 matrix cores" if args.train_precision == "fp32" else "with bf16 operands / fp32 accumulate / fp32 master weights"}, '
+                                   f'{PRODUCTS[args.train_precision]}, '
                                    f'attention / LayerNorm / loss / AdamW fp32 (BASELINE.json configs[4] trains bf16-mixed)',
                        'global_batch': world * B, 'parallelism': f'dp{world}' + (' + RCCL all-reduce of the flat gradient buffer' if world > 1 else '')}}))
     if dist is not None:
