@@ -383,7 +383,7 @@ int parseq_model_set_train_precision(parseq_model* m, int precision);
  *                     parity tests use) and the 64-bit seed of this step's masks.  Eight sites per permutation pass, as in
  *                     the reference (model.py:99-102 embeddings and queries, dropped afresh in every pass; modules.py:33-43,
  *                     70-79 both attentions' probabilities, both projections, the MLP's hidden layer and output).  Masks
- *                     come from a counter-based generator (train_ops.h:drop_factor), not torch's Philox stream: with the
+ *                     come from a counter-based generator (train_rows.h:drop_factor), not torch's Philox stream: with the
  *                     same masks the gradients are exact (tests), against the reference's run they agree in distribution.
  *   loss_out          device fp32 [1 + num_perms]: the loss, then each permutation's mean cross-entropy
  *   grads             device fp32 [parseq_model_grad_elems]: ACCUMULATED into (zero it for a fresh step); encoder slots untouched

@@ -2,7 +2,7 @@
 
 Row N3.  The reference gets its gradients from autograd (`loss.backward()` after strhub/models/parseq/system.py:168-199);
 a HIP implementation has to spell the chain rule out.  This module spells it out ONCE on the CPU, operator by operator and
-in the order the device code launches its kernels (parseq_amd/csrc/train_ops.h, `parseq_train_decoder`), so that
+in the order the device code launches its kernels (parseq_amd/csrc/train_rows.h and train_attn.h, `parseq_train_decoder`), so that
 
   * the derivation itself is checked against autograd through the oracle (tests/test_training.py) with no GPU involved, and
   * every device kernel has a one-line CPU counterpart with identical semantics to be compared with on the GPU.
@@ -77,7 +77,7 @@ def merge_heads(x):                  # [B, H, L, d] -> [B * L, E]
 
 
 def _mix(x):
-    """The 32-bit integer mixer of parseq_amd/csrc/train_ops.h:drop_mix, on int64 tensors holding uint32 values."""
+    """The 32-bit integer mixer of parseq_amd/csrc/train_rows.h:drop_mix, on int64 tensors holding uint32 values."""
     m = 0xFFFFFFFF
     x = x ^ (x >> 16); x = (x * 0x7feb352d) & m
     x = x ^ (x >> 15); x = (x * 0x846ca68b) & m
@@ -85,7 +85,7 @@ def _mix(x):
 
 
 class Dropout:
-    """train_ops.h:DropSpec / drop_factor restated: element idx of site is kept iff hash(seed, site, idx) >= p * 2^32."""
+    """train_rows.h:DropSpec / drop_factor restated: element idx of site is kept iff hash(seed, site, idx) >= p * 2^32."""
 
     def __init__(self, p: float = 0.0, seed: int = 0):
         self.p = p

@@ -46,7 +46,7 @@ E_EPI = 4          # alpha, bias + residual, old C, the final fma
 E_GELU = 8
 GELU_LIP = 1.13    # max |gelu'|
 
-# tile geometry of lib_train.hip / train_ops.h (the plan below mirrors gemm_plan(); the GPU test compares it with the reported route)
+# tile geometry of lib_train.hip / train_gemm.h (the plan below mirrors gemm_plan(); the GPU test compares it with the reported route)
 MG_BM = MG_BN = 128
 MG_BK, BG_BK, BH_BK, SG_BK = 16, 32, 64, 16
 SPLIT_TARGET = 512

@@ -144,6 +144,12 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return fmaf(-u, p * t * e, __builtin_amdgcn_fmed3f(x, 0.0f, __builtin_inff()));      // med3(x, 0, inf) = max(x, 0) in one instruction
 }
 #endif
+// the derivative of the exact-erf GELU (the training step's GEMM epilogues and GELU backward kernels): Phi(v) + v phi(v)
+__device__ __forceinline__ float gelu_grad(float v) {
+    const float cdf = 0.5f * (1.0f + fast_erf(v * 0.70710678118654752440f));
+    const float pdf = __expf(-0.5f * v * v) * 0.39894228040143267794f;
+    return fmaf(v, pdf, cdf);
+}
 
 // GELU for bf16-stored outputs: erf(z) = z * P(z^2) on |z| <= 3.5 (clamped; erf(3.5) = 1 - 7e-7), P of degree 9 from Chebyshev
 // interpolation — 13 full-rate FMAs / MULs that pack into v_pk_fma_f32, no transcendental.  |erf error| <= 7.2e-5,

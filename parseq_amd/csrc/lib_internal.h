@@ -167,7 +167,7 @@ struct parseq_model {
     EncRecordMode enc_record_mode = REC_F32;
     const void* enc_record_ws = nullptr;
     // model constants of the training forward, built on first use: the one-launch encoder's block table (encoder_blocks.h; weight offsets relative
-    // to the workspace's bf16 shadows, parameter offsets into the master) and the table of the one-launch weight-shadow kernel (train_ops.h)
+    // to the workspace's bf16 shadows, parameter offsets into the master) and the table of the one-launch weight-shadow kernel (train_gemm.h)
     EncBlockParams* train_blocks_dev = nullptr;
     void* shadow_tab_dev = nullptr; int shadow_tiles = 0;
     // parseq_train_encoder_backward: one event per gradient segment (parseq_train_grad_segment), recorded on its stream as soon as that

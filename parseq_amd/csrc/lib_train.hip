@@ -1,7 +1,9 @@
 // libparseq_hip.so — the training step.
 #include "lib_internal.h"
 
-#include "train_ops.h"
+#include "train_gemm.h"
+#include "train_rows.h"
+#include "train_attn.h"
 #include "train_attn_wide.h"
 #include "train_vitstr.h"
 
@@ -32,7 +34,7 @@ constexpr int SPLIT_TARGET = 512;      // split-K: how many workgroups a product
 // A product C[M, N] = A B is described by its parts, each of which carries its element type:
 // Operand: where an input matrix lives, its stride along the product's outer axis (m for A, n for B) and along the contraction, both in
 // ELEMENTS of its own type, and whether that type is fp32 or bf16 — constructible from a typed pointer only, so bf16 bytes cannot reach a
-// loader of floats by a cast at a call site.  bf16 operands are the SHADOWS of the bf16-operand mode (train_ops.h SgemmArgs a16 / b16).
+// loader of floats by a cast at a call site.  bf16 operands are the SHADOWS of the bf16-operand mode (train_gemm.h SgemmArgs a16 / b16).
 struct Operand {
     const void* p; long so, sk; bool bf16;
     Operand(const float* q, long outer, long k) : p(q), so(outer), sk(k), bf16(false) {}
@@ -225,7 +227,7 @@ static int lin_bwd(const TrainCtx& cx, const float* x, const float* W, const flo
     }
     return 0;
 }
-// The two backward products on bf16 SHADOW operands (encoder, bf16-operand mode; train_ops.h SgemmArgs): x16 [M, K] and the transposed weight
+// The two backward products on bf16 SHADOW operands (encoder, bf16-operand mode; train_gemm.h SgemmArgs): x16 [M, K] and the transposed weight
 // shadow Wt16 [K, N] are bfloat16 in memory; dy is read as fp32 where it exists (the bias gradient is then summed from the unrounded values) and
 // through its shadow dy16 otherwise — the dX product prefers the shadow; dx16: the result again as bf16 for the next product; dx_gelu_pre16: the
 // pre-activation as bf16.  Bit-identical to lin_bwd on the fp32 copies: the rounding moved, nothing else.
@@ -261,95 +263,104 @@ static int ln_bwd(const TrainCtx& cx, const float* x, const float* gamma, const 
     }
     return launch(colsum_kernel, dim3((2 * E + 63) / 64, 1), dim3(1024), 0, s, part, 2L * E, chunks, 2 * E, dgamma, 1, chunks, dbeta, E);
 }
-// One attention launch of B * heads (or fewer) workgroups: the forward or the backward kernel, both allowed `cap_f` / `cap_b` bytes of dynamic
-// LDS once per device (one LdsAttr pair per pair of kernels)
+// ---- attention -------------------------------------------------------------------------------------------------------------------------
+// Which kernel a training attention call runs and how it is launched.  Routes, first match wins: the two bf16-operand kernels (decoder
+// shapes, the 128-token encoder), the fp32 matrix-core kernel (head width 64, up to 128 keys), the key-streaming kernels past 128
+// tokens (train_attn_wide.h), the VALU kernels; TA_NONE: no kernel.
+enum TrainAttnRoute { TA_DEC_BF16, TA_ENC_BF16, TA_MFMA, TA_WIDE, TA_HD32, TA_HD64, TA_NONE };
+struct TrainAttnPlan { TrainAttnRoute route; dim3 grid; int threads; size_t lds; };
+constexpr size_t TA_LDS_CAP = 150 * 1024;      // what the fp32 kernels may be given of a CU's 160 KiB
+// the shapes train_attn_dec_bf16_kernel takes (bf16-operand mode, head width 32, <= TD_Q queries, <= TD_K keys); train_dec_route asks
+// the same of the cross-attention before there are operands to plan with
+static bool train_attn_dec_bf16_shape(bool bf16_ops, int hd, int Lq, int Lk) { return bf16_ops && hd == TD_HD && Lq <= TD_Q && Lk <= TD_K; }
+// ... and the instantiation by key tiles: up to 128 keys, or for the self-attention the 32-key one (a quarter of the LDS, a third of the registers)
+static int train_attn_dec_kt(const TrainAttnArgs& a) { return a.Lk > 32 ? 8 : 2; }
+// The plan of one call: under each route's match stands everything its kernel asks of the arguments — a field the kernel does not read
+// is refused, not ignored (lse / dsum excepted: the slots of the key-streaming route, which the others leave untouched) — and its
+// capacity, then its grid and LDS bytes (from the function beside the kernel).  out->route is written even when the call is refused.
+static int train_attn_plan(const TrainCtx& cx, const TrainAttnArgs& a, int hd, int B, bool backward, TrainAttnPlan* out) {
+    const bool rows4 = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv)));
+    const bool plain = !a.qmask && !a.kmask && !a.drop.thresh;      // no masks, no dropout
+    // what a route answers whose kernel walks one pass per launch / writes fp32 only / keeps all keys resident
+    auto no_pass_loop = [&] { return a.pass_loop > 1 ? fail(PARSEQ_E_INVALID, "training attention: pass_loop is train_attn_dec_bf16_kernel's alone") : 0; };
+    auto one_pass = [&] {
+        CHK(no_pass_loop());
+        return a.pass_B ? fail(PARSEQ_E_INVALID, "training attention: several passes per launch only at the decoder's head width") : 0;
+    };
+    auto fp32_out = [&] { return (a.o16 || a.dq16 || a.dk16 || a.dv16) ? fail(PARSEQ_E_INVALID, "training attention: a bf16 output is only written by the encoder-shaped bf16 kernel") : 0; };
+    auto fits = [&](size_t lds, bool regs) { return (lds > TA_LDS_CAP || !regs) ? fail(PARSEQ_E_INVALID, "training attention: %d keys of width %d do not fit (LDS %zu bytes)", a.Lk, hd, lds) : 0; };
+    TrainAttnPlan& p = *out;
+    p = TrainAttnPlan{TA_NONE, dim3((unsigned)(B * a.H)), 256, 0};      // one workgroup of four waves per (image, head) unless the route says otherwise
+    if (train_attn_dec_bf16_shape(cx.bf16_ops(), hd, a.Lq, a.Lk) && rows4 && a.q_bstride % 4 == 0) {
+        // masks, dropout, shared queries, pass_B with or without kv_shared; pass_loop: one workgroup per (image, head) walks the passes
+        p.route = TA_DEC_BF16;
+        if (a.pass_loop > 1 && !(a.pass_B > 0 && a.kv_shared && B == a.pass_B * a.pass_loop))
+            return fail(PARSEQ_E_INVALID, "training attention: pass_loop needs pass_B, shared K / V and a batch of pass_B * pass_loop images");
+        CHK(fp32_out());
+        p.grid = dim3((unsigned)((a.pass_loop > 1 ? a.pass_B : B) * a.H)); p.threads = 128; p.lds = train_attn_dec_lds(backward, train_attn_dec_kt(a));
+    } else if (cx.bf16_ops() && hd == TB_HD && a.Lq == TB_N && a.Lk == TB_N && plain && a.q_bstride == (long)a.Lq * a.ldq && rows4) {
+        // per-image queries; o16 / dq16 / dk16 / dv16 in place of the fp32 outputs, dk16 and dv16 together and never accumulated into
+        p.route = TA_ENC_BF16;
+        CHK(one_pass());
+        if (!a.dk16 != !a.dv16 || (a.dk16 && a.kv_accumulate)) return fail(PARSEQ_E_INVALID, "training attention: bf16 dK / dV come as a pair and are stored, not accumulated");
+        p.lds = train_attn_bf16_lds(backward);
+    } else if (hd == TM_HD && a.Lq % TM_QB == 0 && a.Lk % 16 == 0 && a.Lk <= TM_K && plain) {
+        // shared or per-image queries
+        p.route = TA_MFMA;
+        CHK(one_pass()); CHK(fp32_out());
+        p.lds = train_attn_mfma_lds(a.Lk, backward);
+        CHK(fits(p.lds, true));
+    } else if (hd == TW_HD && a.Lk > 128 && a.Lk <= TW_MAXN && a.Lq == a.Lk && plain && !a.pass_B && !a.pass_loop && a.q_bstride == (long)a.Lq * a.ldq) {
+        // per-image queries, one pass; the shapes no resident kernel takes (train_attn_kernel<*, 64> holds at most 128 keys)
+        p.route = TA_WIDE;
+        CHK(fp32_out());
+        if (!a.lse || (backward && !a.dsum)) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: no log-sum-exp / row-sum slot", a.Lk);
+        bool ok = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 && aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.o);
+        if (backward) ok = ok && a.d_o && a.dq && a.dk && a.dv && aligned16(a.d_o);
+        if (!ok) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: operands not laid out in 16-byte rows", a.Lk);
+        p.grid = dim3((unsigned)((a.Lk + TW_BLK - 1) / TW_BLK), (unsigned)(B * a.H));
+    } else if (hd == 32 || hd == 64) {
+        // any strides, masks, dropout; pass_B with or without kv_shared at the decoder's head width
+        p.route = hd == 32 ? TA_HD32 : TA_HD64;
+        CHK(hd == TD_HD ? no_pass_loop() : one_pass()); CHK(fp32_out());
+        p.lds = train_attn_lds_floats(a.Lq, a.Lk, hd, backward) * sizeof(float);
+        CHK(fits(p.lds, (size_t)a.Lk * hd <= (size_t)TA_NACC * 256));
+    } else return fail(PARSEQ_E_INVALID, "training attention: head width %d not in {32, 64}", hd);
+    return 0;
+}
+// One launch of a pair of kernels, forward or backward, both allowed `cap_f` / `cap_b` bytes of dynamic LDS once per device (one LdsAttr
+// pair per pair of kernels): the one place that raises the attribute
 using AttnKernel = void (*)(const TrainAttnArgs);
 template <AttnKernel FWD, AttnKernel BWD>
-static int attn_launch(const TrainCtx& cx, const TrainAttnArgs& a, bool backward, int blocks, int threads, size_t cap_f, size_t cap_b, size_t lds) {
+static int attn_launch(const TrainCtx& cx, const TrainAttnArgs& a, bool backward, const TrainAttnPlan& p, size_t cap_f, size_t cap_b) {
     static LdsAttr attr_f, attr_b;
     HIPCHK(attr_f.ensure(reinterpret_cast<const void*>(FWD), cap_f));
     HIPCHK(attr_b.ensure(reinterpret_cast<const void*>(BWD), cap_b));
-    hipLaunchKernelGGL(backward ? BWD : FWD, dim3(blocks), dim3(threads), lds, cx.s, a);
+    hipLaunchKernelGGL(backward ? BWD : FWD, p.grid, dim3(p.threads), p.lds, cx.s, a);
     HIPCHK(hipGetLastError());
     return 0;
 }
-template <int HD>
-static int train_attn_hd(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    const size_t lds = train_attn_lds_floats(a.Lq, a.Lk, HD, backward) * sizeof(float);
-    if (lds > 150 * 1024 || (size_t)a.Lk * HD > (size_t)TA_NACC * 256)
-        return fail(PARSEQ_E_INVALID, "training attention: %d keys of width %d do not fit (LDS %zu bytes)", a.Lk, HD, lds);
-    return attn_launch<train_attn_kernel<false, HD>, train_attn_kernel<true, HD>>(cx, a, backward, B * a.H, 256, 150 * 1024, 150 * 1024, lds);
-}
-// encoder shape on the matrix cores (train_attn_mfma_kernel): head width 64, whole 32-row query blocks and 16-key tiles, no masks
-static int train_attn_mfma(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    const size_t lds = ((size_t)2 * a.Lk * 65 + (size_t)(backward ? 2 : 1) * 32 * 65 + (size_t)(backward ? 2 : 1) * 32 * (a.Lk + 1)) * sizeof(float);
-    return attn_launch<train_attn_mfma_kernel<false>, train_attn_mfma_kernel<true>>(cx, a, backward, B * a.H, 256, 150 * 1024, 150 * 1024, lds);
-}
-// encoder shape in the bf16-operand mode (train_attn_bf16_kernel): 128 tokens, head width 64, per-image queries, no masks, no dropout
-static int train_attn_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    return attn_launch<train_attn_bf16_kernel<false>, train_attn_bf16_kernel<true>>(cx, a, backward, B * a.H, 256, train_attn_bf16_lds(false),
-                                                                                    train_attn_bf16_lds(true), train_attn_bf16_lds(backward));
-}
-// decoder shapes in the bf16-operand mode (train_attn_dec_bf16_kernel): head width 32, <= 32 queries, <= 128 keys, masks, dropout
 template <int KT>
-static int train_attn_dec_bf16_kt(const TrainCtx& cx, const TrainAttnArgs& a, int blocks, bool backward) {
-    return attn_launch<train_attn_dec_bf16_kernel<false, KT>, train_attn_dec_bf16_kernel<true, KT>>(cx, a, backward, blocks, 128, train_attn_dec_lds(false, KT),
-                                                                                                    train_attn_dec_lds(true, KT), train_attn_dec_lds(backward, KT));
+static int attn_launch_dec(const TrainCtx& cx, const TrainAttnArgs& a, bool backward, const TrainAttnPlan& p) {
+    return attn_launch<train_attn_dec_bf16_kernel<false, KT>, train_attn_dec_bf16_kernel<true, KT>>(cx, a, backward, p, train_attn_dec_lds(false, KT), train_attn_dec_lds(true, KT));
 }
-static int train_attn_dec_bf16(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    if (a.pass_loop > 1 && !(a.pass_B > 0 && a.kv_shared && B == a.pass_B * a.pass_loop))
-        return fail(PARSEQ_E_INVALID, "training attention: pass_loop needs pass_B, shared K / V and a batch of pass_B * pass_loop images");
-    const int blocks = (a.pass_loop > 1 ? a.pass_B : B) * a.H;      // pass_loop: one workgroup per (image, head) walks the passes
-    // up to 128 keys, or for the self-attention the 32-key instantiation (a quarter of the LDS, a third of the registers)
-    return a.Lk > 32 ? train_attn_dec_bf16_kt<8>(cx, a, blocks, backward) : train_attn_dec_bf16_kt<2>(cx, a, blocks, backward);
-}
-// the shapes train_attn_dec_bf16_kernel takes (bf16-operand mode, head width 32, <= TD_Q queries, <= TD_K keys); the decoder's workspace
-// layout asks the same question of its cross-attention (train_decoder_layout's ca_loop)
-static bool train_attn_dec_bf16_shape(bool bf16_ops, int hd, int Lq, int Lk) { return bf16_ops && hd == TD_HD && Lq <= TD_Q && Lk <= TD_K; }
-// encoder self-attention past 128 tokens (train_attn_wide.h): head width 64, N in (128, 256], per-image queries, no masks, no dropout,
-// one pass per launch — the shapes no kernel above takes (train_attn_hd<64> holds at most 128 keys)
-static bool train_attn_is_wide(const TrainAttnArgs& a, int hd) {
-    return hd == TW_HD && a.Lk > 128 && a.Lk <= TW_MAXN && a.Lq == a.Lk && !a.qmask && !a.kmask && !a.drop.thresh && !a.pass_B && !a.pass_loop &&
-           a.q_bstride == (long)a.Lq * a.ldq;
-}
-static int train_attn_wide(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward) {
-    if (!a.lse || (backward && !a.dsum)) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: no log-sum-exp / row-sum slot", a.Lk);
-    bool ok = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && a.q_bstride % 4 == 0 && aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && aligned16(a.o);
-    if (backward) ok = ok && a.d_o && a.dq && a.dk && a.dv && aligned16(a.d_o);
-    if (!ok) return fail(PARSEQ_E_INVALID, "training attention over %d tokens: operands not laid out in 16-byte rows", a.Lk);
-    const dim3 grid((unsigned)((a.Lk + TW_BLK - 1) / TW_BLK), (unsigned)(B * a.H));
-    if (!backward) return launch(train_attn_wide_fwd_kernel, grid, dim3(256), 0, cx.s, a);
-    CHK(launch(train_attn_wide_dq_kernel, grid, dim3(256), 0, cx.s, a));
-    return launch(train_attn_wide_dkv_kernel, grid, dim3(256), 0, cx.s, a);
-}
-// Which kernel a training attention call runs, first match wins: the two bf16-operand kernels (decoder shapes, the 128-token encoder), the
-// fp32 matrix-core kernel (head width 64, up to 128 keys), the key-streaming kernels past 128 tokens, the VALU kernels; TA_NONE: no kernel
-enum TrainAttnRoute { TA_DEC_BF16, TA_ENC_BF16, TA_MFMA, TA_WIDE, TA_HD32, TA_HD64, TA_NONE };
-static TrainAttnRoute train_attn_route(const TrainCtx& cx, const TrainAttnArgs& a, int hd, bool backward) {
-    const bool rows4 = a.ldq % 4 == 0 && a.ldkv % 4 == 0 && a.ldo % 4 == 0 && (!backward || (a.lddq % 4 == 0 && a.lddkv % 4 == 0 && aligned16(a.dk) && aligned16(a.dv)));
-    if (train_attn_dec_bf16_shape(cx.bf16_ops(), hd, a.Lq, a.Lk) && rows4 && a.q_bstride % 4 == 0) return TA_DEC_BF16;
-    if (cx.bf16_ops() && hd == TB_HD && a.Lq == TB_N && a.Lk == TB_N && !a.qmask && !a.kmask && !a.drop.thresh && a.q_bstride == (long)a.Lq * a.ldq && rows4)
-        return TA_ENC_BF16;
-    if (hd == 64 && a.Lq % 32 == 0 && a.Lk % 16 == 0 && a.Lk <= 128 && !a.qmask && !a.kmask && !a.drop.thresh) return TA_MFMA;
-    if (train_attn_is_wide(a, hd)) return TA_WIDE;
-    if (hd == 32) return TA_HD32;
-    if (hd == 64) return TA_HD64;
-    return TA_NONE;
-}
-static int train_attn(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward, int hd) {
-    const TrainAttnRoute r = train_attn_route(cx, a, hd, backward);
-    if (r == TA_DEC_BF16) return train_attn_dec_bf16(cx, a, B, backward);
-    if (a.pass_loop > 1) return fail(PARSEQ_E_INVALID, "training attention: pass_loop is train_attn_dec_bf16_kernel's alone");
-    if (a.pass_B && hd != TD_HD) return fail(PARSEQ_E_INVALID, "training attention: several passes per launch only at the decoder's head width");
-    if (r == TA_ENC_BF16) return train_attn_bf16(cx, a, B, backward);
-    if (a.o16 || a.dq16) return fail(PARSEQ_E_INVALID, "training attention: a bf16 output is only written by the encoder-shaped bf16 kernel");
-    switch (r) {
-        case TA_MFMA: return train_attn_mfma(cx, a, B, backward);
-        case TA_WIDE: return train_attn_wide(cx, a, B, backward);
-        case TA_HD32: return train_attn_hd<32>(cx, a, B, backward);
-        case TA_HD64: return train_attn_hd<64>(cx, a, B, backward);
-        default: return fail(PARSEQ_E_INVALID, "training attention: head width %d not in {32, 64}", hd);
+// Plan, then launch; `took`: the route, also of a call that was refused
+static int train_attn(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool backward, int hd, TrainAttnRoute* took = nullptr) {
+    TrainAttnPlan p;
+    const int rc = train_attn_plan(cx, a, hd, B, backward, &p);
+    if (took) *took = p.route;
+    CHK(rc);
+    switch (p.route) {
+        case TA_DEC_BF16: return train_attn_dec_kt(a) == 8 ? attn_launch_dec<8>(cx, a, backward, p) : attn_launch_dec<2>(cx, a, backward, p);
+        case TA_ENC_BF16: return attn_launch<train_attn_bf16_kernel<false>, train_attn_bf16_kernel<true>>(cx, a, backward, p, train_attn_bf16_lds(false), train_attn_bf16_lds(true));
+        case TA_MFMA: return attn_launch<train_attn_mfma_kernel<false>, train_attn_mfma_kernel<true>>(cx, a, backward, p, TA_LDS_CAP, TA_LDS_CAP);
+        case TA_HD32: return attn_launch<train_attn_kernel<false, 32>, train_attn_kernel<true, 32>>(cx, a, backward, p, TA_LDS_CAP, TA_LDS_CAP);
+        case TA_HD64: return attn_launch<train_attn_kernel<false, 64>, train_attn_kernel<true, 64>>(cx, a, backward, p, TA_LDS_CAP, TA_LDS_CAP);
+        default: break;      // TA_WIDE: static LDS, and the backward is two launches (dQ writes the row sums that dK / dV read)
     }
+    if (!backward) return launch(train_attn_wide_fwd_kernel, p.grid, dim3(p.threads), 0, cx.s, a);
+    CHK(launch(train_attn_wide_dq_kernel, p.grid, dim3(p.threads), 0, cx.s, a));
+    return launch(train_attn_wide_dkv_kernel, p.grid, dim3(p.threads), 0, cx.s, a);
 }
 
 // The training step's encoder attention on its own (the kernels' unit test): the self-attention of `tokens` tokens, `heads` heads of 64,
@@ -364,8 +375,10 @@ extern "C" int parseq_op_train_attention(const float* qkv, float* o, float* lse,
     a.o = o; a.ldo = E; a.d_o = d_o; a.dq = dqkv; a.lddq = 3 * E; a.dk = dqkv ? dqkv + E : nullptr; a.dv = dqkv ? dqkv + 2 * E : nullptr;
     a.lddkv = 3 * E; a.Lq = tokens; a.Lk = tokens; a.H = heads; a.scale = 1.0f / sqrtf((float)TW_HD); a.lse = lse; a.dsum = dsum;
     const TrainCtx cx{(hipStream_t)stream, nullptr, PARSEQ_F32, 0};
-    if (route) *route = train_attn_route(cx, a, TW_HD, backward != 0) == TA_WIDE ? 1 : 0;
-    return train_attn(cx, a, batch, backward != 0, TW_HD);
+    TrainAttnRoute took = TA_NONE;
+    const int rc = train_attn(cx, a, batch, backward != 0, TW_HD, &took);
+    if (route) *route = took == TA_WIDE ? 1 : 0;
+    return rc;
 }
 
 
@@ -453,8 +466,9 @@ static TrainDecRoute train_dec_route(const parseq_model* m, int L, int K) {
     if (const char* e = getenv("PARSEQ_TRAIN_PERM_GROUP")) { const int v = atoi(e); if (v >= 1) g = v; }
     r.KP = std::min(std::max(g, 1), K);
     const int E = m->cfg.embed_dim;
+    // the shape question only (rows of E = dec_heads * 32 floats are 16-byte rows); parseq_train_decoder asks the plan itself once the operands exist
     r.ca_loop = r.KP > 1 && E == m->cfg.dec_heads * TD_HD && train_attn_dec_bf16_shape(m->train_precision == PARSEQ_BF16, TD_HD, L, m->tokens) &&
-                E % 4 == 0 && !getenv("PARSEQ_TRAIN_NO_PASS_LOOP");
+                !getenv("PARSEQ_TRAIN_NO_PASS_LOOP");
     return r;
 }
 
@@ -549,7 +563,7 @@ extern "C" size_t parseq_train_decoder_workspace_bytes(const parseq_model* m, in
     return train_decoder_layout(m, batch, ctx_len, num_perms, train_dec_route(m, ctx_len, num_perms)).total * sizeof(float);
 }
 
-// y = R + dropout(x) over `passes` passes of n_pass elements each (train_ops.h dropout_passes_kernel: R may be null, x == y allowed,
+// y = R + dropout(x) over `passes` passes of n_pass elements each (train_rows.h dropout_passes_kernel: R may be null, x == y allowed,
 // x_shared: one pass of x read by every pass); with dropout off a plain add / copy
 static int dropout_add(const TrainCtx& cx, const float* x, bool x_shared, const float* R, float* y, size_t n_pass, int passes, const DropSpec& d, unsigned site) {
     return launch(dropout_passes_kernel, dim3((unsigned)((n_pass + 255) / 256), (unsigned)passes), dim3(256), 0, cx.s, x, x_shared ? 1 : 0, R, y, n_pass, d, site);
@@ -605,14 +619,15 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     ca.q = w + o.q2; ca.q_bstride = (long)L * E; ca.ldq = E; ca.k = w + o.kvm; ca.v = w + o.kvm + E; ca.ldkv = 2 * E; ca.o = w + o.ca_o; ca.ldo = E;
     ca.d_o = w + o.d_c; ca.dq = w + o.d_a; ca.lddq = E; ca.lddkv = 2 * E; ca.Lq = L; ca.Lk = S; ca.H = H; ca.scale = scale;
     // d K | d V: KP == 1: d_kvm_p IS d_kvm and the passes accumulate; otherwise each pass of the batch writes its own copy — or, in the
-    // bf16-operand mode, one workgroup per (image, head) walks the batch's passes (train_ops.h TrainAttnArgs::pass_loop): the memory's K | V are
+    // bf16-operand mode, one workgroup per (image, head) walks the batch's passes (train_attn.h TrainAttnArgs::pass_loop): the memory's K | V are
     // staged once per batch instead of once per pass and d K | d V go straight into d_kvm (which d_kvm_p then names too), summed over the
     // passes in the accumulators
     ca.dk = w + o.d_kvm_p; ca.dv = w + o.d_kvm_p + E; ca.kv_accumulate = KP == 1 ? 1 : 0;
     ca.drop = drop;
     ca.pass_B = B; ca.qmask_pstride = 0; ca.site_pstride = 8; ca.kv_shared = 1;
     // the route (and with it the layout, which then has no per-pass copies) chose the pass-walking kernel; the kernel's own preconditions must agree
-    if (ca_loop && train_attn_route(cx, ca, 32, true) != TA_DEC_BF16) return fail(PARSEQ_E_STATE, "training decoder: the workspace was laid out for the pass-walking cross-attention, which this call cannot run (its operands are not aligned for it)");
+    TrainAttnPlan ca_plan;      // consulted for its route alone (pass_loop is set per batch below); a refusal by the plan is answered with the message here
+    if (ca_loop && (train_attn_plan(cx, ca, 32, KP * B, true, &ca_plan) != 0 || ca_plan.route != TA_DEC_BF16)) return fail(PARSEQ_E_STATE, "training decoder: the workspace was laid out for the pass-walking cross-attention, which this call cannot run (its operands are not aligned for it)");
     enum { S_CONTENT, S_QUERY, S_SA_PROB, S_SA_OUT, S_CA_PROB, S_CA_OUT, S_FF_HIDDEN, S_FF_OUT };      // dropout sites of one pass
 
     for (int i0 = 0; i0 < K; i0 += KP) {
@@ -713,7 +728,7 @@ struct TrainEncoderLayout {          // offsets in floats
                                              // 150 MB passes per block; the record grows from 10 E to 16 E floats per token per block)
 };
 // How a training encoder call runs, decided once per call (on every call: the switches may change between two steps of one process):
-//   shadows      bf16 shadow operands for the encoder's products (train_ops.h SgemmArgs): the bf16-operand mode at the shapes the bf16
+//   shadows      bf16 shadow operands for the encoder's products (train_gemm.h SgemmArgs): the bf16-operand mode at the shapes the bf16
 //                attention kernel and the 64-deep GEMM take.  The record's n1 / n2 / ao / hact_l slots then hold bf16 (in the first half of
 //                the fp32 slot).  PARSEQ_TRAIN_NO_SHADOWS=1 keeps every operand fp32 in memory (the A/B and the bit-identity test).
 //   bf16_only    level 2 (the default with shadows on): tensors that exist ONLY to be rounded to bf16 by their consumers or to feed a GELU

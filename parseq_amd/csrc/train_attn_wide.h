@@ -1,7 +1,7 @@
 // Encoder attention of the training step past 128 tokens (ViTSTR: 129, PARSeq-patch16-224: 196; any N in (128, 256]), head width 64,
 // non-causal, no masks, no dropout, fp32 operands in both training precisions.
 //
-// The kernels of train_ops.h keep a head's whole K / V (and, backward, its dK / dV) resident: in LDS that stops fitting at ~200 keys and
+// The kernels of train_attn.h keep a head's whole K / V (and, backward, its dK / dV) resident: in LDS that stops fitting at ~200 keys and
 // in registers at 128.  Here the keys stream through LDS in 32-key tiles:
 //   forward   one workgroup per (32-query block, image, head): S = Q K^T tile by tile, online soft-max, O = P V accumulated in
 //             registers; writes O and each query row's log-sum-exp lse = max + log(sum) of the scaled scores ([B, H, N], `a.lse`).
@@ -15,7 +15,7 @@
 // feeds A[row r16][k g] and B[k g][col r16] and receives D[row 4 g + r][col r16], r = 0..3.
 #pragma once
 
-#include "train_ops.h"
+#include "train_attn.h"
 
 constexpr int TW_HD = 64, TW_BLK = 32, TW_MAXN = 256;
 constexpr int TW_PAD = TW_HD + 1;        // [row][d] images

@@ -2,7 +2,7 @@
 // the encoder, the row gathers of the patch-embedding gradient and of the per-token head.  One workgroup per output row, E columns.
 #pragma once
 
-#include "train_ops.h"
+#include "common.h"
 
 // timm VisionTransformer._pos_embed: x[b, 0] = cls + pos[0], x[b, 1 + p] = proj[b, p] + pos[1 + p]   (proj: [B * (S - 1), E], bias included)
 static __global__ __launch_bounds__(256)

@@ -1,4 +1,4 @@
-"""train_precision = 'bf16x3' on the device: the split-bf16 products of the training step (train_ops.h mfma_x3gemm_kernel) one operator
+"""train_precision = 'bf16x3' on the device: the split-bf16 products of the training step (train_gemm.h mfma_x3gemm_kernel) one operator
 at a time through parseq_op_train_gemm / parseq_op_train_linear, and whole steps against the goldens and the library's own fp32 mode.
 
 Operator level: the harness of tests/test_train_gemm.py (NaN tails behind operands, NaN-filled outputs between NaN guards, the route

@@ -783,7 +783,7 @@ def test_overlapped_allreduce_step_equals_the_plain_step():
 @pytest.mark.gpu
 def test_bf16_operand_step_within_the_rounding_budget():
     """system.train_precision = 'bf16' (parseq_model_set_train_precision: both operands of every aligned Linear product rounded to
-    bfloat16, fp32 accumulate, fp32 everything else — train_ops.h mfma_bgemm_kernel) on the batch-64 step whose Linears all take the
+    bfloat16, fp32 accumulate, fp32 everything else — train_gemm.h mfma_bgemm_kernel) on the batch-64 step whose Linears all take the
     matrix-core path: loss and all 175 gradients against the EXACT fp32 CPU backward, within the budget
     test_bf16_operand_rounding_budget measured for this rounding (loss 5e-4 relative, per-tensor L2 error <= 6e-2, cosine >= 0.998) —
     and visibly not the fp32 path (median per-tensor error above 1e-4)."""
@@ -831,7 +831,7 @@ def test_bf16_operand_step_within_the_rounding_budget():
 def test_bf16_shadow_operands_change_no_bit():
     """Round 3: in the bf16-operand mode the encoder's activations that only feed Linear products (LayerNorm outputs, attention output,
     GELU output), the Linear weights and the gradients on the dX side are WRITTEN as bfloat16 by their producers and read by the
-    64-deep matrix-core GEMM (train_ops.h mfma_bgemm16_kernel / the B16 forms of mfma_bgemm_kernel).  That is the same
+    64-deep matrix-core GEMM (train_gemm.h mfma_bgemm16_kernel / the B16 forms of mfma_bgemm_kernel).  That is the same
     round-to-nearest-even the fp32-in-memory path applies on the way into LDS, in the same accumulation order: loss and every one of
     the 175 gradients must be bit-identical with PARSEQ_TRAIN_NO_SHADOWS=1 (every operand fp32 in memory)."""
     import os

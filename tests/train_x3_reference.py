@@ -1,4 +1,4 @@
-"""Float64 references of the training step's SPLIT-bf16 products (train_precision = 'bf16x3', train_ops.h mfma_x3gemm_kernel), with
+"""Float64 references of the training step's SPLIT-bf16 products (train_precision = 'bf16x3', train_gemm.h mfma_x3gemm_kernel), with
 derived bounds on the device's error, on top of oracle/train_gemm_ref.py (cases, inputs, constants and riders are its own).
 
 The kernel splits every fp32 operand element v on its way into LDS into hi = bf16_rne(v) and lo = bf16_rne(v - hi) (the subtraction is

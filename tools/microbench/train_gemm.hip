@@ -1,4 +1,4 @@
-// The training step's all-bf16 products (train_ops.h mfma_bgemm16_kernel: both operands bf16 and k-contiguous in memory) timed ALONE, without
+// The training step's all-bf16 products (train_gemm.h mfma_bgemm16_kernel: both operands bf16 and k-contiguous in memory) timed ALONE, without
 // torch, on the encoder's shapes — to separate a tile's fixed cost (prologue + epilogue) from its per-stage cost and the stores from the rest:
 //   * K sweep at fixed M x N (K = 64 is ONE 64-deep stage): T(K) = fixed + per-stage * K / 64;
 //   * epilogue forms: no store at all (C = c16 = nullptr), bf16 only, fp32 only, fp32 + bf16, bf16 pre-activation + bf16 GELU (fc1's form);
@@ -13,7 +13,7 @@
 #include <vector>
 #include "common.h"
 #include "rowops.h"
-#include "train_ops.h"
+#include "train_gemm.h"
 using namespace pq;
 
 // mfma_bgemm16_kernel<true> again with pieces cut out (MODE): 0 whole, 1 no epilogue, 2 no main loop (epilogue of zeros), 3 empty kernel,
