@@ -418,6 +418,16 @@ int parseq_train_encoder_forward(parseq_model* m, const float* images, int batch
 int parseq_train_encoder_backward(parseq_model* m, const float* dmemory, int batch, float* grads, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* (added under ABI 15: a pure addition, no existing entry or structure changes, so the version number stays)
+ * parseq_train_encoder_forward with the images' type as an argument: PARSEQ_F32 is the entry above, PARSEQ_U8 takes the raw pixels
+ * [batch, 3, H, W] that parseq_resize_bicubic / parseq_augment_resize_bicubic write and normalises them inside the im2col
+ * (ToTensor + Normalize(0.5, 0.5), strhub/data/module.py:78-81) — the three element-wise passes over a float image that a caller would
+ * otherwise make disappear.  u8_table: NULL, or device fp32 [256] = the normalised value of every byte as the CALLER computes it; the
+ * patch rows are then bit for bit the rows of the fp32 entry on table[image].  NULL = ((v / 255) - 0.5) / 0.5 in IEEE fp32, what the
+ * inference loaders apply.  The image pointer should be patch_w-aligned (8- / 16-byte loads; otherwise the bytes are read one by one). */
+int parseq_train_encoder_forward_ex(parseq_model* m, const void* images, int images_dtype, const float* u8_table, int batch,
+                                    float* memory_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* (ABI 10) ViTSTR's training step (strhub/models/vitstr/system.py:75-79 -> base.py:194-204 forward_logits_loss): the encoder entries
  * above take a ViTSTR model too (class token + pos_embed over tokens + 1 rows; the gradient of cls_token, pos_embed and patch_embed
  * ACCUMULATED into `grads`); in between, this entry computes the head on token rows 1 .. T of every image of `memory`
@@ -471,6 +481,19 @@ int parseq_adamw_step(parseq_model* m, const float* grads, float* exp_avg, float
                       void* stream);
 int parseq_model_get_param(const parseq_model* m, const char* key, float* device_ptr, int64_t numel, void* stream);
 int parseq_model_get_params(parseq_model* m, float* const* device_ptrs, int count, void* stream);
+
+/* Stochastic weight averaging (added under ABI 15, pure additions; the reference's train.py:93-95 switches Lightning's callback on, whose
+ * average is torch.optim.swa_utils.AveragedModel's default rule), over flat buffers laid out like the master weights / the gradients:
+ *   parseq_weights_average     avg <- weights when n_averaged == 0, else avg <- avg + (weights - avg) / (n_averaged + 1), over the
+ *                              model's parseq_model_grad_elems master weights; avg: caller-owned device fp32 of that length.  One
+ *                              launch, deterministic, IEEE subtraction / division / addition per element.
+ *   parseq_op_weights_average  the same over any two device buffers of n floats (the single operator, for tests)
+ *   parseq_model_set_params    the master weights <- flat (device fp32 [parseq_model_grad_elems]): how the average becomes the model at the
+ *                              end of training; the flat mirror of parseq_model_get_params.  As after parseq_adamw_step, plans built on
+ *                              the model must be refreshed (parseq_plan_refresh) before the next inference call. */
+int parseq_weights_average(parseq_model* m, float* avg, int64_t n_averaged, void* stream);
+int parseq_op_weights_average(const float* weights, float* avg, int64_t n, int64_t n_averaged, void* stream);
+int parseq_model_set_params(parseq_model* m, const float* flat, void* stream);
 
 /* ---- single operators, exported so each kernel is parity-tested through the C ABI ------------------------------- */
 

@@ -129,6 +129,7 @@ SIGNATURES = {
                                        C.c_int, C.c_float, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_train_encoder_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int]),
     'parseq_train_encoder_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_train_encoder_forward_ex': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_train_encoder_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_train_vitstr_head_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     'parseq_train_vitstr_head': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -142,6 +143,9 @@ SIGNATURES = {
                                     C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_float, C.c_void_p]),
     'parseq_model_get_param': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p]),
     'parseq_model_get_params': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    'parseq_weights_average': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    'parseq_op_weights_average': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    'parseq_model_set_params': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_op_layernorm': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_void_p]),
     'parseq_op_linear': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -266,7 +270,7 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def guard(device):
     """Context manager making `device` (torch.device or tensor) current: for the raw-pointer entry points (parseq_op_*,
-    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_cross_entropy, parseq_grad_norm), which launch on the current device."""
+    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
     import torch
     if hasattr(device, 'device'):
         device = device.device

@@ -946,9 +946,24 @@ static int enc_block_fwd(const TrainCtx& cx, const parseq_model* m, int batch, c
     return lin_fwd(cx, rec.hact, W.lin[LIN_FC2], W(E_FC2_B), rec.x_mid, MS, rec.x_out, MS, E, F);
 }
 
-extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images, int batch, float* memory_out, void* workspace,
-                                            size_t workspace_bytes, void* stream) {
+// The patch rows of `rows` patches into `out`: fp32 images through patches_kernel, raw uint8 pixels through patches_u8_kernel
+static int train_patches(const parseq_model* m, hipStream_t s, const void* images, int images_dtype, const float* u8_table, int rows, float* out) {
+    const int H = m->cfg.img_h, W = m->cfg.img_w, ph = m->cfg.patch_h, pw = m->cfg.patch_w;
+    if (images_dtype == PARSEQ_F32) return launch(patches_kernel, dim3(rows), dim3(256), 0, s, static_cast<const float*>(images), H, W, ph, pw, out);
+    const uint8_t* img = static_cast<const uint8_t*>(images);
+    const size_t segments = (size_t)rows * 3 * ph;
+    const dim3 grid((unsigned)((segments + 255) / 256));
+    const bool aligned = reinterpret_cast<uintptr_t>(img) % (uintptr_t)pw == 0;
+    if (pw == 8 && aligned) return launch(patches_u8_kernel<8>, grid, dim3(256), 0, s, img, u8_table, H, W, ph, pw, segments, out);
+    if (pw == 16 && aligned) return launch(patches_u8_kernel<16>, grid, dim3(256), 0, s, img, u8_table, H, W, ph, pw, segments, out);
+    return launch(patches_u8_kernel<0>, grid, dim3(256), 0, s, img, u8_table, H, W, ph, pw, segments, out);
+}
+
+static int train_encoder_forward(parseq_model* m, const void* images, int images_dtype, const float* u8_table, int batch, float* memory_out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
     if (!images || !memory_out) return fail(PARSEQ_E_INVALID, "null argument");
+    if (images_dtype != PARSEQ_F32 && images_dtype != PARSEQ_U8)
+        return fail(PARSEQ_E_INVALID, "images_dtype %d: the training encoder takes PARSEQ_F32 or PARSEQ_U8 images", images_dtype);
     CHK(train_encoder_check(m, batch, workspace, workspace_bytes));
     DevGuard dg(m->device);
     const TrainEncoderLayout o = train_encoder_layout(m, batch);
@@ -962,11 +977,11 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
     if (m->vitstr) {
         // S - 1 patch rows per image, S token rows: the class token in front (timm _pos_embed), assembled from the patch product in `tmp`
         const int MP = batch * (S - 1);
-        CHK(launch(patches_kernel, dim3(MP), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches));
+        CHK(train_patches(m, s, images, images_dtype, u8_table, MP, w + o.patches));
         CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), nullptr, 0, w + o.tmp, MP, E, PK));
         CHK(launch(vitstr_tokens_kernel, dim3(MS), dim3(256), 0, s, w + o.tmp, P("cls_token"), P("pos_embed"), w + o.x(0), S, E));
     } else {
-        CHK(launch(patches_kernel, dim3(MS), dim3(256), 0, s, images, m->cfg.img_h, m->cfg.img_w, m->cfg.patch_h, m->cfg.patch_w, w + o.patches));
+        CHK(train_patches(m, s, images, images_dtype, u8_table, MS, w + o.patches));
         CHK(lin_fwd(cx, w + o.patches, P("patch_embed.proj.weight"), P("patch_embed.proj.bias"), P("pos_embed"), S, w + o.x(0), MS, E, PK));
     }
     m->enc_record_mode = r.record();      // what the record's slots hold; the backward entry must read them the same way
@@ -992,6 +1007,14 @@ extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images
         for (int i = 0; i < depth; ++i) CHK(enc_block_fwd(cx, m, batch, enc_block_rec(o, w, i, depth, r), W[i]));
     }
     return run_layernorm<float>(s, w + o.x_last, P("norm.weight"), P("norm.bias"), memory_out, nullptr, MS, E, eps);
+}
+extern "C" int parseq_train_encoder_forward(parseq_model* m, const float* images, int batch, float* memory_out, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return train_encoder_forward(m, images, PARSEQ_F32, nullptr, batch, memory_out, workspace, workspace_bytes, stream);
+}
+extern "C" int parseq_train_encoder_forward_ex(parseq_model* m, const void* images, int images_dtype, const float* u8_table, int batch,
+                                               float* memory_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return train_encoder_forward(m, images, images_dtype, u8_table, batch, memory_out, workspace, workspace_bytes, stream);
 }
 
 // ---- gradient segments: the hook for overlapping the data-parallel all-reduce with the encoder's backward -----------------------------
@@ -1256,6 +1279,30 @@ extern "C" int parseq_adamw_step(parseq_model* m, const float* grads, float* exp
                    beta1, beta2, eps, decay ? weight_decay : 0.f, bc1, bc2_sqrt, grad_norm, max_norm));
         i = j;
     }
+    m->version++;
+    return 0;
+}
+
+// Stochastic weight averaging: one grid-stride launch over the flat buffer (train_rows.h weights_average_kernel)
+extern "C" int parseq_op_weights_average(const float* weights, float* avg, int64_t n, int64_t n_averaged, void* stream) {
+    if (!weights || !avg || n <= 0 || n_averaged < 0) return fail(PARSEQ_E_INVALID, "null / empty argument or a negative count");
+    const int vec = (reinterpret_cast<uintptr_t>(weights) | reinterpret_cast<uintptr_t>(avg)) % 16 == 0;
+    const unsigned blocks = (unsigned)std::min<int64_t>(AVERAGE_BLOCKS, (n + 1023) / 1024);
+    return launch(weights_average_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, weights, avg, (size_t)n, n_averaged == 0 ? 1 : 0,
+                  (float)(n_averaged + 1), vec);
+}
+extern "C" int parseq_weights_average(parseq_model* m, float* avg, int64_t n_averaged, void* stream) {
+    if (!m || !avg) return fail(PARSEQ_E_INVALID, "null argument");
+    CHK(require_params_set(m));
+    DevGuard dg(m->device);
+    return parseq_op_weights_average(m->master, avg, (int64_t)m->master_elems, n_averaged, stream);
+}
+// The whole flat buffer back into the master weights (the averaged weights at the end of training): the mirror of parseq_model_get_params
+extern "C" int parseq_model_set_params(parseq_model* m, const float* flat, void* stream) {
+    if (!m || !flat) return fail(PARSEQ_E_INVALID, "null argument");
+    DevGuard dg(m->device);
+    HIPCHK(hipMemcpyAsync(m->master, flat, m->master_elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    for (ParamSpec& ps : m->params) ps.set = true;
     m->version++;
     return 0;
 }

@@ -405,6 +405,59 @@ void patches_kernel(const float* __restrict__ img, int H, int W, int ph, int pw,
     }
 }
 
+// The same im2col from raw uint8 pixels (parseq_train_encoder_forward_ex, PARSEQ_U8): out = norm[img byte], norm the 256 values of
+// ToTensor + Normalize(0.5, 0.5) (strhub/data/module.py:78-81).  `table` != nullptr: the caller's 256 floats (the Python side builds them
+// with the very torch expression its float path uses, so the switch changes no bit whatever way torch rounds it); nullptr: the IEEE
+// expression of the inference loaders (gemm.h norm_u8).  One thread per patch-row SEGMENT (row, c, ky): its PW bytes are contiguous in the
+// image and its PW floats contiguous in the row, so a lane makes one 8- / 16-byte load and PW / 4 16-byte stores, and consecutive lanes
+// write consecutive segments — there is no column loop to outgrow 256 columns (patch16-224: 48 segments of 16).  PW == 0: any patch width,
+// byte by byte.  The image base must be PW-aligned (W is a multiple of pw, so every segment then is).
+template <int PW>
+static __global__ __launch_bounds__(256)
+void patches_u8_kernel(const uint8_t* __restrict__ img, const float* __restrict__ table, int H, int W, int ph, int pw, size_t segments,
+                       float* __restrict__ out) {
+    __shared__ float norm[256];
+    norm[threadIdx.x] = table ? table[threadIdx.x] : ((float)threadIdx.x / 255.0f - 0.5f) / 0.5f;
+    __syncthreads();
+    const size_t seg = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (seg >= segments) return;
+    const int gw = W / pw, gh = H / ph, per_row = 3 * ph;
+    const size_t row = seg / per_row;
+    const int within = (int)(seg - row * per_row), c = within / ph, ky = within - c * ph;
+    const size_t b = row / ((size_t)gh * gw);
+    const int gy = (int)((row / gw) % gh), gx = (int)(row % gw);
+    const uint8_t* src = img + ((b * 3 + c) * H + (size_t)gy * ph + ky) * W + (size_t)gx * pw;
+    float* dst = out + seg * pw;                                  // row * pk + (c * ph + ky) * pw
+    if constexpr (PW == 8 || PW == 16) {
+        unsigned wds[PW / 4];
+        if constexpr (PW == 8) { const uint2 v = *reinterpret_cast<const uint2*>(src); wds[0] = v.x; wds[1] = v.y; }
+        else { const uint4 v = *reinterpret_cast<const uint4*>(src); wds[0] = v.x; wds[1] = v.y; wds[2] = v.z; wds[3] = v.w; }
+#pragma unroll
+        for (int q = 0; q < PW / 4; ++q)
+            *reinterpret_cast<float4*>(dst + 4 * q) = make_float4(norm[wds[q] & 255u], norm[(wds[q] >> 8) & 255u], norm[(wds[q] >> 16) & 255u], norm[wds[q] >> 24]);
+    } else {
+        for (int kx = 0; kx < pw; ++kx) dst[kx] = norm[src[kx]];
+    }
+}
+
+// Stochastic weight averaging over the flat master weights (torch.optim.swa_utils.AveragedModel's default rule): n == 0: avg = w, else
+// avg += (w - avg) / (n + 1) — a subtraction, an IEEE division and an addition per element, nothing to contract.  Grid-stride over
+// 16-byte pieces when both pointers allow it, the tail (and an unaligned pair) one by one; every element has one owner: deterministic.
+constexpr int AVERAGE_BLOCKS = 1024;
+static __global__ __launch_bounds__(256)
+void weights_average_kernel(const float* __restrict__ w, float* __restrict__ avg, size_t n, int first, float count, int vec) {
+    const size_t tid = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const size_t n4 = vec ? n / 4 : 0;
+    for (size_t i = tid; i < n4; i += threads) {
+        const float4 x = reinterpret_cast<const float4*>(w)[i];
+        if (first) { reinterpret_cast<float4*>(avg)[i] = x; continue; }
+        float4 a = reinterpret_cast<const float4*>(avg)[i];
+        a.x = a.x + (x.x - a.x) / count; a.y = a.y + (x.y - a.y) / count; a.z = a.z + (x.z - a.z) / count; a.w = a.w + (x.w - a.w) / count;
+        reinterpret_cast<float4*>(avg)[i] = a;
+    }
+    for (size_t i = n4 * 4 + tid; i < n; i += threads) avg[i] = first ? w[i] : avg[i] + (w[i] - avg[i]) / count;
+}
+
 // -------------------------------------------------------------------------------------------------------------------
 // optimiser step over the flat parameter / gradient buffers (timm create_optimizer_v2('adamw') = torch.optim.AdamW;
 // gradient clipping = torch.nn.utils.clip_grad_norm_, what Lightning's gradient_clip_val applies; configs/main.yaml:39)

@@ -103,6 +103,35 @@ def _set_train_precision(system, native):
     _native.check(_native.lib().parseq_model_set_train_precision(native, _TRAIN_PRECISIONS[mode]))
 
 
+_U8_TABLES: Dict[str, Tensor] = {}
+
+
+def u8_normalise_table(device) -> Tensor:
+    """fp32 [256] on `device`: what the float path's conversion of uint8 crops — `((images.float() / 255.0) - 0.5) / 0.5`, ToTensor +
+    Normalize(0.5, 0.5) of strhub/data/module.py:78-81 — gives for every byte value, computed ONCE by that very expression on that device.
+    The uint8 im2col (parseq_train_encoder_forward_ex) looks the pixels up in it, so handing the training step uint8 crops gives bit for
+    bit the step on the converted floats, however torch rounds the division."""
+    key = str(torch.device(device))
+    table = _U8_TABLES.get(key)
+    if table is None:
+        table = _U8_TABLES[key] = (((torch.arange(256, device=device).to(torch.uint8).float() / 255.0) - 0.5) / 0.5).contiguous()
+    return table
+
+
+def _encoder_forward(lib, native, images: Tensor, B: int, memory: Tensor, ws: Tensor, ws_bytes: int) -> Tensor:
+    """The training encoder's forward on fp32 (normalised) or uint8 (raw, normalised inside the im2col) images; anything else is
+    converted to fp32 first.  Returns the images as they were handed to the library."""
+    stream = _native.stream_ptr(images)
+    if images.dtype == torch.uint8:
+        _native.check(lib.parseq_train_encoder_forward_ex(native, _native.ptr(images), _native.PARSEQ_U8, _native.ptr(u8_normalise_table(images.device)), B,
+                                                          _native.ptr(memory), _native.ptr(ws), ws_bytes, stream))
+        return images
+    if images.dtype != torch.float32:
+        images = images.float()
+    _native.check(lib.parseq_train_encoder_forward(native, _native.ptr(images), B, _native.ptr(memory), _native.ptr(ws), ws_bytes, stream))
+    return images
+
+
 class _PinnedStaging:
     """Host -> device uploads of a step's small integer inputs without stalling anybody.  A `.to(device)` of a pageable tensor makes the
     host wait until the stream has reached the copy — in the middle of a training step that is the end of the encoder's forward, and
@@ -243,9 +272,7 @@ def _vitstr_loss_and_grads(system, images: Tensor, labels, flat: Optional[Tensor
     targets = vitstr_targets(system, labels)                         # before any device work
     lib = _native.lib()
     model = system.model
-    images = model._check_images(images)
-    if images.dtype != torch.float32:
-        images = ((images.float() / 255.0) - 0.5) / 0.5 if images.dtype == torch.uint8 else images.float()
+    images = model._check_images(images)          # uint8 crops go to the library as they are (_encoder_forward)
     dev = images.device
     B, T = targets.shape
     if B != images.shape[0]:
@@ -259,7 +286,7 @@ def _vitstr_loss_and_grads(system, images: Tensor, labels, flat: Optional[Tensor
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
     memory = torch.empty(B, n_tok, model._cfg['embed_dim'], dtype=torch.float32, device=dev)
     stream = _native.stream_ptr(images)
-    _native.check(lib.parseq_train_encoder_forward(native, _native.ptr(images), B, _native.ptr(memory), _native.ptr(ws), ws_bytes, stream))
+    images = _encoder_forward(lib, native, images, B, memory, ws, ws_bytes)
     if flat is None:
         flat = torch.zeros(lib.parseq_model_grad_elems(native), dtype=torch.float32, device=dev)
     else:
@@ -279,7 +306,8 @@ def _vitstr_loss_and_grads(system, images: Tensor, labels, flat: Optional[Tensor
 def loss_and_grads(system, images: Tensor, labels, perms: Optional[Tensor] = None, dropout: Optional[float] = None,
                    seed: Optional[int] = None, inputs: Optional[_DecoderInputs] = None, flat: Optional[Tensor] = None) -> DecoderBackward:
     """Loss and the gradient of EVERY parameter for one batch — the state `loss.backward()` leaves after the reference's
-    `training_step` (system.py:168-199), dropout off.  `images`: fp32 [B, 3, H, W] on the device, normalised.  Everything is enqueued on
+    `training_step` (system.py:168-199), dropout off.  `images`: fp32 [B, 3, H, W] on the device, normalised, or uint8 raw pixels as `resize_batch` /
+    `augment_resize_batch` return them (normalised inside the im2col: the same bits, u8_normalise_table).  Everything is enqueued on
     the CURRENT stream (`inputs`: prepared ahead by the caller — loss_and_grads_micro).  A ViTSTR system takes its own step
     (_vitstr_loss_and_grads: no permutations, no dropout).  `system.train_precision` picks the arithmetic of the Linear products:
     'fp32' exact, 'bf16' operands rounded to bfloat16, 'bf16x3' operands split into bf16 (hi, lo) pairs and three bf16 MFMAs per
@@ -291,9 +319,7 @@ def loss_and_grads(system, images: Tensor, labels, perms: Optional[Tensor] = Non
     check_trainable(system)
     lib = _native.lib()
     model = system.model
-    images = model._check_images(images)
-    if images.dtype != torch.float32:
-        images = ((images.float() / 255.0) - 0.5) / 0.5 if images.dtype == torch.uint8 else images.float()
+    images = model._check_images(images)          # uint8 crops go to the library as they are (_encoder_forward)
     # the decoder's integer inputs first: host work + asynchronous uploads, nothing of it waits for the device (the draws from the system's
     # generators happen in the reference's order: permutations, then the dropout seed inside decoder_backward)
     if inputs is None:
@@ -304,8 +330,7 @@ def loss_and_grads(system, images: Tensor, labels, perms: Optional[Tensor] = Non
     ws_bytes = lib.parseq_train_encoder_workspace_bytes(native, B)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=images.device)
     memory = torch.empty(B, model.encoder.pos_embed.shape[1], model._cfg['embed_dim'], dtype=torch.float32, device=images.device)
-    _native.check(lib.parseq_train_encoder_forward(native, _native.ptr(images), B, _native.ptr(memory), _native.ptr(ws), ws_bytes,
-                                                   _native.stream_ptr(images)))
+    images = _encoder_forward(lib, native, images, B, memory, ws, ws_bytes)
     res = decoder_backward(system, images, labels, perms, memory=memory, dropout=dropout, seed=seed, inputs=inputs, flat=flat)
     _native.check(lib.parseq_train_encoder_backward(native, _native.ptr(res.dmemory), B, _native.ptr(res.flat), _native.ptr(ws), ws_bytes,
                                                     _native.stream_ptr(images)))
@@ -375,20 +400,59 @@ def one_cycle_lr(step_num: int, total_steps: int, max_lr: float, pct_start: floa
     return anneal(max_lr, floor, (step_num - end1) / (end2 - end1))
 
 
+class GradAccumulator:
+    """The bookkeeping of Lightning's `accumulate_grad_batches` = `every` over flat gradient buffers, apart from any device: `add(flat)`
+    takes one call's gradient into the open group's sum, divided by `every`, and calls `step_fn(sum)` when the group is complete (calls
+    `every`, 2 `every`, ...); `flush()` calls it on an incomplete group, the sum still divided by the full count.  Both return whether
+    the optimiser stepped."""
+
+    def __init__(self, every: int, step_fn):
+        if int(every) != every or every < 1:
+            raise ValueError(f'accumulate_grad_batches={every}: a positive integer')
+        self.every, self.step_fn = int(every), step_fn
+        self.sum: Optional[Tensor] = None
+        self.count = 0                      # calls in the open group
+
+    def add(self, flat: Tensor) -> bool:
+        if self.sum is None:
+            self.sum = torch.zeros_like(flat)
+        if self.count == 0:
+            torch.mul(flat, 1.0 / self.every, out=self.sum)
+        else:
+            self.sum.add_(flat, alpha=1.0 / self.every)
+        self.count += 1
+        return self.flush() if self.count == self.every else False
+
+    def flush(self) -> bool:
+        if self.count == 0:
+            return False
+        self.count = 0
+        self.step_fn(self.sum)
+        return True
+
+
 class TrainStep:
     """The per-batch work of `Trainer.fit` on the reference's configuration (base.py:98-110, configs/main.yaml:33-41): forward and
-    backward of `training_step`, gradient averaging across ranks (what DDP does), gradient-norm clipping, one AdamW update under
-    the OneCycle schedule — all on the device, no host synchronisation inside a step.  Epoch loops, checkpoints, logging and
-    SWA are the framework's business and stay outside.  The arithmetic of the step's Linear products is `system.train_precision`
-    ('fp32', 'bf16' or 'bf16x3': _set_train_precision), read at every step."""
+    backward of `training_step`, gradient averaging across ranks (what DDP does), gradient accumulation, gradient-norm clipping, one
+    AdamW update under the OneCycle schedule — all on the device, no host synchronisation inside a step.  The arithmetic of the step's
+    Linear products is `system.train_precision` ('fp32', 'bf16' or 'bf16x3': _set_train_precision), read at every step.
+
+    Accumulation follows Lightning: with `accumulate_grad_batches` = N the optimiser steps at every N-th call; every call's gradient
+    enters the sum divided by N; clipping and AdamW see the sum; the schedule (`step_count`) advances per optimiser step.  `flush()`
+    steps on an incomplete group, still divided by N — what Lightning does with the last batches of an epoch.  N = 1 is the step as it
+    always was.  `lr_fn(step) -> float` replaces the OneCycle value (parseq_amd/fit.py switches to the SWA schedule through it);
+    `state_dict()` / `load_state_dict()` carry the moments, the step count and an open accumulation group, for checkpoints.
+    Epoch loops, validation, checkpoints, logging and SWA live in parseq_amd/fit.py."""
 
     def __init__(self, system, total_steps: int, lr: Optional[float] = None, weight_decay: Optional[float] = None,
                  warmup_pct: Optional[float] = None, clip_val: float = 20.0, betas=(0.9, 0.999), eps: float = 1e-8,
-                 num_devices: Optional[int] = None, accumulate_grad_batches: int = 1, process_group=None, micro_batches: Optional[int] = None):
+                 num_devices: Optional[int] = None, accumulate_grad_batches: int = 1, process_group=None, micro_batches: Optional[int] = None,
+                 lr_fn=None):
         import math
         check_trainable(system)
         if is_vitstr(system) and micro_batches is not None and micro_batches > 1:
             raise ValueError(f'micro_batches={micro_batches}: the ViTSTR training step runs in one piece')
+        self._group = GradAccumulator(accumulate_grad_batches, self._step_on_group)      # refuses a bad count before any device work
         self.system = system
         self.total_steps = total_steps
         if num_devices is None:       # base.py:99 uses trainer.num_devices: default to the data-parallel world this step averages over
@@ -402,6 +466,8 @@ class TrainStep:
         self.pct_start = system.warmup_pct if warmup_pct is None else warmup_pct
         self.clip_val, self.betas, self.eps = clip_val, betas, eps
         self.process_group = process_group
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self.lr_fn = lr_fn                  # None: the OneCycle value of `step_count`
         # micro-batches of a step that run at once on separate streams (loss_and_grads_micro).  Default ONE: measured at batch 384, two parts at
         # once take 27.0 ms against 24.7 ms in one piece, three 28.7, four 34.0 (profiles/r06_train_step.md) — the parts run the same phase at the
         # same time and compete for what that phase is short of; round 5's probe (two free-running half-steps: 23.6 ms) had overlapped DIFFERENT
@@ -428,6 +494,9 @@ class TrainStep:
 
     @property
     def lr(self) -> float:
+        """The learning rate of the next optimiser step."""
+        if self.lr_fn is not None:
+            return float(self.lr_fn(self.step_count))
         return one_cycle_lr(self.step_count, self.total_steps, self.max_lr, self.pct_start)
 
     def _parts(self, batch: int, distributed: bool) -> int:
@@ -440,10 +509,14 @@ class TrainStep:
             n = 1
         return n if n >= 1 and batch % n == 0 else 1
 
+    def _distributed(self) -> bool:
+        return self.process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized())
+
     def __call__(self, images: Tensor, labels, perms: Optional[Tensor] = None) -> Tensor:
         lib = _native.lib()
         system, model = self.system, self.system.model
-        distributed = self.process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized())
+        distributed = self._distributed()
+        accumulating = self.accumulate_grad_batches > 1
         parts = self._parts(images.shape[0], distributed)
         if parts > 1 and is_vitstr(system):
             raise ValueError(f'{parts} micro-batches: the ViTSTR training step runs in one piece')
@@ -454,6 +527,12 @@ class TrainStep:
             res = loss_and_grads_micro(system, images, labels, perms, parts=parts, streams=self._micro_streams, flats=self._micro_flats)
         else:
             res = loss_and_grads(system, images, labels, perms)      # enqueued, not waited for: the device is still in the backward here
+        self.last = res
+        if accumulating:
+            # Lightning's accumulation: loss / N before backward, i.e. every call's gradient enters the sum divided by N; nothing is
+            # exchanged between ranks until the group steps (its no_sync)
+            self._group.add(res.flat)
+            return res.loss
         native = model._sync_native().model
         if distributed:
             from .parallel import average_gradient_segments, average_gradients
@@ -467,20 +546,56 @@ class TrainStep:
                                           comm_stream=self._comm_stream, force=self.force_collectives)
             else:
                 average_gradients(res.flat, self.process_group)
-        stream = _native.stream_ptr(res.flat)
+        self._optimizer_step(res.flat)
+        return res.loss
+
+    def flush(self) -> bool:
+        """Step on the open accumulation group, complete or not (the sum stays divided by the FULL count: Lightning at the end of an
+        epoch).  False when no group is open."""
+        return self._group.flush()
+
+    def _step_on_group(self, flat: Tensor) -> None:
+        if self._distributed():
+            from .parallel import average_gradients
+            average_gradients(flat, self.process_group)
+        self._optimizer_step(flat)
+
+    def _optimizer_step(self, flat: Tensor) -> None:
+        """Clipping and one AdamW update from the flat gradient `flat` under the schedule's learning rate; the module's tensors and the
+        inference plans then carry the new weights."""
+        lib = _native.lib()
+        model = self.system.model
+        native = model._sync_native().model
+        stream = _native.stream_ptr(flat)
         norm = None
         if self.clip_val:
-            with _native.guard(res.flat):
-                _native.check(lib.parseq_grad_norm(_native.ptr(res.flat), res.flat.numel(), _native.ptr(self._norm), _native.ptr(self._norm_ws), stream))
+            with _native.guard(flat):
+                _native.check(lib.parseq_grad_norm(_native.ptr(flat), flat.numel(), _native.ptr(self._norm), _native.ptr(self._norm_ws), stream))
             norm = self._norm
         lr = self.lr
         self.step_count += 1
-        _native.check(lib.parseq_adamw_step(native, _native.ptr(res.flat), _native.ptr(self.exp_avg), _native.ptr(self.exp_avg_sq),
+        _native.check(lib.parseq_adamw_step(native, _native.ptr(flat), _native.ptr(self.exp_avg), _native.ptr(self.exp_avg_sq),
                                             self._decay_flags, lr, self.betas[0], self.betas[1], self.eps, self.weight_decay,
                                             self.step_count, _native.ptr(norm), float(self.clip_val or 0.0), stream))
         model._adopt_native_weights()
-        self.last = res
-        return res.loss
+
+    def state_dict(self) -> dict:
+        """What a resumed run needs beside the weights: AdamW's moments, the optimiser-step count, an open accumulation group (host tensors)."""
+        g = self._group
+        return {'exp_avg': self.exp_avg.cpu(), 'exp_avg_sq': self.exp_avg_sq.cpu(), 'step_count': self.step_count,
+                'accum': g.sum.cpu() if g.count else None, 'accum_count': g.count}
+
+    def load_state_dict(self, state: dict) -> None:
+        if state['exp_avg'].shape != self.exp_avg.shape:
+            raise ValueError(f"moments of {tuple(state['exp_avg'].shape)} elements for a model of {tuple(self.exp_avg.shape)}")
+        count = int(state.get('accum_count', 0))
+        if count >= self.accumulate_grad_batches and count:
+            raise ValueError(f'an open group of {count} calls under accumulate_grad_batches={self.accumulate_grad_batches}')
+        self.exp_avg.copy_(state['exp_avg'])
+        self.exp_avg_sq.copy_(state['exp_avg_sq'])
+        self.step_count = int(state['step_count'])
+        self._group.count = count
+        self._group.sum = state['accum'].to(self.exp_avg.device) if count else None
 
 
 class _TrainingStepFunction(torch.autograd.Function):

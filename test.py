@@ -21,18 +21,18 @@ import argparse
 import os
 import string
 import sys
-import unicodedata
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Tuple
 
 import numpy as np
 import torch
 from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
+from parseq_amd.data import parse_gt_line, preprocess_label, read_gt  # noqa: F401  (the first two keep their names here)
 from parseq_amd.evaluate import Evaluator
 from parseq_amd.preprocess import resize_batch
-from parseq_amd.tokenizer import CharsetAdapter
+from parseq_amd.tokenizer import CharsetAdapter  # noqa: F401
 
 
 @dataclass
@@ -45,35 +45,10 @@ class Result:
     label_length: float
 
 
-def parse_gt_line(line: str) -> Optional[Tuple[str, str]]:
-    """'path label' -> (path, label); the label may contain blanks.  None for a line without both parts."""
-    parts = line.strip().split(maxsplit=1)
-    return (parts[0], parts[1]) if len(parts) == 2 else None
-
-
-def preprocess_label(label: str, adapter: CharsetAdapter, max_label_length: int) -> Optional[str]:
-    """The label as the reference's dataset hands it to the model, or None if the dataset drops the sample."""
-    label = ''.join(label.split())
-    label = unicodedata.normalize('NFKD', label).encode('ascii', 'ignore').decode()
-    if len(label) > max_label_length:            # before the adapter: the raw label may be too long for the model
-        return None
-    return adapter(label) or None
-
-
 def read_dataset(root: str, name: str, charset_test: str, max_label_length: int) -> List[Tuple[str, str]]:
-    """[(image file, label)] of the samples of `root/name/gt.txt` that survive the label filter."""
-    adapter = CharsetAdapter(charset_test)
-    folder = os.path.join(root, name)
-    samples = []
-    with open(os.path.join(folder, 'gt.txt'), encoding='utf-8') as fh:
-        for line in fh:
-            parsed = parse_gt_line(line)
-            if parsed is None:
-                continue
-            label = preprocess_label(parsed[1], adapter, max_label_length)
-            if label is not None:
-                samples.append((os.path.join(folder, parsed[0]), label))
-    return samples
+    """[(image file, label)] of the samples of `root/name/gt.txt` that survive the label filter (parseq_amd.data.read_gt: the filter is
+    the one the training loader applies with `charset_train`)."""
+    return read_gt(os.path.join(root, name), charset_test, max_label_length)
 
 
 def find_datasets(root: str) -> List[str]:
