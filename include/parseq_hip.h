@@ -274,11 +274,26 @@ int parseq_rotate_resize_bicubic(const parseq_rotated_image_desc* images, int ba
  *                            PARSEQ_AUG_BILINEAR or PARSEQ_AUG_BICUBIC.  ShearX / ShearY / TranslateXRel / TranslateYRel keep the size,
  *                            Rotate (expand=True) carries its expanded size (augment.py rotate_expand_map)
  *   PARSEQ_AUG_TURN          Pillow's exact rotation by 90 / 180 / 270 degrees: mode is PARSEQ_ROTATE_90 / _180 / _270
+ *   PARSEQ_AUG_GAUSSIAN_BLUR img.filter(ImageFilter.GaussianBlur(radius)), 0 < radius <= 4, bit-exact with Pillow: three box passes along x,
+ *                            then three along y, each out = (ww * (the 2 r + 1 samples around x) + fw * (the two at distance r + 1) + 2^23)
+ *                            >> 24 in 32-bit unsigned arithmetic, indices clamped to the line in every pass, rounded to uint8 after every
+ *                            pass.  arg.blur = (r, ww, fw) of parseq_amd/augment.py gaussian_box(radius), Pillow's single-precision steps;
+ *                            0 <= r <= 3 and (2 r + 1) ww + 2 fw <= 2^24 (more would overflow the sum)
+ *   PARSEQ_AUG_POISSON_NOISE imgaug's AdditivePoissonNoise(lam) = AddElementwise(RandomSign(Poisson(lam)), per_channel=False), RESTATED from
+ *                            its published definition, not pinned against imgaug: per pixel ONE draw n = +-k, k ~ Poisson(arg.noise.lam),
+ *                            both signs equally likely, added to R, G and B, clipped to 0 .. 255.  The generator is Philox4x32-10 with key
+ *                            (low, high word of arg.noise.seed) and counter (pixel index y * width + x, 0, 0, 0): word 0 is the uniform u,
+ *                            bit 31 of word 1 set means minus; k = the number of thresholds T_j <= u, j = 0 .. 126, T_j = min(floor(C_j
+ *                            2^32), 2^32 - 1), C_j = C_(j-1) + p_j, p_(j+1) = (p_j lam) / (j + 1) in float64 without contraction, p_0 =
+ *                            arg.noise.p0 = exp(-lam) computed by the caller.  1 <= lam <= 41, p0 finite and in (0, 1).  A pixel's noise
+ *                            depends on (seed, index) alone: the same bytes every run
  * out_height / out_width: the image after the operator; every operator but AFFINE and TURN must repeat its input's size.  Factors are
  * finite and >= 0.1, coefficients finite, no side (source or any stage) outside 1 .. PARSEQ_ROTATE_MAX_SIDE.  Every descriptor is checked
- * on the host before anything is launched (PARSEQ_E_INVALID, parseq_last_error names the image and the field). */
+ * on the host before anything is launched (PARSEQ_E_INVALID, parseq_last_error names the image and the field).
+ * The two last operators came after ABI 14 without a new version: the descriptor's layout is unchanged (both fit the 256 bytes of arg) and
+ * an older library refuses them as unknown operators.  The value 9 is no operator and stays refused. */
 enum { PARSEQ_AUG_NONE = 0, PARSEQ_AUG_TABLE = 1, PARSEQ_AUG_AUTOCONTRAST = 2, PARSEQ_AUG_EQUALIZE = 3, PARSEQ_AUG_CONTRAST = 4,
-       PARSEQ_AUG_COLOR = 5, PARSEQ_AUG_AFFINE = 6, PARSEQ_AUG_TURN = 7 };
+       PARSEQ_AUG_COLOR = 5, PARSEQ_AUG_AFFINE = 6, PARSEQ_AUG_TURN = 7, PARSEQ_AUG_GAUSSIAN_BLUR = 8, PARSEQ_AUG_POISSON_NOISE = 10 };
 enum { PARSEQ_AUG_BILINEAR = 2, PARSEQ_AUG_BICUBIC = 3 };      /* Pillow's Image.Resampling values */
 #define PARSEQ_AUGMENT_MAX_OPS 3
 
@@ -286,7 +301,11 @@ typedef struct {
     int32_t op;                       /* PARSEQ_AUG_* (never NONE inside a chain) */
     int32_t mode;                     /* AFFINE: the resampling filter; TURN: the quarter turn; otherwise 0 */
     int32_t out_height, out_width;
-    union { uint8_t table[256]; float factor; double coef[6]; } arg;
+    union {
+        uint8_t table[256]; float factor; double coef[6];
+        struct { int32_t r; uint32_t ww, fw; } blur;                    /* GAUSSIAN_BLUR: one box pass's radius and 8.24 weights */
+        struct { double p0; uint64_t seed; int32_t lam; } noise;        /* POISSON_NOISE: exp(-lam), the Philox key, lam */
+    } arg;
 } parseq_augment_op;
 
 typedef struct {

@@ -36,8 +36,18 @@ class RotatedImageDesc(C.Structure):
                 ('rot_height', C.c_int32), ('rot_width', C.c_int32), ('a', C.c_int32 * 6)]
 
 
+class AugmentBlur(C.Structure):
+    """arg.blur of PARSEQ_AUG_GAUSSIAN_BLUR: one box pass (parseq_amd/augment.py gaussian_box)."""
+    _fields_ = [('r', C.c_int32), ('ww', C.c_uint32), ('fw', C.c_uint32)]
+
+
+class AugmentNoise(C.Structure):
+    """arg.noise of PARSEQ_AUG_POISSON_NOISE: exp(-lam), the Philox key, lam."""
+    _fields_ = [('p0', C.c_double), ('seed', C.c_uint64), ('lam', C.c_int32)]
+
+
 class AugmentArg(C.Union):
-    _fields_ = [('table', C.c_uint8 * 256), ('factor', C.c_float), ('coef', C.c_double * 6)]
+    _fields_ = [('table', C.c_uint8 * 256), ('factor', C.c_float), ('coef', C.c_double * 6), ('blur', AugmentBlur), ('noise', AugmentNoise)]
 
 
 class AugmentOp(C.Structure):

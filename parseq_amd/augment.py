@@ -14,9 +14,21 @@ A chain is a list of at most three `(name, *args)` tuples:
     ('ShearX', f, r)  ('ShearY', f, r)                                  img.transform(img.size, AFFINE, ..., resample=r, fillcolor=(128,) * 3)
     ('TranslateXRel', pct, r)  ('TranslateYRel', pct, r)                the same, by pct of the width / height
     ('Rotate', deg, r)                                                  img.rotate(deg, resample=r, expand=True, fillcolor=(128,) * 3)
+    ('GaussianBlur', radius)                                            img.filter(ImageFilter.GaussianBlur(radius)), 0 <= radius <= 4
+    ('PoissonNoise', lam, seed)                                         imgaug's AdditivePoissonNoise(lam), restated; lam in 1 .. 41
 with r = BILINEAR or BICUBIC.  The host halves are public: `lut_for` (the 256-entry tables, from Pillow's own integer and single-precision
-steps), `affine_coeffs` and `rotate_expand_map` (the six float64 coefficients, from the Python expressions Pillow evaluates).
-`RandAugment` is the policy.  Not covered: GaussianBlur and PoissonNoise (`RandAugment.missing`).
+steps), `affine_coeffs` and `rotate_expand_map` (the six float64 coefficients, from the Python expressions Pillow evaluates) and
+`gaussian_box` (the radius and the two fixed-point weights of Pillow's box passes, from its single-precision steps).
+
+PoissonNoise is a stated definition, not a pinned one (imgaug is not an oracle here): imgaug publishes AdditivePoissonNoise(lam) as
+AddElementwise(RandomSign(Poisson(lam)), per_channel=False), so per pixel ONE draw n = +-k, k ~ Poisson(lam), both signs equally likely,
+is added to R, G and B and the result clipped to 0 .. 255.  The draw is Philox4x32-10 keyed by `seed` (an unsigned 64-bit integer) with
+the pixel's index as the counter: word 0 is the uniform, bit 31 of word 1 the sign, k the number of cumulative float64 thresholds at or
+below the uniform (csrc/augment.h) — a function of (seed, pixel) alone, the same bytes every run.
+
+`RandAugment` is the policy over the fourteen operators that were there first (`RandAugment.missing` names the other two; its draws are
+what existing runs were trained with and do not change); `ReferenceRandAugment` is the reference's policy over all sixteen
+(DESIGN.md sections 14 and 17).
 """
 from __future__ import annotations
 
@@ -32,11 +44,13 @@ from .preprocess import MAX_SIDE, ROTATE_90, ROTATE_180, ROTATE_270, _checked
 
 BILINEAR, BICUBIC = 2, 3                                 # Pillow's Image.Resampling values (PARSEQ_AUG_BILINEAR / _BICUBIC)
 OP_TABLE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_CONTRAST, OP_COLOR, OP_AFFINE, OP_TURN = range(1, 8)      # PARSEQ_AUG_*
+OP_GAUSSIAN_BLUR, OP_POISSON_NOISE = 8, 10               # 9 is no operator: the library refuses it
+MAX_BLUR_RADIUS, MAX_NOISE_LAM = 4, 41                   # the policy's largest radius (magnitude 10); 40 | 1
 MAX_OPS = 3                                              # PARSEQ_AUGMENT_MAX_OPS
 TABLE_OPS = ('Invert', 'Posterize', 'Solarize', 'SolarizeAdd', 'Brightness')
 GEOMETRIC_OPS = ('ShearX', 'ShearY', 'TranslateXRel', 'TranslateYRel', 'Rotate')
 _ARITY = {'AutoContrast': 0, 'Equalize': 0, 'Invert': 0, 'Posterize': 1, 'Solarize': 1, 'SolarizeAdd': 1, 'Color': 1, 'Contrast': 1,
-          'Brightness': 1, 'ShearX': 2, 'ShearY': 2, 'TranslateXRel': 2, 'TranslateYRel': 2, 'Rotate': 2}
+          'Brightness': 1, 'ShearX': 2, 'ShearY': 2, 'TranslateXRel': 2, 'TranslateYRel': 2, 'Rotate': 2, 'GaussianBlur': 1, 'PoissonNoise': 2}
 
 
 def _factor(name: str, factor) -> np.float32:
@@ -129,6 +143,26 @@ def rotate_expand_map(h: int, w: int, deg) -> tuple:
     return None, nh, nw, tuple(m)
 
 
+def gaussian_box(radius) -> tuple:
+    """(r, ww, fw) of the box pass Pillow runs three times along x and three times along y for ImageFilter.GaussianBlur(radius): the integer
+    radius, the 8.24 fixed-point weight of the 2 r + 1 inner samples and that of the two samples at distance r + 1.  Pillow's
+    _gaussian_blur_radius(radius, passes=3) and ImagingBoxBlur, in their single-precision steps."""
+    f = np.float32
+    radius = f(radius)
+    if not (np.isfinite(radius) and 0 <= radius <= MAX_BLUR_RADIUS):
+        raise ValueError(f'GaussianBlur: radius {radius} must be finite and in 0 .. {MAX_BLUR_RADIUS}')
+    sigma2 = f(radius * radius / f(3.0))
+    big = f(np.sqrt(f(f(12.0) * sigma2 + f(1.0))))
+    l = f(np.floor(f((big - f(1.0)) / f(2.0))))
+    a = f(f(f(2.0) * l + f(1.0)) * f(f(l * f(l + f(1.0))) - f(f(3.0) * sigma2)))
+    a = f(a / f(f(6.0) * f(sigma2 - f(f(l + f(1.0)) * f(l + f(1.0))))))
+    fr = f(l + a)
+    r = int(fr)
+    ww = int(np.uint32(f(1 << 24) / f(fr * f(2.0) + f(1.0))))
+    fw = ((1 << 24) - (2 * r + 1) * ww) // 2
+    return r, ww, fw
+
+
 def _fill_op(op, h: int, w: int, name: str, args) -> tuple:
     """Writes one chain entry into `op` (an _native.AugmentOp); returns (used, nh, nw): used is False where the entry is the identity."""
     if name not in _ARITY:
@@ -144,6 +178,19 @@ def _fill_op(op, h: int, w: int, name: str, args) -> tuple:
     elif name in ('Color', 'Contrast'):
         op.op = OP_COLOR if name == 'Color' else OP_CONTRAST
         op.arg.factor = float(_factor(name, args[0]))
+    elif name == 'GaussianBlur':
+        r, ww, fw = gaussian_box(args[0])
+        if float(args[0]) == 0:                          # ImageFilter.GaussianBlur(0) is a copy
+            return False, h, w
+        op.op = OP_GAUSSIAN_BLUR
+        op.arg.blur.r, op.arg.blur.ww, op.arg.blur.fw = r, ww, fw
+    elif name == 'PoissonNoise':
+        lam = _int_arg(name, args[0], 1, MAX_NOISE_LAM)
+        seed = args[1]
+        if int(seed) != seed or not 0 <= seed < 2 ** 64:
+            raise ValueError(f'{name}: seed {seed} must be an unsigned 64-bit integer')
+        op.op = OP_POISSON_NOISE
+        op.arg.noise.p0, op.arg.noise.seed, op.arg.noise.lam = math.exp(-lam), int(seed), lam
     else:
         resample = args[1]
         if resample not in (BILINEAR, BICUBIC):
@@ -245,7 +292,7 @@ class RandAugment:
     uniformly (timm's RandAugment with choice weights, i.e. without replacement) from timm's increasing set minus SharpnessIncreasing,
     each applied with probability 0.5, signed arguments negated with probability 0.5, geometric operators with BILINEAR or BICUBIC at
     random (timm's _RANDOM_INTERPOLATION), fill colour (128, 128, 128).  The reference's set has two more operators, GaussianBlur and
-    PoissonNoise (`missing`): until they exist the draw is among the fourteen of `ops`.
+    PoissonNoise (`missing`): the draw is among the fourteen of `ops`; `ReferenceRandAugment` draws among all sixteen.
     The generator is numpy's, seeded by `seed`; it makes no claim to reproduce the stream of timm's `random` / `np.random` calls."""
 
     ops = ('AutoContrast', 'Equalize', 'Invert', 'Rotate', 'Posterize', 'Solarize', 'SolarizeAdd', 'Color', 'Contrast', 'Brightness',
@@ -266,7 +313,8 @@ class RandAugment:
     def _negate(self, v):
         return -v if self.rng.random() > 0.5 else v
 
-    def _args(self, name: str) -> tuple:
+    def _args(self, name: str, h: int = 0, w: int = 0) -> tuple:
+        """The arguments of `name` on an image of h x w (only the operators of `ReferenceRandAugment` look at the size)."""
         level = self.magnitude / self._LEVEL_DENOM
         if name in self._SIGNED_MAX:                       # aa_overrides.py _level_to_arg: (level / _LEVEL_DENOM) * max, randomly negated
             arg = self._negate(level * self._SIGNED_MAX[name])
@@ -282,15 +330,40 @@ class RandAugment:
         return ()
 
     def sample(self, sizes) -> list:
-        """One chain per entry of `sizes` (the sizes are not needed to draw a chain — every argument is relative — only counted)."""
+        """One chain per (height, width) of `sizes`.  The size is followed through the chain — a Rotate expands it — and handed to `_args`:
+        the fourteen operators of this class take relative arguments and draw the same whatever it is."""
         pool = self.ops
         chains = []
-        for _ in range(len(sizes)):
+        for h, w in sizes:
             chain = []
             for j in self.rng.choice(len(pool), self.num_layers, replace=False):
                 name = pool[j]
                 if self.rng.random() > 0.5:                # timm AugmentOp: prob = 0.5
                     continue
-                chain.append((name,) + self._args(name))
+                entry = (name,) + self._args(name, h, w)
+                chain.append(entry)
+                if name == 'Rotate':
+                    _, h, w, _ = rotate_expand_map(h, w, entry[1])
             chains.append(chain)
         return chains
+
+
+class ReferenceRandAugment(RandAugment):
+    """The reference's whole policy: the sixteen operators of rand_augment_transform() (strhub/data/augment.py:78-112), GaussianBlur and
+    PoissonNoise included, so `missing` is empty.  Their arguments follow strhub/data/augment.py:40-70 on the image as it is when the
+    operator is reached: radius = round(min(4 m / 10, max(1, 0.02 max(h, w)))), lam = round(min(40 m / 10, max(1, 0.2 max(h, w)))) | 1,
+    with Python's round.  The noise's seed is drawn from the policy's generator."""
+
+    ops = RandAugment.ops + ('GaussianBlur', 'PoissonNoise')
+    missing = ()
+
+    @staticmethod
+    def _param(level: float, h: int, w: int, max_dim_factor: float, min_level: float = 1) -> int:      # strhub/data/augment.py _get_param
+        return round(min(level, max(min_level, max_dim_factor * max(h, w))))
+
+    def _args(self, name: str, h: int = 0, w: int = 0) -> tuple:
+        if name == 'GaussianBlur':                         # _level_to_arg: max * level / _LEVEL_DENOM
+            return (self._param(4 * self.magnitude / self._LEVEL_DENOM, h, w, 0.02),)
+        if name == 'PoissonNoise':
+            return (self._param(40 * self.magnitude / self._LEVEL_DENOM, h, w, 0.2) | 1, int(self.rng.integers(0, 2 ** 64, dtype=np.uint64)))
+        return super()._args(name, h, w)

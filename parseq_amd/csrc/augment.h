@@ -8,14 +8,18 @@
 // itself (empty chain), region 0 (one or three operators) or region 1 (two); nothing is ever copied through.
 // augment_plan_kernel places the regions and writes the ImageDesc array that resize_bicubic_kernel (resize.h) then reads.
 //
-// Operators (the Python half, parseq_amd/augment.py, maps the reference's fourteen names onto them):
+// Operators (the Python half, parseq_amd/augment.py, maps the reference's sixteen names onto them):
 //   AUG_TABLE         Invert, Posterize, Solarize, SolarizeAdd, Brightness: a 256-entry table built on the host, one pass;
 //   AUG_AUTOCONTRAST  per-channel histogram -> ImageOps.autocontrast's table (float64, no fused multiply-add);
 //   AUG_EQUALIZE      per-channel histogram -> ImageOps.equalize's table (integers);
 //   AUG_CONTRAST      sum of L = (R 19595 + G 38470 + B 7471 + 0x8000) >> 16 -> rounded mean -> table of Image.blend(mean, v, f);
 //   AUG_COLOR         Image.blend(L of the pixel, pixel, f): not a table, L differs per pixel;
 //   AUG_AFFINE        Image.transform(AFFINE, BILINEAR | BICUBIC, fillcolor 128): ShearX/Y, TranslateX/YRel and Rotate(expand);
-//   AUG_TURN          Rotate by 90 / 180 / 270 degrees: Pillow's exact transposes, whatever the filter.
+//   AUG_TURN          Rotate by 90 / 180 / 270 degrees: Pillow's exact transposes, whatever the filter;
+//   AUG_GAUSSIAN_BLUR Image.filter(ImageFilter.GaussianBlur(radius)): Pillow's three box passes along x, then three along y, in 8.24
+//                     fixed point (aug_blur_tiles below); the host half gaussian_box(radius) gives the pass's (r, ww, fw);
+//   AUG_POISSON_NOISE imgaug's AdditivePoissonNoise(lam), restated: n = +-k, k ~ Poisson(lam), one draw per pixel added to R, G and B and
+//                     clipped; Philox4x32-10 keyed by the seed, counter = the pixel's index, thresholds in float64 (aug_noise_table below).
 // Statistics are gathered in LDS with integer atomics (exact, order-independent: the same bytes every run), the table is built in
 // LDS and applied in the same launch.  An image of more than one tile gathers its statistics once per tile (each workgroup reads
 // the whole image, at most AUG_MAX_TILES times, from L2) — no grid-wide synchronisation, no second launch.
@@ -31,16 +35,28 @@
 
 namespace pq {
 
-enum { AUG_NONE = 0, AUG_TABLE = 1, AUG_AUTOCONTRAST = 2, AUG_EQUALIZE = 3, AUG_CONTRAST = 4, AUG_COLOR = 5, AUG_AFFINE = 6, AUG_TURN = 7 };
+// 9 is no operator: tests/test_augment.py holds the library to refusing it
+enum { AUG_NONE = 0, AUG_TABLE = 1, AUG_AUTOCONTRAST = 2, AUG_EQUALIZE = 3, AUG_CONTRAST = 4, AUG_COLOR = 5, AUG_AFFINE = 6, AUG_TURN = 7,
+       AUG_GAUSSIAN_BLUR = 8, AUG_POISSON_NOISE = 10 };
 enum { AUG_BILINEAR = 2, AUG_BICUBIC = 3 };          // Pillow's Image.Resampling values
 constexpr int AUG_MAX_OPS = 3;
 constexpr int AUG_TILE_PIXELS = 4096;                // pixels of one workgroup's share, until an image has AUG_MAX_TILES of them
 constexpr int AUG_MAX_TILES = 16;
 constexpr int AUG_FILL = 128;
+constexpr int AUG_BLUR_MAX_R = 3;                    // the box radius of GaussianBlur(4), the policy's largest
+constexpr int AUG_BLUR_TILE_H = 32, AUG_BLUR_TILE_W = 64;                         // outputs of one sub-tile of the blur
+constexpr int AUG_BLUR_MAX_HALO = 3 * (AUG_BLUR_MAX_R + 1);                      // three passes, each reaching r + 1 samples
+constexpr int AUG_BLUR_PLANE = (AUG_BLUR_TILE_H + 2 * AUG_BLUR_MAX_HALO) * (AUG_BLUR_TILE_W + 2 * AUG_BLUR_MAX_HALO) * 3;    // 14784 bytes
+constexpr int AUG_NOISE_MAX_LAM = 41;
+constexpr int AUG_NOISE_LEVELS = 127;                // thresholds T_0 .. T_126: k <= 127
 
 struct AugOp {                                       // mirrors parseq_augment_op
     int op, mode, out_height, out_width;
-    union { unsigned char table[256]; float factor; double coef[6]; } arg;
+    union {
+        unsigned char table[256]; float factor; double coef[6];
+        struct { int r; unsigned ww, fw; } blur;
+        struct { double p0; unsigned long long seed; int lam; } noise;
+    } arg;
 };
 struct AugDesc {                                     // mirrors parseq_augment_desc
     const unsigned char* data; int height, width; long long row_stride;
@@ -168,6 +184,100 @@ __device__ __forceinline__ bool aug_affine_pixel(const unsigned char* src, long 
     return true;
 }
 
+// ---- GaussianBlur: Pillow's BoxBlur.c ------------------------------------------------------------------------------------------
+// One box pass over the lh x lw x 3 bytes of a tile in LDS, along x or along y:
+//   out = (ww * sum(in[clamp(. + i)], i = -r .. r) + fw * (in[clamp(. - r - 1)] + in[clamp(. + r + 1)]) + 2^23) >> 24,   32-bit unsigned
+// (the host refuses (2 r + 1) ww + 2 fw > 2^24, so nothing wraps).  Indices are clamped to the TILE: where the tile ends at the image's
+// edge that is Pillow's clamp, applied to this pass's own input; where it ends inside the image the samples are wrong, r + 1 deeper
+// with every pass — the halo of 3 (r + 1) that is never written back.
+template <bool ALONG_X>
+__device__ __forceinline__ void aug_box_pass(const unsigned char* in, unsigned char* out, int lh, int lw, int r, unsigned ww, unsigned fw, int tid) {
+    const int row = lw * 3, n = lh * row;
+    for (int e = tid; e < n; e += 256) {
+        const int y = e / row, xc = e - y * row;
+        unsigned acc = 0, far;
+        if (ALONG_X) {
+            const int x = xc / 3;
+            const unsigned char* line = in + y * row + (xc - x * 3);
+            for (int i = -r; i <= r; ++i) acc += line[aug_clampi(x + i, lw) * 3];
+            far = (unsigned)line[aug_clampi(x - r - 1, lw) * 3] + line[aug_clampi(x + r + 1, lw) * 3];
+        } else {
+            const unsigned char* line = in + xc;
+            for (int i = -r; i <= r; ++i) acc += line[aug_clampi(y + i, lh) * row];
+            far = (unsigned)line[aug_clampi(y - r - 1, lh) * row] + line[aug_clampi(y + r + 1, lh) * row];
+        }
+        out[e] = (unsigned char)((acc * ww + far * fw + (1u << 23)) >> 24);
+    }
+}
+
+// The workgroup's share [p0, p1) of an h x w image, walked in sub-tiles of AUG_BLUR_TILE_H x AUG_BLUR_TILE_W outputs: each is loaded with its
+// halo (cut at the image's edges), runs the six passes between the two planes in LDS and writes the pixels of the share.  Every branch
+// is uniform over the workgroup.
+__device__ __forceinline__ void aug_blur_tiles(const unsigned char* src, long long stride, int h, int w, unsigned char* dst, int p0, int p1,
+                                               int r, unsigned ww, unsigned fw, unsigned char* a, unsigned char* b, int tid) {
+    const int halo = 3 * (r + 1);
+    const int y0 = p0 / w, y1 = (p1 - 1) / w + 1;
+    for (int ty0 = y0; ty0 < y1; ty0 += AUG_BLUR_TILE_H) {
+        const int ty1 = min(y1, ty0 + AUG_BLUR_TILE_H);
+        const int gy0 = max(0, ty0 - halo), lh = min(h, ty1 + halo) - gy0;
+        for (int tx0 = 0; tx0 < w; tx0 += AUG_BLUR_TILE_W) {
+            const int tx1 = min(w, tx0 + AUG_BLUR_TILE_W);
+            if ((ty1 - 1) * w + tx1 - 1 < p0 || ty0 * w + tx0 >= p1) continue;                // no pixel of the share in this sub-tile
+            const int gx0 = max(0, tx0 - halo), lw = min(w, tx1 + halo) - gx0;
+            const int row = lw * 3, n = lh * row;
+            for (int e = tid; e < n; e += 256) {
+                const int y = e / row, xc = e - y * row;
+                a[e] = src[(size_t)(gy0 + y) * stride + (size_t)gx0 * 3 + xc];
+            }
+            __syncthreads();
+            aug_box_pass<true>(a, b, lh, lw, r, ww, fw, tid);  __syncthreads();
+            aug_box_pass<true>(b, a, lh, lw, r, ww, fw, tid);  __syncthreads();
+            aug_box_pass<true>(a, b, lh, lw, r, ww, fw, tid);  __syncthreads();
+            aug_box_pass<false>(b, a, lh, lw, r, ww, fw, tid); __syncthreads();
+            aug_box_pass<false>(a, b, lh, lw, r, ww, fw, tid); __syncthreads();
+            aug_box_pass<false>(b, a, lh, lw, r, ww, fw, tid); __syncthreads();
+            const int tw = tx1 - tx0, outs = (ty1 - ty0) * tw;
+            for (int e = tid; e < outs; e += 256) {
+                const int ly = e / tw, y = ty0 + ly, x = tx0 + (e - ly * tw);
+                const int p = y * w + x;
+                if (p < p0 || p >= p1) continue;
+                const unsigned char* px = a + ((y - gy0) * lw + (x - gx0)) * 3;
+                unsigned char* o = dst + (size_t)p * 3;
+                o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+            }
+            __syncthreads();                                                                 // the next sub-tile loads into `a`
+        }
+    }
+}
+
+// ---- PoissonNoise ------------------------------------------------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11; Random123), counter (c0, c1, 0, 0), key (k0, k1): words 0 and 1 of the output
+__device__ __forceinline__ void aug_philox(unsigned c0, unsigned c1, unsigned k0, unsigned k1, unsigned& w0, unsigned& w1) {
+    unsigned c2 = 0, c3 = 0;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned long long m0 = 0xD2511F53ull * c0, m1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(m1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(m0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)m1; c3 = (unsigned)m0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w0 = c0; w1 = c1;
+}
+
+// T_j = min(floor(C_j 2^32), 2^32 - 1), C_j = C_{j-1} + p_j, p_{j+1} = (p_j lam) / (j + 1), p_0 = exp(-lam) from the host: float64, one
+// thread, in this order.  k of a uniform u is the number of T_j <= u.
+__device__ __forceinline__ void aug_noise_table(unsigned* T, double p0, int lam) {
+    AUG_NO_CONTRACT
+    double p = p0, c = p0;
+    const double dl = (double)lam;
+    for (int j = 0; j < AUG_NOISE_LEVELS; ++j) {
+        const double t = AUG_MUL(c, 4294967296.0);
+        T[j] = t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
+        p = AUG_MUL(p, dl) / (double)(j + 1);
+        c = AUG_ADD(c, p);
+    }
+}
+
 // stage k of every image's chain.  grid = (images, most tiles of an image at this stage)
 static __global__ __launch_bounds__(256)
 void augment_stage_kernel(const AugDesc* __restrict__ descs, const size_t* __restrict__ offsets, unsigned char* regions, int k) {
@@ -176,6 +286,7 @@ void augment_stage_kernel(const AugDesc* __restrict__ descs, const size_t* __res
     __shared__ unsigned char lut[768];
     __shared__ unsigned long long lsum;
     __shared__ int lohi[6];
+    __shared__ unsigned char blur[2][AUG_BLUR_PLANE];
     const AugDesc& d = descs[blockIdx.x];
     if (k >= d.num_ops) return;
     const AugOp& op = d.ops[k];
@@ -191,6 +302,7 @@ void augment_stage_kernel(const AugDesc* __restrict__ descs, const size_t* __res
     unsigned char* dst = base + (size_t)(k & 1) * region;
     const int chunk = (opx + tiles - 1) / tiles;
     const int p0 = (int)blockIdx.y * chunk, p1 = min(opx, p0 + chunk);
+    if (p0 >= p1) return;
     const int tid = threadIdx.x;
     const int kind = op.op;
 
@@ -253,6 +365,9 @@ void augment_stage_kernel(const AugDesc* __restrict__ descs, const size_t* __res
     } else if (kind == AUG_TABLE) {
         for (int t = tid; t < 768; t += blockDim.x) lut[t] = op.arg.table[t & 255];
         __syncthreads();
+    } else if (kind == AUG_POISSON_NOISE) {                                                  // the thresholds take hist's place
+        if (tid == 0) aug_noise_table(hist, op.arg.noise.p0, op.arg.noise.lam);
+        __syncthreads();
     }
 
     if (kind == AUG_AFFINE) {
@@ -280,6 +395,22 @@ void augment_stage_kernel(const AugDesc* __restrict__ descs, const size_t* __res
                 const unsigned char* px = src + (size_t)sy * stride + (size_t)sx * 3;
                 o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
             } else { o[0] = o[1] = o[2] = AUG_FILL; }
+        }
+    } else if (kind == AUG_GAUSSIAN_BLUR) {
+        aug_blur_tiles(src, stride, h, w, dst, p0, p1, min(max(op.arg.blur.r, 0), AUG_BLUR_MAX_R), op.arg.blur.ww, op.arg.blur.fw, blur[0], blur[1], tid);
+    } else if (kind == AUG_POISSON_NOISE) {
+        const unsigned k0 = (unsigned)op.arg.noise.seed, k1 = (unsigned)(op.arg.noise.seed >> 32);
+        for (int p = p0 + tid; p < p1; p += blockDim.x) {
+            const int y = p / ow, x = p - y * ow;
+            unsigned u, sign;
+            aug_philox((unsigned)p, 0u, k0, k1, u, sign);                                    // the pixel's index is below 2^31: its high word is 0
+            int lo = 0, hi = AUG_NOISE_LEVELS;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (hist[mid] <= u) lo = mid + 1; else hi = mid; }
+            const int n = (sign >> 31) ? -lo : lo;
+            const unsigned char* px = src + (size_t)y * stride + (size_t)x * 3;
+            unsigned char* o = dst + (size_t)p * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { const int v = (int)px[c] + n; o[c] = (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
         }
     } else if (kind == AUG_COLOR) {
         const float f = op.arg.factor;

@@ -99,7 +99,9 @@ extern "C" int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t*
 static_assert(sizeof(parseq_augment_op) == sizeof(AugOp) && offsetof(parseq_augment_op, arg) == offsetof(AugOp, arg) &&
               sizeof(parseq_augment_desc) == sizeof(AugDesc) && offsetof(parseq_augment_desc, ops) == offsetof(AugDesc, ops) &&
               PARSEQ_AUGMENT_MAX_OPS == AUG_MAX_OPS && PARSEQ_AUG_TURN == AUG_TURN && PARSEQ_AUG_TABLE == AUG_TABLE &&
-              PARSEQ_AUG_BICUBIC == AUG_BICUBIC, "descriptor layouts must match");
+              PARSEQ_AUG_BICUBIC == AUG_BICUBIC && PARSEQ_AUG_GAUSSIAN_BLUR == AUG_GAUSSIAN_BLUR && PARSEQ_AUG_POISSON_NOISE == AUG_POISSON_NOISE &&
+              sizeof(parseq_augment_op) == 16 + 256 && offsetof(parseq_augment_op, arg.blur.fw) == offsetof(AugOp, arg.blur.fw) &&
+              offsetof(parseq_augment_op, arg.noise.lam) == offsetof(AugOp, arg.noise.lam), "descriptor layouts must match");
 
 static bool aug_side_ok(int v) { return v >= 1 && v <= PARSEQ_ROTATE_MAX_SIDE; }
 
@@ -139,6 +141,21 @@ static int check_augment(const parseq_augment_desc& d, int i) {
                                 h, w, op.out_height, op.out_width);
                 break;
             }
+            case PARSEQ_AUG_GAUSSIAN_BLUR: {
+                if (op.arg.blur.r < 0 || op.arg.blur.r > AUG_BLUR_MAX_R)
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: blur radius r %d is out of range (0 .. %d)", i, k, op.arg.blur.r, AUG_BLUR_MAX_R);
+                const unsigned long long sum = (2ull * (unsigned)op.arg.blur.r + 1) * op.arg.blur.ww + 2ull * op.arg.blur.fw;
+                if (sum > (1ull << 24))
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: blur weights ww %u, fw %u are out of range ((2 r + 1) ww + 2 fw = %llu, above 2^24)",
+                                i, k, op.arg.blur.ww, op.arg.blur.fw, sum);
+                break;
+            }
+            case PARSEQ_AUG_POISSON_NOISE:
+                if (op.arg.noise.lam < 1 || op.arg.noise.lam > AUG_NOISE_MAX_LAM)
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: noise lam %d is out of range (1 .. %d)", i, k, op.arg.noise.lam, AUG_NOISE_MAX_LAM);
+                if (!(std::isfinite(op.arg.noise.p0) && op.arg.noise.p0 > 0.0 && op.arg.noise.p0 < 1.0))
+                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: noise p0 %g is out of range (exp(-lam): finite, in (0, 1))", i, k, op.arg.noise.p0);
+                break;
             default: return fail(PARSEQ_E_INVALID, "image %d, operator %d: unknown operator %d", i, k, op.op);
         }
         if (op.op != PARSEQ_AUG_AFFINE && op.op != PARSEQ_AUG_TURN && !same)

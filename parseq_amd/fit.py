@@ -58,6 +58,7 @@ from torch import Tensor
 from .train import one_cycle_lr
 
 SWA_ANNEAL_EPOCHS = 10
+AUGMENT_POLICIES = ('fourteen', 'reference')           # augment.RandAugment, augment.ReferenceRandAugment
 
 
 # ---- the schedule: pure functions ---------------------------------------------------------------------------------------------------
@@ -210,12 +211,14 @@ def _validate(system, loader) -> dict:
 def fit(system, train_set, val_set, max_epochs: int, val_check_interval: int, out_dir: Optional[str] = None,
         accumulate_grad_batches: int = 1, swa_epoch_start: float = 0.75, augment: bool = True, seed: int = 0, resume: Optional[str] = None,
         workers: int = 8, clip_val: float = 20.0, process_group=None, stop_after_epoch: Optional[int] = None,
-        keep_epoch_snapshots: bool = False, on_batch: Optional[Callable] = None) -> FitResult:
+        keep_epoch_snapshots: bool = False, on_batch: Optional[Callable] = None, augment_policy: str = 'fourteen') -> FitResult:
     """Train `system` (on the GPU) on `train_set`, validating on `val_set` (datasets of parseq_amd.data); see the module docstring.
 
     The batch size is `system.batch_size`, the hyper-parameter the learning rate is scaled with (base.py:98-101), the arithmetic of the
     step `system.train_precision`.  `seed` seeds the shuffle, the augmentation policy, the system's permutation / dropout generator and
-    torch's CPU generator.  `resume`: a checkpoint of this loop written under the same arguments.  For tests and experiments:
+    torch's CPU generator.  `augment_policy`: 'fourteen' (`augment.RandAugment`, the draws of every run so far) or 'reference'
+    (`augment.ReferenceRandAugment`: the reference's sixteen operators, GaussianBlur and PoissonNoise included).  `resume`: a checkpoint
+    of this loop written under the same arguments (one without `augment_policy` reads as 'fourteen').  For tests and experiments:
     `stop_after_epoch=e` returns after epoch e - 1 (schedule and SWA as for `max_epochs`, nothing transferred; `last.ckpt` resumes it),
     `keep_epoch_snapshots` writes `checkpoints/epoch_start=<e>.ckpt` at the start of every epoch, `on_batch(epoch, batch, loss)` is
     called after every batch's step has been enqueued."""
@@ -225,6 +228,8 @@ def fit(system, train_set, val_set, max_epochs: int, val_check_interval: int, ou
     dev = system.device
     if dev.type != 'cuda':
         raise RuntimeError('fit runs on the GPU (no CPU fallback); move the system to the device first')
+    if augment_policy not in AUGMENT_POLICIES:
+        raise ValueError(f'augment_policy {augment_policy!r} must be one of {AUGMENT_POLICIES}')
     name = system.hparams.get('name', 'parseq')
     if out_dir is None:
         out_dir = os.path.join('outputs', name, time.strftime('%Y-%m-%d_%H-%M-%S'))
@@ -233,7 +238,7 @@ def fit(system, train_set, val_set, max_epochs: int, val_check_interval: int, ou
     img_size, batch_size = tuple(system.hparams.img_size), int(system.batch_size)
     config = {'max_epochs': max_epochs, 'val_check_interval': val_check_interval, 'accumulate_grad_batches': accumulate_grad_batches,
               'swa_epoch_start': swa_epoch_start, 'augment': augment, 'seed': seed, 'batch_size': batch_size,
-              'train_precision': getattr(system, 'train_precision', 'fp32'), 'train_samples': len(train_set)}
+              'train_precision': getattr(system, 'train_precision', 'fp32'), 'train_samples': len(train_set), 'augment_policy': augment_policy}
 
     state = None
     if resume is not None:
@@ -241,12 +246,18 @@ def fit(system, train_set, val_set, max_epochs: int, val_check_interval: int, ou
         state = ckpt.get('fit')
         if not state:
             raise ValueError(f'{resume!r} holds no training state (not written by parseq_amd.fit)')
-        if state['config'] != config:
-            raise ValueError(f"resume under a different configuration: the checkpoint's {state['config']}, this run's {config}")
+        saved = dict(state['config'])
+        saved.setdefault('augment_policy', 'fourteen')     # checkpoints from before the key existed were drawn by the fourteen
+        if saved != config:
+            raise ValueError(f"resume under a different configuration: the checkpoint's {saved}, this run's {config}")
         system.load_state_dict(ckpt['state_dict'])
 
     system.train()
-    train_loader = Loader(train_set, batch_size, img_size, dev, shuffle=True, augment=augment, seed=seed, workers=workers)
+    policy = None
+    if augment and augment_policy == 'reference':
+        from .augment import ReferenceRandAugment
+        policy = ReferenceRandAugment(seed=seed)
+    train_loader = Loader(train_set, batch_size, img_size, dev, shuffle=True, augment=augment, seed=seed, workers=workers, policy=policy)
     val_loader = Loader(val_set, batch_size, img_size, dev, shuffle=False, augment=False, workers=workers)
     batches = len(train_loader)
     spe = optimiser_steps_per_epoch(batches, accumulate_grad_batches)

@@ -2,7 +2,8 @@
 """Train a model on a folder of labelled crops — the command line of the reference's `train.py:53-108` on the MI355X backend.
 
     ./train.py parseq-tiny --train_dir data/train --val_dir data/val [--max_epochs 20] [--batch_size 384] [--val_check_interval 1000]
-               [--accumulate_grad_batches 1] [--train_precision bf16x3] [--no_augment] [--ckpt_path run/checkpoints/last.ckpt]
+               [--accumulate_grad_batches 1] [--train_precision bf16x3] [--no_augment] [--augment_policy reference]
+               [--ckpt_path run/checkpoints/last.ckpt]
                [name:type=value ...]
     ./train.py pretrained=parseq --train_dir ... --val_dir ...          # fine-tune the released weights
 
@@ -32,6 +33,8 @@ def main(argv=None):
     parser.add_argument('--accumulate_grad_batches', type=int, default=1)
     parser.add_argument('--train_precision', default='bf16x3', choices=['fp32', 'bf16', 'bf16x3'])
     parser.add_argument('--no_augment', action='store_true', default=False)
+    parser.add_argument('--augment_policy', default='fourteen', choices=['fourteen', 'reference'],
+                        help="'reference': the reference's sixteen operators, GaussianBlur and PoissonNoise included")
     parser.add_argument('--swa_epoch_start', type=float, default=0.75)
     parser.add_argument('--ckpt_path', default=None, help='Resume from this checkpoint of an earlier run')
     parser.add_argument('--out_dir', default=None)
@@ -58,7 +61,7 @@ def main(argv=None):
         out_dir = os.path.dirname(os.path.dirname(os.path.abspath(args.ckpt_path)))
     result = fit(system, train_set, val_set, args.max_epochs, args.val_check_interval, out_dir=out_dir,
                  accumulate_grad_batches=args.accumulate_grad_batches, swa_epoch_start=args.swa_epoch_start, augment=not args.no_augment,
-                 seed=args.seed, resume=args.ckpt_path, workers=args.workers)
+                 seed=args.seed, resume=args.ckpt_path, workers=args.workers, augment_policy=args.augment_policy)
     for record in result.log:
         if record['event'] in ('validation', 'epoch'):
             print(record)
