@@ -206,6 +206,48 @@ int parseq_decode_ex(parseq_plan* p, const int32_t* tokens, int batch, int ctx_l
  * attend to THIS memory until the next encode / forward / set_memory. */
 int parseq_set_memory(parseq_plan* p, const float* memory, int batch, void* stream);
 
+/* ---- beam search (added under ABI 15: pure additions; the reference has none, DESIGN.md section 18 defines it) ------- */
+
+/* Beam-search AR decoding with N-best output for a PARSeq model of dec_depth 1, in every plan precision.  For `batch` crops, beam width
+ * W = beam_width (1 .. PARSEQ_BEAM_MAX_WIDTH, <= num_tokens - 2, batch * W <= the plan's max_batch) and num_steps as in parseq_forward:
+ *   hypothesis  a sequence of class ids (<eos> and the charset); score = sum over its positions of log_softmax(logits)[chosen], natural
+ *               log, fp32, the <eos> term included, no length normalisation
+ *   start       beam 0 = [<bos>] at score 0, beams 1 .. W-1 dead (score -inf; a dead beam offers no candidate)
+ *   step i      every live unfinished beam w offers its C candidates (w, c) at score[w] + logp[w][c], every finished beam itself at its
+ *               score; the W best become the new beams in rank order: higher score, then lower parent, then lower class (a finished
+ *               carry counts as class -1).  Picking <eos> finishes a beam; its later token slots hold pad_id
+ * All num_steps steps always run; the call makes no host read and does not synchronise.  Outputs (device, best first per image):
+ *   tokens_out   int32 [batch, W, num_steps]      lengths_out  int32 [batch, W] characters before <eos> (num_steps if there is none)
+ *   scores_out   fp32  [batch, W]                 finished_out uint8 [batch, W] 0 = no <eos> after the last step
+ * The encoder memory is replicated W times and projected through parseq_set_memory's path, so afterwards the plan's cached K / V are
+ * those of the replicated batch (last batch = batch * W) until the next encode / forward / set_memory.
+ * trace: NULL, or four nullable device pointers filled per step i (tests and diagnosis), rows in the order the decoder ran them:
+ *   logits    fp32  [num_steps][batch * W][C]             the step's logits
+ *   tokens_in int32 [num_steps][batch * W][num_steps]     the histories the step ran on (<bos> first, pad_id past position i)
+ *   parent    int32 [num_steps][batch * W]                new beam r's parent row within its image after the step (-1: dead)
+ *   score     fp32  [num_steps][batch * W]                new beam r's score after the step
+ * workspace: device, parseq_beam_workspace_bytes(...) bytes, the caller's; nothing is allocated inside the call.  Refused with
+ * PARSEQ_E_INVALID before any device work: dec_depth > 1 (its per-layer content cache would need re-parenting), a ViTSTR model, a width
+ * or batch outside the ranges above, a short workspace. */
+#define PARSEQ_BEAM_MAX_WIDTH 16
+typedef struct parseq_beam_trace {
+    float* logits;
+    int32_t* tokens_in;
+    int32_t* parent;
+    float* score;
+} parseq_beam_trace;
+size_t parseq_beam_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps);
+int parseq_forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                        int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                        const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream);
+/* One selection step alone on caller tensors (tests/test_beam.py), in place: logits fp32 [batch * W][C] of step `step`; tokens int32
+ * [batch * W][ldt] histories (step + 1 <= ldt <= 64; position step + 1 is written when it exists), scores fp32, finished uint8, lengths
+ * int32 [batch * W]; parent_out (may be NULL) and picked_out int32 [batch * W]: each new beam's parent (-1: dead) and the class it
+ * picked (pad_id for a finished carry or a dead slot). */
+int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
+                        uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
+                        void* stream);
+
 /* ViTSTR.forward (strhub/models/vitstr/system.py:76-82 -> vitstr/model.py:20-28) for a model created with
  * arch = PARSEQ_ARCH_VITSTR: encoder with class token, head on tokens [1, num_steps], i.e. logits_out fp32
  * [batch, num_steps, num_tokens - 2] with num_steps = min(max_length, max_label_length) + 1.  images as parseq_forward. */

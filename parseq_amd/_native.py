@@ -61,6 +61,11 @@ class AugmentDesc(C.Structure):
                 ('reserved', C.c_int32), ('ops', AugmentOp * 3)]
 
 
+class BeamTrace(C.Structure):
+    """parseq_beam_trace: four nullable device pointers parseq_forward_beam fills per step."""
+    _fields_ = [('logits', C.c_void_p), ('tokens_in', C.c_void_p), ('parent', C.c_void_p), ('score', C.c_void_p)]
+
+
 class GemmOperand(C.Structure):
     _fields_ = [('data', C.c_void_p), ('dtype', C.c_int32), ('outer_stride', C.c_int64), ('k_stride', C.c_int64)]
 
@@ -127,6 +132,11 @@ SIGNATURES = {
     'parseq_decode_ex': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_set_memory': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'parseq_beam_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    'parseq_forward_beam': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(BeamTrace), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_op_beam_step': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'parseq_vitstr_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'parseq_decode_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,5 +1,6 @@
 // libparseq_hip.so — launch orchestration of the decoder passes, the AR loop, refinement and parseq_forward.
 #include "lib_internal.h"
+#include "beam.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -624,4 +625,115 @@ extern "C" int parseq_set_memory(parseq_plan* p, const float* memory, int batch,
     DevGuard dg(p->m->device);
     SplitScope ss(p->precision == PARSEQ_BF16X3);
     return dispatch_t(p, [&](auto te) { return set_memory_impl<typename decltype(te)::T>(p, memory, batch, (hipStream_t)stream); });
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// beam search
+// -------------------------------------------------------------------------------------------------------------------
+// The caller's workspace: the encoder memory of the crops, its W-fold replication (set_memory_impl's operand), one step's logits and the
+// beams' scores / lengths / last picks / flags.  The histories live in p->tok, where the self-attention kernels read them.
+struct BeamWs { size_t memory, memory_rep, logits, score, length, picked, finished, total; };
+static BeamWs beam_ws(const parseq_plan* p, int batch, int W) {
+    const parseq_model* m = p->m;
+    const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim * sizeof(float);
+    BeamWs o; size_t off = 0;
+    o.memory = carve(off, (size_t)batch * img);
+    o.memory_rep = carve(off, rows * img);
+    o.logits = carve(off, rows * m->classes * sizeof(float));
+    o.score = carve(off, rows * sizeof(float));
+    o.length = carve(off, rows * sizeof(int));
+    o.picked = carve(off, rows * sizeof(int));
+    o.finished = carve(off, rows);
+    o.total = off;
+    return o;
+}
+
+static int beam_check(const parseq_plan* p, int batch, int W, int num_steps) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    const parseq_model* m = p->m;
+    if (m->vitstr) return fail(PARSEQ_E_INVALID, "beam search on a ViTSTR model: it has no AR loop");
+    if (m->cfg.dec_depth > 1) return fail(PARSEQ_E_INVALID, "beam search at dec_depth %d: only dec_depth 1 (a deeper decoder's per-layer content cache would need re-parenting)", m->cfg.dec_depth);
+    if (W < 1 || W > PARSEQ_BEAM_MAX_WIDTH || W > m->classes) return fail(PARSEQ_E_INVALID, "beam_width %d outside [1, min(%d, %d classes)]", W, PARSEQ_BEAM_MAX_WIDTH, m->classes);
+    if (batch <= 0 || (long long)batch * W > p->max_batch) return fail(PARSEQ_E_INVALID, "batch %d x beam_width %d rows outside (0, %d]", batch, W, p->max_batch);
+    const int npos = m->cfg.max_label_length + 1;
+    if (num_steps < 1 || num_steps > npos) return fail(PARSEQ_E_INVALID, "num_steps %d outside [1, %d]", num_steps, npos);
+    if (beam_step_lds(W, m->classes, LDT) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", W, m->classes);
+    return 0;
+}
+
+extern "C" size_t parseq_beam_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps) {
+    if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
+    return beam_ws(p, batch, beam_width).total;
+}
+
+static int launch_beam_step(hipStream_t s, const float* logits, int batch, int W, int C, int step, int* tok, int ldt, float* score,
+                            unsigned char* finished, int* length, int* parent_out, int* picked, int eos_id, int pad_id) {
+    return launch(beam_step_kernel, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, ldt), s, logits, W, C, step, tok, ldt, score, finished,
+                  length, parent_out, picked, eos_id, pad_id);
+}
+
+template <typename T, int E>
+static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char* ws, const BeamWs& o, int32_t* tokens_out, float* scores_out,
+                     int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* tr, hipStream_t s) {
+    const parseq_config& c = p->m->cfg;
+    const int C = p->m->classes, rows = B * W;
+    const float* memory = reinterpret_cast<const float*>(ws + o.memory);
+    float* memory_rep = reinterpret_cast<float*>(ws + o.memory_rep);
+    float* logits = reinterpret_cast<float*>(ws + o.logits);
+    float* score = reinterpret_cast<float*>(ws + o.score);
+    int* length = reinterpret_cast<int*>(ws + o.length);
+    int* picked = reinterpret_cast<int*>(ws + o.picked);
+    unsigned char* finished = ws + o.finished;
+    // every beam of an image attends to that image's memory: W copies through the projection every caller-supplied memory takes
+    const size_t per_img4 = (size_t)p->m->tokens * E / 4, total4 = per_img4 * rows;
+    CHK(launch(beam_replicate_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(memory),
+               reinterpret_cast<float4*>(memory_rep), per_img4, W, total4));
+    CHK(set_memory_impl<T>(p, memory_rep, rows, s));
+    CHK(launch(beam_init_kernel, dim3((rows * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, W, c.bos_id, c.pad_id, score, finished, length, picked));
+    const DecW<T> w = dec_weights<T>(p);
+    DecPass a; a.B = rows; a.Lq = 1; a.Ltot = 1; a.argmax_mode = 0; a.fused_step_allowed = false;
+    for (int i = 0; i < num_steps; ++i) {
+        // the per-operation step on every beam's history; a pass writes row b of a [B][Ltot][C] tensor at position i0: base shifted back (decode_entry)
+        a.Lk = i + 1; a.i0 = a.c0 = i; a.logits = logits - (size_t)i * C;
+        CHK((decoder_pass<T, E>(p, s, w, a)));
+        if (tr && tr->logits) HIPCHK(hipMemcpyAsync(tr->logits + (size_t)i * rows * C, logits, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (tr && tr->tokens_in) HIPCHK(hipMemcpy2DAsync(tr->tokens_in + (size_t)i * rows * num_steps, num_steps * sizeof(int), p->tok, LDT * sizeof(int),
+                                                         num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
+        CHK(launch_beam_step(s, logits, B, W, C, i, p->tok, LDT, score, finished, length, tr && tr->parent ? tr->parent + (size_t)i * rows : nullptr,
+                             picked, c.eos_id, c.pad_id));
+        if (tr && tr->score) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+    return launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, num_steps, c.pad_id, score, finished,
+                  length, picked, tokens_out, scores_out, lengths_out, finished_out);
+}
+
+extern "C" int parseq_forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                   int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                   const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream) {
+    CHK(beam_check(p, batch, beam_width, num_steps));
+    CHK(check_call(p, batch, images_dtype));
+    if (!images || !tokens_out || !scores_out || !lengths_out || !finished_out || !workspace) return fail(PARSEQ_E_INVALID, "null images / output / workspace");
+    const BeamWs o = beam_ws(p, batch, beam_width);
+    if (workspace_bytes < o.total) return fail(PARSEQ_E_INVALID, "beam workspace of %zu bytes, %zu needed", workspace_bytes, o.total);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "beam workspace not 16-byte aligned");
+    DevGuard dg(p->m->device);
+    SplitScope ss(p->precision == PARSEQ_BF16X3);
+    hipStream_t s = (hipStream_t)stream;
+    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+    CHK(encode_dispatch(p, images, images_dtype, batch, reinterpret_cast<float*>(ws + o.memory), s));
+    return dispatch_te(p, [&](auto te) {
+        return beam_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, beam_width, num_steps, ws, o, tokens_out, scores_out, lengths_out,
+                                                                    finished_out, trace, s);
+    });
+}
+
+extern "C" int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
+                                   uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
+                                   void* stream) {
+    if (!logits || !tokens || !scores || !finished || !lengths || !picked_out) return fail(PARSEQ_E_INVALID, "null argument");
+    if (batch <= 0 || C < 1 || beam_width < 1 || beam_width > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d", batch, beam_width, PARSEQ_BEAM_MAX_WIDTH, C);
+    if (step < 0 || ldt < step + 1 || ldt > 64) return fail(PARSEQ_E_INVALID, "step %d / ldt %d: need step + 1 <= ldt <= 64", step, ldt);
+    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
+    if (beam_step_lds(beam_width, C, ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", beam_width, C);
+    return launch_beam_step((hipStream_t)stream, logits, batch, beam_width, C, step, tokens, ldt, scores, finished, lengths, parent_out, picked_out, eos_id, pad_id);
 }

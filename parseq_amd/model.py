@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Optional, Sequence
 
 import torch
@@ -22,6 +23,23 @@ from . import _native
 from .tokenizer import Tokenizer
 
 _PRECISIONS = {'bf16': _native.PARSEQ_BF16, 'fp32': _native.PARSEQ_F32, 'f32': _native.PARSEQ_F32, 'bf16x3': _native.PARSEQ_BF16X3}
+
+
+BEAM_MAX_WIDTH = 16      # PARSEQ_BEAM_MAX_WIDTH
+
+
+@dataclass
+class BeamResult:
+    """What `PARSeq.beam_search` returns, on the device, best hypothesis first per image."""
+    tokens: Tensor                       # int32 [B, W, num_steps] class ids; pad_id after a hypothesis' <eos> (and in every slot of a dead beam)
+    scores: Tensor                       # fp32 [B, W] sum of log-probabilities (natural log, <eos> included, no length normalisation)
+    lengths: Tensor                      # int32 [B, W] characters before <eos>
+    finished: Tensor                     # uint8 [B, W] 0 = no <eos> after the last step
+    # trace=True only, per step in the row order the decoder ran (row b * W + w):
+    trace_logits: Optional[Tensor] = None       # fp32 [num_steps, B * W, C]
+    trace_tokens_in: Optional[Tensor] = None    # int32 [num_steps, B * W, num_steps] the histories each step ran on
+    trace_parent: Optional[Tensor] = None       # int32 [num_steps, B * W] each new beam's parent within its image (-1: dead)
+    trace_score: Optional[Tensor] = None        # fp32 [num_steps, B * W] each new beam's score after the step
 
 
 def init_weights(module: nn.Module, name: str = '', exclude: Sequence[str] = ()):
@@ -558,6 +576,47 @@ class PARSeq(_NativeBacked):
         if return_length:
             return logits, out_len.value
         return logits if out_len.value == num_steps else logits[:, :out_len.value]
+
+    def beam_search(self, tokenizer: Tokenizer, images: Tensor, beam_width: int, max_length: Optional[int] = None,
+                    trace: bool = False) -> BeamResult:
+        """Beam-search AR decoding with N-best output (the reference has none): the `beam_width` best hypotheses
+        of every crop with their log-probabilities, best first, no refinement.  One library call on a plan of B * beam_width rows, no
+        host synchronisation; the result stays on the device (`tokenizer.decode_beams` reads it).  `max_length` as in `forward`, except
+        that all min(max_length, max_label_length) + 1 steps always run.  Afterwards the plan's cached memory K / V are the replicated
+        batch's, as after any `forward`."""
+        W = int(beam_width)
+        classes = self._cfg['num_tokens'] - 2
+        if self._cfg['dec_depth'] != 1:
+            raise ValueError(f"beam_search needs dec_depth == 1, this model has dec_depth = {self._cfg['dec_depth']} (a deeper decoder's "
+                             'per-layer content cache would have to be re-parented)')
+        if not 1 <= W <= min(BEAM_MAX_WIDTH, classes):
+            raise ValueError(f'beam_width must be in [1, {min(BEAM_MAX_WIDTH, classes)}] ({BEAM_MAX_WIDTH} at most, and no more than the {classes} classes), got {beam_width}')
+        max_length = self.max_label_length if max_length is None else min(max_length, self.max_label_length)
+        num_steps = max_length + 1
+        images = self._check_images(images)
+        B = images.shape[0]
+        plan = self._plan(B * W)
+        self._memory_key = None                  # this plan's cached K / V become the replicated batch's
+        if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
+            raise RuntimeError('tokenizer special ids changed after the native model was built')
+        lib, dev = _native.lib(), images.device
+        res = BeamResult(torch.empty(B, W, num_steps, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.float32, device=dev),
+                         torch.empty(B, W, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.uint8, device=dev))
+        tr = None
+        if trace:
+            res.trace_logits = torch.empty(num_steps, B * W, classes, dtype=torch.float32, device=dev)
+            res.trace_tokens_in = torch.empty(num_steps, B * W, num_steps, dtype=torch.int32, device=dev)
+            res.trace_parent = torch.empty(num_steps, B * W, dtype=torch.int32, device=dev)
+            res.trace_score = torch.empty(num_steps, B * W, dtype=torch.float32, device=dev)
+            tr = _native.BeamTrace(res.trace_logits.data_ptr(), res.trace_tokens_in.data_ptr(), res.trace_parent.data_ptr(), res.trace_score.data_ptr())
+        nbytes = lib.parseq_beam_workspace_bytes(plan, B, W, num_steps)
+        if nbytes == 0:
+            _native.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # the caller's: a block of torch's caching allocator, stream-ordered
+        _native.check(lib.parseq_forward_beam(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens),
+                                              _native.ptr(res.scores), _native.ptr(res.lengths), _native.ptr(res.finished),
+                                              C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes, _native.stream_ptr(self._device)))
+        return res
 
     # ---- native plumbing ---------------------------------------------------------------------------------------
     def _special_ids(self, tokenizer):

@@ -140,3 +140,17 @@ class Tokenizer(BaseTokenizer):
         ids, lengths, _, conf = self._postprocess(logits)
         ids_h, len_h = ids.cpu().numpy(), lengths.cpu().tolist()
         return [self._ids2tok(row[:k].tolist()) for row, k in zip(ids_h, len_h)], conf.cpu()
+
+    def decode_beams(self, result) -> List[List[Tuple[str, float]]]:
+        """The N-best of `beam_search` as strings: per image the hypotheses best first, each (label, log-probability).  Dead beams
+        (fewer hypotheses than the beam width, score -inf) are left out.  One copy to the host."""
+        b, w, steps = result.tokens.shape
+        packed = torch.cat([result.tokens.reshape(b * w, steps), result.lengths.reshape(b * w, 1).to(torch.int32),
+                            result.scores.reshape(b * w, 1).contiguous().view(torch.int32)], dim=1).cpu()
+        ids, lengths = packed[:, :steps].numpy(), packed[:, steps].tolist()
+        scores = packed[:, steps + 1].contiguous().view(torch.float32).tolist()
+        out = []
+        for i in range(b):
+            rows = range(i * w, (i + 1) * w)
+            out.append([(self._ids2tok(ids[r, :lengths[r]].tolist()), scores[r]) for r in rows if scores[r] != float('-inf')])
+        return out

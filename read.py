@@ -3,6 +3,7 @@
 
     ./read.py pretrained=parseq --images a.png b.jpg [--device cuda] [name:type=value ...]
     ./read.py path/to/lightning.ckpt --images *.png refine_iters:int=2 decode_ar:bool=false
+    ./read.py pretrained=parseq --images a.png --nbest 5 [--beam 8]     the 5 best readings with their log-probabilities under each line
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -30,18 +31,38 @@ def read_files(model, files, device='cuda'):
     return list(zip(files, labels, confidences.tolist()))
 
 
+@torch.inference_mode()
+def read_files_nbest(model, files, nbest, beam_width=None, device='cuda'):
+    """[(file, [(label, log-probability)] best first, at most `nbest`)] through one beam search of width `beam_width` (default `nbest`)."""
+    import numpy as np
+    crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+    if not crops:
+        return []
+    batch = resize_batch(crops, tuple(model.hparams.img_size))
+    beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width or nbest))
+    return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
+
+
 def main(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('checkpoint', help="Model checkpoint (or 'pretrained=<model_id>')")
     parser.add_argument('--images', nargs='+', help='Images to read')
     parser.add_argument('--device', default='cuda')
+    parser.add_argument('--nbest', type=int, default=0, help='Also print the N best readings with their log-probabilities (beam search)')
+    parser.add_argument('--beam', type=int, default=None, help='Beam width of --nbest (default: N)')
     args, unknown = parser.parse_known_args(argv)
     kwargs = parse_model_args(unknown)
     print(f'Additional keyword arguments: {kwargs}')
 
+    if args.beam is not None and (args.nbest <= 0 or args.beam < args.nbest):
+        parser.error('--beam needs --nbest N with N <= the beam width')
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
-    for fname, pred, _ in read_files(model, args.images or [], args.device):
+    files = args.images or []
+    alternatives = dict(read_files_nbest(model, files, args.nbest, args.beam, args.device)) if args.nbest > 0 else {}
+    for fname, pred, _ in read_files(model, files, args.device):
         print(f'{fname}: {pred}')
+        for label, logp in alternatives.get(fname, []):
+            print(f'    {logp:9.4f}  {label}')
 
 
 if __name__ == '__main__':
