@@ -248,6 +248,33 @@ int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, i
                         uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
                         void* stream);
 
+/* ---- lexicon-constrained beam search (pure additions under ABI 15; DESIGN.md section 19 defines it) ------------------ */
+
+/* parseq_forward_beam over a lexicon: the search offers only candidates that are still a prefix of a word, and changes no number — a
+ * score stays the model's log-probability of the reading (the log-soft-max runs over all C classes, nothing is renormalised).
+ *   trie_next  device int32 [trie_nodes][C], C = num_tokens - 2 head classes: next[n][c] >= 0 is the child of node n along class c;
+ *              next[n][eos_id] >= 0 says a word ends at n and is its word id; any negative entry is "not allowed".  Several tries may
+ *              share the table (a forest).  The contents are the caller's: a child id >= trie_nodes is treated as not allowed
+ *   roots      device int32 [batch], each image's root node, or NULL: node 0 for every image.  A root outside [0, trie_nodes) starts its
+ *              image with every beam dead
+ *   words_out  device int32 [batch, W]: the word id of each finished hypothesis, -1 otherwise (unfinished or dead)
+ * Every other argument, output and refusal is parseq_forward_beam's; also refused: a NULL table or words_out, trie_nodes < 1.  A word of
+ * more than num_steps - 1 characters cannot finish and comes back with finished 0.  If the trie under an image's root holds at most W
+ * words no candidate is ever dropped: the finished results are that lexicon, ranked by teacher-forced log-probability.
+ * workspace: parseq_beam_lexicon_workspace_bytes(...) bytes — parseq_beam_workspace_bytes' parts, then node and word int32 [batch * W].
+ * No host synchronisation and no allocation inside the call. */
+size_t parseq_beam_lexicon_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps);
+int parseq_forward_beam_lexicon(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
+                                const int32_t* trie_next, int trie_nodes, const int32_t* roots, int32_t* words_out);
+/* parseq_op_beam_step under a lexicon (tests/test_lexicon_beam.py): its arguments, then the table as above and, in place, nodes and
+ * words int32 [batch * W]: each beam's trie node (-1 for a dead beam; a live unfinished beam whose node is outside [0, trie_nodes) offers
+ * nothing) and the word id of a finished beam (-1 otherwise). */
+int parseq_op_beam_step_lexicon(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
+                                uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
+                                void* stream, const int32_t* trie_next, int trie_nodes, int32_t* nodes, int32_t* words);
+
 /* ViTSTR.forward (strhub/models/vitstr/system.py:76-82 -> vitstr/model.py:20-28) for a model created with
  * arch = PARSEQ_ARCH_VITSTR: encoder with class token, head on tokens [1, num_steps], i.e. logits_out fp32
  * [batch, num_steps, num_tokens - 2] with num_steps = min(max_length, max_label_length) + 1.  images as parseq_forward. */

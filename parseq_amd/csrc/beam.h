@@ -1,7 +1,8 @@
 // Beam search over the AR decoder: the per-step selection kernel, the replication of the encoder memory over the
 // beams of an image, and the small init / write-out kernels.  A beam is a token history (a row of the plan's pitched token array), a
 // score, a finished flag and a length; at decoder depth 1 the self-attention keys are table lookups by (token id, position), so
-// re-parenting a beam is a copy of its history row and nothing else.
+// re-parenting a beam is a copy of its history row and nothing else.  Under a lexicon a beam also carries the trie node
+// its history has reached and, once finished, the id of the word it spelled.
 #pragma once
 #include "common.h"
 
@@ -20,6 +21,10 @@ __device__ __forceinline__ unsigned beam_ordered(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// The lexicon of a constrained step: the dense trie table next [nodes][C] (a negative entry: not allowed; the <eos> column holds word ids)
+// and, per beam row and in place, the node reached and the word finished (-1: none).  Unused by the unconstrained instantiation.
+struct BeamLex { const int* next; int nodes; int* node; int* word; };
+
 // One selection step of one image per workgroup.  In: logits [B * W][C] of the step, and the image's W beams in place — history rows
 // tok[(b W + w) ldt ..], score, finished, length.  Candidates: every live unfinished beam w offers (w, c) at score[w] +
 // log_softmax(logits[w])[c], every finished beam itself at its score (class -1), a dead beam (score -inf) nothing.  The W best become the
@@ -27,20 +32,28 @@ __device__ __forceinline__ unsigned beam_ordered(float v) {
 // score -inf, parent -1, its own row's history kept.  Position step + 1 of a new history holds the picked class (pad_id for a carry or
 // a dead slot); picked[] repeats it for a caller whose rows have no such position (step + 1 == ldt).
 // The histories are re-parented through LDS: every row of the image is loaded before the barrier and written after it.
+// LEX: a live unfinished beam at node n offers (w, c) only where next[n][c] >= 0 (and, for a character, < nodes: the table is the caller's
+// device data, a child id past it is treated as not allowed, as is every class of a beam whose own node is outside [0, nodes)).  The scores
+// are the unconstrained ones: the log-soft-max runs over all C classes.  A new beam's node is next[node_parent][c]; picking <eos> keeps the
+// node and records word = next[node][eos_id]; a carry keeps both; a dead slot holds -1 / -1.  Nodes and words are re-parented like the
+// histories: all W loaded before the first barrier, written after the last.
+template <bool LEX>
 static __global__ __launch_bounds__(BEAM_THREADS)
 void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, int* __restrict__ tok, int ldt, float* __restrict__ score,
                       unsigned char* __restrict__ finished, int* __restrict__ length, int* __restrict__ parent_out, int* __restrict__ picked,
-                      int eos_id, int pad_id) {
+                      int eos_id, int pad_id, BeamLex lx) {
     extern __shared__ float beam_smem[];
     float* cand = beam_smem;                                       // [W * C] fresh candidates, then [W] carries
     int* hist = reinterpret_cast<int*>(beam_smem + (size_t)W * C + W);
     __shared__ float s_score[BEAM_MAX_W], sel_score[BEAM_MAX_W];
     __shared__ int s_len[BEAM_MAX_W], sel_parent[BEAM_MAX_W], sel_cls[BEAM_MAX_W];
     __shared__ unsigned char s_fin[BEAM_MAX_W];
+    __shared__ int s_node[LEX ? BEAM_MAX_W : 1], s_word[LEX ? BEAM_MAX_W : 1];
     __shared__ unsigned long long s_wkey[BEAM_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t row0 = (size_t)blockIdx.x * W;
     if (tid < W) { s_score[tid] = score[row0 + tid]; s_fin[tid] = finished[row0 + tid]; s_len[tid] = length[row0 + tid]; }
+    if constexpr (LEX) { if (tid < W) { s_node[tid] = lx.node[row0 + tid]; s_word[tid] = lx.word[row0 + tid]; } }
     for (int i = tid; i < W * ldt; i += BEAM_THREADS) hist[i] = tok[row0 * ldt + i];
     __syncthreads();
 
@@ -57,9 +70,15 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
             float sum = 0.f;
             for (int c = lane; c < C; c += 64) sum += expf(row[c] - m);
             const float lg = logf(wave_sum(sum));
+            const int* allowed = nullptr;      // LEX: the node's row of the table, null for a node outside it
+            if constexpr (LEX) { const int nd = s_node[w]; if (nd >= 0 && nd < lx.nodes) allowed = lx.next + (size_t)nd * C; }
             for (int c = lane; c < C; c += 64) {
                 float v = sc + ((row[c] - m) - lg);
                 if (v == 0.f) v = 0.f;      // one zero: the ordering below is on the bits
+                if constexpr (LEX) {
+                    const int t = allowed ? allowed[c] : -1;
+                    if (t < 0 || (c != eos_id && t >= lx.nodes)) v = -INFINITY;
+                }
                 out[c] = v;
             }
         } else {
@@ -122,6 +141,16 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
         length[row0 + tid] = dead ? 0 : (carry ? s_len[par] : (cls == eos_id ? step : step + 1));
         picked[row0 + tid] = cls >= 0 ? cls : pad_id;
         if (parent_out) parent_out[row0 + tid] = par;
+        if constexpr (LEX) {
+            int nd = -1, wd = -1;
+            if (carry) { nd = s_node[par]; wd = s_word[par]; }
+            else if (!dead) {      // a picked class was allowed, so the parent's node is inside the table
+                nd = s_node[par];
+                const int t = lx.next[(size_t)nd * C + cls];
+                if (cls == eos_id) wd = t; else nd = t;
+            }
+            lx.node[row0 + tid] = nd; lx.word[row0 + tid] = wd;
+        }
     }
 }
 
@@ -140,6 +169,27 @@ static __global__ void beam_init_kernel(int* __restrict__ tok, int ldt, int rows
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < rows * ldt) tok[i] = (i % ldt == 0) ? bos_id : pad_id;
     if (i < rows) { score[i] = (i % W == 0) ? 0.f : -INFINITY; finished[i] = 0; length[i] = 0; picked[i] = pad_id; }
+}
+
+// The start under a lexicon, after beam_init_kernel: beam 0 of image b stands at roots[b] (0 without roots), the others at -1; an image whose
+// root is outside [0, nodes) starts with every beam dead.
+static __global__ void beam_init_lexicon_kernel(int rows, int W, const int* __restrict__ roots, int nodes, float* __restrict__ score,
+                                                int* __restrict__ node, int* __restrict__ word) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    int nd = -1;
+    if (i % W == 0) {
+        nd = roots ? roots[i / W] : 0;
+        if (nd < 0 || nd >= nodes) { nd = -1; score[i] = -INFINITY; }
+    }
+    node[i] = nd; word[i] = -1;
+}
+
+// The write-out under a lexicon, beside beam_finish_kernel: words_out [rows], the word id of a finished hypothesis, -1 otherwise.
+static __global__ void beam_finish_lexicon_kernel(int rows, const float* __restrict__ score, const unsigned char* __restrict__ finished,
+                                                  const int* __restrict__ word, int* __restrict__ words_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) words_out[i] = (score[i] > -INFINITY && finished[i]) ? word[i] : -1;
 }
 
 // The write-out: the beams are in rank order after every step, so this only drops <bos> and the pitch.  tokens_out [rows][num_steps];

@@ -632,8 +632,9 @@ extern "C" int parseq_set_memory(parseq_plan* p, const float* memory, int batch,
 // -------------------------------------------------------------------------------------------------------------------
 // The caller's workspace: the encoder memory of the crops, its W-fold replication (set_memory_impl's operand), one step's logits and the
 // beams' scores / lengths / last picks / flags.  The histories live in p->tok, where the self-attention kernels read them.
-struct BeamWs { size_t memory, memory_rep, logits, score, length, picked, finished, total; };
-static BeamWs beam_ws(const parseq_plan* p, int batch, int W) {
+// Under a lexicon (section 19) two more parts follow: every beam's trie node and word id.
+struct BeamWs { size_t memory, memory_rep, logits, score, length, picked, finished, node, word, total; };
+static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon = false) {
     const parseq_model* m = p->m;
     const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim * sizeof(float);
     BeamWs o; size_t off = 0;
@@ -644,6 +645,8 @@ static BeamWs beam_ws(const parseq_plan* p, int batch, int W) {
     o.length = carve(off, rows * sizeof(int));
     o.picked = carve(off, rows * sizeof(int));
     o.finished = carve(off, rows);
+    o.node = o.word = 0;
+    if (lexicon) { o.node = carve(off, rows * sizeof(int)); o.word = carve(off, rows * sizeof(int)); }
     o.total = off;
     return o;
 }
@@ -666,15 +669,21 @@ extern "C" size_t parseq_beam_workspace_bytes(const parseq_plan* p, int batch, i
     return beam_ws(p, batch, beam_width).total;
 }
 
+// lx: null for the unconstrained step
 static int launch_beam_step(hipStream_t s, const float* logits, int batch, int W, int C, int step, int* tok, int ldt, float* score,
-                            unsigned char* finished, int* length, int* parent_out, int* picked, int eos_id, int pad_id) {
-    return launch(beam_step_kernel, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, ldt), s, logits, W, C, step, tok, ldt, score, finished,
-                  length, parent_out, picked, eos_id, pad_id);
+                            unsigned char* finished, int* length, int* parent_out, int* picked, int eos_id, int pad_id, const BeamLex* lx = nullptr) {
+    if (lx) return launch(beam_step_kernel<true>, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, ldt), s, logits, W, C, step, tok, ldt, score,
+                          finished, length, parent_out, picked, eos_id, pad_id, *lx);
+    return launch(beam_step_kernel<false>, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, ldt), s, logits, W, C, step, tok, ldt, score, finished,
+                  length, parent_out, picked, eos_id, pad_id, BeamLex{});
 }
+
+// What a constrained search adds to beam_impl's arguments: the caller's table, roots and output.
+struct BeamLexCall { const int32_t* next; int nodes; const int32_t* roots; int32_t* words_out; };
 
 template <typename T, int E>
 static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char* ws, const BeamWs& o, int32_t* tokens_out, float* scores_out,
-                     int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* tr, hipStream_t s) {
+                     int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* tr, hipStream_t s, const BeamLexCall* lc = nullptr) {
     const parseq_config& c = p->m->cfg;
     const int C = p->m->classes, rows = B * W;
     const float* memory = reinterpret_cast<const float*>(ws + o.memory);
@@ -690,6 +699,11 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char*
                reinterpret_cast<float4*>(memory_rep), per_img4, W, total4));
     CHK(set_memory_impl<T>(p, memory_rep, rows, s));
     CHK(launch(beam_init_kernel, dim3((rows * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, W, c.bos_id, c.pad_id, score, finished, length, picked));
+    BeamLex lx{};
+    if (lc) {
+        lx = BeamLex{lc->next, lc->nodes, reinterpret_cast<int*>(ws + o.node), reinterpret_cast<int*>(ws + o.word)};
+        CHK(launch(beam_init_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, W, lc->roots, lc->nodes, score, lx.node, lx.word));
+    }
     const DecW<T> w = dec_weights<T>(p);
     DecPass a; a.B = rows; a.Lq = 1; a.Ltot = 1; a.argmax_mode = 0; a.fused_step_allowed = false;
     for (int i = 0; i < num_steps; ++i) {
@@ -700,20 +714,23 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char*
         if (tr && tr->tokens_in) HIPCHK(hipMemcpy2DAsync(tr->tokens_in + (size_t)i * rows * num_steps, num_steps * sizeof(int), p->tok, LDT * sizeof(int),
                                                          num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
         CHK(launch_beam_step(s, logits, B, W, C, i, p->tok, LDT, score, finished, length, tr && tr->parent ? tr->parent + (size_t)i * rows : nullptr,
-                             picked, c.eos_id, c.pad_id));
+                             picked, c.eos_id, c.pad_id, lc ? &lx : nullptr));
         if (tr && tr->score) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
+    if (lc) CHK(launch(beam_finish_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, score, finished, lx.word, lc->words_out));
     return launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, num_steps, c.pad_id, score, finished,
                   length, picked, tokens_out, scores_out, lengths_out, finished_out);
 }
 
-extern "C" int parseq_forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
-                                   int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
-                                   const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream) {
+static int forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps, int32_t* tokens_out,
+                        float* scores_out, int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* trace, void* workspace,
+                        size_t workspace_bytes, void* stream, const BeamLexCall* lc) {
     CHK(beam_check(p, batch, beam_width, num_steps));
     CHK(check_call(p, batch, images_dtype));
     if (!images || !tokens_out || !scores_out || !lengths_out || !finished_out || !workspace) return fail(PARSEQ_E_INVALID, "null images / output / workspace");
-    const BeamWs o = beam_ws(p, batch, beam_width);
+    if (lc && (!lc->next || !lc->words_out)) return fail(PARSEQ_E_INVALID, "null trie table / words output");
+    if (lc && lc->nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", lc->nodes);
+    const BeamWs o = beam_ws(p, batch, beam_width, lc != nullptr);
     if (workspace_bytes < o.total) return fail(PARSEQ_E_INVALID, "beam workspace of %zu bytes, %zu needed", workspace_bytes, o.total);
     if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "beam workspace not 16-byte aligned");
     DevGuard dg(p->m->device);
@@ -723,8 +740,30 @@ extern "C" int parseq_forward_beam(parseq_plan* p, const void* images, int image
     CHK(encode_dispatch(p, images, images_dtype, batch, reinterpret_cast<float*>(ws + o.memory), s));
     return dispatch_te(p, [&](auto te) {
         return beam_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, beam_width, num_steps, ws, o, tokens_out, scores_out, lengths_out,
-                                                                    finished_out, trace, s);
+                                                                    finished_out, trace, s, lc);
     });
+}
+
+extern "C" int parseq_forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                   int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                   const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream) {
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
+                        workspace_bytes, stream, nullptr);
+}
+
+// lexicon-constrained beam search
+extern "C" size_t parseq_beam_lexicon_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps) {
+    if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
+    return beam_ws(p, batch, beam_width, true).total;
+}
+
+extern "C" int parseq_forward_beam_lexicon(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                           int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                           const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
+                                           const int32_t* trie_next, int trie_nodes, const int32_t* roots, int32_t* words_out) {
+    const BeamLexCall lc{trie_next, trie_nodes, roots, words_out};
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
+                        workspace_bytes, stream, &lc);
 }
 
 extern "C" int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
@@ -736,4 +775,17 @@ extern "C" int parseq_op_beam_step(const float* logits, int batch, int beam_widt
     if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
     if (beam_step_lds(beam_width, C, ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", beam_width, C);
     return launch_beam_step((hipStream_t)stream, logits, batch, beam_width, C, step, tokens, ldt, scores, finished, lengths, parent_out, picked_out, eos_id, pad_id);
+}
+
+extern "C" int parseq_op_beam_step_lexicon(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
+                                           uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
+                                           void* stream, const int32_t* trie_next, int trie_nodes, int32_t* nodes, int32_t* words) {
+    if (!logits || !tokens || !scores || !finished || !lengths || !picked_out || !trie_next || !nodes || !words) return fail(PARSEQ_E_INVALID, "null argument");
+    if (batch <= 0 || C < 1 || beam_width < 1 || beam_width > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d", batch, beam_width, PARSEQ_BEAM_MAX_WIDTH, C);
+    if (step < 0 || ldt < step + 1 || ldt > 64) return fail(PARSEQ_E_INVALID, "step %d / ldt %d: need step + 1 <= ldt <= 64", step, ldt);
+    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
+    if (trie_nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", trie_nodes);
+    if (beam_step_lds(beam_width, C, ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", beam_width, C);
+    const BeamLex lx{trie_next, trie_nodes, nodes, words};
+    return launch_beam_step((hipStream_t)stream, logits, batch, beam_width, C, step, tokens, ldt, scores, finished, lengths, parent_out, picked_out, eos_id, pad_id, &lx);
 }

@@ -42,6 +42,12 @@ class BeamResult:
     trace_score: Optional[Tensor] = None        # fp32 [num_steps, B * W] each new beam's score after the step
 
 
+@dataclass
+class LexiconBeamResult(BeamResult):
+    """`beam_search(..., lexicon=...)`: a `BeamResult` and each hypothesis' word."""
+    words: Optional[Tensor] = None       # int32 [B, W] index into `lexicon.words` of a finished hypothesis, -1 otherwise
+
+
 def init_weights(module: nn.Module, name: str = '', exclude: Sequence[str] = ()):
     """Initialisation scheme of the reference (`strhub/models/utils.py:107-125`): trunc-normal(0.02) Linear / Embedding
     weights, zero biases, unit LayerNorm, Kaiming-normal(fan_out) convolutions.  This is a deliberate statement-for-statement
@@ -578,12 +584,16 @@ class PARSeq(_NativeBacked):
         return logits if out_len.value == num_steps else logits[:, :out_len.value]
 
     def beam_search(self, tokenizer: Tokenizer, images: Tensor, beam_width: int, max_length: Optional[int] = None,
-                    trace: bool = False) -> BeamResult:
+                    trace: bool = False, lexicon=None, roots: Optional[Tensor] = None) -> BeamResult:
         """Beam-search AR decoding with N-best output (the reference has none): the `beam_width` best hypotheses
         of every crop with their log-probabilities, best first, no refinement.  One library call on a plan of B * beam_width rows, no
         host synchronisation; the result stays on the device (`tokenizer.decode_beams` reads it).  `max_length` as in `forward`, except
         that all min(max_length, max_label_length) + 1 steps always run.  Afterwards the plan's cached memory K / V are the replicated
-        batch's, as after any `forward`."""
+        batch's, as after any `forward`.
+
+        `lexicon` (a `parseq_amd.lexicon.Lexicon`) constrains the search to prefixes of its words, the scores staying
+        the model's log-probabilities; `roots` (int32 [B], from `Lexicon.forest`) gives every crop its own trie, none means node 0.  The
+        result is then a `LexiconBeamResult` whose `words` index `lexicon.words`."""
         W = int(beam_width)
         classes = self._cfg['num_tokens'] - 2
         if self._cfg['dec_depth'] != 1:
@@ -591,6 +601,14 @@ class PARSeq(_NativeBacked):
                              'per-layer content cache would have to be re-parented)')
         if not 1 <= W <= min(BEAM_MAX_WIDTH, classes):
             raise ValueError(f'beam_width must be in [1, {min(BEAM_MAX_WIDTH, classes)}] ({BEAM_MAX_WIDTH} at most, and no more than the {classes} classes), got {beam_width}')
+        if lexicon is None and roots is not None:
+            raise ValueError('beam_search: roots without a lexicon')
+        if lexicon is not None and (lexicon.next.dim() != 2 or lexicon.next.shape[1] != classes or lexicon.next.dtype != torch.int32
+                                    or lexicon.next.shape[0] < 1):
+            raise ValueError(f'beam_search: the lexicon table must be int32 [nodes, {classes}] (one column per head class), got '
+                             f'{lexicon.next.dtype} {tuple(lexicon.next.shape)}')
+        if roots is not None and (roots.dim() != 1 or roots.shape[0] != images.shape[0]):
+            raise ValueError(f'beam_search: roots must be [batch] = [{images.shape[0]}], got {tuple(roots.shape)}')
         max_length = self.max_label_length if max_length is None else min(max_length, self.max_label_length)
         num_steps = max_length + 1
         images = self._check_images(images)
@@ -600,8 +618,9 @@ class PARSeq(_NativeBacked):
         if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
             raise RuntimeError('tokenizer special ids changed after the native model was built')
         lib, dev = _native.lib(), images.device
-        res = BeamResult(torch.empty(B, W, num_steps, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.float32, device=dev),
-                         torch.empty(B, W, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.uint8, device=dev))
+        res = (BeamResult if lexicon is None else LexiconBeamResult)(
+            torch.empty(B, W, num_steps, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.float32, device=dev),
+            torch.empty(B, W, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.uint8, device=dev))
         tr = None
         if trace:
             res.trace_logits = torch.empty(num_steps, B * W, classes, dtype=torch.float32, device=dev)
@@ -609,6 +628,8 @@ class PARSeq(_NativeBacked):
             res.trace_parent = torch.empty(num_steps, B * W, dtype=torch.int32, device=dev)
             res.trace_score = torch.empty(num_steps, B * W, dtype=torch.float32, device=dev)
             tr = _native.BeamTrace(res.trace_logits.data_ptr(), res.trace_tokens_in.data_ptr(), res.trace_parent.data_ptr(), res.trace_score.data_ptr())
+        if lexicon is not None:
+            return self._beam_search_lexicon(lexicon, roots, images, plan, res, tr, B, W, num_steps)
         nbytes = lib.parseq_beam_workspace_bytes(plan, B, W, num_steps)
         if nbytes == 0:
             _native.check(-1)
@@ -616,6 +637,23 @@ class PARSeq(_NativeBacked):
         _native.check(lib.parseq_forward_beam(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens),
                                               _native.ptr(res.scores), _native.ptr(res.lengths), _native.ptr(res.finished),
                                               C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes, _native.stream_ptr(self._device)))
+        return res
+
+    def _beam_search_lexicon(self, lexicon, roots, images, plan, res, tr, B, W, num_steps):
+        lib, dev = _native.lib(), images.device
+        table = lexicon.table(dev)
+        if roots is not None:
+            roots = roots.to(dev, torch.int32).contiguous()
+        res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
+        nbytes = lib.parseq_beam_lexicon_workspace_bytes(plan, B, W, num_steps)
+        if nbytes == 0:
+            _native.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.parseq_forward_beam_lexicon(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps,
+                                                      _native.ptr(res.tokens), _native.ptr(res.scores), _native.ptr(res.lengths),
+                                                      _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes,
+                                                      _native.stream_ptr(self._device), _native.ptr(table), table.shape[0],
+                                                      _native.ptr(roots) if roots is not None else None, _native.ptr(res.words)))
         return res
 
     # ---- native plumbing ---------------------------------------------------------------------------------------

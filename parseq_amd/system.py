@@ -249,10 +249,13 @@ class PARSeq(nn.Module):
         refinement and `max_length=None` (the batch-level early exit of model.py:144-145)."""
         return self.model.forward(self.tokenizer, images, max_length, slot, return_length=True)
 
-    def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None):
+    def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None):
         """The `beam_width` best readings of every crop with their log-probabilities (model.PARSeq.beam_search):
-        a `BeamResult` on the device, `self.tokenizer.decode_beams(result)` turns it into strings."""
-        return self.model.beam_search(self.tokenizer, images, beam_width, max_length)
+        a `BeamResult` on the device, `self.tokenizer.decode_beams(result)` turns it into strings.  With a `lexicon` (and per-crop `roots`,
+        section 19) only words of the list are read; `self.tokenizer.decode_beams(result, lexicon)` returns them in the list's spelling."""
+        if lexicon is None and roots is None:
+            return self.model.beam_search(self.tokenizer, images, beam_width, max_length)
+        return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots)
 
     # ---- evaluation glue used by the reference's test.py:121-126 ------------------------------------------------
     def _eval_step(self, batch, validation: bool):

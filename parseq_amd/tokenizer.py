@@ -141,16 +141,29 @@ class Tokenizer(BaseTokenizer):
         ids_h, len_h = ids.cpu().numpy(), lengths.cpu().tolist()
         return [self._ids2tok(row[:k].tolist()) for row, k in zip(ids_h, len_h)], conf.cpu()
 
-    def decode_beams(self, result) -> List[List[Tuple[str, float]]]:
+    def decode_beams(self, result, lexicon=None) -> List[List[Tuple[str, float]]]:
         """The N-best of `beam_search` as strings: per image the hypotheses best first, each (label, log-probability).  Dead beams
-        (fewer hypotheses than the beam width, score -inf) are left out.  One copy to the host."""
+        (fewer hypotheses than the beam width, score -inf) are left out.  One copy to the host.  With the `lexicon` the search ran under,
+        a finished hypothesis comes back in the lexicon's spelling, `lexicon.words[word id]` (an unfinished one, a prefix of a word too
+        long for the steps that ran, as the characters read)."""
         b, w, steps = result.tokens.shape
-        packed = torch.cat([result.tokens.reshape(b * w, steps), result.lengths.reshape(b * w, 1).to(torch.int32),
-                            result.scores.reshape(b * w, 1).contiguous().view(torch.int32)], dim=1).cpu()
+        parts = [result.tokens.reshape(b * w, steps), result.lengths.reshape(b * w, 1).to(torch.int32),
+                 result.scores.reshape(b * w, 1).contiguous().view(torch.int32)]
+        if lexicon is not None:
+            if getattr(result, 'words', None) is None:
+                raise ValueError('decode_beams: a lexicon was given, but the result is not of a search under a lexicon (it has no `words`)')
+            parts.append(result.words.reshape(b * w, 1))
+        packed = torch.cat(parts, dim=1).cpu()
         ids, lengths = packed[:, :steps].numpy(), packed[:, steps].tolist()
         scores = packed[:, steps + 1].contiguous().view(torch.float32).tolist()
+        words = packed[:, steps + 2].tolist() if lexicon is not None else None
+
+        def label(r):
+            if words is not None and words[r] >= 0:
+                return lexicon.words[words[r]]
+            return self._ids2tok(ids[r, :lengths[r]].tolist())
         out = []
         for i in range(b):
             rows = range(i * w, (i + 1) * w)
-            out.append([(self._ids2tok(ids[r, :lengths[r]].tolist()), scores[r]) for r in rows if scores[r] != float('-inf')])
+            out.append([(label(r), scores[r]) for r in rows if scores[r] != float('-inf')])
         return out
