@@ -275,6 +275,49 @@ int parseq_op_beam_step_lexicon(const float* logits, int batch, int beam_width, 
                                 uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
                                 void* stream, const int32_t* trie_next, int trie_nodes, int32_t* nodes, int32_t* words);
 
+/* ---- cloze refinement of the N-best (pure additions under ABI 15; DESIGN.md section 20 defines it) ------------------- */
+
+/* parseq_forward_beam / parseq_forward_beam_lexicon followed by refine_iters iterations of the model's cloze refinement on every beam:
+ * the pass parseq_forward runs on its greedy reading (tgt_in = [<bos>, t[0 .. num_steps - 2]], keys from the first <eos> on padded, the
+ * cloze mask, all num_steps positions at once against the row's image memory) gives logits R[row][i][c]; lp = log_softmax(R[row][i]).
+ *   PARSEQ_BEAM_REFINE_SCORE  every hypothesis keeps its tokens and gets the pseudo-log-likelihood sum_{i <= last} lp[i][t[i]] as its score,
+ *                             last = its <eos> position, or num_steps - 1 without one.  refine_iters must be 1 (it is idempotent)
+ *   PARSEQ_BEAM_REFINE_EDIT   every hypothesis becomes the arg-max reading of R cut at its first <eos> (pad_id after it), scored by the
+ *                             sum of its log-max-probabilities; of equal readings of one image the best-scored (then the lower row) stays,
+ *                             the others become dead beams.  Every iteration runs on the previous one's readings.  Refused under a lexicon
+ * Then the beams of an image are ranked again: higher new score, then the lower previous rank, dead beams last.  Outputs as
+ * parseq_forward_beam's, scores_out the new scores, plus
+ *   ar_scores_out  fp32 [batch, W]  the score the search itself gave the hypothesis each output row descends from
+ * trie_next = NULL: unconstrained (trie_nodes, roots and words_out are ignored); otherwise parseq_forward_beam_lexicon's arguments, the
+ * words following their rows.  refine_trace: NULL, or two nullable device pointers filled per iteration.
+ * workspace: parseq_beam_refine_workspace_bytes(..., lexicon = 0 / 1) bytes: the parts of parseq_beam_workspace_bytes (and the lexicon's),
+ * then, each on a 256-byte boundary, the refinement logits fp32 [batch * W][num_steps][C], three statistics arrays [batch * W][num_steps]
+ * (fp32 lp of the row's token, int32 arg-max class, fp32 its lp) and the search's scores fp32 [batch * W].
+ * Refused with PARSEQ_E_INVALID before any device work, outputs untouched: whatever parseq_forward_beam(_lexicon) refuses, an unknown
+ * mode, EDIT with a trie, SCORE with refine_iters != 1, refine_iters < 1, a short or misaligned workspace, a NULL ar_scores_out.
+ * No host synchronisation and no allocation inside the call. */
+#define PARSEQ_BEAM_REFINE_SCORE 1
+#define PARSEQ_BEAM_REFINE_EDIT 2
+typedef struct parseq_beam_refine_trace {
+    int32_t* tokens_in;      /* int32 [refine_iters][batch * W][num_steps]     the tgt_in rows the iteration ran on */
+    float* logits;           /* fp32  [refine_iters][batch * W][num_steps][C]  the iteration's refinement logits */
+} parseq_beam_refine_trace;
+size_t parseq_beam_refine_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps, int lexicon);
+int parseq_forward_beam_refine(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                               int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                               const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
+                               const int32_t* trie_next, int trie_nodes, const int32_t* roots, int32_t* words_out, int refine_mode,
+                               int refine_iters, float* ar_scores_out, const parseq_beam_refine_trace* refine_trace);
+/* The selection of one iteration alone on caller tensors (tests/test_beam_refine.py), in place: logits fp32 [batch * W][L][C]; the beam
+ * state as parseq_op_beam_step leaves it — tokens int32 [batch * W][ldt] (<bos>, then token i at position i + 1; L <= ldt <= 64, with
+ * L == ldt the last token is picked[row]), scores, finished, lengths, picked; nodes and words (either may be NULL) and ar_scores travel
+ * with their rows.  A dead row comes out with score -inf, length 0, finished 0, word -1 and pad_id in picked and after <bos>.
+ * workspace: parseq_op_beam_refine_workspace_bytes(batch, beam_width, L) device bytes (0: a shape outside the ranges). */
+size_t parseq_op_beam_refine_workspace_bytes(int batch, int beam_width, int L);
+int parseq_op_beam_refine(const float* logits, int batch, int beam_width, int C, int L, int refine_mode, int32_t* tokens, int ldt,
+                          float* scores, uint8_t* finished, int32_t* lengths, int32_t* picked, int32_t* nodes, int32_t* words,
+                          float* ar_scores, int eos_id, int pad_id, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ViTSTR.forward (strhub/models/vitstr/system.py:76-82 -> vitstr/model.py:20-28) for a model created with
  * arch = PARSEQ_ARCH_VITSTR: encoder with class token, head on tokens [1, num_steps], i.e. logits_out fp32
  * [batch, num_steps, num_tokens - 2] with num_steps = min(max_length, max_label_length) + 1.  images as parseq_forward. */

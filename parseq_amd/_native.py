@@ -66,6 +66,11 @@ class BeamTrace(C.Structure):
     _fields_ = [('logits', C.c_void_p), ('tokens_in', C.c_void_p), ('parent', C.c_void_p), ('score', C.c_void_p)]
 
 
+class BeamRefineTrace(C.Structure):
+    """parseq_beam_refine_trace: two nullable device pointers parseq_forward_beam_refine fills per refinement iteration."""
+    _fields_ = [('tokens_in', C.c_void_p), ('logits', C.c_void_p)]
+
+
 class GemmOperand(C.Structure):
     _fields_ = [('data', C.c_void_p), ('dtype', C.c_int32), ('outer_stride', C.c_int64), ('k_stride', C.c_int64)]
 
@@ -142,6 +147,13 @@ SIGNATURES = {
                                               C.POINTER(BeamTrace), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'parseq_op_beam_step_lexicon': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'parseq_beam_refine_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'parseq_forward_beam_refine': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(BeamTrace), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_void_p, C.POINTER(BeamRefineTrace)]),
+    'parseq_op_beam_refine_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'parseq_op_beam_refine': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_vitstr_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'parseq_decode_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 // libparseq_hip.so — launch orchestration of the decoder passes, the AR loop, refinement and parseq_forward.
 #include "lib_internal.h"
 #include "beam.h"
+#include "beam_refine.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -633,8 +634,9 @@ extern "C" int parseq_set_memory(parseq_plan* p, const float* memory, int batch,
 // The caller's workspace: the encoder memory of the crops, its W-fold replication (set_memory_impl's operand), one step's logits and the
 // beams' scores / lengths / last picks / flags.  The histories live in p->tok, where the self-attention kernels read them.
 // Under a lexicon (section 19) two more parts follow: every beam's trie node and word id.
-struct BeamWs { size_t memory, memory_rep, logits, score, length, picked, finished, node, word, total; };
-static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon = false) {
+// A refined search (section 20) adds the refinement logits of all num_steps positions, the row statistics and the search's own scores.
+struct BeamWs { size_t memory, memory_rep, logits, score, length, picked, finished, node, word, rlogits, lp_tok, amax, lp_max, ar_score, total; };
+static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon = false, int refine_steps = 0) {
     const parseq_model* m = p->m;
     const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim * sizeof(float);
     BeamWs o; size_t off = 0;
@@ -647,6 +649,14 @@ static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon = fal
     o.finished = carve(off, rows);
     o.node = o.word = 0;
     if (lexicon) { o.node = carve(off, rows * sizeof(int)); o.word = carve(off, rows * sizeof(int)); }
+    o.rlogits = o.lp_tok = o.amax = o.lp_max = o.ar_score = 0;
+    if (refine_steps > 0) {
+        o.rlogits = carve(off, rows * refine_steps * m->classes * sizeof(float));
+        o.lp_tok = carve(off, rows * refine_steps * sizeof(float));
+        o.amax = carve(off, rows * refine_steps * sizeof(int));
+        o.lp_max = carve(off, rows * refine_steps * sizeof(float));
+        o.ar_score = carve(off, rows * sizeof(float));
+    }
     o.total = off;
     return o;
 }
@@ -680,10 +690,23 @@ static int launch_beam_step(hipStream_t s, const float* logits, int batch, int W
 
 // What a constrained search adds to beam_impl's arguments: the caller's table, roots and output.
 struct BeamLexCall { const int32_t* next; int nodes; const int32_t* roots; int32_t* words_out; };
+// What a refined search adds (section 20): the mode, the iterations, the output of the search's own scores and the optional trace.
+struct BeamRefineCall { int mode, iters; float* ar_scores_out; const parseq_beam_refine_trace* trace; };
+
+// The selection of one refinement iteration on logits [batch * W][L][C]: the row statistics, then the per-image kernel (beam_refine.h).
+static int launch_beam_refine(hipStream_t s, const float* logits, int batch, int W, int C, int L, int mode, int* tok, int ldt, float* score,
+                              unsigned char* finished, int* length, int* picked, int* node, int* word, float* ar_score, float* lp_tok, int* amax,
+                              float* lp_max, int eos_id, int pad_id) {
+    const size_t waves = (size_t)batch * W * L;
+    CHK(launch(beam_refine_stats_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, logits, batch * W, L, C, tok, ldt, picked, lp_tok, amax, lp_max));
+    return launch(beam_refine_select_kernel, dim3(batch), dim3(BEAM_THREADS), beam_refine_lds(W, ldt), s, mode, W, L, lp_tok, amax, lp_max, tok, ldt,
+                  score, finished, length, picked, node, word, ar_score, eos_id, pad_id);
+}
 
 template <typename T, int E>
 static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char* ws, const BeamWs& o, int32_t* tokens_out, float* scores_out,
-                     int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* tr, hipStream_t s, const BeamLexCall* lc = nullptr) {
+                     int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* tr, hipStream_t s, const BeamLexCall* lc = nullptr,
+                     const BeamRefineCall* rc = nullptr) {
     const parseq_config& c = p->m->cfg;
     const int C = p->m->classes, rows = B * W;
     const float* memory = reinterpret_cast<const float*>(ws + o.memory);
@@ -717,6 +740,26 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char*
                              picked, c.eos_id, c.pad_id, lc ? &lx : nullptr));
         if (tr && tr->score) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
+    if (rc) {
+        // cloze refinement of every beam (section 20): forward_impl's refinement pass on rows = B * W, then the selection
+        float* rlogits = reinterpret_cast<float*>(ws + o.rlogits);
+        float* ar_score = reinterpret_cast<float*>(ws + o.ar_score);
+        HIPCHK(hipMemcpyAsync(ar_score, score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+        DecPass ra; ra.B = rows; ra.Lk = ra.Lq = num_steps; ra.i0 = ra.c0 = 0; ra.qmask = ra.cmask = p->cloze; ra.kpm = p->kpm; ra.argmax_mode = 0;
+        ra.fused_step_allowed = false; ra.logits = rlogits; ra.Ltot = num_steps;
+        for (int it = 0; it < rc->iters; ++it) {
+            CHK(launch(refine_prep_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, rlogits, num_steps, C, p->tok, LDT, p->kpm, LDT, rows, c.bos_id, c.eos_id, 0));
+            CHK((decoder_pass<T, E>(p, s, w, ra)));
+            if (rc->trace && rc->trace->tokens_in) HIPCHK(hipMemcpy2DAsync(rc->trace->tokens_in + (size_t)it * rows * num_steps, num_steps * sizeof(int), p->tok,
+                                                                           LDT * sizeof(int), num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
+            if (rc->trace && rc->trace->logits) HIPCHK(hipMemcpyAsync(rc->trace->logits + (size_t)it * rows * num_steps * C, rlogits,
+                                                                      (size_t)rows * num_steps * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+            CHK(launch_beam_refine(s, rlogits, B, W, C, num_steps, rc->mode, p->tok, LDT, score, finished, length, picked, lc ? lx.node : nullptr,
+                                   lc ? lx.word : nullptr, ar_score, reinterpret_cast<float*>(ws + o.lp_tok), reinterpret_cast<int*>(ws + o.amax),
+                                   reinterpret_cast<float*>(ws + o.lp_max), c.eos_id, c.pad_id));
+        }
+        HIPCHK(hipMemcpyAsync(rc->ar_scores_out, ar_score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
     if (lc) CHK(launch(beam_finish_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, score, finished, lx.word, lc->words_out));
     return launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, num_steps, c.pad_id, score, finished,
                   length, picked, tokens_out, scores_out, lengths_out, finished_out);
@@ -724,13 +767,20 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char*
 
 static int forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps, int32_t* tokens_out,
                         float* scores_out, int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* trace, void* workspace,
-                        size_t workspace_bytes, void* stream, const BeamLexCall* lc) {
+                        size_t workspace_bytes, void* stream, const BeamLexCall* lc, const BeamRefineCall* rc = nullptr) {
     CHK(beam_check(p, batch, beam_width, num_steps));
     CHK(check_call(p, batch, images_dtype));
     if (!images || !tokens_out || !scores_out || !lengths_out || !finished_out || !workspace) return fail(PARSEQ_E_INVALID, "null images / output / workspace");
     if (lc && (!lc->next || !lc->words_out)) return fail(PARSEQ_E_INVALID, "null trie table / words output");
     if (lc && lc->nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", lc->nodes);
-    const BeamWs o = beam_ws(p, batch, beam_width, lc != nullptr);
+    if (rc) {
+        if (rc->mode != PARSEQ_BEAM_REFINE_SCORE && rc->mode != PARSEQ_BEAM_REFINE_EDIT) return fail(PARSEQ_E_INVALID, "refine_mode %d: neither PARSEQ_BEAM_REFINE_SCORE nor PARSEQ_BEAM_REFINE_EDIT", rc->mode);
+        if (rc->iters < 1) return fail(PARSEQ_E_INVALID, "refine_iters %d: at least 1", rc->iters);
+        if (rc->mode == PARSEQ_BEAM_REFINE_SCORE && rc->iters != 1) return fail(PARSEQ_E_INVALID, "refine_iters %d in score mode: rescoring is idempotent, it runs once", rc->iters);
+        if (rc->mode == PARSEQ_BEAM_REFINE_EDIT && lc) return fail(PARSEQ_E_INVALID, "edit refinement under a lexicon: an edited reading can leave the word list; use the score mode");
+        if (!rc->ar_scores_out) return fail(PARSEQ_E_INVALID, "null ar_scores_out");
+    }
+    const BeamWs o = beam_ws(p, batch, beam_width, lc != nullptr, rc ? num_steps : 0);
     if (workspace_bytes < o.total) return fail(PARSEQ_E_INVALID, "beam workspace of %zu bytes, %zu needed", workspace_bytes, o.total);
     if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "beam workspace not 16-byte aligned");
     DevGuard dg(p->m->device);
@@ -740,7 +790,7 @@ static int forward_beam(parseq_plan* p, const void* images, int images_dtype, in
     CHK(encode_dispatch(p, images, images_dtype, batch, reinterpret_cast<float*>(ws + o.memory), s));
     return dispatch_te(p, [&](auto te) {
         return beam_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, beam_width, num_steps, ws, o, tokens_out, scores_out, lengths_out,
-                                                                    finished_out, trace, s, lc);
+                                                                    finished_out, trace, s, lc, rc);
     });
 }
 
@@ -764,6 +814,56 @@ extern "C" int parseq_forward_beam_lexicon(parseq_plan* p, const void* images, i
     const BeamLexCall lc{trie_next, trie_nodes, roots, words_out};
     return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
                         workspace_bytes, stream, &lc);
+}
+
+// cloze refinement of the N-best
+static_assert(PARSEQ_BEAM_REFINE_SCORE == BEAM_REFINE_SCORE && PARSEQ_BEAM_REFINE_EDIT == BEAM_REFINE_EDIT, "refinement modes of the header and the kernels");
+extern "C" size_t parseq_beam_refine_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps, int lexicon) {
+    if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
+    return beam_ws(p, batch, beam_width, lexicon != 0, num_steps).total;
+}
+
+extern "C" int parseq_forward_beam_refine(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                          int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                          const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
+                                          const int32_t* trie_next, int trie_nodes, const int32_t* roots, int32_t* words_out, int refine_mode,
+                                          int refine_iters, float* ar_scores_out, const parseq_beam_refine_trace* refine_trace) {
+    const BeamLexCall lc{trie_next, trie_nodes, roots, words_out};
+    const BeamRefineCall rc{refine_mode, refine_iters, ar_scores_out, refine_trace};
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
+                        workspace_bytes, stream, trie_next ? &lc : nullptr, &rc);
+}
+
+// the statistics of parseq_op_beam_refine: lp_tok, amax, lp_max [batch * W][L]
+struct RefineOpWs { size_t lp_tok, amax, lp_max, total; };
+static RefineOpWs refine_op_ws(int batch, int W, int L) {
+    const size_t n = (size_t)batch * W * L;
+    RefineOpWs o; size_t off = 0;
+    o.lp_tok = carve(off, n * sizeof(float)); o.amax = carve(off, n * sizeof(int)); o.lp_max = carve(off, n * sizeof(float));
+    o.total = off;
+    return o;
+}
+static bool refine_op_shape_ok(int batch, int W, int L) { return batch > 0 && W >= 1 && W <= PARSEQ_BEAM_MAX_WIDTH && L >= 1 && L <= BEAM_REFINE_MAX_L; }
+
+extern "C" size_t parseq_op_beam_refine_workspace_bytes(int batch, int beam_width, int L) {
+    return refine_op_shape_ok(batch, beam_width, L) ? refine_op_ws(batch, beam_width, L).total : 0;
+}
+
+extern "C" int parseq_op_beam_refine(const float* logits, int batch, int beam_width, int C, int L, int refine_mode, int32_t* tokens, int ldt,
+                                     float* scores, uint8_t* finished, int32_t* lengths, int32_t* picked, int32_t* nodes, int32_t* words,
+                                     float* ar_scores, int eos_id, int pad_id, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!logits || !tokens || !scores || !finished || !lengths || !picked || !ar_scores || !workspace) return fail(PARSEQ_E_INVALID, "null argument");
+    if (!refine_op_shape_ok(batch, beam_width, L) || C < 1) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d, L %d (1..%d)", batch, beam_width, PARSEQ_BEAM_MAX_WIDTH, C, L, BEAM_REFINE_MAX_L);
+    if (ldt < L || ldt > 64) return fail(PARSEQ_E_INVALID, "L %d / ldt %d: need L <= ldt <= 64", L, ldt);
+    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
+    if (refine_mode != PARSEQ_BEAM_REFINE_SCORE && refine_mode != PARSEQ_BEAM_REFINE_EDIT) return fail(PARSEQ_E_INVALID, "refine_mode %d", refine_mode);
+    const RefineOpWs o = refine_op_ws(batch, beam_width, L);
+    if (workspace_bytes < o.total) return fail(PARSEQ_E_INVALID, "refinement workspace of %zu bytes, %zu needed", workspace_bytes, o.total);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "refinement workspace not 16-byte aligned");
+    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
+    return launch_beam_refine((hipStream_t)stream, logits, batch, beam_width, C, L, refine_mode, tokens, ldt, scores, finished, lengths, picked, nodes, words,
+                              ar_scores, reinterpret_cast<float*>(ws + o.lp_tok), reinterpret_cast<int*>(ws + o.amax), reinterpret_cast<float*>(ws + o.lp_max),
+                              eos_id, pad_id);
 }
 
 extern "C" int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,

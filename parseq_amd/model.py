@@ -26,6 +26,23 @@ _PRECISIONS = {'bf16': _native.PARSEQ_BF16, 'fp32': _native.PARSEQ_F32, 'f32': _
 
 
 BEAM_MAX_WIDTH = 16      # PARSEQ_BEAM_MAX_WIDTH
+BEAM_REFINE_MODES = {'score': 1, 'edit': 2}      # PARSEQ_BEAM_REFINE_SCORE / PARSEQ_BEAM_REFINE_EDIT
+
+
+def check_beam_refine(refine, refine_iters, lexicon=None):
+    """The refusals of `beam_search(..., refine=, refine_iters=)` that need no device."""
+    if refine is None:
+        if refine_iters != 1:
+            raise ValueError(f'beam_search: refine_iters = {refine_iters} without refine')
+        return
+    if refine not in BEAM_REFINE_MODES:
+        raise ValueError(f"beam_search: refine must be None, 'edit' or 'score', got {refine!r}")
+    if not isinstance(refine_iters, int) or isinstance(refine_iters, bool) or refine_iters < 1:
+        raise ValueError(f'beam_search: refine_iters must be an integer >= 1, got {refine_iters!r}')
+    if refine == 'score' and refine_iters != 1:
+        raise ValueError(f"beam_search: refine='score' is idempotent and runs once, got refine_iters = {refine_iters}")
+    if refine == 'edit' and lexicon is not None:
+        raise ValueError("beam_search: refine='edit' under a lexicon (an edited reading can leave the word list); use refine='score'")
 
 
 @dataclass
@@ -40,6 +57,12 @@ class BeamResult:
     trace_tokens_in: Optional[Tensor] = None    # int32 [num_steps, B * W, num_steps] the histories each step ran on
     trace_parent: Optional[Tensor] = None       # int32 [num_steps, B * W] each new beam's parent within its image (-1: dead)
     trace_score: Optional[Tensor] = None        # fp32 [num_steps, B * W] each new beam's score after the step
+    # refine='edit' / 'score' only: `scores` are then the refined scores.  Plain class attributes, set on the instance by
+    # a refined search: a result without refinement has the fields it had (`vars(result)` holds tensors only).
+    ar_scores = None                   # Optional[Tensor] fp32 [B, W] the score the search itself gave the hypothesis a row descends from
+    # ... and trace=True, per refinement iteration:
+    trace_refine_tokens_in = None      # Optional[Tensor] int32 [refine_iters, B * W, num_steps] the tgt_in rows of the iteration
+    trace_refine_logits = None         # Optional[Tensor] fp32 [refine_iters, B * W, num_steps, C] its logits
 
 
 @dataclass
@@ -584,7 +607,8 @@ class PARSeq(_NativeBacked):
         return logits if out_len.value == num_steps else logits[:, :out_len.value]
 
     def beam_search(self, tokenizer: Tokenizer, images: Tensor, beam_width: int, max_length: Optional[int] = None,
-                    trace: bool = False, lexicon=None, roots: Optional[Tensor] = None) -> BeamResult:
+                    trace: bool = False, lexicon=None, roots: Optional[Tensor] = None, refine: Optional[str] = None,
+                    refine_iters: int = 1) -> BeamResult:
         """Beam-search AR decoding with N-best output (the reference has none): the `beam_width` best hypotheses
         of every crop with their log-probabilities, best first, no refinement.  One library call on a plan of B * beam_width rows, no
         host synchronisation; the result stays on the device (`tokenizer.decode_beams` reads it).  `max_length` as in `forward`, except
@@ -593,7 +617,13 @@ class PARSeq(_NativeBacked):
 
         `lexicon` (a `parseq_amd.lexicon.Lexicon`) constrains the search to prefixes of its words, the scores staying
         the model's log-probabilities; `roots` (int32 [B], from `Lexicon.forest`) gives every crop its own trie, none means node 0.  The
-        result is then a `LexiconBeamResult` whose `words` index `lexicon.words`."""
+        result is then a `LexiconBeamResult` whose `words` index `lexicon.words`.
+
+        `refine` runs the model's cloze refinement on every hypothesis after the search, in the same library call:
+        'score' keeps the readings and replaces their scores by the pseudo-log-likelihood (every character given all the others), 'edit'
+        replaces every reading by its refined one, `refine_iters` times, and merges equal readings.  Either way the hypotheses are ranked
+        again by the new `scores`, and `ar_scores` holds the search's own.  Under a lexicon only 'score' is allowed."""
+        check_beam_refine(refine, refine_iters, lexicon)
         W = int(beam_width)
         classes = self._cfg['num_tokens'] - 2
         if self._cfg['dec_depth'] != 1:
@@ -628,6 +658,8 @@ class PARSeq(_NativeBacked):
             res.trace_parent = torch.empty(num_steps, B * W, dtype=torch.int32, device=dev)
             res.trace_score = torch.empty(num_steps, B * W, dtype=torch.float32, device=dev)
             tr = _native.BeamTrace(res.trace_logits.data_ptr(), res.trace_tokens_in.data_ptr(), res.trace_parent.data_ptr(), res.trace_score.data_ptr())
+        if refine is not None:
+            return self._beam_search_refine(lexicon, roots, images, plan, res, tr, B, W, num_steps, refine, refine_iters, trace)
         if lexicon is not None:
             return self._beam_search_lexicon(lexicon, roots, images, plan, res, tr, B, W, num_steps)
         nbytes = lib.parseq_beam_workspace_bytes(plan, B, W, num_steps)
@@ -654,6 +686,33 @@ class PARSeq(_NativeBacked):
                                                       _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes,
                                                       _native.stream_ptr(self._device), _native.ptr(table), table.shape[0],
                                                       _native.ptr(roots) if roots is not None else None, _native.ptr(res.words)))
+        return res
+
+    def _beam_search_refine(self, lexicon, roots, images, plan, res, tr, B, W, num_steps, refine, refine_iters, trace):
+        lib, dev = _native.lib(), images.device
+        classes = self._cfg['num_tokens'] - 2
+        table = None
+        if lexicon is not None:
+            table = lexicon.table(dev)
+            if roots is not None:
+                roots = roots.to(dev, torch.int32).contiguous()
+            res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
+        res.ar_scores = torch.empty(B, W, dtype=torch.float32, device=dev)
+        rtr = None
+        if trace:
+            res.trace_refine_tokens_in = torch.empty(refine_iters, B * W, num_steps, dtype=torch.int32, device=dev)
+            res.trace_refine_logits = torch.empty(refine_iters, B * W, num_steps, classes, dtype=torch.float32, device=dev)
+            rtr = _native.BeamRefineTrace(res.trace_refine_tokens_in.data_ptr(), res.trace_refine_logits.data_ptr())
+        nbytes = lib.parseq_beam_refine_workspace_bytes(plan, B, W, num_steps, int(lexicon is not None))
+        if nbytes == 0:
+            _native.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        _native.check(lib.parseq_forward_beam_refine(
+            plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens), _native.ptr(res.scores),
+            _native.ptr(res.lengths), _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes,
+            _native.stream_ptr(self._device), _native.ptr(table) if table is not None else None, table.shape[0] if table is not None else 0,
+            _native.ptr(roots) if (table is not None and roots is not None) else None, _native.ptr(res.words) if table is not None else None,
+            BEAM_REFINE_MODES[refine], refine_iters, _native.ptr(res.ar_scores), C.byref(rtr) if rtr is not None else None))
         return res
 
     # ---- native plumbing ---------------------------------------------------------------------------------------

@@ -249,10 +249,16 @@ class PARSeq(nn.Module):
         refinement and `max_length=None` (the batch-level early exit of model.py:144-145)."""
         return self.model.forward(self.tokenizer, images, max_length, slot, return_length=True)
 
-    def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None):
+    def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None,
+                    refine: Optional[str] = None, refine_iters: int = 1):
         """The `beam_width` best readings of every crop with their log-probabilities (model.PARSeq.beam_search):
         a `BeamResult` on the device, `self.tokenizer.decode_beams(result)` turns it into strings.  With a `lexicon` (and per-crop `roots`,
-        section 19) only words of the list are read; `self.tokenizer.decode_beams(result, lexicon)` returns them in the list's spelling."""
+        section 19) only words of the list are read; `self.tokenizer.decode_beams(result, lexicon)` returns them in the list's spelling.
+        `refine='score'` / `'edit'` (section 20) refines every hypothesis with the model's cloze pass and ranks them again; `result.ar_scores`
+        keeps the search's own scores."""
+        if refine is not None or refine_iters != 1:
+            return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots, refine=refine,
+                                          refine_iters=refine_iters)
         if lexicon is None and roots is None:
             return self.model.beam_search(self.tokenizer, images, beam_width, max_length)
         return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots)

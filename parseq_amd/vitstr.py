@@ -134,7 +134,8 @@ class ViTSTR(nn.Module):
         max_length = self.max_label_length if max_length is None else min(max_length, self.max_label_length)
         return self.model.forward_sliced(images, max_length + 1, slot)
 
-    def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None):
+    def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None,
+                    refine: Optional[str] = None, refine_iters: int = 1):
         raise ValueError('beam_search: ViTSTR has no AR loop (every position is read in one pass); use a PARSeq model')
 
     def _eval_step(self, batch, validation: bool):

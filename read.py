@@ -5,6 +5,7 @@
     ./read.py path/to/lightning.ckpt --images *.png refine_iters:int=2 decode_ar:bool=false
     ./read.py pretrained=parseq --images a.png --nbest 5 [--beam 8]     the 5 best readings with their log-probabilities under each line
     ./read.py pretrained=parseq --images a.png --lexicon words.txt [--beam 8] [--nbest 3]     read only words of the list (one per line)
+    ./read.py pretrained=parseq --images a.png --nbest 5 --refine-beams edit [--refine-iters 2]     refine every alternative, rank them again
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -33,14 +34,16 @@ def read_files(model, files, device='cuda'):
 
 
 @torch.inference_mode()
-def read_files_nbest(model, files, nbest, beam_width=None, device='cuda'):
-    """[(file, [(label, log-probability)] best first, at most `nbest`)] through one beam search of width `beam_width` (default `nbest`)."""
+def read_files_nbest(model, files, nbest, beam_width=None, device='cuda', refine=None, refine_iters=1):
+    """[(file, [(label, log-probability)] best first, at most `nbest`)] through one beam search of width `beam_width` (default `nbest`);
+    `refine` ('edit' / 'score') refines the alternatives on the device and ranks them by their refined scores."""
     import numpy as np
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     if not crops:
         return []
     batch = resize_batch(crops, tuple(model.hparams.img_size))
-    beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width or nbest))
+    search = {} if refine is None else {'refine': refine, 'refine_iters': refine_iters}
+    beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width or nbest, **search))
     return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
 
 
@@ -54,10 +57,11 @@ def load_word_list(path):
 
 
 @torch.inference_mode()
-def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, device='cuda'):
+def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, device='cuda', refine=None):
     """[(file, [(word, log-probability)] best first, at most `nbest`)]: one beam search of width `beam_width` constrained to `words`
     (DESIGN.md section 19).  A finished reading is a word of the list in the list's spelling; case is folded when the model's charset has
-    only one.  A crop for which no word of the list finishes keeps its unfinished prefixes, or nothing."""
+    only one.  A crop for which no word of the list finishes keeps its unfinished prefixes, or nothing.  `refine='score'` ranks the words by
+    their pseudo-log-likelihood (section 20)."""
     import numpy as np
     from parseq_amd.lexicon import Lexicon
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
@@ -65,7 +69,8 @@ def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, de
         return []
     lexicon = Lexicon(words, model.tokenizer, fold_case=True, max_label_length=model.model.max_label_length).to(device)
     batch = resize_batch(crops, tuple(model.hparams.img_size))
-    beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width, lexicon=lexicon), lexicon)
+    search = {} if refine is None else {'refine': refine}
+    beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width, lexicon=lexicon, **search), lexicon)
     return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
 
 
@@ -78,7 +83,29 @@ def build_parser():
     parser.add_argument('--beam', type=int, default=None, help=f'Beam width of --nbest (default: N) or of --lexicon (default: {LEXICON_BEAM})')
     parser.add_argument('--lexicon', default=None, metavar='FILE',
                         help='Read only words of this list (one per line): a beam search constrained to the list; --nbest N prints the N best words')
+    parser.add_argument('--refine-beams', default=None, choices=['edit', 'score'], dest='refine_beams',
+                        help="Refine the alternatives of --nbest / --lexicon with the model's cloze pass and rank them again: 'edit' replaces every "
+                             "reading by its refined one, 'score' only rescores (the only mode under --lexicon)")
+    parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
     return parser
+
+
+def resolve_refine(parser, args):
+    """(mode, iterations) of --refine-beams, (None, 1) for none; a contradiction ends in parser.error."""
+    if args.refine_beams is None:
+        if args.refine_iters is not None:
+            parser.error('--refine-iters needs --refine-beams')
+        return None, 1
+    if args.lexicon is None and args.nbest <= 0:
+        parser.error('--refine-beams needs --nbest N or --lexicon FILE')
+    iters = 1 if args.refine_iters is None else args.refine_iters
+    if iters < 1:
+        parser.error('--refine-iters must be at least 1')
+    if args.refine_beams == 'score' and iters != 1:
+        parser.error('--refine-beams score runs once: --refine-iters must be 1')
+    if args.refine_beams == 'edit' and args.lexicon is not None:
+        parser.error('--refine-beams edit is not allowed with --lexicon (an edited reading can leave the list); use score')
+    return args.refine_beams, iters
 
 
 def resolve_search(parser, args):
@@ -101,16 +128,17 @@ def main(argv=None):
     print(f'Additional keyword arguments: {kwargs}')
 
     beam, nbest = resolve_search(parser, args)
+    refine, refine_iters = resolve_refine(parser, args)
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     files = args.images or []
     if args.lexicon is not None:
         # the best word of the list where the greedy reading goes; the alternatives only where --nbest asks for them
-        for fname, alts in read_files_lexicon(model, files, load_word_list(args.lexicon), nbest, beam, args.device):
+        for fname, alts in read_files_lexicon(model, files, load_word_list(args.lexicon), nbest, beam, args.device, refine):
             print(f'{fname}: {alts[0][0] if alts else ""}')
             for label, logp in (alts if args.nbest > 0 else []):
                 print(f'    {logp:9.4f}  {label}')
         return
-    alternatives = dict(read_files_nbest(model, files, args.nbest, args.beam, args.device)) if args.nbest > 0 else {}
+    alternatives = dict(read_files_nbest(model, files, args.nbest, args.beam, args.device, refine, refine_iters)) if args.nbest > 0 else {}
     for fname, pred, _ in read_files(model, files, args.device):
         print(f'{fname}: {pred}')
         for label, logp in alternatives.get(fname, []):
