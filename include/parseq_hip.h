@@ -318,6 +318,45 @@ int parseq_op_beam_refine(const float* logits, int batch, int beam_width, int C,
                           float* scores, uint8_t* finished, int32_t* lengths, int32_t* picked, int32_t* nodes, int32_t* words,
                           float* ar_scores, int eos_id, int pad_id, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- character localisation (pure additions under ABI 15; DESIGN.md section 21 defines it) --------------------------- */
+
+/* The map of a reading: ONE decoder pass over all ctx_len positions, set up as the refinement iteration of parseq_forward sets it up
+ * (model.py:154-167: content `tokens`, the cloze query mask, keys from each row's first <eos> on padded), whose last-layer cross-attention
+ * probabilities of the query stream are averaged over the heads (the reference's `ca_weights`, modules.py:74-79):
+ *   A[b][i][t] = mean_h softmax_t(q[b][h][i] . K[b][h][t] / sqrt(32))        t < S = the encoder's patch tokens
+ *   tokens            device int32 [batch, ctx_len]: the content rows [<bos>, reading], as for parseq_decode_logits; 2 <= ctx_len <=
+ *                     max_label_length + 1.  It attends to the memory of the most recent parseq_encode / parseq_forward / parseq_set_memory
+ *   key_padding_mask  device uint8 [batch, ctx_len], or NULL: derived on the device, (an <eos> at a content position <= j)
+ *   attn_out          device fp32 [batch, ctx_len, S].  Row i of image b sums to 1 where key_padding_mask[b][i] is clear — the positions
+ *                     0 .. len(b) of the reading, its <eos> included — and is written as zeros elsewhere
+ *   logits_out        device fp32 [batch, ctx_len, num_tokens - 2] of the same pass, or NULL
+ * Scores, soft-max and head mean are fp32 in every precision, heads summed in ascending order (deterministic).  No allocation, no host
+ * synchronisation.  Refused with PARSEQ_E_INVALID before any device work, outputs untouched: a ViTSTR model (no decoder), dec_depth != 1,
+ * ctx_len outside [2, max_label_length + 1], a batch that is not the last encode's, NULL plan / tokens / attn_out. */
+int parseq_decode_attention(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, const uint8_t* key_padding_mask, float* attn_out,
+                            float* logits_out, void* stream);
+/* The geometry of any map on caller tensors (tests/test_attn_map.py).  attn fp32 [batch, L, gh * gw]; token t is cell (t / gw, t % gw) of
+ * ph x pw pixels with centre x_c = (c + 1/2) pw, y_r = (r + 1/2) ph; lengths int32 [batch]: row i of image b is valid iff i <= lengths[b].
+ *   centres    fp32 [batch, L, 2]  (sum A x_c, sum A y_r)
+ *   boxes      fp32 [batch, L, 4]  (cx - hx, cy - hy, cx + hx, cy + hy) clipped to [0, gw pw] x [0, gh ph], hx = sqrt(3 var_x),
+ *                                  var_x = sum A (x_c - cx)^2 + pw^2 / 12 (two passes), the same in y: the uniform distribution of that variance
+ *   peak       int32 [batch, L]    the arg-max token, lowest index on ties;  peak_mass fp32 [batch, L]  its probability
+ * Invalid rows: zeros, peak -1. */
+int parseq_op_attention_geometry(const float* attn, const int32_t* lengths, int batch, int L, int gh, int gw, int ph, int pw, float* centres,
+                                 float* boxes, int32_t* peak, float* peak_mass, void* stream);
+/* Read and localise in one call, no host synchronisation, no allocation: the encoder; then, with tokens_in NULL, the model's own reading —
+ * parseq_forward with `flags` (PARSEQ_FLAG_DECODE_AR, PARSEQ_FLAG_LATENCY; the early exit never applies) and `refine_iters`, tokens by arg-max on
+ * the device; then the map pass over all L = max_label_length + 1 positions; then the geometry in pixels of the model's input.
+ *   tokens_in    NULL, or device int32 [batch, L]: readings to align instead (characters, <eos>, anything after it)
+ *   tokens_out   device int32 [batch, L]: the reading that was localised — its characters, <eos> at position lengths_out[b], pad_id after
+ *   lengths_out  device int32 [batch]: its number of characters;  attn_out fp32 [batch, L, S];  the rest as parseq_op_attention_geometry
+ *   workspace    device, parseq_localize_workspace_bytes(p, batch) bytes (0: refused, parseq_last_error says why), 16-byte aligned
+ * Refusals as parseq_decode_attention's, plus whatever parseq_forward refuses, a NULL output and a short workspace. */
+size_t parseq_localize_workspace_bytes(const parseq_plan* p, int batch);
+int parseq_localize(parseq_plan* p, const void* images, int images_dtype, int batch, const int32_t* tokens_in, int flags, int refine_iters,
+                    int32_t* tokens_out, int32_t* lengths_out, float* attn_out, float* centres_out, float* boxes_out, int32_t* peak_out,
+                    float* peak_mass_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ViTSTR.forward (strhub/models/vitstr/system.py:76-82 -> vitstr/model.py:20-28) for a model created with
  * arch = PARSEQ_ARCH_VITSTR: encoder with class token, head on tokens [1, num_steps], i.e. logits_out fp32
  * [batch, num_steps, num_tokens - 2] with num_steps = min(max_length, max_label_length) + 1.  images as parseq_forward. */

@@ -2,6 +2,7 @@
 #include "lib_internal.h"
 #include "beam.h"
 #include "beam_refine.h"
+#include "attn_map.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -73,7 +74,7 @@ struct DecPass {
     const unsigned char* qmask = nullptr;      // [npos][LDT] attention mask of the query stream, rows by absolute position; True = masked
     const unsigned char* cmask = nullptr;      // the same for the content stream (read at dec_depth > 1 only)
     const unsigned char* kpm = nullptr;        // [B][LDT] key padding of both streams
-    float* logits = nullptr; int Ltot = 0;
+    float* logits = nullptr; int Ltot = 0;      // null: the pass ends before decoder.norm and the head (the attention map's pass without logits)
     int argmax_mode = 0;      // Lq == 1: greedy pick of position i0 into tok[:, i0 + 1] with the EOS bookkeeping (2: testing, all rows run on)
     const float* user_query = nullptr;
     bool fused_step_allowed = false;      // a single unmasked query may take dec_step_pre / post, which leave no query stream in p->t
@@ -362,6 +363,7 @@ static int decoder_pass(parseq_plan* p, hipStream_t s, const DecW<T>& w, const D
         else CHK((self_attn_tables<T, E>(p, s, w, a)));
         CHK((cross_mlp<T, E>(p, s, y, l, a.B, a.Lq, p->t)));
     }
+    if (!a.logits) return 0;
     return head_pass<T, E>(p, s, w, a);
 }
 
@@ -626,6 +628,117 @@ extern "C" int parseq_set_memory(parseq_plan* p, const float* memory, int batch,
     DevGuard dg(p->m->device);
     SplitScope ss(p->precision == PARSEQ_BF16X3);
     return dispatch_t(p, [&](auto te) { return set_memory_impl<typename decltype(te)::T>(p, memory, batch, (hipStream_t)stream); });
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// character localisation
+// -------------------------------------------------------------------------------------------------------------------
+static int attention_check(const parseq_plan* p, int L) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    const parseq_model* m = p->m;
+    if (m->vitstr) return fail(PARSEQ_E_INVALID, "attention maps on a ViTSTR model: ViTSTR has no decoder");
+    if (m->cfg.dec_depth != 1) return fail(PARSEQ_E_INVALID, "attention maps at dec_depth %d: only dec_depth 1", m->cfg.dec_depth);
+    const int npos = m->cfg.max_label_length + 1;
+    if (L < 2 || L > npos) return fail(PARSEQ_E_INVALID, "ctx_len %d outside [2, %d]", L, npos);
+    if (m->tokens > AM_MAX_S) return fail(PARSEQ_E_INVALID, "attention maps over %d memory tokens: at most %d", m->tokens, AM_MAX_S);
+    return 0;
+}
+
+// The cloze pass of forward_impl's refinement over the content rows in p->tok (key padding in p->kpm), then the map of its last layer's
+// cross-attention: the per-operation pass leaves the projected, unscaled queries of all B * L rows in p->qc (cross_mlp), and the memory's K
+// rows are in whichever form the call that filled the plan left them.
+template <typename T, int E>
+static int attention_pass(parseq_plan* p, hipStream_t s, int B, int L, float* attn_out, float* logits_out) {
+    const DecW<T> w = dec_weights<T>(p);
+    DecPass a; a.B = B; a.Lk = a.Lq = L; a.i0 = a.c0 = 0; a.qmask = a.cmask = p->cloze; a.kpm = p->kpm; a.argmax_mode = 0;
+    a.fused_step_allowed = false; a.logits = logits_out; a.Ltot = L;
+    CHK((decoder_pass<T, E>(p, s, w, a)));
+    const int H = p->m->cfg.dec_heads, S = p->m->tokens;
+    const dim3 grid(B, (L + AM_QB - 1) / AM_QB), block(64 * AM_WAVES);
+    if constexpr (sizeof(T) == 2) return launch(dec_cross_attn_map_kernel<AM_K_BF16>, grid, block, 0, s, p->qc, p->kmem, (size_t)0, p->kpm, LDT, H, L, S, dec_scale(), attn_out);
+    else if (p->kv24) return launch(dec_cross_attn_map_kernel<AM_K_F24>, grid, block, 0, s, p->qc, p->kmem, p->kv_plane_elems, p->kpm, LDT, H, L, S, dec_scale(), attn_out);
+    else return launch(dec_cross_attn_map_kernel<AM_K_F32>, grid, block, 0, s, p->qc, p->kmem, (size_t)0, p->kpm, LDT, H, L, S, dec_scale(), attn_out);
+}
+
+static int launch_geometry(hipStream_t s, const float* attn, const int32_t* lengths, int batch, int L, int gh, int gw, int ph, int pw, float* centres,
+                           float* boxes, int32_t* peak, float* peak_mass) {
+    const int rows = batch * L;
+    return launch(attn_geometry_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, attn, lengths, rows, L, gh * gw, gw, (float)ph, (float)pw,
+                  (float)(gh * ph), (float)(gw * pw), centres, boxes, peak, peak_mass);
+}
+
+extern "C" int parseq_decode_attention(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, const uint8_t* key_padding_mask,
+                                       float* attn_out, float* logits_out, void* stream) {
+    if (!p || !tokens || !attn_out) return fail(PARSEQ_E_INVALID, "null plan / tokens / attn_out");
+    CHK(attention_check(p, ctx_len));
+    if (batch <= 0 || batch > p->max_batch || batch != p->last_batch) return fail(PARSEQ_E_INVALID, "batch %d does not match the last parseq_encode (%d)", batch, p->last_batch);
+    DevGuard dg(p->m->device);
+    SplitScope ss(p->precision == PARSEQ_BF16X3);
+    hipStream_t s = (hipStream_t)stream;
+    const parseq_config& c = p->m->cfg;
+    HIPCHK(hipMemcpy2DAsync(p->tok, LDT * sizeof(int), tokens, ctx_len * sizeof(int), ctx_len * sizeof(int), batch, hipMemcpyDeviceToDevice, s));
+    CHK(launch(clamp_tokens_kernel, dim3((batch * ctx_len + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, c.num_tokens));
+    if (key_padding_mask) HIPCHK(hipMemcpy2DAsync(p->kpm, LDT, key_padding_mask, ctx_len, ctx_len, batch, hipMemcpyDeviceToDevice, s));
+    else CHK(launch(attn_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, c.eos_id, c.pad_id, p->kpm, LDT, (int*)nullptr, (int*)nullptr));
+    return dispatch_te(p, [&](auto te) { return attention_pass<typename decltype(te)::T, decltype(te)::E>(p, s, batch, ctx_len, attn_out, logits_out); });
+}
+
+extern "C" int parseq_op_attention_geometry(const float* attn, const int32_t* lengths, int batch, int L, int gh, int gw, int ph, int pw,
+                                            float* centres, float* boxes, int32_t* peak, float* peak_mass, void* stream) {
+    if (!attn || !lengths || !centres || !boxes || !peak || !peak_mass) return fail(PARSEQ_E_INVALID, "null argument");
+    if (batch <= 0 || L < 1 || gh < 1 || gw < 1 || ph < 1 || pw < 1 || (long long)batch * L > 0x7fffffffLL / 4 || (long long)gh * gw > 0x7fffffffLL / 4)
+        return fail(PARSEQ_E_INVALID, "bad shape: batch %d, L %d, grid %d x %d, patch %d x %d", batch, L, gh, gw, ph, pw);
+    return launch_geometry((hipStream_t)stream, attn, lengths, batch, L, gh, gw, ph, pw, centres, boxes, peak, peak_mass);
+}
+
+// parseq_localize's workspace: the forward's logits [batch][npos][C]
+extern "C" size_t parseq_localize_workspace_bytes(const parseq_plan* p, int batch) {
+    if (!p) { fail(PARSEQ_E_INVALID, "null plan"); return 0; }
+    if (attention_check(p, p->m->cfg.max_label_length + 1) != 0) return 0;
+    if (batch <= 0 || batch > p->max_batch) { fail(PARSEQ_E_INVALID, "batch %d outside (0, %d]", batch, p->max_batch); return 0; }
+    size_t off = 0;
+    carve(off, (size_t)batch * (p->m->cfg.max_label_length + 1) * p->m->classes * sizeof(float));
+    return off;
+}
+
+extern "C" int parseq_localize(parseq_plan* p, const void* images, int images_dtype, int batch, const int32_t* tokens_in, int flags, int refine_iters,
+                               int32_t* tokens_out, int32_t* lengths_out, float* attn_out, float* centres_out, float* boxes_out, int32_t* peak_out,
+                               float* peak_mass_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    const int L = p->m->cfg.max_label_length + 1;
+    CHK(attention_check(p, L));
+    CHK(check_call(p, batch, images_dtype));
+    if (!images || !tokens_out || !lengths_out || !attn_out || !centres_out || !boxes_out || !peak_out || !peak_mass_out || !workspace)
+        return fail(PARSEQ_E_INVALID, "null images / output / workspace");
+    if (refine_iters < 0) return fail(PARSEQ_E_INVALID, "refine_iters %d", refine_iters);
+    const size_t need = parseq_localize_workspace_bytes(p, batch);
+    if (workspace_bytes < need) return fail(PARSEQ_E_INVALID, "localize workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "localize workspace not 16-byte aligned");
+    DevGuard dg(p->m->device);
+    SplitScope ss(p->precision == PARSEQ_BF16X3);
+    hipStream_t s = (hipStream_t)stream;
+    const parseq_config& c = p->m->cfg;
+    const int C = p->m->classes;
+    float* logits = reinterpret_cast<float*>(workspace);
+    CHK(encode_dispatch(p, images, images_dtype, batch, nullptr, s));
+    return dispatch_te(p, [&](auto te) {
+        using T = typename decltype(te)::T;
+        constexpr int E = decltype(te)::E;
+        if (tokens_in) {
+            CHK(launch(attn_content_kernel, dim3((batch * L + 255) / 256), dim3(256), 0, s, tokens_in, batch, L, c.bos_id, p->tok, LDT));
+            CHK(launch(clamp_tokens_kernel, dim3((batch * L + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, L, c.num_tokens));
+            CHK(launch(attn_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, L, c.eos_id, c.pad_id, p->kpm, LDT, tokens_out, lengths_out));
+        } else {
+            // the model's own reading: parseq_forward without the early exit (which only truncates the view), then the context the next
+            // refinement iteration would run on — [<bos>, arg-max of the final logits], keys from the first <eos> on padded
+            CHK((forward_impl<T, E>(p, batch, flags & ~PARSEQ_FLAG_TESTING, refine_iters, L, logits, nullptr, s)));
+            CHK(launch(refine_prep_kernel, dim3((batch + 3) / 4), dim3(256), 0, s, logits, L, C, p->tok, LDT, p->kpm, LDT, batch, c.bos_id, c.eos_id, 1));
+            CHK(launch(attn_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, L, c.eos_id, c.pad_id, (unsigned char*)nullptr, LDT, tokens_out, lengths_out));
+        }
+        CHK((attention_pass<T, E>(p, s, batch, L, attn_out, nullptr)));
+        return launch_geometry(s, attn_out, lengths_out, batch, L, c.img_h / c.patch_h, c.img_w / c.patch_w, c.patch_h, c.patch_w, centres_out, boxes_out,
+                               peak_out, peak_mass_out);
+    });
 }
 
 // -------------------------------------------------------------------------------------------------------------------

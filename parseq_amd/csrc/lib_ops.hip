@@ -395,6 +395,32 @@ extern "C" int parseq_op_linear_cfg(const void* A, const void* W, const float* b
     return op_linear_cfg_impl<float>((const float*)A, (const float*)W, bias, C, act, M, N, K, cfg, (hipStream_t)stream);
 }
 
+// The shared-phase branch kernels (encoder_blocks.h) address their two weight matrices through ONE buffer descriptor with 32-bit offsets
+// (make_wpair).  A model's weights lie in one pack; the two tensors a caller hands to these operator hooks are separate allocations, and
+// blocks of a caching allocator can lie more than 4 GiB apart.  Then the pair is staged side by side for the call (the only allocation
+// and the only synchronisation of these hooks, on that path alone).
+struct StagedPair {
+    void* buf = nullptr;
+    const bf16_t *a = nullptr, *b = nullptr;
+    ~StagedPair() { if (buf) (void)hipFree(buf); }
+};
+static int stage_pair(hipStream_t s, const void* a, size_t a_elems, const void* b, size_t b_elems, StagedPair& o) {
+    o.a = (const bf16_t*)a; o.b = (const bf16_t*)b;
+    WPair wp;
+    if (make_wpair(o.a, a_elems, o.b, b_elems, &wp)) return 0;
+    if (((uintptr_t)a | (uintptr_t)b) & 1) return fail(PARSEQ_E_INVALID, "weight pointer not 2-byte aligned");
+    HIPCHK(hipMalloc(&o.buf, (a_elems + b_elems) * sizeof(bf16_t)));
+    bf16_t* base = reinterpret_cast<bf16_t*>(o.buf);
+    HIPCHK(hipMemcpyAsync(base, a, a_elems * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(base + a_elems, b, b_elems * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+    o.a = base; o.b = base + a_elems;
+    return 0;
+}
+static int release_pair(hipStream_t s, StagedPair& o) {
+    if (o.buf) HIPCHK(hipStreamSynchronize(s));      // the kernel has read the staged copy before it is freed
+    return 0;
+}
+
 // x += fc2(gelu(fc1(LayerNorm(x)))) through the fused MLP kernel (E = 384, hidden 1536, bf16 weights).
 extern "C" int parseq_op_mlp(float* x, const float* gamma, const float* beta, const void* W1, const float* b1, const void* W2,
                              const float* b2, int M, void* stream) {
@@ -411,7 +437,13 @@ extern "C" int parseq_op_mlp_variant(float* x, const float* gamma, const float* 
     switch (variant) {
         case 0: HIPCHK((launch_fused_mlp<384>(s, x, gamma, beta, 1e-6f, (const bf16_t*)W1, b1, (const bf16_t*)W2, b2, M))); break;             // x re-read by the epilogue
         case 10: HIPCHK((launch_fused_mlp<384, true>(s, x, gamma, beta, 1e-6f, (const bf16_t*)W1, b1, (const bf16_t*)W2, b2, M))); break;      // x resident in the accumulators
-        case 11: HIPCHK((launch_mlp_branch<384>(s, x, gamma, beta, 1e-6f, (const bf16_t*)W1, b1, (const bf16_t*)W2, b2, M))); break;           // shared-phase form (encoder_blocks.h)
+        case 11: {                                                                                                                              // shared-phase form (encoder_blocks.h)
+            StagedPair w;
+            CHK(stage_pair(s, W1, (size_t)4 * 384 * 384, W2, (size_t)4 * 384 * 384, w));
+            HIPCHK((launch_mlp_branch<384>(s, x, gamma, beta, 1e-6f, w.a, b1, w.b, b2, M)));
+            CHK(release_pair(s, w));
+            break;
+        }
         default: return fail(PARSEQ_E_INVALID, "variant %d", variant);
     }
     return 0;
@@ -424,7 +456,13 @@ extern "C" int parseq_op_attn_fused(float* x, const float* gamma, const float* b
     hipStream_t s = (hipStream_t)stream;
     switch (variant) {
         case 0: HIPCHK((launch_fused_attn<384>(s, x, gamma, beta, 1e-6f, (const bf16_t*)Wqkv, bqkv, (const bf16_t*)Wproj, bproj, M))); break;
-        case 1: HIPCHK((launch_attn_branch<384>(s, x, gamma, beta, 1e-6f, (const bf16_t*)Wqkv, bqkv, (const bf16_t*)Wproj, bproj, M))); break;   // shared-phase form (encoder_blocks.h)
+        case 1: {                                                                                                                                // shared-phase form (encoder_blocks.h)
+            StagedPair w;
+            CHK(stage_pair(s, Wqkv, (size_t)3 * 384 * 384, Wproj, (size_t)384 * 384, w));
+            HIPCHK((launch_attn_branch<384>(s, x, gamma, beta, 1e-6f, w.a, bqkv, w.b, bproj, M)));
+            CHK(release_pair(s, w));
+            break;
+        }
         default: return fail(PARSEQ_E_INVALID, "variant %d", variant);
     }
     return 0;

@@ -71,6 +71,26 @@ class LexiconBeamResult(BeamResult):
     words: Optional[Tensor] = None       # int32 [B, W] index into `lexicon.words` of a finished hypothesis, -1 otherwise
 
 
+@dataclass
+class Localization:
+    """What `PARSeq.localize` returns, on the device.  L = max_label_length + 1 positions, S = the encoder's patch
+    tokens; coordinates are pixels of the model's input (`img_size`), x to the right and y down."""
+    tokens: Tensor                       # int32 [B, L] the reading that was localised: its characters, <eos> at position `lengths[b]`, pad_id after
+    lengths: Tensor                      # int32 [B] characters before <eos>
+    maps: Tensor                         # fp32 [B, L, S] head-averaged cross-attention of position i over the patch tokens; rows 0 .. lengths[b] sum to 1, the rest are zero
+    centres: Tensor                      # fp32 [B, L, 2] (x, y) centre of mass of the map
+    boxes: Tensor                        # fp32 [B, L, 4] (x0, y0, x1, y1): centre -+ sqrt(3) sigma per axis, clipped to the image
+    peak: Tensor                         # int32 [B, L] the patch token of the largest probability (lowest index on ties); -1 past the reading
+    peak_mass: Tensor                    # fp32 [B, L] that probability
+
+
+def check_labels(labels, max_label_length: int):
+    """The refusal of `localize(images, labels)` that needs no device: a label the model has no positions for."""
+    for y in labels:
+        if len(y) > max_label_length:
+            raise ValueError(f'localize: label {y!r} has {len(y)} characters, the model reads at most max_label_length = {max_label_length}')
+
+
 def init_weights(module: nn.Module, name: str = '', exclude: Sequence[str] = ()):
     """Initialisation scheme of the reference (`strhub/models/utils.py:107-125`): trunc-normal(0.02) Linear / Embedding
     weights, zero biases, unit LayerNorm, Kaiming-normal(fan_out) convolutions.  This is a deliberate statement-for-statement
@@ -670,6 +690,75 @@ class PARSeq(_NativeBacked):
                                               _native.ptr(res.scores), _native.ptr(res.lengths), _native.ptr(res.finished),
                                               C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes, _native.stream_ptr(self._device)))
         return res
+
+    def _check_localizable(self, what: str) -> None:
+        if self._cfg['dec_depth'] != 1:
+            raise ValueError(f"{what} needs dec_depth == 1, this model has dec_depth = {self._cfg['dec_depth']}")
+
+    def attention_maps(self, tokens: Tensor, memory: Optional[Tensor] = None, tgt_padding_mask: Optional[Tensor] = None) -> Tensor:
+        """The map of a reading: head-averaged cross-attention [B, L, S] (fp32) of ONE cloze pass — the pass a
+        refinement iteration of `forward` runs (model.py:154-167) — over `tokens` [B, L]: one reading per row, its characters, then <eos>,
+        then anything; 2 <= L <= max_label_length + 1.  The content is [<bos>, tokens[:, :-1]]; `tgt_padding_mask` [B, L] (True = masked) is the
+        key padding of that content, by default everything from the first <eos> on.  Row i of image b sums to 1 for i <= len(b) (the <eos>
+        position included) and is zero after it.  `memory` as in `decode`."""
+        self._check_localizable('attention_maps')
+        if tokens.dim() != 2:
+            raise RuntimeError(f'tokens must be [B, L], got {list(tokens.shape)}')
+        B, L = tokens.shape
+        if not 2 <= L <= self.max_label_length + 1:
+            raise ValueError(f'attention_maps: {L} positions outside [2, max_label_length + 1 = {self.max_label_length + 1}]')
+        plan = self._plan(B)
+        self._bind_memory(memory, B, plan)
+        tok = tokens.to(device=self._device, dtype=torch.int32)
+        content = torch.cat([torch.full((B, 1), self._make_native_config().bos_id, dtype=torch.int32, device=self._device), tok[:, :-1]], dim=1).contiguous()
+        kpm = tgt_padding_mask.to(device=self._device, dtype=torch.uint8).contiguous() if tgt_padding_mask is not None else None
+        if kpm is not None and tuple(kpm.shape) != (B, L):
+            raise RuntimeError(f'tgt_padding_mask shape {tuple(kpm.shape)} != ({B}, {L})')
+        maps = torch.empty(B, L, self.encoder.pos_embed.shape[1], dtype=torch.float32, device=self._device)
+        _native.check(_native.lib().parseq_decode_attention(plan, _native.ptr(content), B, L, _native.ptr(kpm), _native.ptr(maps), None,
+                                                            _native.stream_ptr(self._device)))
+        return maps
+
+    def localize(self, tokenizer: Tokenizer, images: Tensor, labels=None) -> Localization:
+        """Where every character is: the reading `forward` gives for `images` — or, with `labels` (a list of strings),
+        those strings aligned instead — with the attention map, centre, box and peak of every position.  One library call, no host
+        synchronisation; everything stays on the device (`tokenizer.decode_localization` reads it)."""
+        self._check_localizable('localize')
+        L = self.max_label_length + 1
+        tok_in = None
+        if labels is not None:
+            labels = list(labels)
+            check_labels(labels, self.max_label_length)
+        images = self._check_images(images)
+        B = images.shape[0]
+        dev = images.device
+        if labels is not None:
+            if len(labels) != B:
+                raise ValueError(f'localize: {len(labels)} labels for {B} images')
+            enc = tokenizer.encode(labels)[:, 1:]                      # characters, <eos>, <pad>
+            tok_in = torch.full((B, L), tokenizer.pad_id, dtype=torch.int32)
+            tok_in[:, :enc.shape[1]] = enc
+            tok_in = tok_in.to(dev)
+        plan = self._plan(B)
+        self._memory_key = None                  # this plan's cached K / V now belong to these images
+        if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
+            raise RuntimeError('tokenizer special ids changed after the native model was built')
+        S = self.encoder.pos_embed.shape[1]
+        loc = Localization(torch.empty(B, L, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                           torch.empty(B, L, S, dtype=torch.float32, device=dev), torch.empty(B, L, 2, dtype=torch.float32, device=dev),
+                           torch.empty(B, L, 4, dtype=torch.float32, device=dev), torch.empty(B, L, dtype=torch.int32, device=dev),
+                           torch.empty(B, L, dtype=torch.float32, device=dev))
+        lib = _native.lib()
+        nbytes = lib.parseq_localize_workspace_bytes(plan, B)
+        if nbytes == 0:
+            _native.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        flags = (_native.FLAG_DECODE_AR if self.decode_ar else 0) | _native.FLAG_LATENCY
+        _native.check(lib.parseq_localize(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, _native.ptr(tok_in), flags, int(self.refine_iters),
+                                          _native.ptr(loc.tokens), _native.ptr(loc.lengths), _native.ptr(loc.maps), _native.ptr(loc.centres),
+                                          _native.ptr(loc.boxes), _native.ptr(loc.peak), _native.ptr(loc.peak_mass), _native.ptr(ws), nbytes,
+                                          _native.stream_ptr(self._device)))
+        return loc
 
     def _beam_search_lexicon(self, lexicon, roots, images, plan, res, tr, B, W, num_steps):
         lib, dev = _native.lib(), images.device

@@ -263,6 +263,13 @@ class PARSeq(nn.Module):
             return self.model.beam_search(self.tokenizer, images, beam_width, max_length)
         return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots)
 
+    def localize(self, images: Tensor, labels=None):
+        """Where every character of the reading is (model.PARSeq.localize): a `Localization` on the device with the
+        tokens and lengths that were localised and, per position, the attention map over the patch tokens, its centre, box and peak, in
+        pixels of `img_size`.  `labels`: strings to align to the crops instead of reading them (longer than `max_label_length`: ValueError).
+        `self.tokenizer.decode_localization(result)` turns it into strings and per-character boxes.  uint8 images as in `forward`."""
+        return self.model.localize(self.tokenizer, images, labels)
+
     # ---- evaluation glue used by the reference's test.py:121-126 ------------------------------------------------
     def _eval_step(self, batch, validation: bool):
         return eval_step(self, batch, validation)

@@ -167,3 +167,13 @@ class Tokenizer(BaseTokenizer):
             rows = range(i * w, (i + 1) * w)
             out.append([(label(r), scores[r]) for r in rows if scores[r] != float('-inf')])
         return out
+
+    def decode_localization(self, loc) -> Tuple[List[str], List[List[Tuple[str, Tuple[float, float, float, float]]]]]:
+        """A `Localization` as strings: (labels, per crop the list of (character, (x0, y0, x1, y1)) in reading
+        order), boxes in pixels of the model's input.  One copy to the host."""
+        b, length = loc.tokens.shape
+        packed = torch.cat([loc.tokens, loc.lengths.reshape(b, 1).to(torch.int32), loc.boxes.reshape(b, length * 4).contiguous().view(torch.int32)], dim=1).cpu()
+        ids, lengths = packed[:, :length].numpy(), packed[:, length].tolist()
+        boxes = packed[:, length + 1:].contiguous().view(torch.float32).reshape(b, length, 4).tolist()
+        labels = [self._ids2tok(row[:k].tolist()) for row, k in zip(ids, lengths)]
+        return labels, [[(ch, tuple(boxes[i][j])) for j, ch in enumerate(label)] for i, label in enumerate(labels)]

@@ -138,6 +138,9 @@ class ViTSTR(nn.Module):
                     refine: Optional[str] = None, refine_iters: int = 1):
         raise ValueError('beam_search: ViTSTR has no AR loop (every position is read in one pass); use a PARSeq model')
 
+    def localize(self, images: Tensor, labels=None):
+        raise ValueError('localize: ViTSTR has no decoder, hence no cross-attention over the patch tokens; use a PARSeq model')
+
     def _eval_step(self, batch, validation: bool):
         return eval_step(self, batch, validation)
 

@@ -6,6 +6,7 @@
     ./read.py pretrained=parseq --images a.png --nbest 5 [--beam 8]     the 5 best readings with their log-probabilities under each line
     ./read.py pretrained=parseq --images a.png --lexicon words.txt [--beam 8] [--nbest 3]     read only words of the list (one per line)
     ./read.py pretrained=parseq --images a.png --nbest 5 --refine-beams edit [--refine-iters 2]     refine every alternative, rank them again
+    ./read.py pretrained=parseq --images a.png --boxes     a second line per image: every character with its box in the image's own pixels
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -47,6 +48,27 @@ def read_files_nbest(model, files, nbest, beam_width=None, device='cuda', refine
     return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
 
 
+def scale_box(box, img_size, size):
+    """A box (x0, y0, x1, y1) in pixels of the model's input (`img_size` = (h, w)) in pixels of the original crop (`size` = (h, w)): the resize
+    of the input transform is a plain stretch, so each axis scales on its own."""
+    sx, sy = size[1] / img_size[1], size[0] / img_size[0]
+    return (box[0] * sx, box[1] * sy, box[2] * sx, box[3] * sy)
+
+
+@torch.inference_mode()
+def read_files_boxes(model, files, device='cuda'):
+    """[(file, label, [(character, (x0, y0, x1, y1))])]: the greedy reading of every file and where each of its characters is (DESIGN.md
+    section 21), boxes in pixels of the file's own image.  One batched call."""
+    import numpy as np
+    crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+    if not crops:
+        return []
+    img_size = tuple(model.hparams.img_size)
+    batch = resize_batch(crops, img_size)
+    labels, chars = model.tokenizer.decode_localization(model.localize(batch))
+    return [(f, label, [(ch, scale_box(box, img_size, crop.shape[:2])) for ch, box in row]) for f, label, row, crop in zip(files, labels, chars, crops)]
+
+
 LEXICON_BEAM = 8      # --beam under --lexicon when none is given
 
 
@@ -86,6 +108,9 @@ def build_parser():
     parser.add_argument('--refine-beams', default=None, choices=['edit', 'score'], dest='refine_beams',
                         help="Refine the alternatives of --nbest / --lexicon with the model's cloze pass and rank them again: 'edit' replaces every "
                              "reading by its refined one, 'score' only rescores (the only mode under --lexicon)")
+    parser.add_argument('--boxes', action='store_true',
+                        help="Print a second line per image: every character of the reading with its box (x0,y0,x1,y1) in the image's own pixels; "
+                             'not with --nbest or --lexicon')
     parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
     return parser
 
@@ -127,6 +152,8 @@ def main(argv=None):
     kwargs = parse_model_args(unknown)
     print(f'Additional keyword arguments: {kwargs}')
 
+    if args.boxes and (args.nbest > 0 or args.lexicon is not None):
+        parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
     beam, nbest = resolve_search(parser, args)
     refine, refine_iters = resolve_refine(parser, args)
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
@@ -137,6 +164,11 @@ def main(argv=None):
             print(f'{fname}: {alts[0][0] if alts else ""}')
             for label, logp in (alts if args.nbest > 0 else []):
                 print(f'    {logp:9.4f}  {label}')
+        return
+    if args.boxes:
+        for fname, pred, chars in read_files_boxes(model, files, args.device):
+            print(f'{fname}: {pred}')
+            print('    ' + ' '.join(f'{ch}[{x0:.1f},{y0:.1f},{x1:.1f},{y1:.1f}]' for ch, (x0, y0, x1, y1) in chars))
         return
     alternatives = dict(read_files_nbest(model, files, args.nbest, args.beam, args.device, refine, refine_iters)) if args.nbest > 0 else {}
     for fname, pred, _ in read_files(model, files, args.device):
