@@ -78,6 +78,10 @@ struct DecPass {
     int argmax_mode = 0;      // Lq == 1: greedy pick of position i0 into tok[:, i0 + 1] with the EOS bookkeeping (2: testing, all rows run on)
     const float* user_query = nullptr;
     bool fused_step_allowed = false;      // a single unmasked query may take dec_step_pre / post, which leave no query stream in p->t
+    // A pass writes logits[b][i0 + qi] of a [B][Ltot][C] tensor (the forward's layout).  `out` holds the rows of this pass alone,
+    // [B][Lq][C] with row qi (a decode entry's output, one beam step's logits): hand over the base shifted back by i0 rows, so that the
+    // rows written are exactly [b * Lq + qi] (writing at b * Lq + i0 + qi ran i0 rows past the end of the buffer for i0 > 0).
+    void logits_of_pass(float* out, int C) { logits = out - (size_t)i0 * C; Ltot = Lq; }
 };
 
 // The form a single-query (AR) step takes, decided once per parseq_forward / parseq_decode_* call:
@@ -160,31 +164,26 @@ static int run_cross_attention(parseq_plan* p, hipStream_t s, int layer, int B, 
         case CA_AR24:
             if constexpr (!half && E == 384) {
                 const auto k = qa.nsplit ? dec_cross_attn_ar24_kernel<E, true> : dec_cross_attn_ar24_kernel<E, false>;
-                hipLaunchKernelGGL(k, dim3(B), dim3(E), 0, s, qc_, qa, reinterpret_cast<const unsigned char*>(p->kmem),
-                                   reinterpret_cast<const unsigned char*>(p->vmem), p->kv_plane_elems, scale, ca);
+                return launch(k, dim3(B), dim3(E), 0, s, qc_, qa, reinterpret_cast<const unsigned char*>(p->kmem),
+                              reinterpret_cast<const unsigned char*>(p->vmem), p->kv_plane_elems, scale, ca);
             } else return no_kernel();
-            break;
         case CA_AR: {
             auto k = dec_cross_attn_ar_kernel<T, E, false>;
             if constexpr (E <= 384) { if (qa.nsplit) k = dec_cross_attn_ar_kernel<T, E, true>; }
-            hipLaunchKernelGGL(k, dim3(B), dim3(E), 0, s, qc_, qa, kmem, vmem, scale, ca);
-            break;
+            return launch(k, dim3(B), dim3(E), 0, s, qc_, qa, kmem, vmem, scale, ca);
         }
         case CA_MULTI_MFMA:
-            if constexpr (half) hipLaunchKernelGGL(dec_cross_attn_multi_mfma_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H);
+            if constexpr (half) return launch(dec_cross_attn_multi_mfma_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H);
             else return no_kernel();
-            break;
         case CA_MULTI_X3:      // K / V from the 24-bit rows, or from f32 rows
             if constexpr (half) return no_kernel();
-            else if (kv24) hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<true>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, p->kv_plane_elems);
-            else hipLaunchKernelGGL(dec_cross_attn_multi_mfma_x3_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, (size_t)0);
-            break;
+            else if (kv24) return launch(dec_cross_attn_multi_mfma_x3_kernel<true>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, p->kv_plane_elems);
+            else return launch(dec_cross_attn_multi_mfma_x3_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca, B * H, (size_t)0);
         case CA_MULTI:
             if constexpr (half) return no_kernel();
-            else hipLaunchKernelGGL((dec_cross_attn_multi_kernel<T>), dim3(B * H), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca);
-            break;
+            else return launch(dec_cross_attn_multi_kernel<T>, dim3(B * H), dim3(128), 0, s, qc_, kmem, vmem, H, Lq, scale, ca);
     }
-    HIPCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());      // of the two routes above that set their own dynamic-LDS attribute
     return 0;
 }
 
@@ -197,11 +196,8 @@ static int head_pass(parseq_plan* p, hipStream_t s, const DecW<T>& w, const DecP
     // decoder.norm fused into the head's A operand
     { ProfScope ps_(&p->prof, T_DEC_GEMM, s); CHK((run_ln_gemm<T, E>(s, p->t, w.norm.g, w.norm.b, c.dec_ln_eps, w.head, M, C,
                      epi_store<float>(M, C, w.head_b, a.logits, C, 1.f, a.Lq, a.Ltot, a.i0), p->tn))); }
-    if (a.argmax_mode) {
-        hipLaunchKernelGGL(ar_argmax_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.Ltot, C, p->tok, LDT, a.i0, a.B, c.eos_id,
-                           p->eos_seen, p->counters, p->counters + 1, a.argmax_mode == 2 ? 1 : 0);
-        HIPCHK(hipGetLastError());
-    }
+    if (a.argmax_mode) CHK(launch(ar_argmax_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a.logits, a.Ltot, C, p->tok, LDT, a.i0, a.B, c.eos_id,
+                                  p->eos_seen, p->counters, p->counters + 1, a.argmax_mode == 2 ? 1 : 0));
     return 0;
 }
 
@@ -238,19 +234,18 @@ static int step_pre_post(parseq_plan* p, hipStream_t s, const DecW<bf16_t>& w, c
 // The table self-attention launch of <T, E>: a wave per row up to 512 columns in bf16 and (on the f32 tables) in bf16x3; a thread per
 // column otherwise (fp32, embed_dim 768).
 template <typename T, int E>
-static void launch_self_attn_tables(parseq_plan* p, hipStream_t s, const DecPass& a, T* sa) {
+static int launch_self_attn_tables(parseq_plan* p, hipStream_t s, const DecPass& a, T* sa) {
     const parseq_config& c = p->m->cfg;
     const int M = a.B * a.Lq, npos = c.max_label_length + 1;
     const T* kvtab = reinterpret_cast<const T*>(p->kvtab);
     if constexpr (E <= 512) {
         if (sizeof(T) == 2 || g_split) {
-            hipLaunchKernelGGL((dec_self_attn_wave_kernel<E, T>), dim3((M + 3) / 4), dim3(256), 0, s, p->stab, kvtab, p->tok, LDT, c.num_tokens, npos,
-                               a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, M);
-            return;
+            return launch(dec_self_attn_wave_kernel<E, T>, dim3((M + 3) / 4), dim3(256), 0, s, p->stab, kvtab, p->tok, LDT, c.num_tokens, npos,
+                          a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, M);
         }
     }
-    hipLaunchKernelGGL((dec_self_attn_kernel<T, E>), dim3(M), dim3(E), 0, s, p->stab, kvtab, p->tok, LDT, c.num_tokens, npos,
-                       a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa);
+    return launch(dec_self_attn_kernel<T, E>, dim3(M), dim3(E), 0, s, p->stab, kvtab, p->tok, LDT, c.num_tokens, npos,
+                  a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, (const float*)nullptr);
 }
 
 // Layer 0's self-attention of the position queries, read from the tables (the keys are embeddings: a function of position and token id),
@@ -261,8 +256,7 @@ static int self_attn_tables(parseq_plan* p, hipStream_t s, const DecW<T>& w, con
     T* sa = reinterpret_cast<T*>(p->sa);
     {
         ProfScope ps_(&p->prof, T_DEC_SA, s);
-        launch_self_attn_tables<T, E>(p, s, a, sa);
-        HIPCHK(hipGetLastError());
+        CHK((launch_self_attn_tables<T, E>(p, s, a, sa)));
     }
     ProfScope ps_(&p->prof, T_DEC_GEMM, s);
     return run_gemm<T>(s, ARowMajor<T>{sa, E}, w.layer[0].sa_out, E, M, E, E, epi_table(M, E, w.layer[0].sa_out_b, p->t, E, w.pos_queries, E, a.Lq, a.i0));
@@ -282,11 +276,10 @@ static int self_attn_queries(parseq_plan* p, hipStream_t s, const DecLayerW<T>& 
                      epi_store<float>(M, E, y.sa_in_b, p->qc, E, dec_scale()), p->tn))); }
     {
         ProfScope ps_(&p->prof, T_DEC_SA, s);
-        if (kvself) hipLaunchKernelGGL((dec_self_attn_kv_kernel<T, E>), dim3(M), dim3(E), 0, s, p->qc, reinterpret_cast<const T*>(kvself), npos,
-                                       a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa);
-        else hipLaunchKernelGGL((dec_self_attn_kernel<T, E>), dim3(M), dim3(E), 0, s, p->stab, reinterpret_cast<const T*>(p->kvtab), p->tok, LDT,
-                                c.num_tokens, npos, a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, p->qc);
-        HIPCHK(hipGetLastError());
+        if (kvself) CHK(launch(dec_self_attn_kv_kernel<T, E>, dim3(M), dim3(E), 0, s, p->qc, reinterpret_cast<const T*>(kvself), npos,
+                               a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa));
+        else CHK(launch(dec_self_attn_kernel<T, E>, dim3(M), dim3(E), 0, s, p->stab, reinterpret_cast<const T*>(p->kvtab), p->tok, LDT,
+                        c.num_tokens, npos, a.qmask, LDT, a.kpm, LDT, a.Lk, a.i0, a.Lq, sa, p->qc));
     }
     if (xq != x) HIPCHK(hipMemcpyAsync(x, xq, (size_t)M * E * sizeof(float), hipMemcpyDeviceToDevice, s));
     ProfScope ps_(&p->prof, T_DEC_GEMM, s);
@@ -322,9 +315,7 @@ static int cross_mlp(parseq_plan* p, hipStream_t s, const DecLayerW<T>& y, int l
 template <int E>
 static int content_rows(parseq_plan* p, hipStream_t s, const float* text_embed, const float* pos_queries, int B, int Lc, int i0) {
     const size_t n = (size_t)B * Lc * E;
-    hipLaunchKernelGGL((content_embed_kernel<E>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, text_embed, pos_queries, p->tok, LDT, B, Lc, i0, p->xc);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch(content_embed_kernel<E>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, text_embed, pos_queries, p->tok, LDT, B, Lc, i0, p->xc);
 }
 
 // K | V of norm_c(xc) for layer l's self-attention (modules.py:115, 64): row r of p->xc [M][E] is image r / period at position
@@ -419,16 +410,38 @@ static int ar_loop_fused(parseq_plan* p, hipStream_t s, const DecW<TS>& w, int B
     return 0;
 }
 
+// The cloze pass of a refinement iteration (model.py:154-167) over rows x L positions: every position queried against the whole content
+// in p->tok under the cloze mask, key padding in p->kpm.  `logits` [rows][L][C], or null for the attention map's pass (DecPass::logits).
+// dec_depth > 1: the content stream runs under the same cloze-edited mask (model.py:117, 157: tgt_mask and query_mask are one tensor) over
+// all L positions, those past a row's first EOS key-padded.  After an AR early exit at a length < L that is the reference with
+// tgt_mask[:length, :length] (it raises there: an [L, L] mask against `length` content tokens)
+static DecPass cloze_pass(const parseq_plan* p, int rows, int L, float* logits) {
+    DecPass a; a.B = rows; a.Lk = a.Lq = L; a.qmask = a.cmask = p->cloze; a.kpm = p->kpm; a.logits = logits; a.Ltot = L;
+    return a;
+}
+
+// The content and key padding of a refinement iteration from `logits` [rows][L][C]: tok[:, 0] = <bos>, tok[:, 1:] the arg-max of
+// positions 0 .. L-2 (from_logits 0: tok[:, 1:] already holds them), keys past a row's first EOS padded.
+static int refine_prep(parseq_plan* p, hipStream_t s, int rows, int L, const float* logits, int from_logits) {
+    const parseq_config& c = p->m->cfg;
+    return launch(refine_prep_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, L, p->m->classes, p->tok, LDT, p->kpm, LDT, rows, c.bos_id, c.eos_id, from_logits);
+}
+
+// One refinement iteration: logits [rows][L][C] -> their refinement, in place.
+template <typename T, int E>
+static int refine_iteration(parseq_plan* p, hipStream_t s, const DecW<T>& w, int rows, int L, float* logits, int from_logits) {
+    CHK(refine_prep(p, s, rows, L, logits, from_logits));
+    return decoder_pass<T, E>(p, s, w, cloze_pass(p, rows, L, logits));
+}
+
 template <typename T, int E>
 static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int num_steps, float* logits, int* out_len, hipStream_t s) {
     const parseq_config& c = p->m->cfg;
-    const int C = p->m->classes;
     const bool ar = flags & PARSEQ_FLAG_DECODE_AR, testing = flags & PARSEQ_FLAG_TESTING;
     const DecW<T> w = dec_weights<T>(p);
     const DecRoute route = dec_route(p, flags & PARSEQ_FLAG_LATENCY);
     DecPass a; a.B = B; a.logits = logits; a.Ltot = num_steps; a.fused_step_allowed = route.step == STEP_FUSED;
-    hipLaunchKernelGGL(ar_init_kernel, dim3((B * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, B, c.bos_id, c.pad_id, p->eos_seen, p->counters, 2, num_steps);
-    HIPCHK(hipGetLastError());
+    CHK(launch(ar_init_kernel, dim3((B * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, B, c.bos_id, c.pad_id, p->eos_seen, p->counters, 2, num_steps));
     // model.py:119-147.  All num_steps steps are always run (no per-step host sync); the step at which the reference
     // would have stopped is recorded on the device and only truncates the returned view.
     bool stepwise = ar;      // one decoder_pass per AR step, unless the fused loop runs them all
@@ -446,17 +459,9 @@ static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int 
         CHK((decoder_pass<T, E>(p, s, w, a)));
     }
     for (int it = 0; it < refine_iters; ++it) {
-        // model.py:154-167
         // the first refinement after an AR decode: tok[:, 1:] already holds the greedy picks of positions 0 .. L-2 (the loop computed
         // them from these very logits), so the 95-wide arg-max scan per position (30 us of strided reads at batch 512) is skipped
-        const int from_logits = (ar && it == 0) ? 0 : 1;
-        hipLaunchKernelGGL(refine_prep_kernel, dim3((B + 3) / 4), dim3(256), 0, s, logits, num_steps, C, p->tok, LDT, p->kpm, LDT, B, c.bos_id, c.eos_id, from_logits);
-        HIPCHK(hipGetLastError());
-        // dec_depth > 1: the content stream under the same cloze-edited mask (model.py:117, 157: tgt_mask and query_mask are one tensor) over
-        // all num_steps positions, those past a row's first EOS key-padded.  After an AR early exit at L < num_steps that is the reference
-        // with tgt_mask[:L, :L] (it raises there: a [num_steps, num_steps] mask against L content tokens)
-        a.Lk = a.Lq = num_steps; a.i0 = a.c0 = 0; a.qmask = a.cmask = p->cloze; a.kpm = p->kpm; a.argmax_mode = 0;
-        CHK((decoder_pass<T, E>(p, s, w, a)));
+        CHK((refine_iteration<T, E>(p, s, w, B, num_steps, logits, (ar && it == 0) ? 0 : 1)));
     }
     int L = num_steps;
     if (ar && testing && refine_iters == 0) {
@@ -514,62 +519,73 @@ extern "C" int parseq_forward(parseq_plan* p, const void* images, int images_dty
     return dispatch_te(p, [&](auto te) { return forward_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, flags, refine_iters, num_steps, logits_out, out_len, s); });
 }
 
-static int decode_entry(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len, const uint8_t* query_mask,
-                        const uint8_t* key_padding_mask, float* logits_out, float* hidden_out, void* stream, const float* user_query = nullptr,
-                        const uint8_t* content_mask = nullptr) {
-    if (!p || !tokens || !logits_out) return fail(PARSEQ_E_INVALID, "null argument");
+// A caller's context into the plan's pitched arrays: tokens [batch][ctx_len] -> p->tok (ids clamped to the embedding table), and the key
+// padding [batch][ctx_len] -> p->kpm where there is one.
+static int stage_context(parseq_plan* p, hipStream_t s, const int32_t* tokens, int batch, int ctx_len, const uint8_t* key_padding_mask) {
+    HIPCHK(hipMemcpy2DAsync(p->tok, LDT * sizeof(int), tokens, ctx_len * sizeof(int), ctx_len * sizeof(int), batch, hipMemcpyDeviceToDevice, s));
+    CHK(launch(clamp_tokens_kernel, dim3((batch * ctx_len + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, p->m->cfg.num_tokens));
+    if (key_padding_mask) HIPCHK(hipMemcpy2DAsync(p->kpm, LDT, key_padding_mask, ctx_len, ctx_len, batch, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// What a parseq_decode_* entry asks of decode_entry: the arguments every entry has, then those only some have.  The masks, hidden_out,
+// user_query and content_mask may be null.
+struct DecodeCall {
+    const int32_t* tokens; int batch, ctx_len; const uint8_t *query_mask, *key_padding_mask; float* logits_out; void* stream;
+    int q_start = 0, q_len = 0;
+    float* hidden_out = nullptr;
+    const float* user_query = nullptr;
+    const uint8_t* content_mask = nullptr;
+};
+
+static int decode_entry(parseq_plan* p, const DecodeCall& d) {
+    if (!p || !d.tokens || !d.logits_out) return fail(PARSEQ_E_INVALID, "null argument");
     if (p->m->vitstr) return fail(PARSEQ_E_INVALID, "ViTSTR has no decoder");
     DevGuard dg(p->m->device);
     SplitScope ss(p->precision == PARSEQ_BF16X3);
+    const int batch = d.batch, ctx_len = d.ctx_len, q_start = d.q_start, q_len = d.q_len;
     if (batch <= 0 || batch > p->max_batch || batch != p->last_batch) return fail(PARSEQ_E_INVALID, "batch %d does not match the last parseq_encode (%d)", batch, p->last_batch);
     const int npos = p->m->cfg.max_label_length + 1;
     if (ctx_len < 1 || ctx_len > npos || q_start < 0 || q_len < 1 || q_start + q_len > npos) return fail(PARSEQ_E_INVALID, "bad context / query range");
-    hipStream_t s = (hipStream_t)stream;
-    // stage caller's tokens / masks into the plan's pitched arrays
-    HIPCHK(hipMemcpy2DAsync(p->tok, LDT * sizeof(int), tokens, ctx_len * sizeof(int), ctx_len * sizeof(int), batch, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(clamp_tokens_kernel, dim3((batch * ctx_len + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, p->m->cfg.num_tokens);
-    HIPCHK(hipGetLastError());
-    const unsigned char* kpm = nullptr; const unsigned char* qm = nullptr;
-    if (key_padding_mask) {
-        HIPCHK(hipMemcpy2DAsync(p->kpm, LDT, key_padding_mask, ctx_len, ctx_len, batch, hipMemcpyDeviceToDevice, s));
-        kpm = p->kpm;
+    hipStream_t s = (hipStream_t)d.stream;
+    CHK(stage_context(p, s, d.tokens, batch, ctx_len, d.key_padding_mask));
+    DecPass a; a.B = batch; a.Lk = ctx_len; a.i0 = q_start; a.Lq = q_len; a.user_query = d.user_query;
+    if (d.key_padding_mask) a.kpm = p->kpm;
+    if (d.query_mask) {      // rows are relative to q_start; the kernel indexes by absolute query position
+        HIPCHK(hipMemcpy2DAsync(p->qmask_user + (size_t)q_start * LDT, LDT, d.query_mask, ctx_len, ctx_len, q_len, hipMemcpyDeviceToDevice, s));
+        a.qmask = p->qmask_user;
     }
-    if (query_mask) {      // rows are relative to q_start; the kernel indexes by absolute query position
-        HIPCHK(hipMemcpy2DAsync(p->qmask_user + (size_t)q_start * LDT, LDT, query_mask, ctx_len, ctx_len, q_len, hipMemcpyDeviceToDevice, s));
-        qm = p->qmask_user;
+    if (d.content_mask && p->m->cfg.dec_depth > 1) {      // depth 1 never updates the content stream, so the reference never reads its mask (modules.py:119-124)
+        HIPCHK(hipMemcpy2DAsync(p->cmask_user, LDT, d.content_mask, ctx_len, ctx_len, ctx_len, hipMemcpyDeviceToDevice, s));
+        a.cmask = p->cmask_user;
     }
-    const unsigned char* cm = nullptr;
-    if (content_mask && p->m->cfg.dec_depth > 1) {      // depth 1 never updates the content stream, so the reference never reads its mask (modules.py:119-124)
-        HIPCHK(hipMemcpy2DAsync(p->cmask_user, LDT, content_mask, ctx_len, ctx_len, ctx_len, hipMemcpyDeviceToDevice, s));
-        cm = p->cmask_user;
-    }
-    // A pass writes logits[b][q_start + qi] of a [B][Ltot][C] tensor (the forward's layout).  Here the caller's tensor is
-    // [batch][q_len][C] with row qi: hand over the base shifted back by q_start rows, so that the rows written are exactly
-    // [b * q_len + qi] (writing at b * q_len + q_start + qi ran q_start rows past the end of the buffer for q_start > 0).
-    DecPass a; a.B = batch; a.Lk = ctx_len; a.i0 = q_start; a.Lq = q_len; a.qmask = qm; a.cmask = cm; a.kpm = kpm;
-    a.logits = logits_out - (size_t)q_start * p->m->classes; a.Ltot = q_len; a.user_query = user_query;
-    a.fused_step_allowed = dec_route(p, false).step == STEP_FUSED && !hidden_out;      // hidden_out reads the query stream in p->t
+    a.logits_of_pass(d.logits_out, p->m->classes);      // the caller's tensor is [batch][q_len][C]
+    a.fused_step_allowed = dec_route(p, false).step == STEP_FUSED && !d.hidden_out;      // hidden_out reads the query stream in p->t
     return dispatch_te(p, [&](auto te) {
         using T = typename decltype(te)::T;
         constexpr int E = decltype(te)::E;
         const DecW<T> w = dec_weights<T>(p);
         CHK((decoder_pass<T, E>(p, s, w, a)));
         // model.decode's return value: decoder.norm of the query stream (modules.py:124), fp32
-        if (hidden_out) CHK((run_layernorm<float>(s, p->t, w.norm.g, w.norm.b, hidden_out, nullptr, batch * q_len, E, p->m->cfg.dec_ln_eps)));
+        if (d.hidden_out) CHK((run_layernorm<float>(s, p->t, w.norm.g, w.norm.b, d.hidden_out, nullptr, batch * q_len, E, p->m->cfg.dec_ln_eps)));
         return 0;
     });
 }
 
 extern "C" int parseq_decode_logits(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len,
                                     const uint8_t* query_mask, const uint8_t* key_padding_mask, float* logits_out, void* stream) {
-    return decode_entry(p, tokens, batch, ctx_len, q_start, q_len, query_mask, key_padding_mask, logits_out, nullptr, stream);
+    DecodeCall d{tokens, batch, ctx_len, query_mask, key_padding_mask, logits_out, stream};
+    d.q_start = q_start; d.q_len = q_len;
+    return decode_entry(p, d);
 }
 
 extern "C" int parseq_decode_hidden(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len,
                                     const uint8_t* query_mask, const uint8_t* key_padding_mask, float* hidden_out, float* logits_out,
                                     void* stream) {
     if (!hidden_out) return fail(PARSEQ_E_INVALID, "null hidden_out");
-    return decode_entry(p, tokens, batch, ctx_len, q_start, q_len, query_mask, key_padding_mask, logits_out, hidden_out, stream);
+    DecodeCall d{tokens, batch, ctx_len, query_mask, key_padding_mask, logits_out, stream};
+    d.q_start = q_start; d.q_len = q_len; d.hidden_out = hidden_out;
+    return decode_entry(p, d);
 }
 
 extern "C" int parseq_decode_query(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, const float* query, int q_len,
@@ -578,7 +594,9 @@ extern "C" int parseq_decode_query(parseq_plan* p, const int32_t* tokens, int ba
     if (!query) return fail(PARSEQ_E_INVALID, "null query");
     if (!p) return fail(PARSEQ_E_INVALID, "null plan");
     if (q_len < 1 || q_len > p->m->cfg.max_label_length + 1) return fail(PARSEQ_E_INVALID, "q_len %d outside [1, %d]", q_len, p->m->cfg.max_label_length + 1);
-    return decode_entry(p, tokens, batch, ctx_len, 0, q_len, query_mask, key_padding_mask, logits_out, hidden_out, stream, query);
+    DecodeCall d{tokens, batch, ctx_len, query_mask, key_padding_mask, logits_out, stream};
+    d.q_len = q_len; d.hidden_out = hidden_out; d.user_query = query;
+    return decode_entry(p, d);
 }
 
 extern "C" int parseq_decode_ex(parseq_plan* p, const int32_t* tokens, int batch, int ctx_len, int q_start, int q_len, const float* query,
@@ -586,7 +604,9 @@ extern "C" int parseq_decode_ex(parseq_plan* p, const int32_t* tokens, int batch
                                 float* logits_out, void* stream) {
     if (!p) return fail(PARSEQ_E_INVALID, "null plan");
     if (query && q_start != 0) return fail(PARSEQ_E_INVALID, "q_start %d with a caller-supplied query (must be 0)", q_start);
-    return decode_entry(p, tokens, batch, ctx_len, q_start, q_len, query_mask, key_padding_mask, logits_out, hidden_out, stream, query, content_mask);
+    DecodeCall d{tokens, batch, ctx_len, query_mask, key_padding_mask, logits_out, stream};
+    d.q_start = q_start; d.q_len = q_len; d.hidden_out = hidden_out; d.user_query = query; d.content_mask = content_mask;
+    return decode_entry(p, d);
 }
 
 // The cross-attention K / V of a caller-supplied encoder output (model.decode's `memory` argument, model.py:89): replaces the
@@ -600,8 +620,7 @@ static int set_memory_impl(parseq_plan* p, const float* memory, int B, hipStream
     const T* a;
     if constexpr (sizeof(T) == 2) {
         const size_t n = (size_t)M * E;
-        hipLaunchKernelGGL(cvt_f32_to_bf16_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, memory, reinterpret_cast<bf16_t*>(p->xn), n);
-        HIPCHK(hipGetLastError());
+        CHK(launch(cvt_f32_to_bf16_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, memory, reinterpret_cast<bf16_t*>(p->xn), n));
         a = reinterpret_cast<const T*>(p->xn);
     } else {
         a = memory;
@@ -649,10 +668,7 @@ static int attention_check(const parseq_plan* p, int L) {
 // rows are in whichever form the call that filled the plan left them.
 template <typename T, int E>
 static int attention_pass(parseq_plan* p, hipStream_t s, int B, int L, float* attn_out, float* logits_out) {
-    const DecW<T> w = dec_weights<T>(p);
-    DecPass a; a.B = B; a.Lk = a.Lq = L; a.i0 = a.c0 = 0; a.qmask = a.cmask = p->cloze; a.kpm = p->kpm; a.argmax_mode = 0;
-    a.fused_step_allowed = false; a.logits = logits_out; a.Ltot = L;
-    CHK((decoder_pass<T, E>(p, s, w, a)));
+    CHK((decoder_pass<T, E>(p, s, dec_weights<T>(p), cloze_pass(p, B, L, logits_out))));
     const int H = p->m->cfg.dec_heads, S = p->m->tokens;
     const dim3 grid(B, (L + AM_QB - 1) / AM_QB), block(64 * AM_WAVES);
     if constexpr (sizeof(T) == 2) return launch(dec_cross_attn_map_kernel<AM_K_BF16>, grid, block, 0, s, p->qc, p->kmem, (size_t)0, p->kpm, LDT, H, L, S, dec_scale(), attn_out);
@@ -676,10 +692,8 @@ extern "C" int parseq_decode_attention(parseq_plan* p, const int32_t* tokens, in
     SplitScope ss(p->precision == PARSEQ_BF16X3);
     hipStream_t s = (hipStream_t)stream;
     const parseq_config& c = p->m->cfg;
-    HIPCHK(hipMemcpy2DAsync(p->tok, LDT * sizeof(int), tokens, ctx_len * sizeof(int), ctx_len * sizeof(int), batch, hipMemcpyDeviceToDevice, s));
-    CHK(launch(clamp_tokens_kernel, dim3((batch * ctx_len + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, c.num_tokens));
-    if (key_padding_mask) HIPCHK(hipMemcpy2DAsync(p->kpm, LDT, key_padding_mask, ctx_len, ctx_len, batch, hipMemcpyDeviceToDevice, s));
-    else CHK(launch(attn_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, c.eos_id, c.pad_id, p->kpm, LDT, (int*)nullptr, (int*)nullptr));
+    CHK(stage_context(p, s, tokens, batch, ctx_len, key_padding_mask));
+    if (!key_padding_mask) CHK(launch(attn_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, ctx_len, c.eos_id, c.pad_id, p->kpm, LDT, (int*)nullptr, (int*)nullptr));
     return dispatch_te(p, [&](auto te) { return attention_pass<typename decltype(te)::T, decltype(te)::E>(p, s, batch, ctx_len, attn_out, logits_out); });
 }
 
@@ -718,7 +732,6 @@ extern "C" int parseq_localize(parseq_plan* p, const void* images, int images_dt
     SplitScope ss(p->precision == PARSEQ_BF16X3);
     hipStream_t s = (hipStream_t)stream;
     const parseq_config& c = p->m->cfg;
-    const int C = p->m->classes;
     float* logits = reinterpret_cast<float*>(workspace);
     CHK(encode_dispatch(p, images, images_dtype, batch, nullptr, s));
     return dispatch_te(p, [&](auto te) {
@@ -732,7 +745,7 @@ extern "C" int parseq_localize(parseq_plan* p, const void* images, int images_dt
             // the model's own reading: parseq_forward without the early exit (which only truncates the view), then the context the next
             // refinement iteration would run on — [<bos>, arg-max of the final logits], keys from the first <eos> on padded
             CHK((forward_impl<T, E>(p, batch, flags & ~PARSEQ_FLAG_TESTING, refine_iters, L, logits, nullptr, s)));
-            CHK(launch(refine_prep_kernel, dim3((batch + 3) / 4), dim3(256), 0, s, logits, L, C, p->tok, LDT, p->kpm, LDT, batch, c.bos_id, c.eos_id, 1));
+            CHK(refine_prep(p, s, batch, L, logits, 1));
             CHK(launch(attn_prep_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, p->tok, LDT, batch, L, c.eos_id, c.pad_id, (unsigned char*)nullptr, LDT, tokens_out, lengths_out));
         }
         CHK((attention_pass<T, E>(p, s, batch, L, attn_out, nullptr)));
@@ -744,33 +757,63 @@ extern "C" int parseq_localize(parseq_plan* p, const void* images, int images_dt
 // -------------------------------------------------------------------------------------------------------------------
 // beam search
 // -------------------------------------------------------------------------------------------------------------------
+// The beams' state over rows = batch * W beams, resolved once per call: from the caller's workspace (beam_ws) or from the caller's tensors
+// (the parseq_op_beam_* entries).  A part the call does not have is null.
+struct BeamState {
+    int* tok = nullptr; int ldt = 0;                                                                          // the histories [rows][ldt]
+    float* score = nullptr; unsigned char* finished = nullptr; int* length = nullptr; int* picked = nullptr;  // [rows]
+    int *node = nullptr, *word = nullptr;      // under a lexicon (section 19): every beam's trie node and word id [rows]
+    float* ar_score = nullptr;                 // a refined search (section 20): the search's own score [rows]
+    float* lp_tok = nullptr; int* amax = nullptr; float* lp_max = nullptr;      // ... and the row statistics of an iteration [rows][L]
+
+    static BeamState of_tensors(int32_t* tokens, int ldt, float* scores, uint8_t* finished, int32_t* lengths, int32_t* picked,
+                                int32_t* nodes = nullptr, int32_t* words = nullptr, float* ar_scores = nullptr) {
+        return BeamState{tokens, ldt, scores, finished, lengths, picked, nodes, words, ar_scores};
+    }
+};
+// Where a search's results go, best first per image: tokens [batch][W][num_steps], the others [batch][W]; words under a lexicon, ar_scores
+// of a refined search.
+struct BeamOut { int32_t* tokens; float* scores; int32_t* lengths; uint8_t* finished; int32_t* words = nullptr; float* ar_scores = nullptr; };
+// What a search was asked for beyond the plain one: the per-step trace, a lexicon (the caller's table and roots; forward_beam refuses a
+// null table, so past it trie_next is set exactly under a lexicon), a refinement (the mode, the iterations, its trace).
+struct BeamCall {
+    const parseq_beam_trace* trace = nullptr;
+    bool lexicon = false; const int32_t* trie_next = nullptr; int trie_nodes = 0; const int32_t* roots = nullptr;
+    bool refine = false; int refine_mode = 0, refine_iters = 0; const parseq_beam_refine_trace* refine_trace = nullptr;
+};
+
+// The parts of a caller's workspace, in carve()'s 256-byte steps.  Over a null base only `off`, the size so far, means anything.
+struct Carver {
+    unsigned char* base; size_t off = 0;
+    template <typename T> T* take(size_t count) {
+        const size_t o = carve(off, count * sizeof(T));
+        return base ? reinterpret_cast<T*>(base + o) : nullptr;
+    }
+};
+static void take_refine_stats(Carver& cv, size_t n, BeamState& b) { b.lp_tok = cv.take<float>(n); b.amax = cv.take<int>(n); b.lp_max = cv.take<float>(n); }
+
 // The caller's workspace: the encoder memory of the crops, its W-fold replication (set_memory_impl's operand), one step's logits and the
 // beams' scores / lengths / last picks / flags.  The histories live in p->tok, where the self-attention kernels read them.
 // Under a lexicon (section 19) two more parts follow: every beam's trie node and word id.
 // A refined search (section 20) adds the refinement logits of all num_steps positions, the row statistics and the search's own scores.
-struct BeamWs { size_t memory, memory_rep, logits, score, length, picked, finished, node, word, rlogits, lp_tok, amax, lp_max, ar_score, total; };
-static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon = false, int refine_steps = 0) {
+struct BeamWs { float *memory, *memory_rep, *logits, *rlogits; BeamState st; size_t total; };
+static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon, int refine_steps, void* workspace = nullptr) {
     const parseq_model* m = p->m;
-    const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim * sizeof(float);
-    BeamWs o; size_t off = 0;
-    o.memory = carve(off, (size_t)batch * img);
-    o.memory_rep = carve(off, rows * img);
-    o.logits = carve(off, rows * m->classes * sizeof(float));
-    o.score = carve(off, rows * sizeof(float));
-    o.length = carve(off, rows * sizeof(int));
-    o.picked = carve(off, rows * sizeof(int));
-    o.finished = carve(off, rows);
-    o.node = o.word = 0;
-    if (lexicon) { o.node = carve(off, rows * sizeof(int)); o.word = carve(off, rows * sizeof(int)); }
-    o.rlogits = o.lp_tok = o.amax = o.lp_max = o.ar_score = 0;
+    const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim;
+    Carver cv{reinterpret_cast<unsigned char*>(workspace)};
+    BeamWs o{}; BeamState& b = o.st;
+    b.tok = p->tok; b.ldt = LDT;
+    o.memory = cv.take<float>(batch * img);
+    o.memory_rep = cv.take<float>(rows * img);
+    o.logits = cv.take<float>(rows * m->classes);
+    b.score = cv.take<float>(rows); b.length = cv.take<int>(rows); b.picked = cv.take<int>(rows); b.finished = cv.take<unsigned char>(rows);
+    if (lexicon) { b.node = cv.take<int>(rows); b.word = cv.take<int>(rows); }
     if (refine_steps > 0) {
-        o.rlogits = carve(off, rows * refine_steps * m->classes * sizeof(float));
-        o.lp_tok = carve(off, rows * refine_steps * sizeof(float));
-        o.amax = carve(off, rows * refine_steps * sizeof(int));
-        o.lp_max = carve(off, rows * refine_steps * sizeof(float));
-        o.ar_score = carve(off, rows * sizeof(float));
+        o.rlogits = cv.take<float>(rows * refine_steps * m->classes);
+        take_refine_stats(cv, rows * refine_steps, b);
+        b.ar_score = cv.take<float>(rows);
     }
-    o.total = off;
+    o.total = cv.off;
     return o;
 }
 
@@ -787,146 +830,120 @@ static int beam_check(const parseq_plan* p, int batch, int W, int num_steps) {
     return 0;
 }
 
-extern "C" size_t parseq_beam_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps) {
-    if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
-    return beam_ws(p, batch, beam_width).total;
+// One selection step on logits [batch * W][C] (beam.h); trie_next: null for the unconstrained step
+static int launch_beam_step(hipStream_t s, const float* logits, int batch, int W, int C, int step, const BeamState& b, int* parent_out, int eos_id,
+                            int pad_id, const int32_t* trie_next = nullptr, int trie_nodes = 0) {
+    const auto kernel = trie_next ? beam_step_kernel<true> : beam_step_kernel<false>;
+    return launch(kernel, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, b.ldt), s, logits, W, C, step, b.tok, b.ldt, b.score, b.finished,
+                  b.length, parent_out, b.picked, eos_id, pad_id, trie_next ? BeamLex{trie_next, trie_nodes, b.node, b.word} : BeamLex{});
 }
-
-// lx: null for the unconstrained step
-static int launch_beam_step(hipStream_t s, const float* logits, int batch, int W, int C, int step, int* tok, int ldt, float* score,
-                            unsigned char* finished, int* length, int* parent_out, int* picked, int eos_id, int pad_id, const BeamLex* lx = nullptr) {
-    if (lx) return launch(beam_step_kernel<true>, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, ldt), s, logits, W, C, step, tok, ldt, score,
-                          finished, length, parent_out, picked, eos_id, pad_id, *lx);
-    return launch(beam_step_kernel<false>, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, ldt), s, logits, W, C, step, tok, ldt, score, finished,
-                  length, parent_out, picked, eos_id, pad_id, BeamLex{});
-}
-
-// What a constrained search adds to beam_impl's arguments: the caller's table, roots and output.
-struct BeamLexCall { const int32_t* next; int nodes; const int32_t* roots; int32_t* words_out; };
-// What a refined search adds (section 20): the mode, the iterations, the output of the search's own scores and the optional trace.
-struct BeamRefineCall { int mode, iters; float* ar_scores_out; const parseq_beam_refine_trace* trace; };
 
 // The selection of one refinement iteration on logits [batch * W][L][C]: the row statistics, then the per-image kernel (beam_refine.h).
-static int launch_beam_refine(hipStream_t s, const float* logits, int batch, int W, int C, int L, int mode, int* tok, int ldt, float* score,
-                              unsigned char* finished, int* length, int* picked, int* node, int* word, float* ar_score, float* lp_tok, int* amax,
-                              float* lp_max, int eos_id, int pad_id) {
+static int launch_beam_refine(hipStream_t s, const float* logits, int batch, int W, int C, int L, int mode, const BeamState& b, int eos_id, int pad_id) {
     const size_t waves = (size_t)batch * W * L;
-    CHK(launch(beam_refine_stats_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, logits, batch * W, L, C, tok, ldt, picked, lp_tok, amax, lp_max));
-    return launch(beam_refine_select_kernel, dim3(batch), dim3(BEAM_THREADS), beam_refine_lds(W, ldt), s, mode, W, L, lp_tok, amax, lp_max, tok, ldt,
-                  score, finished, length, picked, node, word, ar_score, eos_id, pad_id);
+    CHK(launch(beam_refine_stats_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, logits, batch * W, L, C, b.tok, b.ldt, b.picked, b.lp_tok,
+               b.amax, b.lp_max));
+    return launch(beam_refine_select_kernel, dim3(batch), dim3(BEAM_THREADS), beam_refine_lds(W, b.ldt), s, mode, W, L, b.lp_tok, b.amax, b.lp_max, b.tok,
+                  b.ldt, b.score, b.finished, b.length, b.picked, b.node, b.word, b.ar_score, eos_id, pad_id);
 }
 
 template <typename T, int E>
-static int beam_impl(parseq_plan* p, int B, int W, int num_steps, unsigned char* ws, const BeamWs& o, int32_t* tokens_out, float* scores_out,
-                     int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* tr, hipStream_t s, const BeamLexCall* lc = nullptr,
-                     const BeamRefineCall* rc = nullptr) {
+static int beam_impl(parseq_plan* p, int B, int W, int num_steps, const BeamWs& ws, const BeamOut& out, const BeamCall& call, hipStream_t s) {
     const parseq_config& c = p->m->cfg;
     const int C = p->m->classes, rows = B * W;
-    const float* memory = reinterpret_cast<const float*>(ws + o.memory);
-    float* memory_rep = reinterpret_cast<float*>(ws + o.memory_rep);
-    float* logits = reinterpret_cast<float*>(ws + o.logits);
-    float* score = reinterpret_cast<float*>(ws + o.score);
-    int* length = reinterpret_cast<int*>(ws + o.length);
-    int* picked = reinterpret_cast<int*>(ws + o.picked);
-    unsigned char* finished = ws + o.finished;
+    const BeamState& b = ws.st;
     // every beam of an image attends to that image's memory: W copies through the projection every caller-supplied memory takes
     const size_t per_img4 = (size_t)p->m->tokens * E / 4, total4 = per_img4 * rows;
-    CHK(launch(beam_replicate_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(memory),
-               reinterpret_cast<float4*>(memory_rep), per_img4, W, total4));
-    CHK(set_memory_impl<T>(p, memory_rep, rows, s));
-    CHK(launch(beam_init_kernel, dim3((rows * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, W, c.bos_id, c.pad_id, score, finished, length, picked));
-    BeamLex lx{};
-    if (lc) {
-        lx = BeamLex{lc->next, lc->nodes, reinterpret_cast<int*>(ws + o.node), reinterpret_cast<int*>(ws + o.word)};
-        CHK(launch(beam_init_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, W, lc->roots, lc->nodes, score, lx.node, lx.word));
-    }
+    CHK(launch(beam_replicate_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(ws.memory),
+               reinterpret_cast<float4*>(ws.memory_rep), per_img4, W, total4));
+    CHK(set_memory_impl<T>(p, ws.memory_rep, rows, s));
+    CHK(launch(beam_init_kernel, dim3((rows * LDT + 255) / 256), dim3(256), 0, s, b.tok, b.ldt, rows, W, c.bos_id, c.pad_id, b.score, b.finished, b.length, b.picked));
+    if (call.lexicon) CHK(launch(beam_init_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, W, call.roots, call.trie_nodes, b.score, b.node, b.word));
     const DecW<T> w = dec_weights<T>(p);
-    DecPass a; a.B = rows; a.Lq = 1; a.Ltot = 1; a.argmax_mode = 0; a.fused_step_allowed = false;
+    const parseq_beam_trace* tr = call.trace;
+    DecPass a; a.B = rows;      // the per-operation step, one query per beam, on every beam's history
     for (int i = 0; i < num_steps; ++i) {
-        // the per-operation step on every beam's history; a pass writes row b of a [B][Ltot][C] tensor at position i0: base shifted back (decode_entry)
-        a.Lk = i + 1; a.i0 = a.c0 = i; a.logits = logits - (size_t)i * C;
+        a.Lk = i + 1; a.i0 = a.c0 = i; a.logits_of_pass(ws.logits, C);      // one step's logits [rows][C]
         CHK((decoder_pass<T, E>(p, s, w, a)));
-        if (tr && tr->logits) HIPCHK(hipMemcpyAsync(tr->logits + (size_t)i * rows * C, logits, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (tr && tr->tokens_in) HIPCHK(hipMemcpy2DAsync(tr->tokens_in + (size_t)i * rows * num_steps, num_steps * sizeof(int), p->tok, LDT * sizeof(int),
+        if (tr && tr->logits) HIPCHK(hipMemcpyAsync(tr->logits + (size_t)i * rows * C, ws.logits, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (tr && tr->tokens_in) HIPCHK(hipMemcpy2DAsync(tr->tokens_in + (size_t)i * rows * num_steps, num_steps * sizeof(int), b.tok, LDT * sizeof(int),
                                                          num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
-        CHK(launch_beam_step(s, logits, B, W, C, i, p->tok, LDT, score, finished, length, tr && tr->parent ? tr->parent + (size_t)i * rows : nullptr,
-                             picked, c.eos_id, c.pad_id, lc ? &lx : nullptr));
-        if (tr && tr->score) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+        CHK(launch_beam_step(s, ws.logits, B, W, C, i, b, tr && tr->parent ? tr->parent + (size_t)i * rows : nullptr, c.eos_id, c.pad_id, call.trie_next,
+                             call.trie_nodes));
+        if (tr && tr->score) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, b.score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    if (rc) {
-        // cloze refinement of every beam (section 20): forward_impl's refinement pass on rows = B * W, then the selection
-        float* rlogits = reinterpret_cast<float*>(ws + o.rlogits);
-        float* ar_score = reinterpret_cast<float*>(ws + o.ar_score);
-        HIPCHK(hipMemcpyAsync(ar_score, score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
-        DecPass ra; ra.B = rows; ra.Lk = ra.Lq = num_steps; ra.i0 = ra.c0 = 0; ra.qmask = ra.cmask = p->cloze; ra.kpm = p->kpm; ra.argmax_mode = 0;
-        ra.fused_step_allowed = false; ra.logits = rlogits; ra.Ltot = num_steps;
-        for (int it = 0; it < rc->iters; ++it) {
-            CHK(launch(refine_prep_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, rlogits, num_steps, C, p->tok, LDT, p->kpm, LDT, rows, c.bos_id, c.eos_id, 0));
-            CHK((decoder_pass<T, E>(p, s, w, ra)));
-            if (rc->trace && rc->trace->tokens_in) HIPCHK(hipMemcpy2DAsync(rc->trace->tokens_in + (size_t)it * rows * num_steps, num_steps * sizeof(int), p->tok,
-                                                                           LDT * sizeof(int), num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
-            if (rc->trace && rc->trace->logits) HIPCHK(hipMemcpyAsync(rc->trace->logits + (size_t)it * rows * num_steps * C, rlogits,
-                                                                      (size_t)rows * num_steps * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-            CHK(launch_beam_refine(s, rlogits, B, W, C, num_steps, rc->mode, p->tok, LDT, score, finished, length, picked, lc ? lx.node : nullptr,
-                                   lc ? lx.word : nullptr, ar_score, reinterpret_cast<float*>(ws + o.lp_tok), reinterpret_cast<int*>(ws + o.amax),
-                                   reinterpret_cast<float*>(ws + o.lp_max), c.eos_id, c.pad_id));
+    if (call.refine) {
+        // cloze refinement of every beam (section 20): forward_impl's refinement iteration on rows = B * W, then the selection
+        const parseq_beam_refine_trace* rt = call.refine_trace;
+        HIPCHK(hipMemcpyAsync(b.ar_score, b.score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+        for (int it = 0; it < call.refine_iters; ++it) {
+            CHK((refine_iteration<T, E>(p, s, w, rows, num_steps, ws.rlogits, 0)));
+            if (rt && rt->tokens_in) HIPCHK(hipMemcpy2DAsync(rt->tokens_in + (size_t)it * rows * num_steps, num_steps * sizeof(int), b.tok, LDT * sizeof(int),
+                                                             num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
+            if (rt && rt->logits) HIPCHK(hipMemcpyAsync(rt->logits + (size_t)it * rows * num_steps * C, ws.rlogits, (size_t)rows * num_steps * C * sizeof(float),
+                                                        hipMemcpyDeviceToDevice, s));
+            CHK(launch_beam_refine(s, ws.rlogits, B, W, C, num_steps, call.refine_mode, b, c.eos_id, c.pad_id));
         }
-        HIPCHK(hipMemcpyAsync(rc->ar_scores_out, ar_score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(out.ar_scores, b.ar_score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-    if (lc) CHK(launch(beam_finish_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, score, finished, lx.word, lc->words_out));
-    return launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, p->tok, LDT, rows, num_steps, c.pad_id, score, finished,
-                  length, picked, tokens_out, scores_out, lengths_out, finished_out);
+    if (call.lexicon) CHK(launch(beam_finish_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, b.score, b.finished, b.word, out.words));
+    return launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, b.tok, b.ldt, rows, num_steps, c.pad_id, b.score, b.finished,
+                  b.length, b.picked, out.tokens, out.scores, out.lengths, out.finished);
 }
 
-static int forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps, int32_t* tokens_out,
-                        float* scores_out, int32_t* lengths_out, uint8_t* finished_out, const parseq_beam_trace* trace, void* workspace,
-                        size_t workspace_bytes, void* stream, const BeamLexCall* lc, const BeamRefineCall* rc = nullptr) {
+// The three search entries: the refusals in one order, the encoder into the workspace, then beam_impl.
+static int forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps, const BeamOut& out,
+                        const BeamCall& call, void* workspace, size_t workspace_bytes, void* stream) {
     CHK(beam_check(p, batch, beam_width, num_steps));
     CHK(check_call(p, batch, images_dtype));
-    if (!images || !tokens_out || !scores_out || !lengths_out || !finished_out || !workspace) return fail(PARSEQ_E_INVALID, "null images / output / workspace");
-    if (lc && (!lc->next || !lc->words_out)) return fail(PARSEQ_E_INVALID, "null trie table / words output");
-    if (lc && lc->nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", lc->nodes);
-    if (rc) {
-        if (rc->mode != PARSEQ_BEAM_REFINE_SCORE && rc->mode != PARSEQ_BEAM_REFINE_EDIT) return fail(PARSEQ_E_INVALID, "refine_mode %d: neither PARSEQ_BEAM_REFINE_SCORE nor PARSEQ_BEAM_REFINE_EDIT", rc->mode);
-        if (rc->iters < 1) return fail(PARSEQ_E_INVALID, "refine_iters %d: at least 1", rc->iters);
-        if (rc->mode == PARSEQ_BEAM_REFINE_SCORE && rc->iters != 1) return fail(PARSEQ_E_INVALID, "refine_iters %d in score mode: rescoring is idempotent, it runs once", rc->iters);
-        if (rc->mode == PARSEQ_BEAM_REFINE_EDIT && lc) return fail(PARSEQ_E_INVALID, "edit refinement under a lexicon: an edited reading can leave the word list; use the score mode");
-        if (!rc->ar_scores_out) return fail(PARSEQ_E_INVALID, "null ar_scores_out");
+    if (!images || !out.tokens || !out.scores || !out.lengths || !out.finished || !workspace) return fail(PARSEQ_E_INVALID, "null images / output / workspace");
+    if (call.lexicon && (!call.trie_next || !out.words)) return fail(PARSEQ_E_INVALID, "null trie table / words output");
+    if (call.lexicon && call.trie_nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", call.trie_nodes);
+    if (call.refine) {
+        const int mode = call.refine_mode, iters = call.refine_iters;
+        if (mode != PARSEQ_BEAM_REFINE_SCORE && mode != PARSEQ_BEAM_REFINE_EDIT) return fail(PARSEQ_E_INVALID, "refine_mode %d: neither PARSEQ_BEAM_REFINE_SCORE nor PARSEQ_BEAM_REFINE_EDIT", mode);
+        if (iters < 1) return fail(PARSEQ_E_INVALID, "refine_iters %d: at least 1", iters);
+        if (mode == PARSEQ_BEAM_REFINE_SCORE && iters != 1) return fail(PARSEQ_E_INVALID, "refine_iters %d in score mode: rescoring is idempotent, it runs once", iters);
+        if (mode == PARSEQ_BEAM_REFINE_EDIT && call.lexicon) return fail(PARSEQ_E_INVALID, "edit refinement under a lexicon: an edited reading can leave the word list; use the score mode");
+        if (!out.ar_scores) return fail(PARSEQ_E_INVALID, "null ar_scores_out");
     }
-    const BeamWs o = beam_ws(p, batch, beam_width, lc != nullptr, rc ? num_steps : 0);
-    if (workspace_bytes < o.total) return fail(PARSEQ_E_INVALID, "beam workspace of %zu bytes, %zu needed", workspace_bytes, o.total);
+    const BeamWs ws = beam_ws(p, batch, beam_width, call.lexicon, call.refine ? num_steps : 0, workspace);
+    if (workspace_bytes < ws.total) return fail(PARSEQ_E_INVALID, "beam workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
     if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "beam workspace not 16-byte aligned");
     DevGuard dg(p->m->device);
     SplitScope ss(p->precision == PARSEQ_BF16X3);
     hipStream_t s = (hipStream_t)stream;
-    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-    CHK(encode_dispatch(p, images, images_dtype, batch, reinterpret_cast<float*>(ws + o.memory), s));
-    return dispatch_te(p, [&](auto te) {
-        return beam_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, beam_width, num_steps, ws, o, tokens_out, scores_out, lengths_out,
-                                                                    finished_out, trace, s, lc, rc);
-    });
+    CHK(encode_dispatch(p, images, images_dtype, batch, ws.memory, s));
+    return dispatch_te(p, [&](auto te) { return beam_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, beam_width, num_steps, ws, out, call, s); });
+}
+
+extern "C" size_t parseq_beam_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps) {
+    if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
+    return beam_ws(p, batch, beam_width, false, 0).total;
 }
 
 extern "C" int parseq_forward_beam(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
                                    int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
                                    const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
-                        workspace_bytes, stream, nullptr);
+    BeamCall call; call.trace = trace;
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, {tokens_out, scores_out, lengths_out, finished_out}, call, workspace,
+                        workspace_bytes, stream);
 }
 
 // lexicon-constrained beam search
 extern "C" size_t parseq_beam_lexicon_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps) {
     if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
-    return beam_ws(p, batch, beam_width, true).total;
+    return beam_ws(p, batch, beam_width, true, 0).total;
 }
 
 extern "C" int parseq_forward_beam_lexicon(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
                                            int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
                                            const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
                                            const int32_t* trie_next, int trie_nodes, const int32_t* roots, int32_t* words_out) {
-    const BeamLexCall lc{trie_next, trie_nodes, roots, words_out};
-    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
-                        workspace_bytes, stream, &lc);
+    BeamCall call; call.trace = trace;
+    call.lexicon = true; call.trie_next = trie_next; call.trie_nodes = trie_nodes; call.roots = roots;
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, {tokens_out, scores_out, lengths_out, finished_out, words_out}, call,
+                        workspace, workspace_bytes, stream);
 }
 
 // cloze refinement of the N-best
@@ -941,25 +958,24 @@ extern "C" int parseq_forward_beam_refine(parseq_plan* p, const void* images, in
                                           const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
                                           const int32_t* trie_next, int trie_nodes, const int32_t* roots, int32_t* words_out, int refine_mode,
                                           int refine_iters, float* ar_scores_out, const parseq_beam_refine_trace* refine_trace) {
-    const BeamLexCall lc{trie_next, trie_nodes, roots, words_out};
-    const BeamRefineCall rc{refine_mode, refine_iters, ar_scores_out, refine_trace};
-    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, tokens_out, scores_out, lengths_out, finished_out, trace, workspace,
-                        workspace_bytes, stream, trie_next ? &lc : nullptr, &rc);
+    BeamCall call; call.trace = trace;
+    call.lexicon = trie_next != nullptr; call.trie_next = trie_next; call.trie_nodes = trie_nodes; call.roots = roots;      // no table: an unconstrained search
+    call.refine = true; call.refine_mode = refine_mode; call.refine_iters = refine_iters; call.refine_trace = refine_trace;
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, {tokens_out, scores_out, lengths_out, finished_out, words_out, ar_scores_out},
+                        call, workspace, workspace_bytes, stream);
 }
 
-// the statistics of parseq_op_beam_refine: lp_tok, amax, lp_max [batch * W][L]
-struct RefineOpWs { size_t lp_tok, amax, lp_max, total; };
-static RefineOpWs refine_op_ws(int batch, int W, int L) {
-    const size_t n = (size_t)batch * W * L;
-    RefineOpWs o; size_t off = 0;
-    o.lp_tok = carve(off, n * sizeof(float)); o.amax = carve(off, n * sizeof(int)); o.lp_max = carve(off, n * sizeof(float));
-    o.total = off;
-    return o;
+// the workspace of parseq_op_beam_refine: the statistics lp_tok, amax, lp_max [batch * W][L]
+static size_t refine_op_ws(int batch, int W, int L, void* workspace, BeamState& b) {
+    Carver cv{reinterpret_cast<unsigned char*>(workspace)};
+    take_refine_stats(cv, (size_t)batch * W * L, b);
+    return cv.off;
 }
 static bool refine_op_shape_ok(int batch, int W, int L) { return batch > 0 && W >= 1 && W <= PARSEQ_BEAM_MAX_WIDTH && L >= 1 && L <= BEAM_REFINE_MAX_L; }
 
 extern "C" size_t parseq_op_beam_refine_workspace_bytes(int batch, int beam_width, int L) {
-    return refine_op_shape_ok(batch, beam_width, L) ? refine_op_ws(batch, beam_width, L).total : 0;
+    BeamState b;
+    return refine_op_shape_ok(batch, beam_width, L) ? refine_op_ws(batch, beam_width, L, nullptr, b) : 0;
 }
 
 extern "C" int parseq_op_beam_refine(const float* logits, int batch, int beam_width, int C, int L, int refine_mode, int32_t* tokens, int ldt,
@@ -970,35 +986,36 @@ extern "C" int parseq_op_beam_refine(const float* logits, int batch, int beam_wi
     if (ldt < L || ldt > 64) return fail(PARSEQ_E_INVALID, "L %d / ldt %d: need L <= ldt <= 64", L, ldt);
     if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
     if (refine_mode != PARSEQ_BEAM_REFINE_SCORE && refine_mode != PARSEQ_BEAM_REFINE_EDIT) return fail(PARSEQ_E_INVALID, "refine_mode %d", refine_mode);
-    const RefineOpWs o = refine_op_ws(batch, beam_width, L);
-    if (workspace_bytes < o.total) return fail(PARSEQ_E_INVALID, "refinement workspace of %zu bytes, %zu needed", workspace_bytes, o.total);
+    BeamState b = BeamState::of_tensors(tokens, ldt, scores, finished, lengths, picked, nodes, words, ar_scores);
+    const size_t need = refine_op_ws(batch, beam_width, L, workspace, b);
+    if (workspace_bytes < need) return fail(PARSEQ_E_INVALID, "refinement workspace of %zu bytes, %zu needed", workspace_bytes, need);
     if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "refinement workspace not 16-byte aligned");
-    unsigned char* ws = reinterpret_cast<unsigned char*>(workspace);
-    return launch_beam_refine((hipStream_t)stream, logits, batch, beam_width, C, L, refine_mode, tokens, ldt, scores, finished, lengths, picked, nodes, words,
-                              ar_scores, reinterpret_cast<float*>(ws + o.lp_tok), reinterpret_cast<int*>(ws + o.amax), reinterpret_cast<float*>(ws + o.lp_max),
-                              eos_id, pad_id);
+    return launch_beam_refine((hipStream_t)stream, logits, batch, beam_width, C, L, refine_mode, b, eos_id, pad_id);
+}
+
+// The two parseq_op_beam_step* entries: their refusals, then the step.  trie_next, nodes and words: the lexicon entry's.
+static int beam_step_op(hipStream_t s, const float* logits, int batch, int W, int C, int step, const BeamState& b, int* parent_out, int eos_id, int pad_id,
+                        bool lexicon, const int32_t* trie_next = nullptr, int trie_nodes = 0) {
+    if (!logits || !b.tok || !b.score || !b.finished || !b.length || !b.picked || (lexicon && (!trie_next || !b.node || !b.word))) return fail(PARSEQ_E_INVALID, "null argument");
+    if (batch <= 0 || C < 1 || W < 1 || W > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d", batch, W, PARSEQ_BEAM_MAX_WIDTH, C);
+    if (step < 0 || b.ldt < step + 1 || b.ldt > 64) return fail(PARSEQ_E_INVALID, "step %d / ldt %d: need step + 1 <= ldt <= 64", step, b.ldt);
+    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
+    if (lexicon && trie_nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", trie_nodes);
+    if (beam_step_lds(W, C, b.ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", W, C);
+    return launch_beam_step(s, logits, batch, W, C, step, b, parent_out, eos_id, pad_id, trie_next, trie_nodes);
 }
 
 extern "C" int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
                                    uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
                                    void* stream) {
-    if (!logits || !tokens || !scores || !finished || !lengths || !picked_out) return fail(PARSEQ_E_INVALID, "null argument");
-    if (batch <= 0 || C < 1 || beam_width < 1 || beam_width > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d", batch, beam_width, PARSEQ_BEAM_MAX_WIDTH, C);
-    if (step < 0 || ldt < step + 1 || ldt > 64) return fail(PARSEQ_E_INVALID, "step %d / ldt %d: need step + 1 <= ldt <= 64", step, ldt);
-    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
-    if (beam_step_lds(beam_width, C, ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", beam_width, C);
-    return launch_beam_step((hipStream_t)stream, logits, batch, beam_width, C, step, tokens, ldt, scores, finished, lengths, parent_out, picked_out, eos_id, pad_id);
+    return beam_step_op((hipStream_t)stream, logits, batch, beam_width, C, step, BeamState::of_tensors(tokens, ldt, scores, finished, lengths, picked_out),
+                        parent_out, eos_id, pad_id, false);
 }
 
 extern "C" int parseq_op_beam_step_lexicon(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
                                            uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
                                            void* stream, const int32_t* trie_next, int trie_nodes, int32_t* nodes, int32_t* words) {
-    if (!logits || !tokens || !scores || !finished || !lengths || !picked_out || !trie_next || !nodes || !words) return fail(PARSEQ_E_INVALID, "null argument");
-    if (batch <= 0 || C < 1 || beam_width < 1 || beam_width > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d", batch, beam_width, PARSEQ_BEAM_MAX_WIDTH, C);
-    if (step < 0 || ldt < step + 1 || ldt > 64) return fail(PARSEQ_E_INVALID, "step %d / ldt %d: need step + 1 <= ldt <= 64", step, ldt);
-    if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
-    if (trie_nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", trie_nodes);
-    if (beam_step_lds(beam_width, C, ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", beam_width, C);
-    const BeamLex lx{trie_next, trie_nodes, nodes, words};
-    return launch_beam_step((hipStream_t)stream, logits, batch, beam_width, C, step, tokens, ldt, scores, finished, lengths, parent_out, picked_out, eos_id, pad_id, &lx);
+    return beam_step_op((hipStream_t)stream, logits, batch, beam_width, C, step,
+                        BeamState::of_tensors(tokens, ldt, scores, finished, lengths, picked_out, nodes, words), parent_out, eos_id, pad_id, true, trie_next,
+                        trie_nodes);
 }

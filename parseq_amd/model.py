@@ -605,16 +605,12 @@ class PARSeq(_NativeBacked):
         spreads over more compute units, a shorter dependent chain.  An explicit slot (0 included) says other batches are in flight
         and keeps the narrower step, whose compute units they need; the two forms differ by rounding only."""
         testing = max_length is None
-        max_length = self.max_label_length if max_length is None else min(max_length, self.max_label_length)
-        num_steps = max_length + 1
+        num_steps = self._num_steps(max_length)
         images = self._check_images(images)
         B = images.shape[0]
         plan = self._plan(B, 0 if slot is None else slot)
-        key = getattr(self, '_memory_key', None)
-        if key is not None and key[2] == plan.value:
-            self._memory_key = None             # this plan's cached K / V now belong to these images, not to an encode() result
-        if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
-            raise RuntimeError('tokenizer special ids changed after the native model was built')
+        self._memory_replaced(plan)
+        self._check_tokenizer(tokenizer)
         logits = torch.empty(B, num_steps, self._cfg['num_tokens'] - 2, dtype=torch.float32, device=images.device)
         flags = ((_native.FLAG_DECODE_AR if self.decode_ar else 0) | (_native.FLAG_TESTING if testing else 0)
                  | (_native.FLAG_LATENCY if slot is None else 0))
@@ -659,36 +655,46 @@ class PARSeq(_NativeBacked):
                              f'{lexicon.next.dtype} {tuple(lexicon.next.shape)}')
         if roots is not None and (roots.dim() != 1 or roots.shape[0] != images.shape[0]):
             raise ValueError(f'beam_search: roots must be [batch] = [{images.shape[0]}], got {tuple(roots.shape)}')
-        max_length = self.max_label_length if max_length is None else min(max_length, self.max_label_length)
-        num_steps = max_length + 1
+        num_steps = self._num_steps(max_length)
         images = self._check_images(images)
         B = images.shape[0]
         plan = self._plan(B * W)
-        self._memory_key = None                  # this plan's cached K / V become the replicated batch's
-        if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
-            raise RuntimeError('tokenizer special ids changed after the native model was built')
+        self._memory_replaced()                  # by the replicated batch's
+        self._check_tokenizer(tokenizer)
         lib, dev = _native.lib(), images.device
         res = (BeamResult if lexicon is None else LexiconBeamResult)(
             torch.empty(B, W, num_steps, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.float32, device=dev),
             torch.empty(B, W, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.uint8, device=dev))
-        tr = None
+        tr = rtr = table = None
         if trace:
             res.trace_logits = torch.empty(num_steps, B * W, classes, dtype=torch.float32, device=dev)
             res.trace_tokens_in = torch.empty(num_steps, B * W, num_steps, dtype=torch.int32, device=dev)
             res.trace_parent = torch.empty(num_steps, B * W, dtype=torch.int32, device=dev)
             res.trace_score = torch.empty(num_steps, B * W, dtype=torch.float32, device=dev)
             tr = _native.BeamTrace(res.trace_logits.data_ptr(), res.trace_tokens_in.data_ptr(), res.trace_parent.data_ptr(), res.trace_score.data_ptr())
-        if refine is not None:
-            return self._beam_search_refine(lexicon, roots, images, plan, res, tr, B, W, num_steps, refine, refine_iters, trace)
         if lexicon is not None:
-            return self._beam_search_lexicon(lexicon, roots, images, plan, res, tr, B, W, num_steps)
-        nbytes = lib.parseq_beam_workspace_bytes(plan, B, W, num_steps)
-        if nbytes == 0:
-            _native.check(-1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # the caller's: a block of torch's caching allocator, stream-ordered
-        _native.check(lib.parseq_forward_beam(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens),
-                                              _native.ptr(res.scores), _native.ptr(res.lengths), _native.ptr(res.finished),
-                                              C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes, _native.stream_ptr(self._device)))
+            table = lexicon.table(dev)
+            if roots is not None:
+                roots = roots.to(dev, torch.int32).contiguous()
+            res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
+        if refine is not None:
+            res.ar_scores = torch.empty(B, W, dtype=torch.float32, device=dev)
+            if trace:
+                res.trace_refine_tokens_in = torch.empty(refine_iters, B * W, num_steps, dtype=torch.int32, device=dev)
+                res.trace_refine_logits = torch.empty(refine_iters, B * W, num_steps, classes, dtype=torch.float32, device=dev)
+                rtr = _native.BeamRefineTrace(res.trace_refine_tokens_in.data_ptr(), res.trace_refine_logits.data_ptr())
+        # the entry of this combination, its workspace, and what it takes after the arguments all three share
+        lex_args = [None, 0, None, None] if table is None else [_native.ptr(table), table.shape[0], _native.ptr(roots), _native.ptr(res.words)]
+        if refine is not None:
+            entry, ws = lib.parseq_forward_beam_refine, self._workspace(lib.parseq_beam_refine_workspace_bytes, plan, B, W, num_steps, int(table is not None))
+            extra = lex_args + [BEAM_REFINE_MODES[refine], refine_iters, _native.ptr(res.ar_scores), C.byref(rtr) if rtr is not None else None]
+        elif lexicon is not None:
+            entry, ws, extra = lib.parseq_forward_beam_lexicon, self._workspace(lib.parseq_beam_lexicon_workspace_bytes, plan, B, W, num_steps), lex_args
+        else:
+            entry, ws, extra = lib.parseq_forward_beam, self._workspace(lib.parseq_beam_workspace_bytes, plan, B, W, num_steps), []
+        _native.check(entry(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens), _native.ptr(res.scores),
+                            _native.ptr(res.lengths), _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), ws.numel(),
+                            _native.stream_ptr(self._device), *extra))
         return res
 
     def _check_localizable(self, what: str) -> None:
@@ -740,74 +746,49 @@ class PARSeq(_NativeBacked):
             tok_in[:, :enc.shape[1]] = enc
             tok_in = tok_in.to(dev)
         plan = self._plan(B)
-        self._memory_key = None                  # this plan's cached K / V now belong to these images
-        if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
-            raise RuntimeError('tokenizer special ids changed after the native model was built')
+        self._memory_replaced()
+        self._check_tokenizer(tokenizer)
         S = self.encoder.pos_embed.shape[1]
         loc = Localization(torch.empty(B, L, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
                            torch.empty(B, L, S, dtype=torch.float32, device=dev), torch.empty(B, L, 2, dtype=torch.float32, device=dev),
                            torch.empty(B, L, 4, dtype=torch.float32, device=dev), torch.empty(B, L, dtype=torch.int32, device=dev),
                            torch.empty(B, L, dtype=torch.float32, device=dev))
         lib = _native.lib()
-        nbytes = lib.parseq_localize_workspace_bytes(plan, B)
-        if nbytes == 0:
-            _native.check(-1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = self._workspace(lib.parseq_localize_workspace_bytes, plan, B)
         flags = (_native.FLAG_DECODE_AR if self.decode_ar else 0) | _native.FLAG_LATENCY
         _native.check(lib.parseq_localize(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, _native.ptr(tok_in), flags, int(self.refine_iters),
                                           _native.ptr(loc.tokens), _native.ptr(loc.lengths), _native.ptr(loc.maps), _native.ptr(loc.centres),
-                                          _native.ptr(loc.boxes), _native.ptr(loc.peak), _native.ptr(loc.peak_mass), _native.ptr(ws), nbytes,
+                                          _native.ptr(loc.boxes), _native.ptr(loc.peak), _native.ptr(loc.peak_mass), _native.ptr(ws), ws.numel(),
                                           _native.stream_ptr(self._device)))
         return loc
-
-    def _beam_search_lexicon(self, lexicon, roots, images, plan, res, tr, B, W, num_steps):
-        lib, dev = _native.lib(), images.device
-        table = lexicon.table(dev)
-        if roots is not None:
-            roots = roots.to(dev, torch.int32).contiguous()
-        res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
-        nbytes = lib.parseq_beam_lexicon_workspace_bytes(plan, B, W, num_steps)
-        if nbytes == 0:
-            _native.check(-1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _native.check(lib.parseq_forward_beam_lexicon(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps,
-                                                      _native.ptr(res.tokens), _native.ptr(res.scores), _native.ptr(res.lengths),
-                                                      _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes,
-                                                      _native.stream_ptr(self._device), _native.ptr(table), table.shape[0],
-                                                      _native.ptr(roots) if roots is not None else None, _native.ptr(res.words)))
-        return res
-
-    def _beam_search_refine(self, lexicon, roots, images, plan, res, tr, B, W, num_steps, refine, refine_iters, trace):
-        lib, dev = _native.lib(), images.device
-        classes = self._cfg['num_tokens'] - 2
-        table = None
-        if lexicon is not None:
-            table = lexicon.table(dev)
-            if roots is not None:
-                roots = roots.to(dev, torch.int32).contiguous()
-            res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
-        res.ar_scores = torch.empty(B, W, dtype=torch.float32, device=dev)
-        rtr = None
-        if trace:
-            res.trace_refine_tokens_in = torch.empty(refine_iters, B * W, num_steps, dtype=torch.int32, device=dev)
-            res.trace_refine_logits = torch.empty(refine_iters, B * W, num_steps, classes, dtype=torch.float32, device=dev)
-            rtr = _native.BeamRefineTrace(res.trace_refine_tokens_in.data_ptr(), res.trace_refine_logits.data_ptr())
-        nbytes = lib.parseq_beam_refine_workspace_bytes(plan, B, W, num_steps, int(lexicon is not None))
-        if nbytes == 0:
-            _native.check(-1)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _native.check(lib.parseq_forward_beam_refine(
-            plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens), _native.ptr(res.scores),
-            _native.ptr(res.lengths), _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), nbytes,
-            _native.stream_ptr(self._device), _native.ptr(table) if table is not None else None, table.shape[0] if table is not None else 0,
-            _native.ptr(roots) if (table is not None and roots is not None) else None, _native.ptr(res.words) if table is not None else None,
-            BEAM_REFINE_MODES[refine], refine_iters, _native.ptr(res.ar_scores), C.byref(rtr) if rtr is not None else None))
-        return res
 
     # ---- native plumbing ---------------------------------------------------------------------------------------
     def _special_ids(self, tokenizer):
         self._tok_ids = getattr(self, '_tok_ids', None) or (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id)
         return self._tok_ids
+
+    def _check_tokenizer(self, tokenizer) -> None:
+        if (tokenizer.bos_id, tokenizer.eos_id, tokenizer.pad_id) != self._special_ids(tokenizer):
+            raise RuntimeError('tokenizer special ids changed after the native model was built')
+
+    def _num_steps(self, max_length: Optional[int]) -> int:
+        """`max_length` as `forward` takes it (None: the model's) -> the positions decoded, the <eos> included."""
+        return (self.max_label_length if max_length is None else min(max_length, self.max_label_length)) + 1
+
+    def _memory_replaced(self, plan=None) -> None:
+        """A call that encodes its own images: the plan's cached K / V now belong to them, not to an `encode()` result.  With `plan`,
+        only if the remembered memory is that plan's (`forward` on another slot leaves it alone)."""
+        key = getattr(self, '_memory_key', None)
+        if plan is None or (key is not None and key[2] == plan.value):
+            self._memory_key = None
+
+    def _workspace(self, sizer, *args) -> Tensor:
+        """The caller's workspace of a library call, sized by its `*_workspace_bytes` function (0: a refusal, raised with the library's
+        message): a block of torch's caching allocator, stream-ordered."""
+        nbytes = sizer(*args)
+        if nbytes == 0:
+            _native.check(-1)
+        return torch.empty(nbytes, dtype=torch.uint8, device=self._device)
 
     def _make_native_config(self):
         tok_ids = getattr(self, '_tok_ids', None)
