@@ -479,6 +479,43 @@ size_t parseq_augment_workspace_bytes(const parseq_augment_desc* descs, int batc
 int parseq_augment_resize_bicubic(const parseq_augment_desc* descs, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* ---- rectification of quadrilateral text regions ------------------------------------------- */
+
+/* What a caller with a text detector does first: cut every detected quadrilateral out of the scene and straighten it.  A region names one
+ * of the call's source images and carries the size of its rectified crop and Pillow's PERSPECTIVE data; any number of regions may name
+ * the same image.  The result is, byte for byte, Image.fromarray(src).transform((width, height), Image.PERSPECTIVE, coef, Image.BICUBIC)
+ * with fill 0: for output pixel (x, y), X = x + 0.5, Y = y + 0.5, in double precision without contraction and with correctly rounded
+ * divisions,
+ *     sx = (coef[0] X + coef[1] Y + coef[2]) / (coef[6] X + coef[7] Y + 1),   sy = (coef[3] X + coef[4] Y + coef[5]) / (the same);
+ * the pixel stays 0 unless 0 <= sx < width and 0 <= sy < height of the source; otherwise Pillow's bicubic filter (sixteen clamped taps)
+ * around (sx - 0.5, sy - 0.5), clipped to 0 .. 255 and truncated.  The library does no geometry: the caller derives the coefficients from
+ * its quadrilateral (parseq_amd/preprocess.py quad_coeffs).  Came after ABI 15 without a new version: pure additions.
+ * Refused with PARSEQ_E_INVALID before any device work, outputs untouched: an image index outside 0 .. n_images - 1, a side outside
+ * 1 .. PARSEQ_ROTATE_MAX_SIDE, a coefficient that is not finite, a denominator coef[6] X + coef[7] Y + 1 that is not > 0 at one of the
+ * four corners of the output rectangle (0, 0), (width, 0), (width, height), (0, height) — it is linear, so it is then positive at every
+ * pixel —, a source image whose row_stride * height does not fit 31 bits, a workspace that is too small. */
+typedef struct {
+    int32_t image;                    /* index into the call's images */
+    int32_t height, width;            /* of the rectified region */
+    double coef[8];
+} parseq_region_desc;
+
+/* Bytes of workspace the two calls below need for these regions (HOST array) and n_images source images: the device copies of both
+ * arrays, the tile table, the region images of the resize and one slot of 3 * width * height bytes per region (rounded up to 256).
+ * 0 if a region's size is out of range (parseq_last_error says why). */
+size_t parseq_rectify_workspace_bytes(const parseq_region_desc* regions, int n_regions, int n_images);
+
+/* The rectified regions themselves, one launch for all of them: outs = HOST array of n_regions device pointers, region i written to
+ * outs[i] as uint8 [height_i, width_i, 3], dense.  images, regions and outs are copied on `stream`: keep them alive until the stream has
+ * passed.  No allocation, no synchronisation inside. */
+int parseq_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions, uint8_t* const* outs,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* parseq_rectify into the workspace's slots, then parseq_resize_bicubic's arithmetic (the same kernel) on the rectified regions: out =
+ * device uint8 [n_regions, 3, out_h, out_w], the PARSEQ_U8 input of the model, with no host round trip. */
+int parseq_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions,
+                                  int out_h, int out_w, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- post-processing --------------------------------------------------------------- */
 
 /* Numeric half of `preds, probs = tokenizer.decode(logits.softmax(-1))` (strhub/models/base.py:132-137,

@@ -36,6 +36,11 @@ class RotatedImageDesc(C.Structure):
                 ('rot_height', C.c_int32), ('rot_width', C.c_int32), ('a', C.c_int32 * 6)]
 
 
+class RegionDesc(C.Structure):
+    """parseq_region_desc: a source image's index, the rectified size and Pillow's PERSPECTIVE data (parseq_amd/preprocess.py quad_coeffs)."""
+    _fields_ = [('image', C.c_int32), ('height', C.c_int32), ('width', C.c_int32), ('coef', C.c_double * 8)]
+
+
 class AugmentBlur(C.Structure):
     """arg.blur of PARSEQ_AUG_GAUSSIAN_BLUR: one box pass (parseq_amd/augment.py gaussian_box)."""
     _fields_ = [('r', C.c_int32), ('ww', C.c_uint32), ('fw', C.c_uint32)]
@@ -121,6 +126,10 @@ SIGNATURES = {
     'parseq_augment_workspace_bytes': (C.c_size_t, [C.POINTER(AugmentDesc), C.c_int]),
     'parseq_augment_resize_bicubic': (C.c_int, [C.POINTER(AugmentDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_op_augment': (C.c_int, [C.POINTER(AugmentDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_rectify_workspace_bytes': (C.c_size_t, [C.POINTER(RegionDesc), C.c_int, C.c_int]),
+    'parseq_rectify': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(RegionDesc), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_rectify_resize_bicubic': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(RegionDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.c_void_p]),
     'parseq_cross_entropy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_eval_metrics': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -313,7 +322,7 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def guard(device):
     """Context manager making `device` (torch.device or tensor) current: for the raw-pointer entry points (parseq_op_*,
-    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
+    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_rectify, parseq_rectify_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
     import torch
     if hasattr(device, 'device'):
         device = device.device

@@ -131,6 +131,37 @@ __device__ __forceinline__ double aug_cubic(double v1, double v2, double v3, dou
 
 __device__ __forceinline__ int aug_clampi(int v, int n) { return v < 0 ? 0 : (v < n ? v : n - 1); }
 
+// Pillow's bicubic_filter32RGB around source pixel (fx, fy) with the fractions (dx, dy): sixteen clamped taps, a row outside the image
+// repeating the value of the row above, clipped and truncated.  Shared by the affine operator below and the projective map of rectify.h.
+__device__ __forceinline__ void aug_bicubic_taps(const unsigned char* src, long long stride, int h, int w, int fx, int fy, double dx, double dy,
+                                                 unsigned char* out) {
+    AUG_NO_CONTRACT
+    size_t xs[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) xs[t] = (size_t)aug_clampi(fx - 1 + t, w) * 3;
+    const unsigned char* rows[4];
+    bool has[4];
+    rows[0] = src + (size_t)aug_clampi(fy - 1, h) * stride; has[0] = true;
+#pragma unroll
+    for (int t = 1; t < 4; ++t) {
+        const int yy = fy - 1 + t;
+        has[t] = yy >= 0 && yy < h;
+        rows[t] = src + (size_t)(has[t] ? yy : 0) * stride;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double v[4];
+        v[0] = aug_cubic(rows[0][xs[0] + c], rows[0][xs[1] + c], rows[0][xs[2] + c], rows[0][xs[3] + c], dx);
+#pragma unroll
+        for (int t = 1; t < 4; ++t) {
+            if (has[t]) v[t] = aug_cubic(rows[t][xs[0] + c], rows[t][xs[1] + c], rows[t][xs[2] + c], rows[t][xs[3] + c], dx);
+            else v[t] = v[t - 1];                  // a missing row repeats the value of the row above
+        }
+        const double r = aug_cubic(v[0], v[1], v[2], v[3], dy);
+        out[c] = r <= 0.0 ? 0 : (r >= 255.0 ? 255 : (unsigned char)(int)r);
+    }
+}
+
 // one output pixel of Image.transform(AFFINE): false where the fill colour stays
 __device__ __forceinline__ bool aug_affine_pixel(const unsigned char* src, long long stride, int h, int w, const double* a, int resample,
                                                  int x, int y, unsigned char* out) {
@@ -156,30 +187,7 @@ __device__ __forceinline__ bool aug_affine_pixel(const unsigned char* src, long 
             out[c] = (unsigned char)(int)AUG_ADD(v1, AUG_MUL(AUG_ADD(v2, -v1), dy));
         }
     } else {
-        size_t xs[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) xs[t] = (size_t)aug_clampi(fx - 1 + t, w) * 3;
-        const unsigned char* rows[4];
-        bool has[4];
-        rows[0] = src + (size_t)aug_clampi(fy - 1, h) * stride; has[0] = true;
-#pragma unroll
-        for (int t = 1; t < 4; ++t) {
-            const int yy = fy - 1 + t;
-            has[t] = yy >= 0 && yy < h;
-            rows[t] = src + (size_t)(has[t] ? yy : 0) * stride;
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double v[4];
-            v[0] = aug_cubic(rows[0][xs[0] + c], rows[0][xs[1] + c], rows[0][xs[2] + c], rows[0][xs[3] + c], dx);
-#pragma unroll
-            for (int t = 1; t < 4; ++t) {
-                if (has[t]) v[t] = aug_cubic(rows[t][xs[0] + c], rows[t][xs[1] + c], rows[t][xs[2] + c], rows[t][xs[3] + c], dx);
-                else v[t] = v[t - 1];                  // a missing row repeats the value of the row above
-            }
-            const double r = aug_cubic(v[0], v[1], v[2], v[3], dy);
-            out[c] = r <= 0.0 ? 0 : (r >= 255.0 ? 255 : (unsigned char)(int)r);
-        }
+        aug_bicubic_taps(src, stride, h, w, fx, fy, dx, dy, out);
     }
     return true;
 }

@@ -1,7 +1,7 @@
 // libparseq_hip.so — input resize, post-process, and the per-kernel entry points the parity tests call.
 #include "lib_internal.h"
 #include "eval_metrics.h"
-#include "augment.h"
+#include "rectify.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 static int resize_taps(int in_size, int out_size) {
@@ -247,6 +247,135 @@ extern "C" int parseq_op_augment(const parseq_augment_desc* desc, uint8_t* out, 
     const int h = n ? desc->ops[n - 1].out_height : desc->height, w = n ? desc->ops[n - 1].out_width : desc->width;
     const unsigned char* last = n ? static_cast<unsigned char*>(workspace) + l.regions + (size_t)((n - 1) & 1) * aug_region_bytes(*desc) : desc->data;
     HIPCHK(hipMemcpy2DAsync(out, (size_t)w * 3, last, n ? (size_t)w * 3 : (size_t)desc->row_stride, (size_t)w * 3, (size_t)h, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// rectification of quadrilateral regions (rectify.h), alone and ahead of the resize above
+// -------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(parseq_region_desc) == sizeof(RegionDesc) && offsetof(parseq_region_desc, coef) == offsetof(RegionDesc, coef) &&
+              offsetof(parseq_region_desc, width) == offsetof(RegionDesc, width), "descriptor layouts must match");
+
+struct RectLayout { size_t regions, images, tiles, dst, finals, outs, slots, total; long long n_tiles; };
+
+static int check_region_size(const parseq_region_desc& r, int i) {
+    if (!aug_side_ok(r.height) || !aug_side_ok(r.width))
+        return fail(PARSEQ_E_INVALID, "region %d: size %dx%d, each side must be in 1 .. %d", i, r.height, r.width, PARSEQ_ROTATE_MAX_SIDE);
+    return 0;
+}
+
+// sizes only: what parseq_rectify_workspace_bytes can know
+static RectLayout rect_layout(const parseq_region_desc* regions, int n, int n_images) {
+    RectLayout l;
+    l.regions = 0;
+    l.images = l.regions + aug_align((size_t)n * sizeof(RegionDesc));
+    l.tiles = l.images + aug_align((size_t)n_images * sizeof(ImageDesc));
+    l.dst = l.tiles + aug_align((size_t)(n + 1) * sizeof(int));
+    l.finals = l.dst + aug_align((size_t)n * sizeof(unsigned char*));
+    l.outs = l.finals + aug_align((size_t)n * sizeof(ImageDesc));
+    l.slots = l.outs + aug_align((size_t)n * sizeof(unsigned char*));
+    l.total = l.slots;
+    l.n_tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        l.total += rect_slot_bytes(regions[i].height, regions[i].width);
+        l.n_tiles += rect_tiles(regions[i].height, regions[i].width);
+    }
+    return l;
+}
+
+extern "C" size_t parseq_rectify_workspace_bytes(const parseq_region_desc* regions, int n_regions, int n_images) {
+    if (!regions || n_regions <= 0 || n_images <= 0) { fail(PARSEQ_E_INVALID, "null regions / %d regions / %d images", n_regions, n_images); return 0; }
+    for (int i = 0; i < n_regions; ++i)
+        if (check_region_size(regions[i], i)) return 0;
+    return rect_layout(regions, n_regions, n_images).total;
+}
+
+static int check_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n) {
+    if (!images || !regions) return fail(PARSEQ_E_INVALID, "null images / regions");
+    if (n_images <= 0 || n <= 0) return fail(PARSEQ_E_INVALID, "bad shape: %d images, %d regions", n_images, n);
+    for (int i = 0; i < n_images; ++i) {
+        const parseq_image_desc& d = images[i];
+        if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
+            return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
+        if (d.row_stride > INT32_MAX / d.height)
+            return fail(PARSEQ_E_INVALID, "image %d: %d rows of %lld bytes do not fit 31 bits", i, d.height, (long long)d.row_stride);
+    }
+    for (int i = 0; i < n; ++i) {
+        const parseq_region_desc& r = regions[i];
+        if (r.image < 0 || r.image >= n_images) return fail(PARSEQ_E_INVALID, "region %d: image index %d is outside 0 .. %d", i, r.image, n_images - 1);
+        CHK(check_region_size(r, i));
+        for (int t = 0; t < 8; ++t)
+            if (!std::isfinite(r.coef[t])) return fail(PARSEQ_E_INVALID, "region %d: coefficient %d is not finite", i, t);
+        const double w = r.width, h = r.height;
+        const double corners[4][2] = {{0.0, 0.0}, {w, 0.0}, {w, h}, {0.0, h}};
+        for (const auto& c : corners) {
+            const double den = r.coef[6] * c[0] + r.coef[7] * c[1] + 1.0;
+            if (!(den > 0.0))
+                return fail(PARSEQ_E_INVALID, "region %d: the denominator is %g at output corner (%g, %g), it must be > 0 over the output", i, den, c[0], c[1]);
+        }
+    }
+    return 0;
+}
+
+// copies images, regions (and outs, if any) into the workspace, plans and rectifies on `s`: ONE launch for all regions after the plan
+static int rectify_run(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n, uint8_t* const* outs, void* workspace,
+                       size_t workspace_bytes, hipStream_t s, RectLayout* layout) {
+    if (!workspace) return fail(PARSEQ_E_INVALID, "null workspace");
+    const RectLayout l = rect_layout(regions, n, n_images);
+    if (workspace_bytes < l.total)
+        return fail(PARSEQ_E_INVALID, "workspace of %zu bytes, %zu needed (parseq_rectify_workspace_bytes)", workspace_bytes, l.total);
+    if (l.n_tiles > RECT_MAX_TILES)                      // 256 work-items each: the launch holds fewer than 2^32 of them
+        return fail(PARSEQ_E_INVALID, "%lld tiles of %dx%d pixels in one call, at most %d", l.n_tiles, RECT_TILE, RECT_TILE, RECT_MAX_TILES);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    const RegionDesc* rr = reinterpret_cast<const RegionDesc*>(ws + l.regions);
+    const ImageDesc* ii = reinterpret_cast<const ImageDesc*>(ws + l.images);
+    int* tile_start = reinterpret_cast<int*>(ws + l.tiles);
+    unsigned char** dst = reinterpret_cast<unsigned char**>(ws + l.dst);
+    unsigned char** douts = nullptr;
+    HIPCHK(hipMemcpyAsync(ws + l.regions, regions, (size_t)n * sizeof(RegionDesc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ws + l.images, images, (size_t)n_images * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
+    if (outs) {
+        douts = reinterpret_cast<unsigned char**>(ws + l.outs);
+        HIPCHK(hipMemcpyAsync(douts, outs, (size_t)n * sizeof(unsigned char*), hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(rectify_plan_kernel, dim3(1), dim3(256), 0, s, rr, n, douts, ws + l.slots, tile_start, dst, reinterpret_cast<ImageDesc*>(ws + l.finals));
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(rectify_kernel, dim3((unsigned)l.n_tiles), dim3(256), 0, s, ii, n_images, rr, n, tile_start, dst);
+    HIPCHK(hipGetLastError());
+    *layout = l;
+    return 0;
+}
+
+extern "C" int parseq_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions, uint8_t* const* outs,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(sizeof(parseq_image_desc) == sizeof(ImageDesc), "descriptor layouts must match");
+    CHK(check_rectify(images, n_images, regions, n_regions));
+    if (!outs) return fail(PARSEQ_E_INVALID, "null outs");
+    for (int i = 0; i < n_regions; ++i)
+        if (!outs[i]) return fail(PARSEQ_E_INVALID, "region %d: null output", i);
+    RectLayout l;
+    return rectify_run(images, n_images, regions, n_regions, outs, workspace, workspace_bytes, (hipStream_t)stream, &l);
+}
+
+extern "C" int parseq_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions,
+                                             int out_h, int out_w, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!out) return fail(PARSEQ_E_INVALID, "null out");
+    if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
+    CHK(check_rectify(images, n_images, regions, n_regions));
+    int ksh = 1, ksv = 1;
+    for (int i = 0; i < n_regions; ++i) {
+        ksh = std::max(ksh, resize_taps(regions[i].width, out_w));
+        ksv = std::max(ksv, resize_taps(regions[i].height, out_h));
+    }
+    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
+    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "a rectified region is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
+    hipStream_t s = (hipStream_t)stream;
+    RectLayout l;
+    CHK(rectify_run(images, n_images, regions, n_regions, nullptr, workspace, workspace_bytes, s, &l));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(n_regions), dim3(256), lds, s,
+                       reinterpret_cast<const ImageDesc*>(static_cast<unsigned char*>(workspace) + l.finals), out_h, out_w, ksh, ksv, out);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

@@ -7,6 +7,7 @@
     ./read.py pretrained=parseq --images a.png --lexicon words.txt [--beam 8] [--nbest 3]     read only words of the list (one per line)
     ./read.py pretrained=parseq --images a.png --nbest 5 --refine-beams edit [--refine-iters 2]     refine every alternative, rank them again
     ./read.py pretrained=parseq --images a.png --boxes     a second line per image: every character with its box in the image's own pixels
+    ./read.py pretrained=parseq --images scene.jpg --regions scene.txt [--boxes]     read every quadrilateral of the file (x1,y1,..,x4,y4 per line)
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -69,6 +70,85 @@ def read_files_boxes(model, files, device='cuda'):
     return [(f, label, [(ch, scale_box(box, img_size, crop.shape[:2])) for ch, box in row]) for f, label, row, crop in zip(files, labels, chars, crops)]
 
 
+def load_regions(path):
+    """The quadrilaterals of an ICDAR-2015 style file: every non-empty line is `x1,y1,x2,y2,x3,y3,x4,y4[,transcription]`, the corners
+    clockwise from the text's top-left; whatever follows an eighth comma is ignored.  Returns [((x1, y1), .. (x4, y4))] as floats; a line
+    that is not eight finite numbers is a ValueError naming file and line."""
+    import math
+    quads = []
+    with open(path, encoding='utf-8-sig') as fh:
+        for number, line in enumerate(fh, 1):
+            if not line.strip():
+                continue
+            try:
+                v = [float(field) for field in line.split(',')[:8]]
+                if len(v) != 8 or not all(math.isfinite(x) for x in v):
+                    raise ValueError
+            except ValueError:
+                raise ValueError(f'{path}, line {number}: expected eight comma-separated numbers x1,y1,..,x4,y4, got {line.strip()!r}') from None
+            quads.append(tuple(zip(v[0::2], v[1::2])))
+    return quads
+
+
+@torch.inference_mode()
+def load_region_batch(model, files, region_files, device='cuda'):
+    """The regions of `region_files[i]` cut out of `files[i]` and straightened, as one batch for the model: every
+    scene is decoded and uploaded once, all regions of all scenes go through ONE rectify-and-resize call.  Returns (names, batch, back):
+    `file#k` per region, k counting from 0 within its file; uint8 [N, 3, H, W] (None without regions); per region the (coefficients, (h, w))
+    with which `map_to_source` leads from the model's input back into the scene."""
+    import numpy as np
+    from parseq_amd.preprocess import rectify_resize_batch, region_descs
+    names, regions = [], []
+    for i, (f, rf) in enumerate(zip(files, region_files)):
+        for k, quad in enumerate(load_regions(rf)):
+            names.append(f'{f}#{k}')
+            regions.append((i, quad))
+    if not regions:
+        return [], None, []
+    described = region_descs(regions, n_images=len(files))
+    scenes = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+    batch = rectify_resize_batch(scenes, [(index, coeffs, size) for index, size, coeffs in described], tuple(model.hparams.img_size))
+    return names, batch, [(coeffs, size) for _, size, coeffs in described]
+
+
+@torch.inference_mode()
+def read_regions(model, files, region_files, beam=None, nbest=0, words=None, list_words=False, refine=None, refine_iters=1, boxes=False, device='cuda'):
+    """The lines `--regions` prints, for the same flags as the whole-crop readings above, on the batch of `load_region_batch`: `words` is the
+    list of --lexicon (its alternatives are listed only with `list_words`), `boxes` adds every character's quadrilateral in the scene."""
+    from parseq_amd.preprocess import map_to_source
+    names, batch, back = load_region_batch(model, files, region_files, device)
+    if not names:
+        return []
+    lines = []
+    if words is not None:
+        from parseq_amd.lexicon import Lexicon
+        lexicon = Lexicon(words, model.tokenizer, fold_case=True, max_label_length=model.model.max_label_length).to(device)
+        search = {} if refine is None else {'refine': refine}
+        beams = model.tokenizer.decode_beams(model.beam_search(batch, beam, lexicon=lexicon, **search), lexicon)
+        for name, alts in zip(names, beams):
+            alts = alts[:nbest]
+            lines.append(f'{name}: {alts[0][0] if alts else ""}')
+            lines += [f'    {logp:9.4f}  {label}' for label, logp in (alts if list_words else [])]
+        return lines
+    if boxes:
+        img_size = tuple(model.hparams.img_size)
+        labels, chars = model.tokenizer.decode_localization(model.localize(batch))
+        for name, label, row, (coeffs, size) in zip(names, labels, chars, back):
+            lines.append(f'{name}: {label}')
+            quads = [(ch, map_to_source(coeffs, size, img_size, ((x0, y0), (x1, y0), (x1, y1), (x0, y1)))) for ch, (x0, y0, x1, y1) in row]
+            lines.append('    ' + ' '.join(f'{ch}[' + ','.join(f'{v:.1f}' for p in quad for v in p) + ']' for ch, quad in quads))
+        return lines
+    alternatives = [[]] * len(names)
+    if nbest > 0:
+        search = {} if refine is None else {'refine': refine, 'refine_iters': refine_iters}
+        alternatives = [alts[:nbest] for alts in model.tokenizer.decode_beams(model.beam_search(batch, beam or nbest, **search))]
+    labels, _ = model.tokenizer.read(model(batch))
+    for name, label, alts in zip(names, labels, alternatives):
+        lines.append(f'{name}: {label}')
+        lines += [f'    {logp:9.4f}  {alt}' for alt, logp in alts]
+    return lines
+
+
 LEXICON_BEAM = 8      # --beam under --lexicon when none is given
 
 
@@ -111,6 +191,10 @@ def build_parser():
     parser.add_argument('--boxes', action='store_true',
                         help="Print a second line per image: every character of the reading with its box (x0,y0,x1,y1) in the image's own pixels; "
                              'not with --nbest or --lexicon')
+    parser.add_argument('--regions', nargs='+', default=None, metavar='FILE',
+                        help='One file of quadrilaterals per image, in order (ICDAR-2015 style: x1,y1,x2,y2,x3,y3,x4,y4[,text] per line, clockwise '
+                             "from the text's top-left): read every region of the scene, printed as image#k; with --boxes every character's "
+                             "quadrilateral in the scene's pixels")
     parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
     return parser
 
@@ -156,8 +240,15 @@ def main(argv=None):
         parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
     beam, nbest = resolve_search(parser, args)
     refine, refine_iters = resolve_refine(parser, args)
-    model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     files = args.images or []
+    if args.regions is not None and len(args.regions) != len(files):
+        parser.error(f'--regions takes one file per image, in order: {len(args.regions)} files for {len(files)} images')
+    model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
+    if args.regions is not None:
+        words = load_word_list(args.lexicon) if args.lexicon is not None else None
+        for line in read_regions(model, files, args.regions, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device):
+            print(line)
+        return
     if args.lexicon is not None:
         # the best word of the list where the greedy reading goes; the alternatives only where --nbest asks for them
         for fname, alts in read_files_lexicon(model, files, load_word_list(args.lexicon), nbest, beam, args.device, refine):
