@@ -357,6 +357,62 @@ int parseq_localize(parseq_plan* p, const void* images, int images_dtype, int ba
                     int32_t* tokens_out, int32_t* lengths_out, float* attn_out, float* centres_out, float* boxes_out, int32_t* peak_out,
                     float* peak_mass_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- lexicon matching (pure additions under ABI 15; DESIGN.md section 23 defines it) --------------------------------- */
+
+/* The n words of a list nearest to every reading in Levenshtein distance (unit costs), on caller tensors (tests/test_lexicon_match.py),
+ * ordered by (distance, word id) ascending.  All integer arithmetic; the result is the same for every crops_per_block.
+ *   readings   device int32 [batch, ldt], 1 <= ldt <= 32; lengths device int32 [batch] or NULL (= ldt).  Reading b is its first
+ *              min(lengths[b], ldt) ids up to the first eos_id, none of them included; an empty reading is legal; an id outside [0, C)
+ *              equals no character of any word
+ *   table      device, 16-byte aligned, n_rows rows of PARSEQ_LEXICON_ROW_BYTES bytes, one word each: bytes 0 .. 30 its class ids (< C <= 256),
+ *              byte 31 its length (1 .. 31).  Row order is the order of the ties: rows ascend in word id
+ *   row_ids    device int32 [n_rows] or NULL: the word id of every row (NULL: the row index)
+ *   ranges     device int32 [batch, 2] or NULL: crop b is matched against rows [begin, end) only, clipped to the table; begin >= end: an
+ *              empty list
+ *   fold       device int32 [C] or NULL: every id of a reading inside [0, C) goes through this map before it is compared (the rows of a
+ *              case-folded table went through it on the host)
+ *   n          1 .. PARSEQ_BEAM_MAX_WIDTH;  crops_per_block: 0 (the library's choice) or how many crops one workgroup walks
+ *   word_ids_out, distances_out   device int32 [batch, n]; a slot beyond the list holds -1 and PARSEQ_LEXICON_MATCH_DEAD
+ *   workspace  device, parseq_op_lexicon_match_workspace_bytes(batch, n_rows, n) bytes (0: a shape outside the ranges), 16-byte aligned
+ * Refused with PARSEQ_E_INVALID before any device work: a NULL or empty table, more than 2^26 rows, shapes outside the ranges above. */
+#define PARSEQ_LEXICON_ROW_BYTES 32
+#define PARSEQ_LEXICON_MATCH_DEAD 0x7FFFFFFF
+size_t parseq_op_lexicon_match_workspace_bytes(int batch, int n_rows, int n);
+int parseq_op_lexicon_match(const int32_t* readings, int ldt, const int32_t* lengths, int batch, const uint8_t* table, int n_rows,
+                            const int32_t* row_ids, const int32_t* ranges, const int32_t* fold, int C, int eos_id, int n, int crops_per_block,
+                            int32_t* word_ids_out, int32_t* distances_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Read freely, match, rescore — one call, no host synchronisation, no allocation, for a PARSeq model of dec_depth 1 in every plan precision:
+ * the encoder; the reading parseq_forward gives with `flags` (PARSEQ_FLAG_DECODE_AR, PARSEQ_FLAG_LATENCY; the early exit never applies) and
+ * `refine_iters` over all L = max_label_length + 1 positions, arg-max on the device; the match above against `table`; then W = n (+ 1 with
+ * keep_reading) hypotheses per crop as a beam state — a word's own characters (table_own), <eos>, pad_id — which, with rescore != 0, get
+ * parseq_forward_beam_refine's PARSEQ_BEAM_REFINE_SCORE pass: the pseudo-log-likelihood as score, ranked by it, ties by (distance, word id).
+ * Without rescore the order is (distance, word id) and a live hypothesis' score is 0.
+ *   keep_reading   the reading itself competes: word id -1, distance 0, first in (distance, id) order; unfinished when its L positions hold no
+ *                  <eos>.  It is dead when a word has distance 0 (it is that word)
+ *   table_own      the rows whose characters are scored, NULL = table (a case-folded table matches on folded ids and scores the words' own)
+ * Outputs, device, W per crop: tokens_out int32 [batch, W, L], scores_out fp32, lengths_out int32, finished_out uint8, words_out int32 (the word id,
+ * -1: none) as parseq_forward_beam_lexicon's; distances_out int32 [batch, W]; a dead slot (beyond the list; a word of more than
+ * max_label_length characters) has score -inf, word -1, distance PARSEQ_LEXICON_MATCH_DEAD, pad_id tokens and sorts last.  reading_tokens_out int32
+ * [batch, L]: the arg-max of every position; reading_lengths_out int32 [batch]: the index of its first <eos> (L: none).
+ * workspace: parseq_forward_lexicon_match_workspace_bytes(p, batch, args) device bytes (0: refused, parseq_last_error says why), 16-byte
+ * aligned.  Afterwards the plan's cached memory K / V are the replicated batch's (rescore) or the batch's.
+ * Refused with PARSEQ_E_INVALID before any device work, outputs untouched: a ViTSTR model, dec_depth > 1, n outside [1, PARSEQ_BEAM_MAX_WIDTH -
+ * keep_reading], batch * W above the plan's max_batch, a NULL or empty table, more than 256 classes, whatever parseq_forward refuses, a
+ * NULL output, a short or misaligned workspace. */
+typedef struct parseq_lexicon_match_args {
+    const uint8_t* table;        /* the rows that are matched */
+    const uint8_t* table_own;    /* the rows that are scored, or NULL */
+    const int32_t* row_ids;      /* [n_rows] or NULL */
+    const int32_t* ranges;       /* [batch, 2] or NULL */
+    const int32_t* fold;         /* [num_tokens - 2] or NULL */
+    int32_t n_rows, n, rescore, keep_reading;
+} parseq_lexicon_match_args;
+size_t parseq_forward_lexicon_match_workspace_bytes(const parseq_plan* p, int batch, const parseq_lexicon_match_args* args);
+int parseq_forward_lexicon_match(parseq_plan* p, const void* images, int images_dtype, int batch, int flags, int refine_iters,
+                                 const parseq_lexicon_match_args* args, int32_t* tokens_out, float* scores_out, int32_t* lengths_out,
+                                 uint8_t* finished_out, int32_t* words_out, int32_t* distances_out, int32_t* reading_tokens_out,
+                                 int32_t* reading_lengths_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ViTSTR.forward (strhub/models/vitstr/system.py:76-82 -> vitstr/model.py:20-28) for a model created with
  * arch = PARSEQ_ARCH_VITSTR: encoder with class token, head on tokens [1, num_steps], i.e. logits_out fp32
  * [batch, num_steps, num_tokens - 2] with num_steps = min(max_length, max_label_length) + 1.  images as parseq_forward. */

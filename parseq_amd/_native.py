@@ -76,6 +76,12 @@ class BeamRefineTrace(C.Structure):
     _fields_ = [('tokens_in', C.c_void_p), ('logits', C.c_void_p)]
 
 
+class LexiconMatchArgs(C.Structure):
+    """parseq_lexicon_match_args: the word table of a match (parseq_amd/lexicon.py) and what the call is asked for."""
+    _fields_ = [('table', C.c_void_p), ('table_own', C.c_void_p), ('row_ids', C.c_void_p), ('ranges', C.c_void_p), ('fold', C.c_void_p),
+                ('n_rows', C.c_int32), ('n', C.c_int32), ('rescore', C.c_int32), ('keep_reading', C.c_int32)]
+
+
 class GemmOperand(C.Structure):
     _fields_ = [('data', C.c_void_p), ('dtype', C.c_int32), ('outer_stride', C.c_int64), ('k_stride', C.c_int64)]
 
@@ -169,6 +175,12 @@ SIGNATURES = {
     'parseq_localize_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int]),
     'parseq_localize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_op_lexicon_match_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    'parseq_op_lexicon_match': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_forward_lexicon_match_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.POINTER(LexiconMatchArgs)]),
+    'parseq_forward_lexicon_match': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LexiconMatchArgs), C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_vitstr_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'parseq_decode_logits': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -3,6 +3,7 @@
 #include "beam.h"
 #include "beam_refine.h"
 #include "attn_map.h"
+#include "lexicon_match.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -1018,4 +1019,164 @@ extern "C" int parseq_op_beam_step_lexicon(const float* logits, int batch, int b
     return beam_step_op((hipStream_t)stream, logits, batch, beam_width, C, step,
                         BeamState::of_tensors(tokens, ldt, scores, finished, lengths, picked_out, nodes, words), parent_out, eos_id, pad_id, true, trie_next,
                         trie_nodes);
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// lexicon matching
+// -------------------------------------------------------------------------------------------------------------------
+static_assert(PARSEQ_LEXICON_MATCH_DEAD == LM_DEAD_DISTANCE && PARSEQ_LEXICON_ROW_BYTES == LM_ROW_BYTES, "lexicon matching constants of the header and the kernels");
+
+// What the matching kernel reads besides the readings: the caller's table and the optional arrays beside it.
+struct LexMatch { const uint8_t* table; int n_rows; const int32_t *row_ids, *ranges, *fold; int C, eos_id, n; };
+
+static int lexmatch_shape_check(int batch, int ldt, const LexMatch& m) {
+    if (batch <= 0) return fail(PARSEQ_E_INVALID, "batch %d", batch);
+    if (ldt < 1 || ldt > LM_MAX_READING) return fail(PARSEQ_E_INVALID, "readings of %d positions: 1 .. %d", ldt, LM_MAX_READING);
+    if (!m.table || m.n_rows < 1) return fail(PARSEQ_E_INVALID, "null or empty word table (n_rows %d)", m.n_rows);
+    if (m.n_rows > (1 << LM_KEY_SHIFT)) return fail(PARSEQ_E_INVALID, "word table of %d rows: at most 2^%d", m.n_rows, LM_KEY_SHIFT);
+    if ((uintptr_t)m.table % 16) return fail(PARSEQ_E_INVALID, "word table not 16-byte aligned");
+    if (m.C < 1 || m.C > LM_MAX_CLASSES) return fail(PARSEQ_E_INVALID, "%d classes: a class id of the table is a byte, 1 .. %d", m.C, LM_MAX_CLASSES);
+    if (m.eos_id < 0 || m.eos_id >= m.C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", m.eos_id, m.C);
+    if (m.n < 1 || m.n > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "n %d outside [1, %d]", m.n, PARSEQ_BEAM_MAX_WIDTH);
+    if ((long long)batch * lm_chunks(m.n_rows) * m.n > 0x7fffffffLL) return fail(PARSEQ_E_INVALID, "batch %d x %d rows x n %d: the partial lists pass 2^31 keys", batch, m.n_rows, m.n);
+    return 0;
+}
+
+static size_t lexmatch_partial_keys(int batch, int n_rows, int n) { return (size_t)batch * lm_chunks(n_rows) * n; }
+
+// The match of `batch` readings [batch][ldt]: the partial lists, then the merge.  crops_per_block 0: enough workgroups to fill the device
+// (about 2048) where the list alone does not give them.  The result does not depend on it.
+static int launch_lexicon_match(hipStream_t s, const int32_t* readings, int ldt, const int32_t* lengths, int batch, const LexMatch& m, int crops_per_block,
+                                unsigned* partial, int32_t* word_ids, int32_t* distances, int32_t* rows_out) {
+    const int wblocks = (m.n_rows + LM_THREADS - 1) / LM_THREADS, tiles = (batch + LM_TC - 1) / LM_TC, chunks = lm_chunks(m.n_rows);
+    if (crops_per_block <= 0) {
+        const int groups = std::max(1, std::min(tiles, (2048 + wblocks - 1) / wblocks));
+        crops_per_block = (tiles + groups - 1) / groups * LM_TC;
+    }
+    const int groups = (batch + crops_per_block - 1) / crops_per_block;
+    if (groups > 65535) return fail(PARSEQ_E_INVALID, "crops_per_block %d at batch %d: more than 65535 crop groups", crops_per_block, batch);
+    CHK(launch(lexicon_match_kernel, dim3(wblocks, groups), dim3(LM_THREADS), 0, s, readings, ldt, lengths, batch, reinterpret_cast<const unsigned*>(m.table),
+               m.n_rows, m.ranges, m.fold, m.C, m.eos_id, m.n, partial, chunks, crops_per_block));
+    return launch(lexicon_match_merge_kernel, dim3(batch), dim3(LM_THREADS), 0, s, partial, chunks, m.n_rows, m.ranges, m.row_ids, m.n, word_ids, distances, rows_out);
+}
+
+extern "C" size_t parseq_op_lexicon_match_workspace_bytes(int batch, int n_rows, int n) {
+    if (batch <= 0 || n_rows < 1 || n_rows > (1 << LM_KEY_SHIFT) || n < 1 || n > PARSEQ_BEAM_MAX_WIDTH || (long long)batch * lm_chunks(n_rows) * n > 0x7fffffffLL) return 0;
+    size_t off = 0;
+    carve(off, lexmatch_partial_keys(batch, n_rows, n) * sizeof(unsigned));
+    return off;
+}
+
+extern "C" int parseq_op_lexicon_match(const int32_t* readings, int ldt, const int32_t* lengths, int batch, const uint8_t* table, int n_rows,
+                                       const int32_t* row_ids, const int32_t* ranges, const int32_t* fold, int C, int eos_id, int n, int crops_per_block,
+                                       int32_t* word_ids_out, int32_t* distances_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!readings || !word_ids_out || !distances_out || !workspace) return fail(PARSEQ_E_INVALID, "null readings / output / workspace");
+    const LexMatch m{table, n_rows, row_ids, ranges, fold, C, eos_id, n};
+    CHK(lexmatch_shape_check(batch, ldt, m));
+    if (crops_per_block < 0) return fail(PARSEQ_E_INVALID, "crops_per_block %d", crops_per_block);
+    const size_t need = parseq_op_lexicon_match_workspace_bytes(batch, n_rows, n);
+    if (workspace_bytes < need) return fail(PARSEQ_E_INVALID, "lexicon match workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "lexicon match workspace not 16-byte aligned");
+    return launch_lexicon_match((hipStream_t)stream, readings, ldt, lengths, batch, m, crops_per_block, reinterpret_cast<unsigned*>(workspace), word_ids_out,
+                                distances_out, nullptr);
+}
+
+// The whole call's refusals, in beam_check's style; W = n (+ 1 with keep_reading) hypotheses per crop.
+static int lexmatch_check(const parseq_plan* p, int batch, const parseq_lexicon_match_args* a) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    if (!a) return fail(PARSEQ_E_INVALID, "null lexicon match arguments");
+    const parseq_model* m = p->m;
+    if (m->vitstr) return fail(PARSEQ_E_INVALID, "lexicon matching on a ViTSTR model: it has no decoder to rescore with");
+    if (m->cfg.dec_depth > 1) return fail(PARSEQ_E_INVALID, "lexicon matching at dec_depth %d: only dec_depth 1", m->cfg.dec_depth);
+    const int keep = a->keep_reading ? 1 : 0;
+    if (a->n < 1 || a->n + keep > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "n %d outside [1, %d]%s", a->n, PARSEQ_BEAM_MAX_WIDTH - keep, keep ? " (one slot is the reading's)" : "");
+    if (batch <= 0 || (long long)batch * (a->n + keep) > p->max_batch) return fail(PARSEQ_E_INVALID, "batch %d x %d hypotheses outside (0, %d]", batch, a->n + keep, p->max_batch);
+    const LexMatch lm{a->table, a->n_rows, a->row_ids, a->ranges, a->fold, m->classes, m->cfg.eos_id, a->n};
+    CHK(lexmatch_shape_check(batch, m->cfg.max_label_length + 1, lm));
+    if (a->table_own && (uintptr_t)a->table_own % 16) return fail(PARSEQ_E_INVALID, "word table not 16-byte aligned");
+    return 0;
+}
+
+// The caller's workspace: the forward's logits, the match (partial lists, rows, ids, distances), the beam state, and with rescoring the
+// memory, its W-fold replication, the refinement logits and the row statistics.
+struct LexMatchWs { float *memory, *memory_rep, *logits, *rlogits; unsigned* partial; int *m_rows, *m_ids, *m_dist; BeamState st; size_t total; };
+static LexMatchWs lexmatch_ws(const parseq_plan* p, int batch, const parseq_lexicon_match_args* a, void* workspace = nullptr) {
+    const parseq_model* m = p->m;
+    const int W = a->n + (a->keep_reading ? 1 : 0), L = m->cfg.max_label_length + 1;
+    const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim;
+    Carver cv{reinterpret_cast<unsigned char*>(workspace)};
+    LexMatchWs o{}; BeamState& b = o.st;
+    b.tok = p->tok; b.ldt = LDT;
+    o.logits = cv.take<float>((size_t)batch * L * m->classes);
+    o.partial = cv.take<unsigned>(lexmatch_partial_keys(batch, a->n_rows, a->n));
+    o.m_rows = cv.take<int>((size_t)batch * a->n); o.m_ids = cv.take<int>((size_t)batch * a->n); o.m_dist = cv.take<int>((size_t)batch * a->n);
+    b.score = cv.take<float>(rows); b.length = cv.take<int>(rows); b.picked = cv.take<int>(rows); b.finished = cv.take<unsigned char>(rows);
+    b.node = cv.take<int>(rows); b.word = cv.take<int>(rows);      // node: the hypothesis' distance, which moves with its row as a trie node does
+    b.ar_score = cv.take<float>(rows);
+    if (a->rescore) {
+        o.memory = cv.take<float>(batch * img);
+        o.memory_rep = cv.take<float>(rows * img);
+        o.rlogits = cv.take<float>(rows * L * m->classes);
+        take_refine_stats(cv, rows * L, b);
+    }
+    o.total = cv.off;
+    return o;
+}
+
+extern "C" size_t parseq_forward_lexicon_match_workspace_bytes(const parseq_plan* p, int batch, const parseq_lexicon_match_args* args) {
+    if (lexmatch_check(p, batch, args) != 0) return 0;
+    return lexmatch_ws(p, batch, args).total;
+}
+
+struct LexMatchOut { int32_t* tokens; float* scores; int32_t* lengths; uint8_t* finished; int32_t *words, *distances, *reading, *reading_len; };
+
+template <typename T, int E>
+static int lexmatch_impl(parseq_plan* p, int B, int flags, int refine_iters, const parseq_lexicon_match_args* a, const LexMatchWs& ws, const LexMatchOut& out,
+                         hipStream_t s) {
+    const parseq_config& c = p->m->cfg;
+    const int C = p->m->classes, L = c.max_label_length + 1, N = a->n, W = N + (a->keep_reading ? 1 : 0), rows = B * W;
+    const BeamState& b = ws.st;
+    // the reading forward would give: its logits, then the arg-max of every position and the index of the first <eos>
+    CHK((forward_impl<T, E>(p, B, flags & ~PARSEQ_FLAG_TESTING, refine_iters, L, ws.logits, nullptr, s)));
+    CHK(launch(postprocess_kernel, dim3((B + 3) / 4), dim3(256), 0, s, ws.logits, B, L, C, c.eos_id, out.reading, out.reading_len, (float*)nullptr, (float*)nullptr));
+    const LexMatch lm{a->table, a->n_rows, a->row_ids, a->ranges, a->fold, C, c.eos_id, N};
+    CHK(launch_lexicon_match(s, out.reading, L, out.reading_len, B, lm, 0, ws.partial, ws.m_ids, ws.m_dist, ws.m_rows));
+    const size_t cells = (size_t)rows * b.ldt;
+    CHK(launch(lexicon_seed_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, B, N, a->keep_reading ? 1 : 0, L, a->table_own ? a->table_own : a->table,
+               ws.m_rows, ws.m_ids, ws.m_dist, out.reading, out.reading_len, c.bos_id, c.eos_id, c.pad_id, b.tok, b.ldt, b.score, b.finished, b.length, b.picked,
+               b.word, b.node, b.ar_score));
+    if (a->rescore) {
+        // section 20's 'score' selection on the seeded rows: every candidate against its crop's memory, one cloze pass
+        const size_t per_img4 = (size_t)p->m->tokens * E / 4, total4 = per_img4 * rows;
+        CHK(launch(beam_replicate_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(ws.memory),
+                   reinterpret_cast<float4*>(ws.memory_rep), per_img4, W, total4));
+        CHK(set_memory_impl<T>(p, ws.memory_rep, rows, s));
+        const DecW<T> w = dec_weights<T>(p);
+        CHK((refine_iteration<T, E>(p, s, w, rows, L, ws.rlogits, 0)));
+        CHK(launch_beam_refine(s, ws.rlogits, B, W, C, L, PARSEQ_BEAM_REFINE_SCORE, b, c.eos_id, c.pad_id));
+    }
+    HIPCHK(hipMemcpyAsync(out.distances, b.node, (size_t)rows * sizeof(int), hipMemcpyDeviceToDevice, s));
+    CHK(launch(beam_finish_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, b.score, b.finished, b.word, out.words));
+    return launch(beam_finish_kernel, dim3((rows * L + 255) / 256), dim3(256), 0, s, b.tok, b.ldt, rows, L, c.pad_id, b.score, b.finished, b.length, b.picked,
+                  out.tokens, out.scores, out.lengths, out.finished);
+}
+
+extern "C" int parseq_forward_lexicon_match(parseq_plan* p, const void* images, int images_dtype, int batch, int flags, int refine_iters,
+                                            const parseq_lexicon_match_args* args, int32_t* tokens_out, float* scores_out, int32_t* lengths_out,
+                                            uint8_t* finished_out, int32_t* words_out, int32_t* distances_out, int32_t* reading_tokens_out,
+                                            int32_t* reading_lengths_out, void* workspace, size_t workspace_bytes, void* stream) {
+    CHK(lexmatch_check(p, batch, args));
+    CHK(check_call(p, batch, images_dtype));
+    if (!images || !tokens_out || !scores_out || !lengths_out || !finished_out || !words_out || !distances_out || !reading_tokens_out || !reading_lengths_out || !workspace)
+        return fail(PARSEQ_E_INVALID, "null images / output / workspace");
+    if (refine_iters < 0) return fail(PARSEQ_E_INVALID, "refine_iters %d", refine_iters);
+    const LexMatchWs ws = lexmatch_ws(p, batch, args, workspace);
+    if (workspace_bytes < ws.total) return fail(PARSEQ_E_INVALID, "lexicon match workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "lexicon match workspace not 16-byte aligned");
+    DevGuard dg(p->m->device);
+    SplitScope ss(p->precision == PARSEQ_BF16X3);
+    hipStream_t s = (hipStream_t)stream;
+    CHK(encode_dispatch(p, images, images_dtype, batch, ws.memory, s));      // (without rescoring ws.memory is null: nothing reads the memory again)
+    const LexMatchOut out{tokens_out, scores_out, lengths_out, finished_out, words_out, distances_out, reading_tokens_out, reading_lengths_out};
+    return dispatch_te(p, [&](auto te) { return lexmatch_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, flags, refine_iters, args, ws, out, s); });
 }

@@ -5,6 +5,10 @@ The table is dense: `next` int32 [nodes, C] over the head's C classes (`<eos>` a
 into `Lexicon.words`; every other entry is -1.  Nodes are numbered breadth first, children in ascending class order, so the same words in
 the same order always give the same table.  Several tries may share one table (`Lexicon.forest`): per-image word lists in one call, each
 image starting at its own root.  `nodes * C * 4` bytes: about 95 MB for a 250 k-node trie at C = 95.
+
+The same words also have a packed form for lexicon matching, built on first use: one 32-byte row per entered word in
+ascending word id — bytes 0 .. 30 the class ids, byte 31 the length — with the word id of every row beside it and, for a forest, every
+list's [begin, end) range of rows.  32 bytes a word whatever the list shares: about 3 MB for 90 k words.
 """
 from __future__ import annotations
 
@@ -50,6 +54,10 @@ class Lexicon:
         charset = ''.join(self._stoi)
         self._fold = (str.lower if charset == charset.lower() else str.upper if charset == charset.upper() else None) if fold_case else None
         self._device_tables: Dict[torch.device, Tensor] = {}
+        self._entries: List[Tuple[int, List[int]]] = []      # (word id, class ids) of every word entered into a trie, in ascending id
+        self._list_rows: List[Tuple[int, int]] = []          # per list its [begin, end) range of `_entries`
+        self._packed: Dict[bool, np.ndarray] = {}
+        self._device_packed: Dict[Tuple[torch.device, bool], Dict[str, Optional[Tensor]]] = {}
 
     def _encode(self, word: str) -> Optional[List[int]]:
         if self._fold is not None:
@@ -68,6 +76,7 @@ class Lexicon:
             # the trie in insertion order: per node a {class: node} dictionary and the word that ends there
             children: List[Dict[int, int]] = [{}]
             ends: List[int] = [-1]
+            begin = len(self._entries)
             for k, word in enumerate(words):
                 ids = self._encode(word)
                 if ids is None:
@@ -84,6 +93,8 @@ class Lexicon:
                     n = nxt
                 if ends[n] < 0:
                     ends[n] = first_id + k
+                    self._entries.append((first_id + k, ids))
+            self._list_rows.append((begin, len(self._entries)))
             # renumbered breadth first, children in ascending class order
             base = sum(r.shape[0] for r in rows)
             order, number = [0], {0: 0}
@@ -127,3 +138,125 @@ class Lexicon:
         if device not in self._device_tables:
             self._device_tables[device] = self.next.to(device)
         return self._device_tables[device]
+
+    # ---- the packed form --------------------------------------------------------------------------
+    ROW_BYTES = 32             # PARSEQ_LEXICON_ROW_BYTES
+    MAX_READING = 32           # characters of a reading the matching kernel compares
+
+    @property
+    def num_rows(self) -> int:
+        """Words in the packed table: the entered ones (skipped words and repeats of a word within its list have no row)."""
+        return len(self._entries)
+
+    @property
+    def row_ids(self) -> Tensor:
+        """int32 [num_rows]: the word id (index into `words`) of every row, ascending."""
+        return torch.tensor([k for k, _ in self._entries], dtype=torch.int32)
+
+    @property
+    def list_ranges(self) -> Tensor:
+        """int32 [lists, 2]: every list's [begin, end) range of rows (one list for a plain `Lexicon`)."""
+        return torch.tensor(self._list_rows, dtype=torch.int32).reshape(-1, 2)
+
+    def fold_map(self) -> Tensor:
+        """int32 [C]: the class a class is matched as under `ignore_case` — a letter's lower-case class where the charset has one, itself
+        otherwise (`<eos>`, digits, signs, and every class of a single-case charset)."""
+        fold = list(range(self.num_classes))
+        for ch, i in self._stoi.items():
+            fold[i] = self._stoi.get(ch.lower(), i) if len(ch.lower()) == 1 else i
+        return torch.tensor(fold, dtype=torch.int32)
+
+    def rows(self, ignore_case: bool = False) -> Tensor:
+        """uint8 [num_rows, 32] on the host: the words' class ids (through `fold_map` with `ignore_case`) and, in byte 31, their lengths."""
+        if self.num_classes > 256 or self.max_label_length > self.ROW_BYTES - 1:
+            raise ValueError(f'the packed word table holds class ids below 256 and words of at most 31 characters; this lexicon has {self.num_classes} '
+                             f'classes and max_label_length {self.max_label_length}')
+        if ignore_case not in self._packed:
+            table = np.zeros((len(self._entries), self.ROW_BYTES), dtype=np.uint8)
+            fold = self.fold_map().numpy() if ignore_case else None
+            for r, (_, ids) in enumerate(self._entries):
+                table[r, :len(ids)] = ids if fold is None else fold[ids]
+                table[r, self.ROW_BYTES - 1] = len(ids)
+            self._packed[ignore_case] = table
+        return torch.from_numpy(self._packed[ignore_case])
+
+    @property
+    def rows_nbytes(self) -> int:
+        return self.num_rows * self.ROW_BYTES
+
+    def match_table(self, device, ignore_case: bool = False) -> Dict[str, Optional[Tensor]]:
+        """The packed form on `device`, uploaded once (as `table(device)` is): `table` the rows that are matched, `own` the words' own rows
+        (the same tensor without `ignore_case`), `row_ids`, `ranges` [lists, 2] and `fold` (None without `ignore_case`)."""
+        device = torch.device(device)
+        if device.type != 'cpu' and device.index is None:
+            device = torch.device(device.type, torch.cuda.current_device())
+        key = (device, bool(ignore_case))
+        if key not in self._device_packed:
+            own = self._device_packed[(device, False)]['own'] if (device, False) in self._device_packed else self.rows(False).to(device)
+            self._device_packed[key] = {'table': self.rows(True).to(device) if ignore_case else own, 'own': own, 'row_ids': self.row_ids.to(device),
+                                        'ranges': self.list_ranges.to(device), 'fold': self.fold_map().to(device) if ignore_case else None}
+        return self._device_packed[key]
+
+    def encode_readings(self, readings: Sequence[str]) -> Tuple[Tensor, Tensor]:
+        """(int32 [B, 32] class ids, int32 [B] lengths) of strings as the matching kernel reads them: a character outside the charset is -1 (it
+        equals no character of any word), the case is folded as the words' was (`fold_case`).  More than 32 characters: ValueError."""
+        tok = np.full((len(readings), self.MAX_READING), self.eos_id, dtype=np.int32)
+        lengths = np.zeros(len(readings), dtype=np.int32)
+        for b, text in enumerate(readings):
+            if self._fold is not None:
+                text = self._fold(text)
+            if len(text) > self.MAX_READING:
+                raise ValueError(f'a reading of {len(text)} characters: the matching kernel compares at most {self.MAX_READING}')
+            tok[b, :len(text)] = [self._stoi.get(ch, -1) for ch in text]
+            lengths[b] = len(text)
+        return torch.from_numpy(tok), torch.from_numpy(lengths)
+
+    def nearest(self, readings, n: int, lists=None, ignore_case: bool = False, device='cuda', crops_per_block: int = 0) -> Tuple[Tensor, Tensor]:
+        """The `n` words nearest to every reading in Levenshtein distance, no model involved: (word ids int32 [B, n],
+        distances int32 [B, n]) on `device`, ordered by (distance, word id); a slot beyond the list holds -1 and `MATCH_DEAD`.  `readings`:
+        strings, or an int tensor [B, L <= 32] of class ids in which a reading ends before its first `<eos>`.  `lists` (a forest's list index
+        per reading) matches every reading against its own list.  One launch pair on the device, nothing read back."""
+        from . import _native
+        if isinstance(readings, Tensor):
+            if readings.dim() != 2 or not 1 <= readings.shape[1] <= self.MAX_READING:
+                raise ValueError(f'nearest: readings must be [B, L] with 1 <= L <= {self.MAX_READING}, got {tuple(readings.shape)}')
+            tok, lengths = readings.to(device, torch.int32).contiguous(), None
+        else:
+            tok, lengths = (t.to(device) for t in self.encode_readings(list(readings)))
+        B = tok.shape[0]
+        if not 1 <= int(n) <= MATCH_MAX_N:
+            raise ValueError(f'nearest: n must be in [1, {MATCH_MAX_N}], got {n}')
+        if self.num_rows == 0:
+            raise ValueError('nearest: no word of the lexicon was entered (the packed table is empty)')
+        t = self.match_table(tok.device, ignore_case)
+        ranges = self.crop_ranges(lists, B, tok.device)
+        ids = torch.empty(B, n, dtype=torch.int32, device=tok.device)
+        dist = torch.empty(B, n, dtype=torch.int32, device=tok.device)
+        if B == 0:
+            return ids, dist
+        lib = _native.lib()
+        need = lib.parseq_op_lexicon_match_workspace_bytes(B, self.num_rows, int(n))
+        if need == 0:
+            raise ValueError(f'nearest: {B} readings x {self.num_rows} words x n = {n} is outside what one call matches')
+        ws = torch.empty(need, dtype=torch.uint8, device=tok.device)
+        with _native.guard(tok):
+            _native.check(lib.parseq_op_lexicon_match(_native.ptr(tok), tok.shape[1], _native.ptr(lengths), B, _native.ptr(t['table']), self.num_rows,
+                                                      _native.ptr(t['row_ids']), _native.ptr(ranges), _native.ptr(t['fold']), self.num_classes, self.eos_id,
+                                                      int(n), int(crops_per_block), _native.ptr(ids), _native.ptr(dist), _native.ptr(ws), need,
+                                                      _native.stream_ptr(tok)))
+        return ids, dist
+
+    def crop_ranges(self, lists, batch: int, device) -> Optional[Tensor]:
+        """int32 [batch, 2] on `device`: the rows of list `lists[b]` for crop b; None for `lists=None` (every crop against every row)."""
+        if lists is None:
+            return None
+        lists = torch.as_tensor(lists, dtype=torch.int64).cpu()
+        if lists.dim() != 1 or lists.shape[0] != batch:
+            raise ValueError(f'lists must be [batch] = [{batch}], got {tuple(lists.shape)}')
+        if batch and (int(lists.min()) < 0 or int(lists.max()) >= len(self._list_rows)):
+            raise ValueError(f'lists: a list index outside [0, {len(self._list_rows)})')
+        return self.list_ranges[lists].to(device).contiguous()
+
+
+MATCH_MAX_N = 16                # PARSEQ_BEAM_MAX_WIDTH
+MATCH_DEAD = 0x7FFFFFFF         # PARSEQ_LEXICON_MATCH_DEAD: the distance of a slot beyond the list

@@ -72,6 +72,28 @@ class LexiconBeamResult(BeamResult):
 
 
 @dataclass
+class LexiconMatchResult(LexiconBeamResult):
+    """What `PARSeq.lexicon_match` returns: the fields of a `LexiconBeamResult` over W = n (+ 1 with `keep_reading`)
+    hypotheses per crop — `words` -1 for the reading itself and for a dead slot, `scores` 0 for a live hypothesis without rescoring — plus:"""
+    distances: Optional[Tensor] = None          # int32 [B, W] Levenshtein distance of the hypothesis to the reading; MATCH_DEAD for a dead slot
+    reading_tokens: Optional[Tensor] = None     # int32 [B, L] the free reading: the arg-max of every position of `forward`'s logits
+    reading_lengths: Optional[Tensor] = None    # int32 [B] its characters: the index of the first <eos> (L: none)
+
+
+def check_lexicon_match(n, keep_reading, lexicon, max_label_length, classes):
+    """The refusals of `lexicon_match` that need no device."""
+    width = BEAM_MAX_WIDTH - (1 if keep_reading else 0)
+    if not isinstance(n, int) or isinstance(n, bool) or not 1 <= n <= width:
+        raise ValueError(f'lexicon_match: n must be an integer in [1, {width}]' + (' (one of the 16 slots is the reading\'s)' if keep_reading else '') + f', got {n!r}')
+    if lexicon.num_classes != classes:
+        raise ValueError(f'lexicon_match: the lexicon was built for {lexicon.num_classes} classes, the model has {classes}')
+    if lexicon.max_label_length > max_label_length:
+        raise ValueError(f'lexicon_match: the lexicon holds words of up to {lexicon.max_label_length} characters, the model reads {max_label_length}')
+    if lexicon.num_rows == 0:
+        raise ValueError('lexicon_match: no word of the lexicon was entered (the word table is empty)')
+
+
+@dataclass
 class Localization:
     """What `PARSeq.localize` returns, on the device.  L = max_label_length + 1 positions, S = the encoder's patch
     tokens; coordinates are pixels of the model's input (`img_size`), x to the right and y down."""
@@ -695,6 +717,41 @@ class PARSeq(_NativeBacked):
         _native.check(entry(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, W, num_steps, _native.ptr(res.tokens), _native.ptr(res.scores),
                             _native.ptr(res.lengths), _native.ptr(res.finished), C.byref(tr) if tr is not None else None, _native.ptr(ws), ws.numel(),
                             _native.stream_ptr(self._device), *extra))
+        return res
+
+    def lexicon_match(self, tokenizer: Tokenizer, images: Tensor, lexicon, n: int, lists=None, rescore: bool = True, keep_reading: bool = False,
+                      ignore_case: bool = False) -> LexiconMatchResult:
+        """Read freely, then choose among the list's nearest words: the reading `forward` gives for `images`, the `n`
+        words of `lexicon` nearest to it in Levenshtein distance, and — with `rescore` — the pseudo-log-likelihood of each of them
+        (section 20's 'score'), best first; without it they stay in (distance, word id) order.  `lists` (a list index of `Lexicon.forest`
+        per crop) gives every crop its own list.  `keep_reading` lets the reading itself compete (word -1) unless it is a word of the list.
+        `ignore_case` matches a cased charset against the list case-insensitively; what is scored is the word's own spelling.  One library
+        call on a plan of B * W rows, no host synchronisation; `tokenizer.decode_beams(result, lexicon)` reads the result."""
+        classes = self._cfg['num_tokens'] - 2
+        self._check_localizable('lexicon_match')
+        check_lexicon_match(n, keep_reading, lexicon, self.max_label_length, classes)
+        images = self._check_images(images)
+        B, dev = images.shape[0], images.device
+        W, L = n + (1 if keep_reading else 0), self.max_label_length + 1
+        t = lexicon.match_table(dev, ignore_case)
+        ranges = lexicon.crop_ranges(lists, B, dev)
+        plan = self._plan(B * W)
+        self._memory_replaced()
+        self._check_tokenizer(tokenizer)
+        res = LexiconMatchResult(
+            torch.empty(B, W, L, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.float32, device=dev),
+            torch.empty(B, W, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.uint8, device=dev),
+            words=torch.empty(B, W, dtype=torch.int32, device=dev), distances=torch.empty(B, W, dtype=torch.int32, device=dev),
+            reading_tokens=torch.empty(B, L, dtype=torch.int32, device=dev), reading_lengths=torch.empty(B, dtype=torch.int32, device=dev))
+        args = _native.LexiconMatchArgs(t['table'].data_ptr(), t['own'].data_ptr(), t['row_ids'].data_ptr(), ranges.data_ptr() if ranges is not None else None,
+                                        t['fold'].data_ptr() if t['fold'] is not None else None, lexicon.num_rows, n, int(bool(rescore)), int(bool(keep_reading)))
+        lib = _native.lib()
+        ws = self._workspace(lib.parseq_forward_lexicon_match_workspace_bytes, plan, B, C.byref(args))
+        flags = (_native.FLAG_DECODE_AR if self.decode_ar else 0) | _native.FLAG_LATENCY
+        _native.check(lib.parseq_forward_lexicon_match(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, flags, int(self.refine_iters), C.byref(args),
+                                                       _native.ptr(res.tokens), _native.ptr(res.scores), _native.ptr(res.lengths), _native.ptr(res.finished),
+                                                       _native.ptr(res.words), _native.ptr(res.distances), _native.ptr(res.reading_tokens),
+                                                       _native.ptr(res.reading_lengths), _native.ptr(ws), ws.numel(), _native.stream_ptr(self._device)))
         return res
 
     def _check_localizable(self, what: str) -> None:

@@ -263,6 +263,14 @@ class PARSeq(nn.Module):
             return self.model.beam_search(self.tokenizer, images, beam_width, max_length)
         return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots)
 
+    def lexicon_match(self, images: Tensor, lexicon, n: int, lists=None, rescore: bool = True, keep_reading: bool = False, ignore_case: bool = False):
+        """Read freely, then let the model choose among the `n` words of `lexicon` nearest to the reading in edit distance
+        (model.PARSeq.lexicon_match; DESIGN.md section 23): a `LexiconMatchResult` on the device, best first per crop;
+        `self.tokenizer.decode_beams(result, lexicon)` returns the words in the list's spelling.  Unlike `beam_search(lexicon=...)` it does not
+        commit from the left: a misread first character costs one edit.  `lists`: a list index of `Lexicon.forest` per crop; `rescore=False`
+        keeps the (distance, word id) order; `keep_reading` lets the reading itself compete; `ignore_case` matches case-insensitively."""
+        return self.model.lexicon_match(self.tokenizer, images, lexicon, n, lists=lists, rescore=rescore, keep_reading=keep_reading, ignore_case=ignore_case)
+
     def localize(self, images: Tensor, labels=None):
         """Where every character of the reading is (model.PARSeq.localize): a `Localization` on the device with the
         tokens and lengths that were localised and, per position, the attention map over the patch tokens, its centre, box and peak, in

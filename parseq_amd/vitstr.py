@@ -138,6 +138,9 @@ class ViTSTR(nn.Module):
                     refine: Optional[str] = None, refine_iters: int = 1):
         raise ValueError('beam_search: ViTSTR has no AR loop (every position is read in one pass); use a PARSeq model')
 
+    def lexicon_match(self, images: Tensor, lexicon, n: int, lists=None, rescore: bool = True, keep_reading: bool = False, ignore_case: bool = False):
+        raise ValueError('lexicon_match: ViTSTR has no decoder to rescore the candidates with; use a PARSeq model (Lexicon.nearest matches strings without a model)')
+
     def localize(self, images: Tensor, labels=None):
         raise ValueError('localize: ViTSTR has no decoder, hence no cross-attention over the patch tokens; use a PARSeq model')
 

@@ -5,6 +5,7 @@
     ./read.py path/to/lightning.ckpt --images *.png refine_iters:int=2 decode_ar:bool=false
     ./read.py pretrained=parseq --images a.png --nbest 5 [--beam 8]     the 5 best readings with their log-probabilities under each line
     ./read.py pretrained=parseq --images a.png --lexicon words.txt [--beam 8] [--nbest 3]     read only words of the list (one per line)
+    ./read.py pretrained=parseq --images a.png --lexicon words.txt --match [8] [--nbest 3]     read freely, then choose among the list's 8 nearest words
     ./read.py pretrained=parseq --images a.png --nbest 5 --refine-beams edit [--refine-iters 2]     refine every alternative, rank them again
     ./read.py pretrained=parseq --images a.png --boxes     a second line per image: every character with its box in the image's own pixels
     ./read.py pretrained=parseq --images scene.jpg --regions scene.txt [--boxes]     read every quadrilateral of the file (x1,y1,..,x4,y4 per line)
@@ -112,14 +113,20 @@ def load_region_batch(model, files, region_files, device='cuda'):
 
 
 @torch.inference_mode()
-def read_regions(model, files, region_files, beam=None, nbest=0, words=None, list_words=False, refine=None, refine_iters=1, boxes=False, device='cuda'):
+def read_regions(model, files, region_files, beam=None, nbest=0, words=None, list_words=False, refine=None, refine_iters=1, boxes=False, device='cuda',
+                 match=None):
     """The lines `--regions` prints, for the same flags as the whole-crop readings above, on the batch of `load_region_batch`: `words` is the
-    list of --lexicon (its alternatives are listed only with `list_words`), `boxes` adds every character's quadrilateral in the scene."""
+    list of --lexicon (its alternatives are listed only with `list_words`), `boxes` adds every character's quadrilateral in the scene, `match`
+    the N of --match."""
     from parseq_amd.preprocess import map_to_source
     names, batch, back = load_region_batch(model, files, region_files, device)
     if not names:
         return []
     lines = []
+    if words is not None and match is not None:
+        for name, alts in zip(names, match_batch(model, batch, words, match, device)):
+            lines += match_lines(name, alts[:nbest], list_words)
+        return lines
     if words is not None:
         from parseq_amd.lexicon import Lexicon
         lexicon = Lexicon(words, model.tokenizer, fold_case=True, max_label_length=model.model.max_label_length).to(device)
@@ -150,6 +157,7 @@ def read_regions(model, files, region_files, beam=None, nbest=0, words=None, lis
 
 
 LEXICON_BEAM = 8      # --beam under --lexicon when none is given
+MATCH_N = 8           # --match without a number
 
 
 def load_word_list(path):
@@ -176,6 +184,33 @@ def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, de
     return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
 
 
+def match_batch(model, batch, words, n, device='cuda'):
+    """Per crop of `batch` [(word, pseudo-log-likelihood, distance)] best first: the free reading, the `n` words of `words` nearest to it in
+    edit distance, rescored by the model.  Fewer than `n` where the list is shorter."""
+    from parseq_amd.lexicon import Lexicon
+    lexicon = Lexicon(words, model.tokenizer, fold_case=True, max_label_length=model.model.max_label_length).to(device)
+    result = model.lexicon_match(batch, lexicon, n)
+    beams = model.tokenizer.decode_beams(result, lexicon)
+    distances = result.distances.cpu().tolist()
+    return [[(label, logp, d) for (label, logp), d in zip(alts, dist)] for alts, dist in zip(beams, distances)]      # dead slots come last in both
+
+
+def match_lines(name, alts, list_all):
+    """What --match prints for one image: the best word where the greedy reading goes; with --nbest the candidates, score and distance first."""
+    lines = [f'{name}: {alts[0][0] if alts else ""}']
+    return lines + [f'    {logp:9.4f}  d={d:<2d} {label}' for label, logp, d in (alts if list_all else [])]
+
+
+@torch.inference_mode()
+def read_files_match(model, files, words, n=MATCH_N, device='cuda'):
+    """[(file, [(word, pseudo-log-likelihood, distance)] best first)] for image files: one batched `lexicon_match` call."""
+    import numpy as np
+    crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+    if not crops:
+        return []
+    return list(zip(files, match_batch(model, resize_batch(crops, tuple(model.hparams.img_size)), words, n, device)))
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('checkpoint', help="Model checkpoint (or 'pretrained=<model_id>')")
@@ -185,6 +220,10 @@ def build_parser():
     parser.add_argument('--beam', type=int, default=None, help=f'Beam width of --nbest (default: N) or of --lexicon (default: {LEXICON_BEAM})')
     parser.add_argument('--lexicon', default=None, metavar='FILE',
                         help='Read only words of this list (one per line): a beam search constrained to the list; --nbest N prints the N best words')
+    parser.add_argument('--match', type=int, nargs='?', const=MATCH_N, default=None, metavar='N',
+                        help=f'With --lexicon: read freely, then let the model choose among the N (default {MATCH_N}) words of the list nearest to the '
+                             'reading in edit distance, instead of a search constrained to the list; --nbest K prints the K best with score and distance; '
+                             'not with --beam or --refine-beams edit')
     parser.add_argument('--refine-beams', default=None, choices=['edit', 'score'], dest='refine_beams',
                         help="Refine the alternatives of --nbest / --lexicon with the model's cloze pass and rank them again: 'edit' replaces every "
                              "reading by its refined one, 'score' only rescores (the only mode under --lexicon)")
@@ -217,6 +256,23 @@ def resolve_refine(parser, args):
     return args.refine_beams, iters
 
 
+def resolve_match(parser, args):
+    """N of --match, None without it; a contradiction ends in parser.error."""
+    if args.match is None:
+        return None
+    if args.lexicon is None:
+        parser.error('--match needs --lexicon FILE')
+    if args.beam is not None:
+        parser.error('--match is not a beam search: not with --beam')
+    if args.refine_beams == 'edit':
+        parser.error('--match with --refine-beams edit: an edited reading can leave the list (the candidates of --match are rescored already)')
+    if not 1 <= args.match <= 16:
+        parser.error('--match N must be in [1, 16]')
+    if args.nbest > args.match:
+        parser.error('--nbest must be at most --match N')
+    return args.match
+
+
 def resolve_search(parser, args):
     """(beam width, N) of the search the flags ask for, (None, 0) for none; a contradiction ends in parser.error."""
     if args.lexicon is not None:
@@ -238,6 +294,7 @@ def main(argv=None):
 
     if args.boxes and (args.nbest > 0 or args.lexicon is not None):
         parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
+    match = resolve_match(parser, args)
     beam, nbest = resolve_search(parser, args)
     refine, refine_iters = resolve_refine(parser, args)
     files = args.images or []
@@ -246,8 +303,13 @@ def main(argv=None):
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     if args.regions is not None:
         words = load_word_list(args.lexicon) if args.lexicon is not None else None
-        for line in read_regions(model, files, args.regions, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device):
+        for line in read_regions(model, files, args.regions, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device, match):
             print(line)
+        return
+    if match is not None:
+        for fname, alts in read_files_match(model, files, load_word_list(args.lexicon), match, args.device):
+            for line in match_lines(fname, alts[:nbest], args.nbest > 0):
+                print(line)
         return
     if args.lexicon is not None:
         # the best word of the list where the greedy reading goes; the alternatives only where --nbest asks for them
