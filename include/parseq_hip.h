@@ -413,6 +413,39 @@ int parseq_forward_lexicon_match(parseq_plan* p, const void* images, int images_
                                  uint8_t* finished_out, int32_t* words_out, int32_t* distances_out, int32_t* reading_tokens_out,
                                  int32_t* reading_lengths_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- beam search over a weighted automaton (pure additions under ABI 15; DESIGN.md section 24 defines it) ------------ */
+
+/* parseq_forward_beam_lexicon with a weight on every arc of the table, which then need not be a tree (cycles and shared states are
+ * allowed): a word list with frequencies, a character n-gram model or a regular pattern (parseq_amd/automaton.py builds all three).
+ *   next       device int32 [states][C], exactly trie_next above; the <eos> column holds a non-negative tag where the state accepts
+ *   weight     device fp32 [states][C], the natural-log weight of taking class c from state s (the <eos> column: the final weight).  A
+ *              non-finite weight makes its arc not allowed
+ *   roots      as above (each image's start state)
+ *   alpha, beta   finite: the prior weight and the per-character bonus
+ * A beam also carries wsum, the sum of the weights along its path.  A candidate (w, c) of model score m = score[w] + logp[w][c] is
+ * ranked by f = m + (alpha (wsum[w] + weight[n][c]) + beta k), k the characters the hypothesis would have (<eos> not counted), every
+ * operation rounded to fp32 on its own (a candidate whose f overflows is not allowed); a finished beam carries at score + (alpha wsum + beta length).  Ties as in parseq_forward_beam.
+ *   scores_out        the fused value f the ranking used        model_scores_out  fp32 [batch, W] the model's own sum of log-probabilities
+ *   priors_out        fp32 [batch, W] wsum (0 for a dead beam)  words_out         the tag of a finished hypothesis, -1 otherwise
+ * trace->score holds the fused values.  With alpha = beta = 0 every output equals parseq_forward_beam_lexicon's on the same table; with a
+ * one-state table that allows every class at weight 0 and beta = 0, parseq_forward_beam's.
+ * Refused before any device work, outputs untouched: whatever parseq_forward_beam_lexicon refuses, a NULL weight, model_scores_out or
+ * priors_out, a non-finite alpha or beta.
+ * workspace: parseq_beam_automaton_workspace_bytes(...) bytes — parseq_beam_lexicon_workspace_bytes' parts, then wsum fp32 [batch * W]. */
+size_t parseq_beam_automaton_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps);
+int parseq_forward_beam_automaton(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                  int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                  const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
+                                  const int32_t* next, const float* weight, int states, const int32_t* roots, float alpha, float beta,
+                                  int32_t* words_out, float* model_scores_out, float* priors_out);
+/* parseq_op_beam_step under a weighted automaton (tests/test_automaton.py): parseq_op_beam_step_lexicon's arguments with the weights
+ * beside the table, then alpha, beta and, in place, wsums fp32 [batch * W]; scores stay the model's sums, fused_out fp32 [batch * W]
+ * (may be NULL) receives each new beam's fused value (-inf for a dead slot). */
+int parseq_op_beam_step_automaton(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
+                                  uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
+                                  void* stream, const int32_t* next, const float* weight, int states, int32_t* nodes, int32_t* words,
+                                  float alpha, float beta, float* wsums, float* fused_out);
+
 /* ViTSTR.forward (strhub/models/vitstr/system.py:76-82 -> vitstr/model.py:20-28) for a model created with
  * arch = PARSEQ_ARCH_VITSTR: encoder with class token, head on tokens [1, num_steps], i.e. logits_out fp32
  * [batch, num_steps, num_tokens - 2] with num_steps = min(max_length, max_label_length) + 1.  images as parseq_forward. */

@@ -2,8 +2,10 @@
 // beams of an image, and the small init / write-out kernels.  A beam is a token history (a row of the plan's pitched token array), a
 // score, a finished flag and a length; at decoder depth 1 the self-attention keys are table lookups by (token id, position), so
 // re-parenting a beam is a copy of its history row and nothing else.  Under a lexicon a beam also carries the trie node
-// its history has reached and, once finished, the id of the word it spelled.
+// its history has reached and, once finished, the id of the word it spelled.  Under a weighted automaton the table
+// has a weight per arc, a beam also carries the sum of the weights along its path, and the ranking is by the fused value.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace pq {
@@ -24,6 +26,21 @@ __device__ __forceinline__ unsigned beam_ordered(float v) {
 // The lexicon of a constrained step: the dense trie table next [nodes][C] (a negative entry: not allowed; the <eos> column holds word ids)
 // and, per beam row and in place, the node reached and the word finished (-1: none).  Unused by the unconstrained instantiation.
 struct BeamLex { const int* next; int nodes; int* node; int* word; };
+// The automaton of a weighted step: BeamLex's members with `nodes` the number of states, then the arc weights weight [nodes][C] (natural
+// log; a non-finite one: not allowed), per beam row and in place the sum of the weights along its path, the prior weight alpha and the
+// per-character bonus beta, and fused [rows] (may be null): where each new beam's fused value goes.
+struct BeamAut { const int* next; int nodes; int* node; int* word; const float* weight; float* wsum; float alpha, beta; float* fused; };
+
+// The fused value of a hypothesis of model score m, weight sum ws and k characters: m + (alpha ws + beta k), every operation rounded on
+// its own — the pragma forbids contraction into an fma, which the compiler's default allows — so that the step, the carry and the write-out
+// give the same bits from the same (m, ws, k).  A finite alpha can still overflow a product: a value that is not finite comes back as -inf,
+// "no candidate", so neither +inf nor NaN ever enters the ranking.
+__device__ __forceinline__ float beam_fused(float m, float ws, int k, float alpha, float beta) {
+#pragma clang fp contract(off)
+    const float f = m + (alpha * ws + beta * (float)k);
+    if (!(f - f == 0.f)) return -INFINITY;
+    return f == 0.f ? 0.f : f;      // one zero, as for the scores
+}
 
 // One selection step of one image per workgroup.  In: logits [B * W][C] of the step, and the image's W beams in place — history rows
 // tok[(b W + w) ldt ..], score, finished, length.  Candidates: every live unfinished beam w offers (w, c) at score[w] +
@@ -37,11 +54,21 @@ struct BeamLex { const int* next; int nodes; int* node; int* word; };
 // are the unconstrained ones: the log-soft-max runs over all C classes.  A new beam's node is next[node_parent][c]; picking <eos> keeps the
 // node and records word = next[node][eos_id]; a carry keeps both; a dead slot holds -1 / -1.  Nodes and words are re-parented like the
 // histories: all W loaded before the first barrier, written after the last.
-template <bool LEX>
+// WGT (with LEX; lx is then a BeamAut): the candidate array holds the fused value f = m + (alpha (wsum[w] + weight[n][c]) + beta k), m the
+// score above and k the characters the hypothesis would have (step + 1, step for <eos>); a finished beam carries at score + (alpha wsum +
+// beta length).  An arc whose weight, or whose sum with the beam's wsum, is not finite is not allowed, so no product sees an infinity;
+// alpha and beta are finite (the entries refuse others), and a candidate or carry whose f overflows all the same is not allowed either
+// (beam_fused).  The ranking, the ties and the keys are the same, on f.  score[] stays the
+// model's sum: for a picked candidate it is RECOMPUTED from the row's kept maximum and log-sum (two floats per beam in LDS, one logit read
+// per new beam) by the expression that made the candidate, which gives the same bits, rather than kept in a second [W][C] array that would
+// double the LDS.  wsum is re-parented like node and word: loaded before the first barrier, written after the last; a dead slot holds 0.
+// f is never carried: the next step and the write-out recompute it from (score, wsum, length).
+template <bool LEX, bool WGT = false>
 static __global__ __launch_bounds__(BEAM_THREADS)
 void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, int* __restrict__ tok, int ldt, float* __restrict__ score,
                       unsigned char* __restrict__ finished, int* __restrict__ length, int* __restrict__ parent_out, int* __restrict__ picked,
-                      int eos_id, int pad_id, BeamLex lx) {
+                      int eos_id, int pad_id, std::conditional_t<WGT, BeamAut, BeamLex> lx) {
+    static_assert(LEX || !WGT, "a weighted step walks a table");
     extern __shared__ float beam_smem[];
     float* cand = beam_smem;                                       // [W * C] fresh candidates, then [W] carries
     int* hist = reinterpret_cast<int*>(beam_smem + (size_t)W * C + W);
@@ -49,11 +76,13 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
     __shared__ int s_len[BEAM_MAX_W], sel_parent[BEAM_MAX_W], sel_cls[BEAM_MAX_W];
     __shared__ unsigned char s_fin[BEAM_MAX_W];
     __shared__ int s_node[LEX ? BEAM_MAX_W : 1], s_word[LEX ? BEAM_MAX_W : 1];
+    __shared__ float s_wsum[WGT ? BEAM_MAX_W : 1], s_rmax[WGT ? BEAM_MAX_W : 1], s_rlg[WGT ? BEAM_MAX_W : 1];
     __shared__ unsigned long long s_wkey[BEAM_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const size_t row0 = (size_t)blockIdx.x * W;
     if (tid < W) { s_score[tid] = score[row0 + tid]; s_fin[tid] = finished[row0 + tid]; s_len[tid] = length[row0 + tid]; }
     if constexpr (LEX) { if (tid < W) { s_node[tid] = lx.node[row0 + tid]; s_word[tid] = lx.word[row0 + tid]; } }
+    if constexpr (WGT) { if (tid < W) s_wsum[tid] = lx.wsum[row0 + tid]; }
     for (int i = tid; i < W * ldt; i += BEAM_THREADS) hist[i] = tok[row0 * ldt + i];
     __syncthreads();
 
@@ -72,6 +101,11 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
             const float lg = logf(wave_sum(sum));
             const int* allowed = nullptr;      // LEX: the node's row of the table, null for a node outside it
             if constexpr (LEX) { const int nd = s_node[w]; if (nd >= 0 && nd < lx.nodes) allowed = lx.next + (size_t)nd * C; }
+            const float* wrow = nullptr;       // WGT: the node's row of the weights, null with `allowed`
+            if constexpr (WGT) {
+                if (allowed) wrow = lx.weight + (size_t)s_node[w] * C;
+                if (lane == 0) { s_rmax[w] = m; s_rlg[w] = lg; }
+            }
             for (int c = lane; c < C; c += 64) {
                 float v = sc + ((row[c] - m) - lg);
                 if (v == 0.f) v = 0.f;      // one zero: the ordering below is on the bits
@@ -79,12 +113,19 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
                     const int t = allowed ? allowed[c] : -1;
                     if (t < 0 || (c != eos_id && t >= lx.nodes)) v = -INFINITY;
                 }
+                if constexpr (WGT) {
+                    if (v > -INFINITY) {      // an allowed arc, so wrow is set
+                        const float ws = s_wsum[w] + wrow[c];
+                        v = (ws - ws == 0.f) ? beam_fused(v, ws, c == eos_id ? step : step + 1, lx.alpha, lx.beta) : -INFINITY;
+                    }
+                }
                 out[c] = v;
             }
         } else {
             for (int c = lane; c < C; c += 64) out[c] = -INFINITY;
         }
-        if (lane == 0) cand[(size_t)W * C + w] = (alive && fin) ? (sc == 0.f ? 0.f : sc) : -INFINITY;
+        if constexpr (WGT) { if (lane == 0) cand[(size_t)W * C + w] = (alive && fin) ? beam_fused(sc, s_wsum[w], s_len[w], lx.alpha, lx.beta) : -INFINITY; }
+        else if (lane == 0) cand[(size_t)W * C + w] = (alive && fin) ? (sc == 0.f ? 0.f : sc) : -INFINITY;
     }
     __syncthreads();
 
@@ -136,7 +177,7 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
     if (tid < W) {
         const int par = sel_parent[tid], cls = sel_cls[tid];
         const bool dead = par < 0, carry = !dead && cls < 0;
-        score[row0 + tid] = sel_score[tid];
+        if constexpr (!WGT) score[row0 + tid] = sel_score[tid];
         finished[row0 + tid] = dead ? 0 : (carry || cls == eos_id ? 1 : 0);
         length[row0 + tid] = dead ? 0 : (carry ? s_len[par] : (cls == eos_id ? step : step + 1));
         picked[row0 + tid] = cls >= 0 ? cls : pad_id;
@@ -150,6 +191,17 @@ void beam_step_kernel(const float* __restrict__ logits, int W, int C, int step, 
                 if (cls == eos_id) wd = t; else nd = t;
             }
             lx.node[row0 + tid] = nd; lx.word[row0 + tid] = wd;
+        }
+        if constexpr (WGT) {
+            float ms = -INFINITY, ws = 0.f;
+            if (carry) { ms = s_score[par]; ws = s_wsum[par]; }
+            else if (!dead) {      // the candidate's own expressions again: the same bits
+                ms = s_score[par] + ((logits[(row0 + par) * C + cls] - s_rmax[par]) - s_rlg[par]);
+                ws = s_wsum[par] + lx.weight[(size_t)s_node[par] * C + cls];
+            }
+            score[row0 + tid] = ms == 0.f ? 0.f : ms;
+            lx.wsum[row0 + tid] = ws;
+            if (lx.fused) lx.fused[row0 + tid] = sel_score[tid];
         }
     }
 }
@@ -190,6 +242,24 @@ static __global__ void beam_finish_lexicon_kernel(int rows, const float* __restr
                                                   const int* __restrict__ word, int* __restrict__ words_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < rows) words_out[i] = (score[i] > -INFINITY && finished[i]) ? word[i] : -1;
+}
+
+// The start under a weighted automaton, after beam_init_lexicon_kernel: every beam's weight sum is 0.
+static __global__ void beam_init_automaton_kernel(int rows, float* __restrict__ wsum) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < rows) wsum[i] = 0.f;
+}
+
+// The write-out under a weighted automaton, after beam_finish_kernel: scores_out [rows] becomes the fused value the ranking used, recomputed
+// from the carried (score, wsum, length); model_scores_out the carried score, priors_out the weight sum (-inf, -inf and 0 for a dead beam).
+static __global__ void beam_finish_automaton_kernel(int rows, const float* __restrict__ score, const float* __restrict__ wsum,
+                                                    const int* __restrict__ length, float alpha, float beta, float* __restrict__ scores_out,
+                                                    float* __restrict__ model_scores_out, float* __restrict__ priors_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    const bool dead = !(score[i] > -INFINITY);
+    scores_out[i] = dead ? -INFINITY : beam_fused(score[i], wsum[i], length[i], alpha, beta);
+    model_scores_out[i] = score[i]; priors_out[i] = dead ? 0.f : wsum[i];
 }
 
 // The write-out: the beams are in rank order after every step, so this only drops <bos> and the pitch.  tokens_out [rows][num_steps];

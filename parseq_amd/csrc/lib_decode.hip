@@ -766,6 +766,7 @@ struct BeamState {
     int *node = nullptr, *word = nullptr;      // under a lexicon (section 19): every beam's trie node and word id [rows]
     float* ar_score = nullptr;                 // a refined search (section 20): the search's own score [rows]
     float* lp_tok = nullptr; int* amax = nullptr; float* lp_max = nullptr;      // ... and the row statistics of an iteration [rows][L]
+    float* wsum = nullptr;                     // under a weighted automaton (section 24): the sum of the arc weights along every beam's path [rows]
 
     static BeamState of_tensors(int32_t* tokens, int ldt, float* scores, uint8_t* finished, int32_t* lengths, int32_t* picked,
                                 int32_t* nodes = nullptr, int32_t* words = nullptr, float* ar_scores = nullptr) {
@@ -774,13 +775,19 @@ struct BeamState {
 };
 // Where a search's results go, best first per image: tokens [batch][W][num_steps], the others [batch][W]; words under a lexicon, ar_scores
 // of a refined search.
-struct BeamOut { int32_t* tokens; float* scores; int32_t* lengths; uint8_t* finished; int32_t* words = nullptr; float* ar_scores = nullptr; };
+// Under a weighted automaton scores are the fused values, model_scores the model's own sums and priors the weight sums.
+struct BeamOut { int32_t* tokens; float* scores; int32_t* lengths; uint8_t* finished; int32_t* words = nullptr; float* ar_scores = nullptr;
+                 float* model_scores = nullptr; float* priors = nullptr; };
+// The weights of an automaton over the table of a lexicon (section 24): weight [nodes][C], the prior weight and the per-character bonus
+struct BeamWeights { const float* weight = nullptr; float alpha = 0.f, beta = 0.f; };
 // What a search was asked for beyond the plain one: the per-step trace, a lexicon (the caller's table and roots; forward_beam refuses a
-// null table, so past it trie_next is set exactly under a lexicon), a refinement (the mode, the iterations, its trace).
+// null table, so past it trie_next is set exactly under a lexicon), a refinement (the mode, the iterations, its trace), the weights that
+// make the table an automaton (weighted implies lexicon; forward_beam refuses null weights).
 struct BeamCall {
     const parseq_beam_trace* trace = nullptr;
     bool lexicon = false; const int32_t* trie_next = nullptr; int trie_nodes = 0; const int32_t* roots = nullptr;
     bool refine = false; int refine_mode = 0, refine_iters = 0; const parseq_beam_refine_trace* refine_trace = nullptr;
+    bool weighted = false; BeamWeights wt;
 };
 
 // The parts of a caller's workspace, in carve()'s 256-byte steps.  Over a null base only `off`, the size so far, means anything.
@@ -797,8 +804,9 @@ static void take_refine_stats(Carver& cv, size_t n, BeamState& b) { b.lp_tok = c
 // beams' scores / lengths / last picks / flags.  The histories live in p->tok, where the self-attention kernels read them.
 // Under a lexicon (section 19) two more parts follow: every beam's trie node and word id.
 // A refined search (section 20) adds the refinement logits of all num_steps positions, the row statistics and the search's own scores.
+// A weighted automaton (section 24) adds, last, every beam's weight sum.
 struct BeamWs { float *memory, *memory_rep, *logits, *rlogits; BeamState st; size_t total; };
-static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon, int refine_steps, void* workspace = nullptr) {
+static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon, int refine_steps, void* workspace = nullptr, bool weighted = false) {
     const parseq_model* m = p->m;
     const size_t rows = (size_t)batch * W, img = (size_t)m->tokens * m->cfg.embed_dim;
     Carver cv{reinterpret_cast<unsigned char*>(workspace)};
@@ -814,6 +822,7 @@ static BeamWs beam_ws(const parseq_plan* p, int batch, int W, bool lexicon, int 
         take_refine_stats(cv, rows * refine_steps, b);
         b.ar_score = cv.take<float>(rows);
     }
+    if (weighted) b.wsum = cv.take<float>(rows);
     o.total = cv.off;
     return o;
 }
@@ -831,9 +840,14 @@ static int beam_check(const parseq_plan* p, int batch, int W, int num_steps) {
     return 0;
 }
 
-// One selection step on logits [batch * W][C] (beam.h); trie_next: null for the unconstrained step
+// One selection step on logits [batch * W][C] (beam.h); trie_next: null for the unconstrained step; wt: the weights of a weighted step,
+// whose fused values go to fused_out (may be null)
 static int launch_beam_step(hipStream_t s, const float* logits, int batch, int W, int C, int step, const BeamState& b, int* parent_out, int eos_id,
-                            int pad_id, const int32_t* trie_next = nullptr, int trie_nodes = 0) {
+                            int pad_id, const int32_t* trie_next = nullptr, int trie_nodes = 0, const BeamWeights* wt = nullptr, float* fused_out = nullptr) {
+    if (wt)
+        return launch(beam_step_kernel<true, true>, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, b.ldt), s, logits, W, C, step, b.tok, b.ldt, b.score,
+                      b.finished, b.length, parent_out, b.picked, eos_id, pad_id,
+                      BeamAut{trie_next, trie_nodes, b.node, b.word, wt->weight, b.wsum, wt->alpha, wt->beta, fused_out});
     const auto kernel = trie_next ? beam_step_kernel<true> : beam_step_kernel<false>;
     return launch(kernel, dim3(batch), dim3(BEAM_THREADS), beam_step_lds(W, C, b.ldt), s, logits, W, C, step, b.tok, b.ldt, b.score, b.finished,
                   b.length, parent_out, b.picked, eos_id, pad_id, trie_next ? BeamLex{trie_next, trie_nodes, b.node, b.word} : BeamLex{});
@@ -860,6 +874,7 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, const BeamWs& 
     CHK(set_memory_impl<T>(p, ws.memory_rep, rows, s));
     CHK(launch(beam_init_kernel, dim3((rows * LDT + 255) / 256), dim3(256), 0, s, b.tok, b.ldt, rows, W, c.bos_id, c.pad_id, b.score, b.finished, b.length, b.picked));
     if (call.lexicon) CHK(launch(beam_init_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, W, call.roots, call.trie_nodes, b.score, b.node, b.word));
+    if (call.weighted) CHK(launch(beam_init_automaton_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, b.wsum));
     const DecW<T> w = dec_weights<T>(p);
     const parseq_beam_trace* tr = call.trace;
     DecPass a; a.B = rows;      // the per-operation step, one query per beam, on every beam's history
@@ -869,9 +884,11 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, const BeamWs& 
         if (tr && tr->logits) HIPCHK(hipMemcpyAsync(tr->logits + (size_t)i * rows * C, ws.logits, (size_t)rows * C * sizeof(float), hipMemcpyDeviceToDevice, s));
         if (tr && tr->tokens_in) HIPCHK(hipMemcpy2DAsync(tr->tokens_in + (size_t)i * rows * num_steps, num_steps * sizeof(int), b.tok, LDT * sizeof(int),
                                                          num_steps * sizeof(int), rows, hipMemcpyDeviceToDevice, s));
+        // the traced score of a weighted step is the fused value, which the kernel writes itself (b.score stays the model's sum)
+        float* trace_score = tr && tr->score ? tr->score + (size_t)i * rows : nullptr;
         CHK(launch_beam_step(s, ws.logits, B, W, C, i, b, tr && tr->parent ? tr->parent + (size_t)i * rows : nullptr, c.eos_id, c.pad_id, call.trie_next,
-                             call.trie_nodes));
-        if (tr && tr->score) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, b.score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+                             call.trie_nodes, call.weighted ? &call.wt : nullptr, trace_score));
+        if (trace_score && !call.weighted) HIPCHK(hipMemcpyAsync(tr->score + (size_t)i * rows, b.score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (call.refine) {
         // cloze refinement of every beam (section 20): forward_impl's refinement iteration on rows = B * W, then the selection
@@ -888,8 +905,11 @@ static int beam_impl(parseq_plan* p, int B, int W, int num_steps, const BeamWs& 
         HIPCHK(hipMemcpyAsync(out.ar_scores, b.ar_score, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     if (call.lexicon) CHK(launch(beam_finish_lexicon_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, b.score, b.finished, b.word, out.words));
-    return launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, b.tok, b.ldt, rows, num_steps, c.pad_id, b.score, b.finished,
-                  b.length, b.picked, out.tokens, out.scores, out.lengths, out.finished);
+    CHK(launch(beam_finish_kernel, dim3((rows * num_steps + 255) / 256), dim3(256), 0, s, b.tok, b.ldt, rows, num_steps, c.pad_id, b.score, b.finished,
+               b.length, b.picked, out.tokens, out.scores, out.lengths, out.finished));
+    if (call.weighted) CHK(launch(beam_finish_automaton_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, rows, b.score, b.wsum, b.length, call.wt.alpha,
+                                  call.wt.beta, out.scores, out.model_scores, out.priors));
+    return 0;
 }
 
 // The three search entries: the refusals in one order, the encoder into the workspace, then beam_impl.
@@ -900,6 +920,10 @@ static int forward_beam(parseq_plan* p, const void* images, int images_dtype, in
     if (!images || !out.tokens || !out.scores || !out.lengths || !out.finished || !workspace) return fail(PARSEQ_E_INVALID, "null images / output / workspace");
     if (call.lexicon && (!call.trie_next || !out.words)) return fail(PARSEQ_E_INVALID, "null trie table / words output");
     if (call.lexicon && call.trie_nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", call.trie_nodes);
+    if (call.weighted) {
+        if (!call.wt.weight || !out.model_scores || !out.priors) return fail(PARSEQ_E_INVALID, "null automaton weights / model_scores / priors output");
+        if (!std::isfinite(call.wt.alpha) || !std::isfinite(call.wt.beta)) return fail(PARSEQ_E_INVALID, "alpha %g / beta %g: both must be finite", (double)call.wt.alpha, (double)call.wt.beta);
+    }
     if (call.refine) {
         const int mode = call.refine_mode, iters = call.refine_iters;
         if (mode != PARSEQ_BEAM_REFINE_SCORE && mode != PARSEQ_BEAM_REFINE_EDIT) return fail(PARSEQ_E_INVALID, "refine_mode %d: neither PARSEQ_BEAM_REFINE_SCORE nor PARSEQ_BEAM_REFINE_EDIT", mode);
@@ -908,7 +932,7 @@ static int forward_beam(parseq_plan* p, const void* images, int images_dtype, in
         if (mode == PARSEQ_BEAM_REFINE_EDIT && call.lexicon) return fail(PARSEQ_E_INVALID, "edit refinement under a lexicon: an edited reading can leave the word list; use the score mode");
         if (!out.ar_scores) return fail(PARSEQ_E_INVALID, "null ar_scores_out");
     }
-    const BeamWs ws = beam_ws(p, batch, beam_width, call.lexicon, call.refine ? num_steps : 0, workspace);
+    const BeamWs ws = beam_ws(p, batch, beam_width, call.lexicon, call.refine ? num_steps : 0, workspace, call.weighted);
     if (workspace_bytes < ws.total) return fail(PARSEQ_E_INVALID, "beam workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
     if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "beam workspace not 16-byte aligned");
     DevGuard dg(p->m->device);
@@ -945,6 +969,25 @@ extern "C" int parseq_forward_beam_lexicon(parseq_plan* p, const void* images, i
     call.lexicon = true; call.trie_next = trie_next; call.trie_nodes = trie_nodes; call.roots = roots;
     return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, {tokens_out, scores_out, lengths_out, finished_out, words_out}, call,
                         workspace, workspace_bytes, stream);
+}
+
+// beam search over a weighted automaton
+extern "C" size_t parseq_beam_automaton_workspace_bytes(const parseq_plan* p, int batch, int beam_width, int num_steps) {
+    if (beam_check(p, batch, beam_width, num_steps) != 0) return 0;
+    return beam_ws(p, batch, beam_width, true, 0, nullptr, true).total;
+}
+
+extern "C" int parseq_forward_beam_automaton(parseq_plan* p, const void* images, int images_dtype, int batch, int beam_width, int num_steps,
+                                             int32_t* tokens_out, float* scores_out, int32_t* lengths_out, uint8_t* finished_out,
+                                             const parseq_beam_trace* trace, void* workspace, size_t workspace_bytes, void* stream,
+                                             const int32_t* next, const float* weight, int states, const int32_t* roots, float alpha, float beta,
+                                             int32_t* words_out, float* model_scores_out, float* priors_out) {
+    BeamCall call; call.trace = trace;
+    call.lexicon = true; call.trie_next = next; call.trie_nodes = states; call.roots = roots;
+    call.weighted = true; call.wt = BeamWeights{weight, alpha, beta};
+    BeamOut out{tokens_out, scores_out, lengths_out, finished_out, words_out};
+    out.model_scores = model_scores_out; out.priors = priors_out;
+    return forward_beam(p, images, images_dtype, batch, beam_width, num_steps, out, call, workspace, workspace_bytes, stream);
 }
 
 // cloze refinement of the N-best
@@ -994,16 +1037,19 @@ extern "C" int parseq_op_beam_refine(const float* logits, int batch, int beam_wi
     return launch_beam_refine((hipStream_t)stream, logits, batch, beam_width, C, L, refine_mode, b, eos_id, pad_id);
 }
 
-// The two parseq_op_beam_step* entries: their refusals, then the step.  trie_next, nodes and words: the lexicon entry's.
+// The three parseq_op_beam_step* entries: their refusals, then the step.  trie_next, nodes and words: the lexicon entry's; wt and
+// fused_out: the automaton entry's.
 static int beam_step_op(hipStream_t s, const float* logits, int batch, int W, int C, int step, const BeamState& b, int* parent_out, int eos_id, int pad_id,
-                        bool lexicon, const int32_t* trie_next = nullptr, int trie_nodes = 0) {
+                        bool lexicon, const int32_t* trie_next = nullptr, int trie_nodes = 0, const BeamWeights* wt = nullptr, float* fused_out = nullptr) {
     if (!logits || !b.tok || !b.score || !b.finished || !b.length || !b.picked || (lexicon && (!trie_next || !b.node || !b.word))) return fail(PARSEQ_E_INVALID, "null argument");
+    if (wt && (!wt->weight || !b.wsum)) return fail(PARSEQ_E_INVALID, "null automaton weights / weight sums");
+    if (wt && (!std::isfinite(wt->alpha) || !std::isfinite(wt->beta))) return fail(PARSEQ_E_INVALID, "alpha %g / beta %g: both must be finite", (double)wt->alpha, (double)wt->beta);
     if (batch <= 0 || C < 1 || W < 1 || W > PARSEQ_BEAM_MAX_WIDTH) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, beam_width %d (1..%d), C %d", batch, W, PARSEQ_BEAM_MAX_WIDTH, C);
     if (step < 0 || b.ldt < step + 1 || b.ldt > 64) return fail(PARSEQ_E_INVALID, "step %d / ldt %d: need step + 1 <= ldt <= 64", step, b.ldt);
     if (eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "eos_id %d outside [0, %d)", eos_id, C);
     if (lexicon && trie_nodes < 1) return fail(PARSEQ_E_INVALID, "trie_nodes %d: a trie has at least its root", trie_nodes);
     if (beam_step_lds(W, C, b.ldt) > BEAM_LDS_MAX) return fail(PARSEQ_E_INVALID, "beam_width %d x %d classes does not fit the step kernel's LDS", W, C);
-    return launch_beam_step(s, logits, batch, W, C, step, b, parent_out, eos_id, pad_id, trie_next, trie_nodes);
+    return launch_beam_step(s, logits, batch, W, C, step, b, parent_out, eos_id, pad_id, trie_next, trie_nodes, wt, fused_out);
 }
 
 extern "C" int parseq_op_beam_step(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
@@ -1019,6 +1065,16 @@ extern "C" int parseq_op_beam_step_lexicon(const float* logits, int batch, int b
     return beam_step_op((hipStream_t)stream, logits, batch, beam_width, C, step,
                         BeamState::of_tensors(tokens, ldt, scores, finished, lengths, picked_out, nodes, words), parent_out, eos_id, pad_id, true, trie_next,
                         trie_nodes);
+}
+
+extern "C" int parseq_op_beam_step_automaton(const float* logits, int batch, int beam_width, int C, int step, int32_t* tokens, int ldt, float* scores,
+                                             uint8_t* finished, int32_t* lengths, int32_t* parent_out, int32_t* picked_out, int eos_id, int pad_id,
+                                             void* stream, const int32_t* next, const float* weight, int states, int32_t* nodes, int32_t* words,
+                                             float alpha, float beta, float* wsums, float* fused_out) {
+    BeamState b = BeamState::of_tensors(tokens, ldt, scores, finished, lengths, picked_out, nodes, words);
+    b.wsum = wsums;
+    const BeamWeights wt{weight, alpha, beta};
+    return beam_step_op((hipStream_t)stream, logits, batch, beam_width, C, step, b, parent_out, eos_id, pad_id, true, next, states, &wt, fused_out);
 }
 
 // -------------------------------------------------------------------------------------------------------------------

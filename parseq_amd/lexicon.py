@@ -19,6 +19,27 @@ import torch
 from torch import Tensor
 
 
+class CharsetEncoder:
+    """Strings as the head's class ids (`<eos>` and the charset: the tokenizer's ids 0 .. C - 1), for the host builders of search tables
+    (`Lexicon`, `parseq_amd.automaton.Automaton`).  `fold_case=True` folds to the charset's only case when it has one."""
+
+    def __init__(self, tokenizer, fold_case: bool = False) -> None:
+        self.eos_id = int(tokenizer.eos_id)
+        self.num_classes = len(tokenizer) - 2
+        self.stoi: Dict[str, int] = {ch: i for i, ch in enumerate(tokenizer._itos[:self.num_classes]) if i != self.eos_id}
+        charset = ''.join(self.stoi)
+        self.fold = (str.lower if charset == charset.lower() else str.upper if charset == charset.upper() else None) if fold_case else None
+
+    def encode(self, text: str) -> Optional[List[int]]:
+        """The class ids of `text` (folded), None if it has a character outside the charset."""
+        if self.fold is not None:
+            text = self.fold(text)
+        try:
+            return [self.stoi[ch] for ch in text]
+        except KeyError:
+            return None
+
+
 class Lexicon:
     """`Lexicon(words, tokenizer, fold_case=False)`.  `words` is kept as given: a finished hypothesis' word id indexes it, so a caller gets
     the list's own spelling back.  Left out of the trie and counted in `.skipped`: empty words, words with a character outside the
@@ -46,28 +67,27 @@ class Lexicon:
 
     # ---- construction --------------------------------------------------------------------------------------------------
     def _setup(self, tokenizer, fold_case, max_label_length):
-        self.eos_id = int(tokenizer.eos_id)
-        self.num_classes = len(tokenizer) - 2
+        self.encoder = CharsetEncoder(tokenizer, fold_case)
+        self.eos_id, self.num_classes = self.encoder.eos_id, self.encoder.num_classes
         self.max_label_length = int(max_label_length)
         self.skipped = 0
-        self._stoi: Dict[str, int] = {ch: i for i, ch in enumerate(tokenizer._itos[:self.num_classes]) if i != self.eos_id}
-        charset = ''.join(self._stoi)
-        self._fold = (str.lower if charset == charset.lower() else str.upper if charset == charset.upper() else None) if fold_case else None
+        self._stoi, self._fold = self.encoder.stoi, self.encoder.fold
         self._device_tables: Dict[torch.device, Tensor] = {}
         self._entries: List[Tuple[int, List[int]]] = []      # (word id, class ids) of every word entered into a trie, in ascending id
         self._list_rows: List[Tuple[int, int]] = []          # per list its [begin, end) range of `_entries`
         self._packed: Dict[bool, np.ndarray] = {}
         self._device_packed: Dict[Tuple[torch.device, bool], Dict[str, Optional[Tensor]]] = {}
 
-    def _encode(self, word: str) -> Optional[List[int]]:
-        if self._fold is not None:
-            word = self._fold(word)
-        if not 0 < len(word) <= self.max_label_length:
+    def encode_word(self, word: str) -> Optional[List[int]]:
+        """The class ids a word is entered as, None for a word the trie leaves out."""
+        if not 0 < len(self._fold(word) if self._fold is not None else word) <= self.max_label_length:
             return None
-        try:
-            return [self._stoi[ch] for ch in word]
-        except KeyError:
-            return None
+        return self.encoder.encode(word)
+
+    @property
+    def entries(self) -> List[Tuple[int, List[int]]]:
+        """(word id, class ids) of every word entered into a trie, in ascending id (skipped words and repeats have none)."""
+        return self._entries
 
     def _build(self, lists: List[List[str]]) -> Tuple[Tensor, List[int]]:
         rows: List[np.ndarray] = []
@@ -78,7 +98,7 @@ class Lexicon:
             ends: List[int] = [-1]
             begin = len(self._entries)
             for k, word in enumerate(words):
-                ids = self._encode(word)
+                ids = self.encode_word(word)
                 if ids is None:
                     self.skipped += 1
                     continue

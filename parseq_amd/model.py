@@ -11,6 +11,7 @@ library through `parseq_amd._native`; on a CPU tensor or without the library the
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -63,12 +64,34 @@ class BeamResult:
     # ... and trace=True, per refinement iteration:
     trace_refine_tokens_in = None      # Optional[Tensor] int32 [refine_iters, B * W, num_steps] the tgt_in rows of the iteration
     trace_refine_logits = None         # Optional[Tensor] fp32 [refine_iters, B * W, num_steps, C] its logits
+    # automaton= only, set on the instance likewise: `scores` (and `trace_score`) are then the fused values the ranking used.
+    model_scores = None                # Optional[Tensor] fp32 [B, W] the model's own sum of log-probabilities
+    priors = None                      # Optional[Tensor] fp32 [B, W] the sum of the automaton's weights along the hypothesis (0 for a dead beam)
 
 
 @dataclass
 class LexiconBeamResult(BeamResult):
     """`beam_search(..., lexicon=...)`: a `BeamResult` and each hypothesis' word."""
     words: Optional[Tensor] = None       # int32 [B, W] index into `lexicon.words` of a finished hypothesis, -1 otherwise
+
+
+def check_beam_automaton(automaton, alpha, beta, lexicon, refine, classes):
+    """The refusals of `beam_search(..., automaton=, alpha=, beta=)` that need no device."""
+    if automaton is None:
+        if alpha != 1.0 or beta != 0.0:
+            raise ValueError('beam_search: alpha / beta without an automaton')
+        return
+    if lexicon is not None:
+        raise ValueError('beam_search: automaton= and lexicon= exclude each other (Automaton.from_lexicon gives a word list its weights)')
+    if refine is not None:
+        raise ValueError('beam_search: refine= under a weighted automaton is refused: ranking pseudo-log-likelihoods with a prior is not defined yet')
+    if not all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in (alpha, beta)):
+        raise ValueError(f'beam_search: alpha and beta must be finite numbers, got {alpha!r} and {beta!r}')
+    nxt, weight = automaton.next, automaton.weight
+    if (nxt.dim() != 2 or nxt.shape[1] != classes or nxt.dtype != torch.int32 or nxt.shape[0] < 1 or weight.shape != nxt.shape
+            or weight.dtype != torch.float32):
+        raise ValueError(f'beam_search: the automaton tables must be int32 and fp32 [states, {classes}] (one column per head class), got '
+                         f'{nxt.dtype} {tuple(nxt.shape)} and {weight.dtype} {tuple(weight.shape)}')
 
 
 @dataclass
@@ -646,7 +669,7 @@ class PARSeq(_NativeBacked):
 
     def beam_search(self, tokenizer: Tokenizer, images: Tensor, beam_width: int, max_length: Optional[int] = None,
                     trace: bool = False, lexicon=None, roots: Optional[Tensor] = None, refine: Optional[str] = None,
-                    refine_iters: int = 1) -> BeamResult:
+                    refine_iters: int = 1, automaton=None, alpha: float = 1.0, beta: float = 0.0) -> BeamResult:
         """Beam-search AR decoding with N-best output (the reference has none): the `beam_width` best hypotheses
         of every crop with their log-probabilities, best first, no refinement.  One library call on a plan of B * beam_width rows, no
         host synchronisation; the result stays on the device (`tokenizer.decode_beams` reads it).  `max_length` as in `forward`, except
@@ -660,16 +683,23 @@ class PARSeq(_NativeBacked):
         `refine` runs the model's cloze refinement on every hypothesis after the search, in the same library call:
         'score' keeps the readings and replaces their scores by the pseudo-log-likelihood (every character given all the others), 'edit'
         replaces every reading by its refined one, `refine_iters` times, and merges equal readings.  Either way the hypotheses are ranked
-        again by the new `scores`, and `ar_scores` holds the search's own.  Under a lexicon only 'score' is allowed."""
+        again by the new `scores`, and `ar_scores` holds the search's own.  Under a lexicon only 'score' is allowed.
+
+        `automaton` (a `parseq_amd.automaton.Automaton`) is a soft prior instead: a weighted word list, a character
+        n-gram model or a pattern.  The search walks its table as it walks a lexicon's (`roots` gives every crop its start state) and ranks
+        by the model's score plus `alpha` times the weights along the path plus `beta` per character.  The result is a `LexiconBeamResult`
+        whose `scores` are those fused values, with `model_scores`, `priors` and `words` (the accept tags) beside them.  It excludes
+        `lexicon` and `refine`."""
         check_beam_refine(refine, refine_iters, lexicon)
         W = int(beam_width)
         classes = self._cfg['num_tokens'] - 2
+        check_beam_automaton(automaton, alpha, beta, lexicon, refine, classes)
         if self._cfg['dec_depth'] != 1:
             raise ValueError(f"beam_search needs dec_depth == 1, this model has dec_depth = {self._cfg['dec_depth']} (a deeper decoder's "
                              'per-layer content cache would have to be re-parented)')
         if not 1 <= W <= min(BEAM_MAX_WIDTH, classes):
             raise ValueError(f'beam_width must be in [1, {min(BEAM_MAX_WIDTH, classes)}] ({BEAM_MAX_WIDTH} at most, and no more than the {classes} classes), got {beam_width}')
-        if lexicon is None and roots is not None:
+        if lexicon is None and automaton is None and roots is not None:
             raise ValueError('beam_search: roots without a lexicon')
         if lexicon is not None and (lexicon.next.dim() != 2 or lexicon.next.shape[1] != classes or lexicon.next.dtype != torch.int32
                                     or lexicon.next.shape[0] < 1):
@@ -684,7 +714,7 @@ class PARSeq(_NativeBacked):
         self._memory_replaced()                  # by the replicated batch's
         self._check_tokenizer(tokenizer)
         lib, dev = _native.lib(), images.device
-        res = (BeamResult if lexicon is None else LexiconBeamResult)(
+        res = (BeamResult if lexicon is None and automaton is None else LexiconBeamResult)(
             torch.empty(B, W, num_steps, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.float32, device=dev),
             torch.empty(B, W, dtype=torch.int32, device=dev), torch.empty(B, W, dtype=torch.uint8, device=dev))
         tr = rtr = table = None
@@ -699,6 +729,13 @@ class PARSeq(_NativeBacked):
             if roots is not None:
                 roots = roots.to(dev, torch.int32).contiguous()
             res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
+        if automaton is not None:
+            table, weight = automaton.table(dev)
+            if roots is not None:
+                roots = roots.to(dev, torch.int32).contiguous()
+            res.words = torch.empty(B, W, dtype=torch.int32, device=dev)
+            res.model_scores = torch.empty(B, W, dtype=torch.float32, device=dev)
+            res.priors = torch.empty(B, W, dtype=torch.float32, device=dev)
         if refine is not None:
             res.ar_scores = torch.empty(B, W, dtype=torch.float32, device=dev)
             if trace:
@@ -710,6 +747,10 @@ class PARSeq(_NativeBacked):
         if refine is not None:
             entry, ws = lib.parseq_forward_beam_refine, self._workspace(lib.parseq_beam_refine_workspace_bytes, plan, B, W, num_steps, int(table is not None))
             extra = lex_args + [BEAM_REFINE_MODES[refine], refine_iters, _native.ptr(res.ar_scores), C.byref(rtr) if rtr is not None else None]
+        elif automaton is not None:
+            entry, ws = lib.parseq_forward_beam_automaton, self._workspace(lib.parseq_beam_automaton_workspace_bytes, plan, B, W, num_steps)
+            extra = [_native.ptr(table), _native.ptr(weight), table.shape[0], _native.ptr(roots), float(alpha), float(beta), _native.ptr(res.words),
+                     _native.ptr(res.model_scores), _native.ptr(res.priors)]
         elif lexicon is not None:
             entry, ws, extra = lib.parseq_forward_beam_lexicon, self._workspace(lib.parseq_beam_lexicon_workspace_bytes, plan, B, W, num_steps), lex_args
         else:

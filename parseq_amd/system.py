@@ -250,12 +250,17 @@ class PARSeq(nn.Module):
         return self.model.forward(self.tokenizer, images, max_length, slot, return_length=True)
 
     def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None,
-                    refine: Optional[str] = None, refine_iters: int = 1):
+                    refine: Optional[str] = None, refine_iters: int = 1, automaton=None, alpha: float = 1.0, beta: float = 0.0):
         """The `beam_width` best readings of every crop with their log-probabilities (model.PARSeq.beam_search):
         a `BeamResult` on the device, `self.tokenizer.decode_beams(result)` turns it into strings.  With a `lexicon` (and per-crop `roots`,
         section 19) only words of the list are read; `self.tokenizer.decode_beams(result, lexicon)` returns them in the list's spelling.
         `refine='score'` / `'edit'` (section 20) refines every hypothesis with the model's cloze pass and ranks them again; `result.ar_scores`
-        keeps the search's own scores."""
+        keeps the search's own scores.  With an `automaton` (`parseq_amd.automaton.Automaton`, section 24: a weighted word list, a character
+        n-gram model or a pattern; it excludes `lexicon` and `refine`) the ranking is by the model's score plus `alpha` times the automaton's
+        weights plus `beta` per character; `result.scores` are those fused values, `result.model_scores` and `result.priors` their parts."""
+        if automaton is not None or alpha != 1.0 or beta != 0.0:
+            return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots, refine=refine,
+                                          refine_iters=refine_iters, automaton=automaton, alpha=alpha, beta=beta)
         if refine is not None or refine_iters != 1:
             return self.model.beam_search(self.tokenizer, images, beam_width, max_length, lexicon=lexicon, roots=roots, refine=refine,
                                           refine_iters=refine_iters)

@@ -145,7 +145,8 @@ class Tokenizer(BaseTokenizer):
         """The N-best of `beam_search` as strings: per image the hypotheses best first, each (label, log-probability).  Dead beams
         (fewer hypotheses than the beam width, score -inf) are left out.  One copy to the host.  With the `lexicon` the search ran under,
         a finished hypothesis comes back in the lexicon's spelling, `lexicon.words[word id]` (an unfinished one, a prefix of a word too
-        long for the steps that ran, as the characters read)."""
+        long for the steps that ran, as the characters read).  `lexicon` may be the `Automaton` the search ran over:
+        one with `words` is read the same way, one without (an n-gram model, a pattern) as the characters."""
         b, w, steps = result.tokens.shape
         parts = [result.tokens.reshape(b * w, steps), result.lengths.reshape(b * w, 1).to(torch.int32),
                  result.scores.reshape(b * w, 1).contiguous().view(torch.int32)]
@@ -159,7 +160,7 @@ class Tokenizer(BaseTokenizer):
         words = packed[:, steps + 2].tolist() if lexicon is not None else None
 
         def label(r):
-            if words is not None and words[r] >= 0:
+            if words is not None and words[r] >= 0 and lexicon.words is not None:      # (an automaton without words: tags, not word ids)
                 return lexicon.words[words[r]]
             return self._ids2tok(ids[r, :lengths[r]].tolist())
         out = []

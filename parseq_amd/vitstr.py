@@ -135,7 +135,7 @@ class ViTSTR(nn.Module):
         return self.model.forward_sliced(images, max_length + 1, slot)
 
     def beam_search(self, images: Tensor, beam_width: int, max_length: Optional[int] = None, lexicon=None, roots: Optional[Tensor] = None,
-                    refine: Optional[str] = None, refine_iters: int = 1):
+                    refine: Optional[str] = None, refine_iters: int = 1, automaton=None, alpha: float = 1.0, beta: float = 0.0):
         raise ValueError('beam_search: ViTSTR has no AR loop (every position is read in one pass); use a PARSeq model')
 
     def lexicon_match(self, images: Tensor, lexicon, n: int, lists=None, rescore: bool = True, keep_reading: bool = False, ignore_case: bool = False):

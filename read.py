@@ -6,6 +6,9 @@
     ./read.py pretrained=parseq --images a.png --nbest 5 [--beam 8]     the 5 best readings with their log-probabilities under each line
     ./read.py pretrained=parseq --images a.png --lexicon words.txt [--beam 8] [--nbest 3]     read only words of the list (one per line)
     ./read.py pretrained=parseq --images a.png --lexicon words.txt --match [8] [--nbest 3]     read freely, then choose among the list's 8 nearest words
+    ./read.py pretrained=parseq --images a.png --lexicon counts.txt --priors [--lm-weight 0.5]     the list's second column is a count: a prior over the words
+    ./read.py pretrained=parseq --images a.png --lm corpus.txt [--lm-order 3] [--lm-weight 0.3] [--char-bonus 0.5]     fuse a character n-gram model into the search
+    ./read.py pretrained=parseq --images a.png --pattern '[A-Z]{2}[0-9]{4}'     read only what the pattern matches
     ./read.py pretrained=parseq --images a.png --nbest 5 --refine-beams edit [--refine-iters 2]     refine every alternative, rank them again
     ./read.py pretrained=parseq --images a.png --boxes     a second line per image: every character with its box in the image's own pixels
     ./read.py pretrained=parseq --images scene.jpg --regions scene.txt [--boxes]     read every quadrilateral of the file (x1,y1,..,x4,y4 per line)
@@ -114,15 +117,19 @@ def load_region_batch(model, files, region_files, device='cuda'):
 
 @torch.inference_mode()
 def read_regions(model, files, region_files, beam=None, nbest=0, words=None, list_words=False, refine=None, refine_iters=1, boxes=False, device='cuda',
-                 match=None):
+                 match=None, prior=None):
     """The lines `--regions` prints, for the same flags as the whole-crop readings above, on the batch of `load_region_batch`: `words` is the
     list of --lexicon (its alternatives are listed only with `list_words`), `boxes` adds every character's quadrilateral in the scene, `match`
-    the N of --match."""
+    the N of --match, `prior` the (automaton, alpha, beta) of --priors / --lm / --pattern."""
     from parseq_amd.preprocess import map_to_source
     names, batch, back = load_region_batch(model, files, region_files, device)
     if not names:
         return []
     lines = []
+    if prior is not None:
+        for name, alts in zip(names, automaton_batch(model, batch, beam, *prior)):
+            lines += automaton_lines(name, alts[:nbest], list_words)
+        return lines
     if words is not None and match is not None:
         for name, alts in zip(names, match_batch(model, batch, words, match, device)):
             lines += match_lines(name, alts[:nbest], list_words)
@@ -158,6 +165,7 @@ def read_regions(model, files, region_files, beam=None, nbest=0, words=None, lis
 
 LEXICON_BEAM = 8      # --beam under --lexicon when none is given
 MATCH_N = 8           # --match without a number
+LM_ORDER = 3          # --lm without --lm-order
 
 
 def load_word_list(path):
@@ -182,6 +190,63 @@ def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, de
     search = {} if refine is None else {'refine': refine}
     beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width, lexicon=lexicon, **search), lexicon)
     return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
+
+
+def load_word_counts(path):
+    """(words, counts) of a lexicon file with priors: per non-empty line a word and, after white space, its count (a number, not negative)."""
+    words, counts = [], []
+    with open(path, encoding='utf-8') as fh:
+        for number, line in enumerate(fh, 1):
+            fields = line.split()
+            if not fields:
+                continue
+            try:
+                if len(fields) != 2 or not float(fields[1]) >= 0 or float(fields[1]) == float('inf'):
+                    raise ValueError
+            except ValueError:
+                raise ValueError(f'{path}, line {number}: expected a word and its count, got {line.strip()!r}') from None
+            words.append(fields[0])
+            counts.append(float(fields[1]))
+    return words, counts
+
+
+def build_automaton(model, kind, args):
+    """The automaton of --priors / --lm / --pattern for the model's charset, on the device."""
+    from parseq_amd.automaton import Automaton
+    if kind == 'priors':
+        automaton = Automaton.from_lexicon(*load_word_counts(args.lexicon), model.tokenizer, fold_case=True)
+    elif kind == 'lm':
+        with open(args.lm, encoding='utf-8') as fh:
+            texts = [line.rstrip('\r\n') for line in fh]
+            automaton = Automaton.ngram([t for t in texts if t.strip()], args.lm_order or LM_ORDER, model.tokenizer, fold_case=True)      # (blank lines separate, they are no empty sequences)
+    else:
+        automaton = Automaton.pattern(args.pattern, model.tokenizer)
+    return automaton.to(args.device)
+
+
+def automaton_batch(model, batch, beam_width, automaton, alpha, beta):
+    """Per crop of `batch` [(label, fused score, model log-probability, prior)] best first: one beam search over `automaton`."""
+    result = model.beam_search(batch, beam_width, automaton=automaton, alpha=alpha, beta=beta)
+    beams = model.tokenizer.decode_beams(result, automaton)
+    parts = torch.stack([result.model_scores, result.priors], -1).cpu().tolist()
+    return [[(label, f, m, p) for (label, f), (m, p) in zip(alts, rows)] for alts, rows in zip(beams, parts)]      # dead beams come last in both
+
+
+def automaton_lines(name, alts, list_all):
+    """What a search over an automaton prints for one image: the best reading; with --nbest the alternatives — fused score, the model's
+    log-probability and the prior first."""
+    lines = [f'{name}: {alts[0][0] if alts else ""}']
+    return lines + [f'    {f:9.4f}  lp={m:9.4f} prior={p:9.4f}  {label}' for label, f, m, p in (alts if list_all else [])]
+
+
+@torch.inference_mode()
+def read_files_automaton(model, files, automaton, beam_width=8, alpha=1.0, beta=0.0, device='cuda'):
+    """[(file, [(label, fused score, model log-probability, prior)] best first)] for image files: one batched search over `automaton`."""
+    import numpy as np
+    crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+    if not crops:
+        return []
+    return list(zip(files, automaton_batch(model, resize_batch(crops, tuple(model.hparams.img_size)), beam_width, automaton, alpha, beta)))
 
 
 def match_batch(model, batch, words, n, device='cuda'):
@@ -234,6 +299,18 @@ def build_parser():
                         help='One file of quadrilaterals per image, in order (ICDAR-2015 style: x1,y1,x2,y2,x3,y3,x4,y4[,text] per line, clockwise '
                              "from the text's top-left): read every region of the scene, printed as image#k; with --boxes every character's "
                              "quadrilateral in the scene's pixels")
+    parser.add_argument('--priors', action='store_true',
+                        help='With --lexicon: the list has a second white-space separated column, a count; the words are then a prior (their smoothed '
+                             'relative frequencies enter the ranking), not only a constraint')
+    parser.add_argument('--lm', default=None, metavar='FILE',
+                        help='Fuse a character n-gram model counted from this text file (one sequence per line, blank lines skipped) into a beam search (open vocabulary)')
+    parser.add_argument('--lm-order', type=int, default=None, dest='lm_order', metavar='N', help=f'Order of --lm, 1 to 4 (default {LM_ORDER})')
+    parser.add_argument('--pattern', default=None, metavar='REGEX',
+                        help='Read only what fully matches this regular expression (literals, ., [...], \\d, \\w, groups, |, ? * + {m} {m,n})')
+    parser.add_argument('--lm-weight', type=float, default=None, dest='lm_weight', metavar='A',
+                        help='Weight of the prior of --priors / --lm / --pattern in the ranking (default 1)')
+    parser.add_argument('--char-bonus', type=float, default=None, dest='char_bonus', metavar='B',
+                        help='Added to the ranking per character read, with --priors / --lm / --pattern (default 0)')
     parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
     return parser
 
@@ -273,9 +350,39 @@ def resolve_match(parser, args):
     return args.match
 
 
+def resolve_automaton(parser, args):
+    """(kind, alpha, beta) of the weighted automaton the flags ask for — 'priors', 'lm' or 'pattern', None for none; a contradiction ends in
+    parser.error."""
+    import math
+    kinds = [k for k, on in (('priors', args.priors), ('lm', args.lm is not None), ('pattern', args.pattern is not None)) if on]
+    if len(kinds) > 1:
+        parser.error('--priors, --lm and --pattern are one automaton each: give one of them')
+    if args.priors and args.lexicon is None:
+        parser.error('--priors needs --lexicon FILE')
+    if args.lm_order is not None and args.lm is None:
+        parser.error('--lm-order needs --lm FILE')
+    if args.lm_order is not None and not 1 <= args.lm_order <= 4:
+        parser.error('--lm-order must be in [1, 4]')
+    if not kinds:
+        if args.lm_weight is not None or args.char_bonus is not None:
+            parser.error('--lm-weight and --char-bonus need --priors, --lm or --pattern')
+        return None, 1.0, 0.0
+    if args.lexicon is not None and not args.priors:
+        parser.error(f'--{kinds[0]} with --lexicon: the search walks one table (--lexicon FILE --priors makes the list the prior)')
+    if args.refine_beams is not None or args.match is not None:
+        parser.error(f'--{kinds[0]} with --refine-beams or --match: refinement under a weighted automaton is not defined')
+    if args.boxes:
+        parser.error(f'--{kinds[0]} is a beam search: not with --boxes')
+    alpha = 1.0 if args.lm_weight is None else args.lm_weight
+    beta = 0.0 if args.char_bonus is None else args.char_bonus
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        parser.error('--lm-weight and --char-bonus must be finite')
+    return kinds[0], alpha, beta
+
+
 def resolve_search(parser, args):
     """(beam width, N) of the search the flags ask for, (None, 0) for none; a contradiction ends in parser.error."""
-    if args.lexicon is not None:
+    if args.lexicon is not None or args.lm is not None or args.pattern is not None:
         nbest = args.nbest if args.nbest > 0 else 1
         beam = args.beam if args.beam is not None else max(LEXICON_BEAM, nbest)
         if beam < nbest:
@@ -294,6 +401,7 @@ def main(argv=None):
 
     if args.boxes and (args.nbest > 0 or args.lexicon is not None):
         parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
+    kind, alpha, beta = resolve_automaton(parser, args)
     match = resolve_match(parser, args)
     beam, nbest = resolve_search(parser, args)
     refine, refine_iters = resolve_refine(parser, args)
@@ -301,6 +409,16 @@ def main(argv=None):
     if args.regions is not None and len(args.regions) != len(files):
         parser.error(f'--regions takes one file per image, in order: {len(args.regions)} files for {len(files)} images')
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
+    if kind is not None:
+        automaton = build_automaton(model, kind, args)
+        if args.regions is not None:
+            lines = read_regions(model, files, args.regions, beam, nbest, list_words=args.nbest > 0, device=args.device, prior=(automaton, alpha, beta))
+        else:
+            lines = [line for fname, alts in read_files_automaton(model, files, automaton, beam, alpha, beta, args.device)
+                     for line in automaton_lines(fname, alts[:nbest], args.nbest > 0)]
+        for line in lines:
+            print(line)
+        return
     if args.regions is not None:
         words = load_word_list(args.lexicon) if args.lexicon is not None else None
         for line in read_regions(model, files, args.regions, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device, match):
