@@ -605,6 +605,49 @@ int parseq_rectify(const parseq_image_desc* images, int n_images, const parseq_r
 int parseq_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions,
                                   int out_h, int out_w, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- rectification of polygon text regions -------------------------------------------------- */
+
+/* The same step for a detector of curved text: a region is a row of strips side by side, each a box (x0, 0, x1, height) of the output
+ * painted through a bilinear map of one source quadrilateral.  The result is, byte for byte,
+ * Image.fromarray(src).transform((width, height), Image.MESH, [((x0, 0, x1, height), quad), ...], Image.BICUBIC) with fill 0: for output
+ * pixel (x, y) of the strip with x0 <= x < x1, X = (x - x0) + 0.5, Y = y + 0.5, in double precision without contraction, left to right,
+ *     sx = coef[0] + coef[1] X + coef[2] Y + coef[3] X Y,   sy = coef[4] + coef[5] X + coef[6] Y + coef[7] X Y;
+ * the inside test and the bicubic filter are those of parseq_rectify above.  The library does no geometry: coef is what Pillow derives
+ * for QUAD from the strip's box and quadrilateral (parseq_amd/preprocess.py polygon_mesh).  Came after ABI 15 without a new version: pure
+ * additions.  Refused with PARSEQ_E_INVALID before any device work, outputs untouched: everything parseq_rectify refuses about images,
+ * sizes and the workspace; a coefficient that is not finite; a region with fewer than 1 or more than PARSEQ_MESH_MAX_STRIPS strips; a
+ * strip range [first_strip, first_strip + n_strips) outside the strips array; strips that do not tile [0, width) in order without gap
+ * or overlap (the first x0 is 0, every x1 > x0, every next x0 the previous x1, the last x1 the width). */
+#define PARSEQ_MESH_MAX_STRIPS 64
+
+typedef struct {
+    int32_t x0, x1;                   /* the strip's output columns x0 .. x1 - 1 */
+    double coef[8];
+} parseq_mesh_strip;
+
+typedef struct {
+    int32_t image;                    /* index into the call's images */
+    int32_t height, width;            /* of the rectified region */
+    int32_t first_strip, n_strips;    /* its strips in the call's strips array, left to right */
+} parseq_mesh_region_desc;
+
+/* Bytes of workspace the two calls below need: what parseq_rectify_workspace_bytes counts, and the device copy of the n_strips strips.
+ * 0 if a region's size is out of range (parseq_last_error says why). */
+size_t parseq_mesh_rectify_workspace_bytes(const parseq_mesh_region_desc* regions, int n_regions, const parseq_mesh_strip* strips, int n_strips,
+                                           int n_images);
+
+/* parseq_rectify for strips: region i written to outs[i] as uint8 [height_i, width_i, 3], dense, one launch for all regions.  images,
+ * regions, strips and outs are HOST arrays copied on `stream`: keep them alive until the stream has passed.  No allocation, no
+ * synchronisation inside. */
+int parseq_mesh_rectify(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n_regions,
+                        const parseq_mesh_strip* strips, int n_strips, uint8_t* const* outs, void* workspace, size_t workspace_bytes, void* stream);
+
+/* parseq_mesh_rectify into the workspace's slots, then parseq_resize_bicubic's arithmetic (the same kernel): out = device uint8
+ * [n_regions, 3, out_h, out_w]. */
+int parseq_mesh_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n_regions,
+                                       const parseq_mesh_strip* strips, int n_strips, int out_h, int out_w, uint8_t* out, void* workspace,
+                                       size_t workspace_bytes, void* stream);
+
 /* ---- post-processing --------------------------------------------------------------- */
 
 /* Numeric half of `preds, probs = tokenizer.decode(logits.softmax(-1))` (strhub/models/base.py:132-137,

@@ -41,6 +41,19 @@ class RegionDesc(C.Structure):
     _fields_ = [('image', C.c_int32), ('height', C.c_int32), ('width', C.c_int32), ('coef', C.c_double * 8)]
 
 
+MESH_MAX_STRIPS = 64      # PARSEQ_MESH_MAX_STRIPS
+
+
+class MeshStrip(C.Structure):
+    """parseq_mesh_strip: the output columns x0 .. x1 - 1 of a region and the QUAD data Pillow derives for them (parseq_amd/preprocess.py polygon_mesh)."""
+    _fields_ = [('x0', C.c_int32), ('x1', C.c_int32), ('coef', C.c_double * 8)]
+
+
+class MeshRegionDesc(C.Structure):
+    """parseq_mesh_region_desc: a source image's index, the rectified size and the region's run of strips in the call's strips array."""
+    _fields_ = [('image', C.c_int32), ('height', C.c_int32), ('width', C.c_int32), ('first_strip', C.c_int32), ('n_strips', C.c_int32)]
+
+
 class AugmentBlur(C.Structure):
     """arg.blur of PARSEQ_AUG_GAUSSIAN_BLUR: one box pass (parseq_amd/augment.py gaussian_box)."""
     _fields_ = [('r', C.c_int32), ('ww', C.c_uint32), ('fw', C.c_uint32)]
@@ -136,6 +149,11 @@ SIGNATURES = {
     'parseq_rectify': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(RegionDesc), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_rectify_resize_bicubic': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(RegionDesc), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_size_t, C.c_void_p]),
+    'parseq_mesh_rectify_workspace_bytes': (C.c_size_t, [C.POINTER(MeshRegionDesc), C.c_int, C.POINTER(MeshStrip), C.c_int, C.c_int]),
+    'parseq_mesh_rectify': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(MeshRegionDesc), C.c_int, C.POINTER(MeshStrip), C.c_int, C.POINTER(C.c_void_p),
+                                      C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_mesh_rectify_resize_bicubic': (C.c_int, [C.POINTER(ImageDesc), C.c_int, C.POINTER(MeshRegionDesc), C.c_int, C.POINTER(MeshStrip), C.c_int, C.c_int,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_cross_entropy': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_eval_metrics': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -341,7 +359,7 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def guard(device):
     """Context manager making `device` (torch.device or tensor) current: for the raw-pointer entry points (parseq_op_*,
-    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_rectify, parseq_rectify_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
+    parseq_postprocess, parseq_eval_metrics, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_rectify, parseq_rectify_resize_bicubic, parseq_mesh_rectify, parseq_mesh_rectify_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
     import torch
     if hasattr(device, 'device'):
         device = device.device

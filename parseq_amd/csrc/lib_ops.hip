@@ -1,7 +1,7 @@
 // libparseq_hip.so — input resize, post-process, and the per-kernel entry points the parity tests call.
 #include "lib_internal.h"
 #include "eval_metrics.h"
-#include "rectify.h"
+#include "rectify_mesh.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 static int resize_taps(int in_size, int out_size) {
@@ -256,19 +256,23 @@ extern "C" int parseq_op_augment(const parseq_augment_desc* desc, uint8_t* out, 
 static_assert(sizeof(parseq_region_desc) == sizeof(RegionDesc) && offsetof(parseq_region_desc, coef) == offsetof(RegionDesc, coef) &&
               offsetof(parseq_region_desc, width) == offsetof(RegionDesc, width), "descriptor layouts must match");
 
-struct RectLayout { size_t regions, images, tiles, dst, finals, outs, slots, total; long long n_tiles; };
+// `strips`: the strip table of polygon regions (rectify_mesh.h), empty for quadrilaterals
+struct RectLayout { size_t regions, strips, images, tiles, dst, finals, outs, slots, total; long long n_tiles; };
 
-static int check_region_size(const parseq_region_desc& r, int i) {
+template <class Region>
+static int check_region_size(const Region& r, int i) {
     if (!aug_side_ok(r.height) || !aug_side_ok(r.width))
         return fail(PARSEQ_E_INVALID, "region %d: size %dx%d, each side must be in 1 .. %d", i, r.height, r.width, PARSEQ_ROTATE_MAX_SIDE);
     return 0;
 }
 
 // sizes only: what parseq_rectify_workspace_bytes can know
-static RectLayout rect_layout(const parseq_region_desc* regions, int n, int n_images) {
+template <class Region>
+static RectLayout rect_layout(const Region* regions, int n, int n_images, int n_strips = 0) {
     RectLayout l;
     l.regions = 0;
-    l.images = l.regions + aug_align((size_t)n * sizeof(RegionDesc));
+    l.strips = l.regions + aug_align((size_t)n * sizeof(Region));
+    l.images = l.strips + aug_align((size_t)n_strips * sizeof(MeshStrip));
     l.tiles = l.images + aug_align((size_t)n_images * sizeof(ImageDesc));
     l.dst = l.tiles + aug_align((size_t)(n + 1) * sizeof(int));
     l.finals = l.dst + aug_align((size_t)n * sizeof(unsigned char*));
@@ -290,9 +294,8 @@ extern "C" size_t parseq_rectify_workspace_bytes(const parseq_region_desc* regio
     return rect_layout(regions, n_regions, n_images).total;
 }
 
-static int check_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n) {
-    if (!images || !regions) return fail(PARSEQ_E_INVALID, "null images / regions");
-    if (n_images <= 0 || n <= 0) return fail(PARSEQ_E_INVALID, "bad shape: %d images, %d regions", n_images, n);
+// the source images of a rectification, quadrilaterals or strips
+static int check_rect_images(const parseq_image_desc* images, int n_images) {
     for (int i = 0; i < n_images; ++i) {
         const parseq_image_desc& d = images[i];
         if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
@@ -300,6 +303,13 @@ static int check_rectify(const parseq_image_desc* images, int n_images, const pa
         if (d.row_stride > INT32_MAX / d.height)
             return fail(PARSEQ_E_INVALID, "image %d: %d rows of %lld bytes do not fit 31 bits", i, d.height, (long long)d.row_stride);
     }
+    return 0;
+}
+
+static int check_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n) {
+    if (!images || !regions) return fail(PARSEQ_E_INVALID, "null images / regions");
+    if (n_images <= 0 || n <= 0) return fail(PARSEQ_E_INVALID, "bad shape: %d images, %d regions", n_images, n);
+    CHK(check_rect_images(images, n_images));
     for (int i = 0; i < n; ++i) {
         const parseq_region_desc& r = regions[i];
         if (r.image < 0 || r.image >= n_images) return fail(PARSEQ_E_INVALID, "region %d: image index %d is outside 0 .. %d", i, r.image, n_images - 1);
@@ -338,7 +348,7 @@ static int rectify_run(const parseq_image_desc* images, int n_images, const pars
         douts = reinterpret_cast<unsigned char**>(ws + l.outs);
         HIPCHK(hipMemcpyAsync(douts, outs, (size_t)n * sizeof(unsigned char*), hipMemcpyHostToDevice, s));
     }
-    hipLaunchKernelGGL(rectify_plan_kernel, dim3(1), dim3(256), 0, s, rr, n, douts, ws + l.slots, tile_start, dst, reinterpret_cast<ImageDesc*>(ws + l.finals));
+    hipLaunchKernelGGL(rectify_plan_kernel<RegionDesc>, dim3(1), dim3(256), 0, s, rr, n, douts, ws + l.slots, tile_start, dst, reinterpret_cast<ImageDesc*>(ws + l.finals));
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(rectify_kernel, dim3((unsigned)l.n_tiles), dim3(256), 0, s, ii, n_images, rr, n, tile_start, dst);
     HIPCHK(hipGetLastError());
@@ -357,26 +367,144 @@ extern "C" int parseq_rectify(const parseq_image_desc* images, int n_images, con
     return rectify_run(images, n_images, regions, n_regions, outs, workspace, workspace_bytes, (hipStream_t)stream, &l);
 }
 
+// the resize behind a rectification: the taps and the LDS its regions need (before any device work), then resize_bicubic_kernel on the
+// ImageDesc array the plan kernel wrote
+struct RectResize { int ksh, ksv; size_t lds; };
+
+template <class Region>
+static int rect_resize_plan(const Region* regions, int n, int out_h, int out_w, RectResize* z) {
+    z->ksh = z->ksv = 1;
+    for (int i = 0; i < n; ++i) {
+        z->ksh = std::max(z->ksh, resize_taps(regions[i].width, out_w));
+        z->ksv = std::max(z->ksv, resize_taps(regions[i].height, out_h));
+    }
+    z->lds = sizeof(int) * ((size_t)out_w * z->ksh + (size_t)out_h * z->ksv + 2 * (size_t)(out_w + out_h));
+    if (z->lds > 150 * 1024)
+        return fail(PARSEQ_E_INVALID, "a rectified region is too large for the on-chip weight tables (%zu bytes of LDS needed)", z->lds);
+    return 0;
+}
+
+static int rect_resize_run(const unsigned char* finals, int n, const RectResize& z, int out_h, int out_w, uint8_t* out, hipStream_t s) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)z.lds));
+    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(n), dim3(256), z.lds, s, reinterpret_cast<const ImageDesc*>(finals), out_h, out_w, z.ksh, z.ksv, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int parseq_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions,
                                              int out_h, int out_w, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
     if (!out) return fail(PARSEQ_E_INVALID, "null out");
     if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
     CHK(check_rectify(images, n_images, regions, n_regions));
-    int ksh = 1, ksv = 1;
-    for (int i = 0; i < n_regions; ++i) {
-        ksh = std::max(ksh, resize_taps(regions[i].width, out_w));
-        ksv = std::max(ksv, resize_taps(regions[i].height, out_h));
-    }
-    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
-    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "a rectified region is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
+    RectResize z;
+    CHK(rect_resize_plan(regions, n_regions, out_h, out_w, &z));
     hipStream_t s = (hipStream_t)stream;
     RectLayout l;
     CHK(rectify_run(images, n_images, regions, n_regions, nullptr, workspace, workspace_bytes, s, &l));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(n_regions), dim3(256), lds, s,
-                       reinterpret_cast<const ImageDesc*>(static_cast<unsigned char*>(workspace) + l.finals), out_h, out_w, ksh, ksv, out);
-    HIPCHK(hipGetLastError());
+    return rect_resize_run(static_cast<unsigned char*>(workspace) + l.finals, n_regions, z, out_h, out_w, out, s);
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// rectification of polygon regions as strips (rectify_mesh.h): the same plan, workspace and resize, one more table
+// -------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(parseq_mesh_strip) == sizeof(MeshStrip) && offsetof(parseq_mesh_strip, coef) == offsetof(MeshStrip, coef) &&
+              sizeof(parseq_mesh_region_desc) == sizeof(MeshRegionDesc) && offsetof(parseq_mesh_region_desc, n_strips) == offsetof(MeshRegionDesc, n_strips) &&
+              PARSEQ_MESH_MAX_STRIPS == MESH_MAX_STRIPS, "descriptor layouts must match");
+
+extern "C" size_t parseq_mesh_rectify_workspace_bytes(const parseq_mesh_region_desc* regions, int n_regions, const parseq_mesh_strip* strips, int n_strips,
+                                                      int n_images) {
+    if (!regions || !strips || n_regions <= 0 || n_strips <= 0 || n_images <= 0) {
+        fail(PARSEQ_E_INVALID, "null regions / strips / %d regions / %d strips / %d images", n_regions, n_strips, n_images);
+        return 0;
+    }
+    for (int i = 0; i < n_regions; ++i)
+        if (check_region_size(regions[i], i)) return 0;
+    return rect_layout(regions, n_regions, n_images, n_strips).total;
+}
+
+static int check_mesh(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n, const parseq_mesh_strip* strips,
+                      int n_strips) {
+    if (!images || !regions || !strips) return fail(PARSEQ_E_INVALID, "null images / regions / strips");
+    if (n_images <= 0 || n <= 0 || n_strips <= 0) return fail(PARSEQ_E_INVALID, "bad shape: %d images, %d regions, %d strips", n_images, n, n_strips);
+    CHK(check_rect_images(images, n_images));
+    for (int i = 0; i < n; ++i) {
+        const parseq_mesh_region_desc& r = regions[i];
+        if (r.image < 0 || r.image >= n_images) return fail(PARSEQ_E_INVALID, "region %d: image index %d is outside 0 .. %d", i, r.image, n_images - 1);
+        CHK(check_region_size(r, i));
+        if (r.n_strips < 1 || r.n_strips > PARSEQ_MESH_MAX_STRIPS)
+            return fail(PARSEQ_E_INVALID, "region %d: %d strips, a region has 1 .. %d", i, r.n_strips, PARSEQ_MESH_MAX_STRIPS);
+        if (r.first_strip < 0 || r.first_strip > n_strips - r.n_strips)
+            return fail(PARSEQ_E_INVALID, "region %d: strips %d .. %d are outside the strips array of %d", i, r.first_strip, r.first_strip + r.n_strips - 1, n_strips);
+        int at = 0;
+        for (int k = 0; k < r.n_strips; ++k) {
+            const parseq_mesh_strip& s = strips[r.first_strip + k];
+            if (s.x0 != at || s.x1 <= s.x0 || s.x1 > r.width)
+                return fail(PARSEQ_E_INVALID, "region %d: strip %d covers columns %d .. %d where %d begins: the strips must tile 0 .. %d in order", i, k, s.x0,
+                            s.x1, at, r.width);
+            at = s.x1;
+            for (int t = 0; t < 8; ++t)
+                if (!std::isfinite(s.coef[t])) return fail(PARSEQ_E_INVALID, "region %d: strip %d: coefficient %d is not finite", i, k, t);
+        }
+        if (at != r.width) return fail(PARSEQ_E_INVALID, "region %d: the strips end at column %d: they must tile 0 .. %d", i, at, r.width);
+    }
     return 0;
+}
+
+// rectify_run with the strip table: ONE launch for all regions after the plan
+static int mesh_run(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n, const parseq_mesh_strip* strips, int n_strips,
+                    uint8_t* const* outs, void* workspace, size_t workspace_bytes, hipStream_t s, RectLayout* layout) {
+    if (!workspace) return fail(PARSEQ_E_INVALID, "null workspace");
+    const RectLayout l = rect_layout(regions, n, n_images, n_strips);
+    if (workspace_bytes < l.total)
+        return fail(PARSEQ_E_INVALID, "workspace of %zu bytes, %zu needed (parseq_mesh_rectify_workspace_bytes)", workspace_bytes, l.total);
+    if (l.n_tiles > RECT_MAX_TILES)
+        return fail(PARSEQ_E_INVALID, "%lld tiles of %dx%d pixels in one call, at most %d", l.n_tiles, RECT_TILE, RECT_TILE, RECT_MAX_TILES);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    const MeshRegionDesc* rr = reinterpret_cast<const MeshRegionDesc*>(ws + l.regions);
+    const MeshStrip* ss = reinterpret_cast<const MeshStrip*>(ws + l.strips);
+    const ImageDesc* ii = reinterpret_cast<const ImageDesc*>(ws + l.images);
+    int* tile_start = reinterpret_cast<int*>(ws + l.tiles);
+    unsigned char** dst = reinterpret_cast<unsigned char**>(ws + l.dst);
+    unsigned char** douts = nullptr;
+    HIPCHK(hipMemcpyAsync(ws + l.regions, regions, (size_t)n * sizeof(MeshRegionDesc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ws + l.strips, strips, (size_t)n_strips * sizeof(MeshStrip), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ws + l.images, images, (size_t)n_images * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
+    if (outs) {
+        douts = reinterpret_cast<unsigned char**>(ws + l.outs);
+        HIPCHK(hipMemcpyAsync(douts, outs, (size_t)n * sizeof(unsigned char*), hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(rectify_plan_kernel<MeshRegionDesc>, dim3(1), dim3(256), 0, s, rr, n, douts, ws + l.slots, tile_start, dst,
+                       reinterpret_cast<ImageDesc*>(ws + l.finals));
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mesh_rectify_kernel, dim3((unsigned)l.n_tiles), dim3(256), 0, s, ii, n_images, rr, n, ss, tile_start, dst);
+    HIPCHK(hipGetLastError());
+    *layout = l;
+    return 0;
+}
+
+extern "C" int parseq_mesh_rectify(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n_regions,
+                                   const parseq_mesh_strip* strips, int n_strips, uint8_t* const* outs, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    CHK(check_mesh(images, n_images, regions, n_regions, strips, n_strips));
+    if (!outs) return fail(PARSEQ_E_INVALID, "null outs");
+    for (int i = 0; i < n_regions; ++i)
+        if (!outs[i]) return fail(PARSEQ_E_INVALID, "region %d: null output", i);
+    RectLayout l;
+    return mesh_run(images, n_images, regions, n_regions, strips, n_strips, outs, workspace, workspace_bytes, (hipStream_t)stream, &l);
+}
+
+extern "C" int parseq_mesh_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n_regions,
+                                                  const parseq_mesh_strip* strips, int n_strips, int out_h, int out_w, uint8_t* out, void* workspace,
+                                                  size_t workspace_bytes, void* stream) {
+    if (!out) return fail(PARSEQ_E_INVALID, "null out");
+    if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
+    CHK(check_mesh(images, n_images, regions, n_regions, strips, n_strips));
+    RectResize z;
+    CHK(rect_resize_plan(regions, n_regions, out_h, out_w, &z));
+    hipStream_t s = (hipStream_t)stream;
+    RectLayout l;
+    CHK(mesh_run(images, n_images, regions, n_regions, strips, n_strips, nullptr, workspace, workspace_bytes, s, &l));
+    return rect_resize_run(static_cast<unsigned char*>(workspace) + l.finals, n_regions, z, out_h, out_w, out, s);
 }
 
 // -------------------------------------------------------------------------------------------------------------------

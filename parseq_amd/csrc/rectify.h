@@ -34,9 +34,11 @@ __host__ __device__ inline int rect_tiles(int h, int w) { return ((h + RECT_TILE
 __host__ __device__ inline size_t rect_slot_bytes(int h, int w) { return ((size_t)h * (size_t)w * 3 + 255) & ~(size_t)255; }
 
 // tile_start[i] = first tile of region i (tile_start[n] = all tiles); dst[i] = where region i is written: outs[i] if the caller brought
-// buffers, else its slot; finals[i] = the rectified region as an image for the resize.
+// buffers, else its slot; finals[i] = the rectified region as an image for the resize.  Region is any descriptor with a height and a width
+// (RegionDesc here, MeshRegionDesc in rectify_mesh.h).
+template <class Region>
 static __global__ __launch_bounds__(256)
-void rectify_plan_kernel(const RegionDesc* __restrict__ regions, int n, unsigned char* const* __restrict__ outs, unsigned char* slots,
+void rectify_plan_kernel(const Region* __restrict__ regions, int n, unsigned char* const* __restrict__ outs, unsigned char* slots,
                          int* __restrict__ tile_start, unsigned char** __restrict__ dst, ImageDesc* __restrict__ finals) {
     __shared__ int st[256];
     __shared__ unsigned long long sb[256];
@@ -71,18 +73,24 @@ void rectify_plan_kernel(const RegionDesc* __restrict__ regions, int n, unsigned
     if (tid == 0) tile_start[n] = tiles_before;
 }
 
-// one output pixel of Image.transform(PERSPECTIVE, BICUBIC): false where the fill stays
-__device__ __forceinline__ bool rect_pixel(const unsigned char* src, long long stride, int h, int w, const double* a, int x, int y, unsigned char* out) {
+// the tail every Image.transform map shares: the inside test and the bicubic taps around the source position (sx, sy); false where the fill stays
+__device__ __forceinline__ bool rect_sample(const unsigned char* src, long long stride, int h, int w, double sx, double sy, unsigned char* out) {
     AUG_NO_CONTRACT
-    const double xin = (double)x + 0.5, yin = (double)y + 0.5;
-    const double den = AUG_ADD(AUG_ADD(AUG_MUL(a[6], xin), AUG_MUL(a[7], yin)), 1.0);
-    double sx = AUG_DIV(AUG_ADD(AUG_ADD(AUG_MUL(a[0], xin), AUG_MUL(a[1], yin)), a[2]), den);
-    double sy = AUG_DIV(AUG_ADD(AUG_ADD(AUG_MUL(a[3], xin), AUG_MUL(a[4], yin)), a[5]), den);
     if (!(sx >= 0.0 && sx < (double)w && sy >= 0.0 && sy < (double)h)) return false;
     sx = AUG_ADD(sx, -0.5); sy = AUG_ADD(sy, -0.5);
     const int fx = (int)floor(sx), fy = (int)floor(sy);
     aug_bicubic_taps(src, stride, h, w, fx, fy, AUG_ADD(sx, -(double)fx), AUG_ADD(sy, -(double)fy), out);
     return true;
+}
+
+// one output pixel of Image.transform(PERSPECTIVE, BICUBIC): false where the fill stays
+__device__ __forceinline__ bool rect_pixel(const unsigned char* src, long long stride, int h, int w, const double* a, int x, int y, unsigned char* out) {
+    AUG_NO_CONTRACT
+    const double xin = (double)x + 0.5, yin = (double)y + 0.5;
+    const double den = AUG_ADD(AUG_ADD(AUG_MUL(a[6], xin), AUG_MUL(a[7], yin)), 1.0);
+    const double sx = AUG_DIV(AUG_ADD(AUG_ADD(AUG_MUL(a[0], xin), AUG_MUL(a[1], yin)), a[2]), den);
+    const double sy = AUG_DIV(AUG_ADD(AUG_ADD(AUG_MUL(a[3], xin), AUG_MUL(a[4], yin)), a[5]), den);
+    return rect_sample(src, stride, h, w, sx, sy, out);
 }
 
 // grid = tile_start[n] workgroups.  Region i is written HWC, tight, at dst[i].

@@ -10,6 +10,10 @@ map as six 16.16 fixed-point integers, from the same float64 expressions Pillow 
 `rectify_resize_batch` is the step in front of all that for a caller with a text detector: quadrilateral regions
 of full scenes, straightened as Pillow's Image.transform(PERSPECTIVE, BICUBIC) straightens them and resized, in one library call on
 scenes that were uploaded once.  `region_size`, `quad_coeffs` and `map_to_source` are its host geometry, in float64.
+
+`mesh_rectify_resize_batch` is the same step for a detector of curved text: polygons of 2N points, straightened
+strip by strip as Pillow's Image.transform(MESH, BICUBIC) straightens them.  `polygon_size`, `polygon_mesh` and `mesh_to_source` are its
+host geometry.
 """
 from __future__ import annotations
 
@@ -258,11 +262,16 @@ def region_descs(regions, sizes=None, n_images=None):
     return out
 
 
-def _native_regions(keep, described):
+def _image_descs(keep):
     images = (_native.ImageDesc * len(keep))()
     for d, im in zip(images, keep):
         d.data = im.data_ptr()
         d.height, d.width, d.row_stride = im.shape[0], im.shape[1], im.stride(0)
+    return images
+
+
+def _native_regions(keep, described):
+    images = _image_descs(keep)
     regions = (_native.RegionDesc * len(described))()
     for d, (index, (h, w), coeffs) in zip(regions, described):
         d.image, d.height, d.width = index, h, w
@@ -319,5 +328,221 @@ def rectify_resize_batch(images: Sequence[Tensor], regions, size=(32, 128), size
     with _native.guard(dev):
         _native.check(lib.parseq_rectify_resize_bicubic(image_descs, len(keep), region_array, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), need,
                                                         _native.stream_ptr(dev)))
+    torch.cuda.current_stream(dev).synchronize()
+    return out
+
+
+# ---- polygon regions of a scene --------------------------------------------------------------------------------
+# A polygon is 2N points (x, y), N >= 2, clockwise from the TEXT's own top-left as above: top[0 .. N-1] left to right, then
+# bottom[N-1 .. 0] right to left — what a detector of curved text returns.  It is N - 1 quadrilaterals side by side, each painted into its
+# own strip of output columns through Pillow's bilinear QUAD map: Image.transform(size, Image.MESH, ...).  The rungs top[i] - bottom[i]
+# are shared by neighbouring strips, so the map is continuous across the seams.  A 4-point polygon is a one-strip mesh: a BILINEAR map
+# of the quadrilateral, not section 22's projective one — the two differ on a trapezoid by design.
+MESH_MAX_STRIPS = _native.MESH_MAX_STRIPS          # PARSEQ_MESH_MAX_STRIPS
+
+
+def _polygon_sides(polygon):
+    """(top, bottom), both left to right, as float pairs; ValueError for an odd number of points, fewer than four, or a value not finite."""
+    pts = [(float(x), float(y)) for x, y in polygon]
+    if len(pts) < 4 or len(pts) % 2:
+        raise ValueError(f'a polygon has an even number of points, at least 4 (N along the top, N back along the bottom), got {len(pts)}')
+    if not all(math.isfinite(v) for p in pts for v in p):
+        raise ValueError(f'polygon {pts} is not finite')
+    n = len(pts) // 2
+    return pts[:n], pts[:n - 1:-1]
+
+
+def _dist(p, q):
+    return math.hypot(q[0] - p[0], q[1] - p[1])
+
+
+def polygon_size(polygon, max_side: int = REGION_MAX_SIDE):
+    """(h, w) of the rectified crop of `polygon`: w the longer of its top and bottom polylines, h its longest rung |top[i] - bottom[i]|,
+    rounded half up, each clamped to 1 .. max_side (the rule of `region_size`)."""
+    top, bottom = _polygon_sides(polygon)
+    along = max(sum(_dist(side[i], side[i + 1]) for i in range(len(side) - 1)) for side in (top, bottom))
+    w = math.floor(along + 0.5)
+    h = math.floor(max(_dist(t, b) for t, b in zip(top, bottom)) + 0.5)
+    return min(max(h, 1), max_side), min(max(w, 1), max_side)
+
+
+def quad_strip_coeffs(x0: int, x1: int, h: int, nw, sw, se, ne):
+    """What Pillow's Image.__transformer derives for QUAD from the box (x0, 0, x1, h) and the corners NW, SW, SE, NE, in its own
+    expression order (the stored bytes depend on the last bit of these numbers)."""
+    x0s, y0s = nw
+    As = 1.0 / (x1 - x0)
+    At = 1.0 / h
+    return (x0s, (ne[0] - x0s) * As, (sw[0] - x0s) * At, (se[0] - sw[0] - ne[0] + x0s) * As * At,
+            y0s, (ne[1] - y0s) * As, (sw[1] - y0s) * At, (se[1] - sw[1] - ne[1] + y0s) * As * At)
+
+
+def polygon_mesh(polygon, h: int, w: int):
+    """The strips [(x0, x1, coef8)] of `polygon` in an output of h x w.  Segment i weighs the mean length of top[i] -> top[i+1] and
+    bottom[i] -> bottom[i+1]; the cuts are cut[0] = 0, cut[N-1] = w and floor(cum_i / total * w + 0.5) in between; a segment whose cuts
+    coincide yields no strip, so the strips tile [0, w) exactly, each at least one column wide.  Strip i is Pillow's box
+    (cut[i], 0, cut[i+1], h) with the quad NW = top[i], SW = bottom[i], SE = bottom[i+1], NE = top[i+1].  ValueError for what has no such
+    mesh: a total weight of 0, a strip whose quad is not clockwise (mirrored or folded text), more than MESH_MAX_STRIPS strips."""
+    top, bottom = _polygon_sides(polygon)
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f'size {h} x {w}: each side must be at least 1')
+    n = len(top)
+    weights = [0.5 * (_dist(top[i], top[i + 1]) + _dist(bottom[i], bottom[i + 1])) for i in range(n - 1)]
+    total = 0.0
+    for v in weights:
+        total += v
+    if not total > 0.0:
+        raise ValueError(f'polygon {top + bottom[::-1]} has no length: every segment weighs 0')
+    cuts, cum = [0], 0.0
+    for v in weights[:-1]:
+        cum += v
+        cuts.append(math.floor(cum / total * w + 0.5))
+    cuts.append(w)
+    strips = []
+    for i in range(n - 1):
+        if cuts[i + 1] <= cuts[i]:
+            continue
+        quad = (top[i], top[i + 1], bottom[i + 1], bottom[i])
+        area2 = sum(quad[k][0] * quad[(k + 1) % 4][1] - quad[(k + 1) % 4][0] * quad[k][1] for k in range(4))
+        if not area2 > 0.0:
+            raise ValueError(f'segment {i} of the polygon, {quad}, is not clockwise from the top-left (the text is mirrored or folded there)')
+        strips.append((cuts[i], cuts[i + 1], quad_strip_coeffs(cuts[i], cuts[i + 1], h, top[i], bottom[i], bottom[i + 1], top[i + 1])))
+    if len(strips) > MESH_MAX_STRIPS:
+        raise ValueError(f'{len(strips)} strips, at most {MESH_MAX_STRIPS}')
+    return strips
+
+
+def check_strips(strips, h: int, w: int):
+    """The strips as [(int, int, 8 floats)], or ValueError: none or more than MESH_MAX_STRIPS, a coefficient that is not finite, strips
+    that do not tile [0, w) in order without gap or overlap."""
+    if h < 1 or w < 1:
+        raise ValueError(f'region of {h} x {w}: each side must be at least 1')
+    out = []
+    for x0, x1, coef in strips:
+        coef = tuple(map(float, coef))
+        if len(coef) != 8:
+            raise ValueError(f'{len(coef)} coefficients, a bilinear map has 8')
+        if not all(map(math.isfinite, coef)):
+            raise ValueError(f'coefficients {coef} are not all finite')
+        out.append((int(x0), int(x1), coef))
+    if not 1 <= len(out) <= MESH_MAX_STRIPS:
+        raise ValueError(f'{len(out)} strips, a region has 1 .. {MESH_MAX_STRIPS}')
+    at = 0
+    for x0, x1, _ in out:
+        if x0 != at or x1 <= x0:
+            raise ValueError(f'strip of columns {x0} .. {x1} where {at} begins: the strips must tile 0 .. {w} in order without gap or overlap')
+        at = x1
+    if at != w:
+        raise ValueError(f'the strips end at column {at}: they must tile 0 .. {w}')
+    return out
+
+
+def mesh_to_source(strips, size, img_size, points):
+    """The way back from the model's input to the scene, as `map_to_source`: `points` (x, y) in pixels of the model's input (`img_size` =
+    (h, w)) of a region rectified to `size` = (h, w) with `strips`, as [(x, y)] in pixels of the source image — the stretch of the resize
+    undone, the strip chosen by X (the last one also owns X = w, and what lies beyond either end continues the outermost strip), then its
+    bilinear map at (X - x0, Y), without the half-pixel shift, in float64."""
+    strips = list(strips)
+    out = []
+    for x, y in points:
+        X, Y = x * size[1] / img_size[1], y * size[0] / img_size[0]
+        x0, _, a = next((s for s in strips[:-1] if X < s[1]), strips[-1])
+        u = X - x0
+        out.append((a[0] + a[1] * u + a[2] * Y + a[3] * u * Y, a[4] + a[5] * u + a[6] * Y + a[7] * u * Y))
+    return out
+
+
+def polygon_descs(regions, sizes=None, n_images=None):
+    """[(image_index, (h, w), strips)] of `regions`: each (image_index, polygon) — sized by `sizes[i]` or `polygon_size` — or
+    (image_index, strips, (h, w)) verbatim.  Everything the library would refuse is a ValueError here, naming the region."""
+    regions = list(regions)
+    if len(regions) == 0:
+        raise ValueError('no regions')
+    if sizes is not None and len(sizes) != len(regions):
+        raise ValueError(f'{len(sizes)} sizes for {len(regions)} regions')
+    out = []
+    for i, region in enumerate(regions):
+        try:
+            if len(region) == 3:
+                index, strips, (h, w) = region
+                if sizes is not None and sizes[i] is not None:
+                    h, w = sizes[i]
+                h, w = int(h), int(w)
+                strips = check_strips(strips, h, w)
+            else:
+                index, polygon = region
+                h, w = sizes[i] if sizes is not None and sizes[i] is not None else polygon_size(polygon)
+                h, w = int(h), int(w)
+                strips = polygon_mesh(polygon, h, w)
+        except ValueError as e:
+            raise ValueError(f'region {i}: {e}') from None
+        index = int(index)
+        if n_images is not None and not 0 <= index < n_images:
+            raise ValueError(f'region {i}: image index {index} is outside 0 .. {n_images - 1}')
+        if h > MAX_SIDE or w > MAX_SIDE:
+            raise ValueError(f'region {i}: size {h} x {w}, each side must be at most {MAX_SIDE}')
+        out.append((index, (h, w), strips))
+    return out
+
+
+def _native_mesh(keep, described):
+    images = _image_descs(keep)
+    regions = (_native.MeshRegionDesc * len(described))()
+    strips = (_native.MeshStrip * sum(len(s) for _, _, s in described))()
+    at = 0
+    for d, (index, (h, w), region_strips) in zip(regions, described):
+        d.image, d.height, d.width, d.first_strip, d.n_strips = index, h, w, at, len(region_strips)
+        for x0, x1, coef in region_strips:
+            strips[at].x0, strips[at].x1 = x0, x1
+            strips[at].coef[:] = coef
+            at += 1
+    return images, regions, strips
+
+
+def mesh_rectify_batch(images: Sequence[Tensor], regions, sizes=None) -> list:
+    """images: CUDA uint8 tensors [H_i, W_i, 3], the scenes; regions: (image_index, polygon) each (see `polygon_descs`).  Returns the uint8
+    [h_i, w_i, 3] crops PIL's Image.transform((w, h), MESH, the boxes and quads of polygon_mesh(polygon, h, w), BICUBIC) cuts out of them, all
+    in one launch (parseq_mesh_rectify; views of one buffer), as `rectify_batch` does for quadrilaterals."""
+    keep = _checked(images)
+    dev = keep[0].device
+    described = polygon_descs(regions, sizes, len(keep))
+    image_descs, region_array, strip_array = _native_mesh(keep, described)
+    lib = _native.lib()
+    n = len(described)
+    offsets, total = [], 0
+    for _, (h, w), _ in described:
+        offsets.append(total)
+        total += _slot(h, w)
+    flat = torch.empty((total,), dtype=torch.uint8, device=dev)
+    outs = [flat[o:o + 3 * h * w].view(h, w, 3) for o, (_, (h, w), _) in zip(offsets, described)]
+    pointers = (_native.C.c_void_p * n)(*[flat.data_ptr() + o for o in offsets])
+    need = lib.parseq_mesh_rectify_workspace_bytes(region_array, n, strip_array, len(strip_array), len(keep))
+    if need == 0:
+        _native.check(-1)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    with _native.guard(dev):
+        _native.check(lib.parseq_mesh_rectify(image_descs, len(keep), region_array, n, strip_array, len(strip_array), pointers, _native.ptr(ws), need,
+                                              _native.stream_ptr(dev)))
+    torch.cuda.current_stream(dev).synchronize()          # the four host arrays are read by asynchronous copies
+    return outs
+
+
+def mesh_rectify_resize_batch(images: Sequence[Tensor], regions, size=(32, 128), sizes=None) -> Tensor:
+    """`resize_batch(mesh_rectify_batch(images, regions, sizes), size)` without the crops ever leaving the library's workspace: uint8
+    [N, 3, size[0], size[1]], one row per region, the model's input."""
+    keep = _checked(images)
+    dev = keep[0].device
+    described = polygon_descs(regions, sizes, len(keep))
+    image_descs, region_array, strip_array = _native_mesh(keep, described)
+    lib = _native.lib()
+    n = len(described)
+    out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
+    need = lib.parseq_mesh_rectify_workspace_bytes(region_array, n, strip_array, len(strip_array), len(keep))
+    if need == 0:
+        _native.check(-1)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    with _native.guard(dev):
+        _native.check(lib.parseq_mesh_rectify_resize_bicubic(image_descs, len(keep), region_array, n, strip_array, len(strip_array), size[0], size[1],
+                                                             _native.ptr(out), _native.ptr(ws), need, _native.stream_ptr(dev)))
     torch.cuda.current_stream(dev).synchronize()
     return out

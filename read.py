@@ -12,6 +12,7 @@
     ./read.py pretrained=parseq --images a.png --nbest 5 --refine-beams edit [--refine-iters 2]     refine every alternative, rank them again
     ./read.py pretrained=parseq --images a.png --boxes     a second line per image: every character with its box in the image's own pixels
     ./read.py pretrained=parseq --images scene.jpg --regions scene.txt [--boxes]     read every quadrilateral of the file (x1,y1,..,x4,y4 per line)
+    ./read.py pretrained=parseq --images scene.jpg --polygons scene.txt [--boxes]     read every polygon of the file (x1,y1,..,xK,yK per line): curved text
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -94,35 +95,67 @@ def load_regions(path):
     return quads
 
 
+def load_polygons(path):
+    """The polygons of a Total-Text / CTW1500 style file: every non-empty line is `x1,y1,..,xK,yK[,transcription]`, K = 2N >= 4 points, N
+    along the text's upper edge from its top-left, then N back along its lower edge.  The coordinates are the longest leading run of fields
+    that parse as finite numbers; if that run is odd, its last field belongs to the transcription (a numeric one) and is dropped.  Returns
+    [((x1, y1), .. (xK, yK))] as floats; a line that leaves anything but an even number of points, at least 4, is a ValueError naming
+    file and line."""
+    import math
+    polygons = []
+    with open(path, encoding='utf-8-sig') as fh:
+        for number, line in enumerate(fh, 1):
+            if not line.strip():
+                continue
+            v = []
+            for field in line.split(','):
+                try:
+                    value = float(field)
+                except ValueError:
+                    break
+                if not math.isfinite(value):
+                    break
+                v.append(value)
+            v = v[:len(v) - len(v) % 2]
+            if len(v) < 8 or len(v) % 4:
+                raise ValueError(f'{path}, line {number}: expected an even number of points, at least 4, as comma-separated numbers '
+                                 f'x1,y1,..,xK,yK, got {len(v) // 2} in {line.strip()!r}')
+            polygons.append(tuple(zip(v[0::2], v[1::2])))
+    return polygons
+
+
 @torch.inference_mode()
-def load_region_batch(model, files, region_files, device='cuda'):
+def load_region_batch(model, files, region_files, device='cuda', polygons=False):
     """The regions of `region_files[i]` cut out of `files[i]` and straightened, as one batch for the model: every
     scene is decoded and uploaded once, all regions of all scenes go through ONE rectify-and-resize call.  Returns (names, batch, back):
     `file#k` per region, k counting from 0 within its file; uint8 [N, 3, H, W] (None without regions); per region the (coefficients, (h, w))
-    with which `map_to_source` leads from the model's input back into the scene."""
+    with which `map_to_source` leads from the model's input back into the scene.  With `polygons` the files hold polygons (`load_polygons`),
+    straightened strip by strip (section 25), and `back` holds per region the (strips, (h, w)) of `mesh_to_source`."""
     import numpy as np
-    from parseq_amd.preprocess import rectify_resize_batch, region_descs
+    from parseq_amd.preprocess import mesh_rectify_resize_batch, polygon_descs, rectify_resize_batch, region_descs
+    load, describe, rectify = (load_polygons, polygon_descs, mesh_rectify_resize_batch) if polygons else (load_regions, region_descs, rectify_resize_batch)
     names, regions = [], []
     for i, (f, rf) in enumerate(zip(files, region_files)):
-        for k, quad in enumerate(load_regions(rf)):
+        for k, quad in enumerate(load(rf)):
             names.append(f'{f}#{k}')
             regions.append((i, quad))
     if not regions:
         return [], None, []
-    described = region_descs(regions, n_images=len(files))
+    described = describe(regions, n_images=len(files))
     scenes = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
-    batch = rectify_resize_batch(scenes, [(index, coeffs, size) for index, size, coeffs in described], tuple(model.hparams.img_size))
+    batch = rectify(scenes, [(index, coeffs, size) for index, size, coeffs in described], tuple(model.hparams.img_size))
     return names, batch, [(coeffs, size) for _, size, coeffs in described]
 
 
 @torch.inference_mode()
 def read_regions(model, files, region_files, beam=None, nbest=0, words=None, list_words=False, refine=None, refine_iters=1, boxes=False, device='cuda',
-                 match=None, prior=None):
+                 match=None, prior=None, polygons=False):
     """The lines `--regions` prints, for the same flags as the whole-crop readings above, on the batch of `load_region_batch`: `words` is the
     list of --lexicon (its alternatives are listed only with `list_words`), `boxes` adds every character's quadrilateral in the scene, `match`
-    the N of --match, `prior` the (automaton, alpha, beta) of --priors / --lm / --pattern."""
-    from parseq_amd.preprocess import map_to_source
-    names, batch, back = load_region_batch(model, files, region_files, device)
+    the N of --match, `prior` the (automaton, alpha, beta) of --priors / --lm / --pattern; `polygons` makes the files those of --polygons."""
+    from parseq_amd.preprocess import map_to_source, mesh_to_source
+    to_source = mesh_to_source if polygons else map_to_source
+    names, batch, back = load_region_batch(model, files, region_files, device, polygons)
     if not names:
         return []
     lines = []
@@ -149,7 +182,7 @@ def read_regions(model, files, region_files, beam=None, nbest=0, words=None, lis
         labels, chars = model.tokenizer.decode_localization(model.localize(batch))
         for name, label, row, (coeffs, size) in zip(names, labels, chars, back):
             lines.append(f'{name}: {label}')
-            quads = [(ch, map_to_source(coeffs, size, img_size, ((x0, y0), (x1, y0), (x1, y1), (x0, y1)))) for ch, (x0, y0, x1, y1) in row]
+            quads = [(ch, to_source(coeffs, size, img_size, ((x0, y0), (x1, y0), (x1, y1), (x0, y1)))) for ch, (x0, y0, x1, y1) in row]
             lines.append('    ' + ' '.join(f'{ch}[' + ','.join(f'{v:.1f}' for p in quad for v in p) + ']' for ch, quad in quads))
         return lines
     alternatives = [[]] * len(names)
@@ -299,6 +332,10 @@ def build_parser():
                         help='One file of quadrilaterals per image, in order (ICDAR-2015 style: x1,y1,x2,y2,x3,y3,x4,y4[,text] per line, clockwise '
                              "from the text's top-left): read every region of the scene, printed as image#k; with --boxes every character's "
                              "quadrilateral in the scene's pixels")
+    parser.add_argument('--polygons', nargs='+', default=None, metavar='FILE',
+                        help='One file of polygons per image, in order (Total-Text / CTW1500 style: x1,y1,..,xK,yK[,text] per line, K = 2N >= 4 points, '
+                             "N along the text's upper edge from its top-left, then N back along its lower edge): read every curved region of the "
+                             'scene like --regions does; not together with --regions')
     parser.add_argument('--priors', action='store_true',
                         help='With --lexicon: the list has a second white-space separated column, a count; the words are then a prior (their smoothed '
                              'relative frequencies enter the ranking), not only a constraint')
@@ -406,22 +443,28 @@ def main(argv=None):
     beam, nbest = resolve_search(parser, args)
     refine, refine_iters = resolve_refine(parser, args)
     files = args.images or []
-    if args.regions is not None and len(args.regions) != len(files):
-        parser.error(f'--regions takes one file per image, in order: {len(args.regions)} files for {len(files)} images')
+    if args.regions is not None and args.polygons is not None:
+        parser.error('--polygons and --regions are two ways to cut the same scenes: give one of them')
+    polygons = args.polygons is not None
+    region_files = args.polygons if polygons else args.regions
+    if region_files is not None and len(region_files) != len(files):
+        parser.error(f'--{"polygons" if polygons else "regions"} takes one file per image, in order: {len(region_files)} files for {len(files)} images')
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     if kind is not None:
         automaton = build_automaton(model, kind, args)
-        if args.regions is not None:
-            lines = read_regions(model, files, args.regions, beam, nbest, list_words=args.nbest > 0, device=args.device, prior=(automaton, alpha, beta))
+        if region_files is not None:
+            lines = read_regions(model, files, region_files, beam, nbest, list_words=args.nbest > 0, device=args.device, prior=(automaton, alpha, beta),
+                                 polygons=polygons)
         else:
             lines = [line for fname, alts in read_files_automaton(model, files, automaton, beam, alpha, beta, args.device)
                      for line in automaton_lines(fname, alts[:nbest], args.nbest > 0)]
         for line in lines:
             print(line)
         return
-    if args.regions is not None:
+    if region_files is not None:
         words = load_word_list(args.lexicon) if args.lexicon is not None else None
-        for line in read_regions(model, files, args.regions, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device, match):
+        for line in read_regions(model, files, region_files, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device, match,
+                                 polygons=polygons):
             print(line)
         return
     if match is not None:
