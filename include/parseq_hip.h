@@ -654,7 +654,9 @@ int parseq_mesh_rectify_resize_bicubic(const parseq_image_desc* images, int n_im
  * strhub/data/utils.py:79-99 greedy max per position, :120-129 truncation at the first EOS) on the device, so a caller
  * moves B*L ids + B lengths (+ probabilities) to the host instead of B*L*C probabilities and one .tolist() per row.
  * logits: device fp32 [batch, L, C] contiguous (L <= 64).  Outputs (device):
- *   ids_out      int32 [batch, L]  arg-max class per position (first maximum), for every position
+ *   ids_out      int32 [batch, L]  arg-max class per position (first maximum), for every position.  A position whose logits hold a NaN
+ *                                  or a +inf, or nothing but -inf, has no finite soft-max: its id is 0 and its probability NaN, which is
+ *                                  what the reference's `max` over NaN probabilities returns (so the label is cut there if eos_id is 0)
  *   lengths_out  int32 [batch]     index of the first position whose id is eos_id, or L: the label is ids_out[b, :len]
  *   probs_out    fp32  [batch, L]  max soft-max probability per position (NULL to skip); the reference's per-label
  *                                  probability tensor is probs_out[b, :min(len + 1, L)] (it keeps the EOS probability)

@@ -57,7 +57,8 @@ void beam_refine_stats_kernel(const float* __restrict__ logits, int rows, int L,
 //   edit mode:  t'[i] = amax[i] up to and including the first <eos>, pad_id after it; length' = its index (L without one), finished' = there
 //               is one; new score = sum_{i <= last'} lp_max[i].  Of live rows with the same new reading the one with the higher new score
 //               stays (then the lower row), the others become dead.
-// fp32 sums in ascending i.  Then the rows are ranked on (beam_ordered(new score), ~row): higher score first, then the lower row, dead rows
+// fp32 sums in ascending i.  A sum that is not a number (a summed position's logits hold a NaN or a +inf, or nothing but -inf) is -inf: the
+// row becomes dead, so no NaN enters the ranking below.  Then the rows are ranked on (beam_ordered(new score), ~row): higher score first, then the lower row, dead rows
 // last in their order, and every field moves with its row: history, picked, length, finished, node, word (either may be null) and ar_score.
 // A dead row comes out as score -inf, length 0, finished 0, word -1, pad_id in picked and in every history slot after <bos>.
 // Everything is loaded into LDS before the first barrier and written after the last (the race of section 18).
@@ -110,6 +111,7 @@ void beam_refine_select_kernel(int mode, int W, int L, const float* __restrict__
             const int last = s_last[tid];
             for (int i = 0; i <= last; ++i) s += s_lp[tid][i];
             if (s == 0.f) s = 0.f;      // one zero: the ordering below is on the bits
+            if (s != s) s = -INFINITY;  // a summed position whose log-sum is no number (a NaN or +inf logit, a row of -inf): no score, a dead row
         }
         s_new[tid] = s;
     }

@@ -216,7 +216,9 @@ static __global__ void ar_init_kernel(int* __restrict__ tok, int ldt, int B, int
 // Device-side numeric half of `Tokenizer.decode(logits.softmax(-1))` (strhub/models/base.py:132-135,
 // strhub/data/utils.py:79-99 greedy max per position, :120-129 cut at the first EOS keeping the EOS probability).
 // One wave per image, lane l ends up owning position l (L <= 64):
-//   ids[b][l]   = argmax_c logits[b][l][c]  (first maximum; soft-max is monotone, so this is the arg-max of the probabilities)
+//   ids[b][l]   = argmax_c softmax(logits[b][l])[c]: the first maximum of the logits (soft-max is monotone) where the soft-max is finite.
+//                 A row that holds a NaN or a +inf, or nothing but -inf, has no finite soft-max: every probability is NaN, and the
+//                 reference's `max` over them returns index 0 — so ids = 0 (<eos> in the reference's tokenizer) and probs = NaN there
 //   probs[b][l] = max_c softmax(logits[b][l])[c] = 1 / sum_c exp(logit_c - max)
 //   lengths[b]  = index of the first EOS, or L            (number of characters)
 //   conf[b]     = prod_{l < min(lengths[b] + 1, L)} probs[b][l]   (base.py:137 `prob.prod()`)
@@ -239,6 +241,7 @@ void postprocess_kernel(const float* __restrict__ logits, int B, int L, int C, i
         float sum = 0.f;
         for (int c = lane; c < C; c += 64) sum += expf(row[c] - best);
         sum = wave_sum(sum);
+        if (sum != sum) bi = 0;      // NaN - NaN, inf - inf or -inf - -inf among the terms: no finite soft-max (wave-uniform)
         if (lane == l) { my_p = 1.0f / sum; my_id = bi; }
     }
     const unsigned long long eos_lanes = __ballot(lane < L && my_id == eos_id);

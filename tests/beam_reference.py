@@ -33,7 +33,8 @@ class StepResult:
 
 def rank_candidates(logits, scores, finished):
     """Every candidate (score, parent, class) of one image, best first: higher score, then lower parent, then lower class; a finished
-    beam offers itself once as class -1, a dead beam (score -inf) nothing."""
+    beam offers itself once as class -1, a dead beam (score -inf) nothing.  A candidate whose value is not finite is not a candidate: a -inf
+    logit's class, and every class of a row that holds a NaN or a +inf or nothing but -inf (its log-sum is not a number)."""
     logp = torch.log_softmax(torch.as_tensor(logits).double(), -1)
     cands = []
     for w, s in enumerate(scores):
@@ -42,7 +43,7 @@ def rank_candidates(logits, scores, finished):
         if finished[w]:
             cands.append((float(s), w, -1))
         else:
-            cands += [(float(s) + lp, w, c) for c, lp in enumerate(logp[w].tolist())]
+            cands += [(float(s) + lp, w, c) for c, lp in enumerate(logp[w].tolist()) if math.isfinite(float(s) + lp)]
     cands.sort(key=lambda t: (-t[0], t[1], t[2]))
     return cands
 

@@ -1,6 +1,8 @@
 """Cloze refinement of beam hypotheses as DESIGN.md section 20 defines it, restated on the CPU.   *** TEST INFRASTRUCTURE ***
 
-float64 log-soft-max and sums, plain Python for the cut, the duplicate rule and the ranking.  A hypothesis is its L tokens t[0 .. L) (class
+float64 log-soft-max and sums, plain Python for the cut, the duplicate rule and the ranking.  Logits need not be finite: the arg-max
+follows argmax_take's rule (`first_argmax_rows`), and a row whose new score is not a number (one of its summed positions holds a NaN, a
++inf or nothing but -inf) comes out dead, like one whose score is -inf.  A hypothesis is its L tokens t[0 .. L) (class
 ids, pad_id after its <eos>), a score (-inf: dead), a length, a finished flag, a trie node, a word id and the score the search gave it.
 
   refine_image   one iteration on the W rows of one image (what `parseq_op_beam_refine` does per workgroup)
@@ -43,14 +45,24 @@ def first_argmax(row: torch.Tensor) -> int:
     return int((row == row.max()).nonzero()[0])
 
 
+def first_argmax_rows(logits: torch.Tensor) -> torch.Tensor:
+    """argmax_take's rule on any input, over the last dimension: the first NaN where there is one, else the lowest class id among the
+    maxima (so 0 for a row of -inf)."""
+    C = logits.shape[-1]
+    idx = torch.arange(C)
+    nan = torch.isnan(logits)
+    clean = torch.where(nan, torch.full_like(logits, NEG_INF), logits)
+    first_max = torch.where(clean == clean.amax(-1, keepdim=True), idx, C).amin(-1)
+    return torch.where(nan.any(-1), torch.where(nan, idx, C).amin(-1), first_max)
+
+
 def refine_image(logits, mode: str, rows: Rows, eos_id: int, pad_id: int) -> Rows:
     """One iteration on one image.  logits [W, L, C] (any float dtype; the values are taken as they are)."""
     assert mode in MODES
     logits = torch.as_tensor(logits)
     W, L, _ = logits.shape
     logp = torch.log_softmax(logits.double(), -1)
-    C = logits.shape[-1]
-    picks_all = torch.where(logits == logits.amax(-1, keepdim=True), torch.arange(C), C).amin(-1).tolist()      # first_argmax of every row
+    picks_all = first_argmax_rows(logits).tolist()
     new = []      # per input row: (score, tokens, finished, length, last)
     for w in range(W):
         if rows.scores[w] == NEG_INF:
@@ -68,6 +80,8 @@ def refine_image(logits, mode: str, rows: Rows, eos_id: int, pad_id: int) -> Row
         s = 0.0
         for i in range(last + 1):
             s += float(logp[w, i, t[i]])
+        if s != s:      # a NaN, +inf or all -inf logit row among the summed positions: no score, so no hypothesis
+            s = NEG_INF
         new.append((s, t, fin, length, last))
     gaps = []
     dead = [n[0] == NEG_INF for n in new]
