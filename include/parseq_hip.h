@@ -693,6 +693,34 @@ int parseq_eval_metrics(const float* logits, int batch, int L, int C, int eos_id
                         const int32_t* gt_len, int gt_width, int32_t* ids_out, int32_t* lengths_out, float* confidence_out,
                         int32_t* rows_out, double* workspace, void* accum, void* stream);
 
+/* The same for an N-best: the metrics of the first live hypothesis of every image, and where in the list the label stands.  Nothing is
+ * copied back or allocated, the call does not synchronise and uses no atomics (fixed summation order: equal inputs, bit-identical totals).
+ *   tokens, scores, lengths   device int32 [B, W, T], fp32 [B, W], int32 [B, W]: a beam result.  A slot is LIVE iff its score is not -inf;
+ *                  its live rank is the number of live slots before it in its image.  A hypothesis is its first lengths[b, w] tokens
+ *                  (clamped to [0, min(T, 32)]) mapped through adapter_table; ids outside [0, C) and entries -1 are dropped.
+ *   conf_scores    device fp32 [B, W]: the log-probability the confidence exp((double)conf_scores[b, w]) of the top-1 is taken from
+ *                  (`scores` itself, or the model's own scores under a weighted automaton)
+ *   gt, gt_len, G, adapter_table   as parseq_eval_metrics takes them; the W hypotheses of image b share label b
+ *   hyp_rows_out   int32 [B * W, 4]: {length of the adapted hypothesis, length of the label, Levenshtein distance, 1 if equal}; a dead
+ *                  slot's row is {-1, -1, -1, 0}
+ *   image_rows_out int32 [B, 8]: {m, n, distance, exact} of the top-1 (the first live slot; an image without one reads as the empty
+ *                  string: m 0, distance n, not exact), live rank of the first exact live hypothesis or -1, smallest distance over the live
+ *                  slots, number of live slots, slot of the top-1 or -1
+ *   workspace      device, B * (W + 3) doubles: distance / max(m, n, 1) of every hypothesis (-1 for a dead slot), then per image the
+ *                  top-1's, the smallest over the live slots, and the confidence
+ *   accum          device, PARSEQ_EVAL_BEAMS_ACCUM_BYTES, ACCUMULATED into: int64 num_samples, correct, label_length, top1_distance,
+ *                  oracle_correct, oracle_distance, live, miss, first_hit[PARSEQ_EVAL_MAX_BEAMS]; double ned, confidence, oracle_ned.
+ *                  Calls that share an accumulator must be ordered (one stream).
+ * The per-image step and the sums run in ONE workgroup: its time grows linearly with B on one compute unit (12 us at B = 512); split a
+ * far larger batch into several calls, the accumulator adds up.
+ * PARSEQ_E_INVALID, before any device work and with every output untouched: W outside 1 .. PARSEQ_EVAL_MAX_BEAMS, T outside 1 .. 32,
+ * G outside 1 .. PARSEQ_EVAL_MAX_GT, B < 1 (or above 2^26), C < 1, a null pointer. */
+#define PARSEQ_EVAL_MAX_BEAMS 17
+#define PARSEQ_EVAL_BEAMS_ACCUM_BYTES 224
+int parseq_eval_beams(const int32_t* tokens, const float* scores, const int32_t* lengths, const float* conf_scores, int B, int W, int T, int C,
+                      const int32_t* adapter_table, const int32_t* gt, const int32_t* gt_len, int G, int32_t* hyp_rows_out,
+                      int32_t* image_rows_out, double* workspace, void* accum, void* stream);
+
 /* ---- "next" row N3: training step, decoder side (strhub/models/parseq/system.py:168-199 + loss.backward()) ---------- */
 
 /* Offset (in floats) of parameter `index` inside a gradient buffer, and the buffer's length: gradients are laid out like

@@ -18,42 +18,38 @@ struct EvalAccum {
 };
 static_assert(sizeof(EvalAccum) == 40, "the binding views the accumulator as 3 x int64 + 2 x float64");
 
-// One wave per row.  Lane j < lengths[b] owns prediction character j.
+// The two steps of a row, shared by eval_rows_kernel and the N-best kernel of eval_beams.h.  One wave per row, lane j < plen owns character j.
 //   adapter: table[id] is the code point CharsetAdapter (strhub/data/utils.py:26-43) turns train token `id` into, or -1 if it drops it;
-//            the kept characters are compacted to lanes 0 .. m-1 through LDS (order preserved).
-//   distance: Myers' bit-vector recurrence in Hyyro's form for the global (Levenshtein) distance, pattern = adapted prediction (m <= 32
-//            bits of a 64-bit word), text = ground truth.  The match mask of a text character is a 64-lane ballot, everything else is
-//            wave-uniform integer arithmetic: len(gt) short steps, unit costs, no transpositions (nltk.edit_distance defaults).
-//   rows[b] = {m, n, distance, pred == gt};  row_ned[b] = distance / max(m, n, 1) in double, summed by eval_reduce_kernel.
-static __global__ __launch_bounds__(256)
-void eval_rows_kernel(const int* __restrict__ ids, const int* __restrict__ lengths, int B, int L, int C, const int* __restrict__ table,
-                      const int* __restrict__ gt, const int* __restrict__ gt_len, int G, int* __restrict__ rows, double* __restrict__ row_ned) {
-    __shared__ int spred[4][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int b = blockIdx.x * 4 + w;
-    const bool active = b < B;                               // a wave past the batch only keeps the barrier company
-    const int plen = active ? min(max(lengths[b], 0), min(L, EVAL_MAX_PRED)) : 0;
+//            the kept characters are compacted to lanes 0 .. m-1 through LDS (order preserved).  EVERY wave of the block calls this (it
+//            holds the block's one barrier), a wave without a row with plen = 0.  Returns m; `pc` is the adapted character `lane`, -1 past m.
+static __device__ __forceinline__ int eval_adapt_row(const int* __restrict__ ids_row, int plen, int C, const int* __restrict__ table, int* spred_w,
+                                                     int lane, int& pc) {
     int cp = -1;
     if (lane < plen) {
-        const int id = ids[(size_t)b * L + lane];
+        const int id = ids_row[lane];
         if (id >= 0 && id < C) cp = table[id];
     }
     const unsigned long long kept = __ballot(cp >= 0);
     const int m = __popcll(kept);
-    spred[w][lane] = -1;
-    if (cp >= 0) spred[w][__popcll(kept & ((1ull << lane) - 1ull))] = cp;      // kept lanes < 32, so the shift is defined
+    spred_w[lane] = -1;
+    if (cp >= 0) spred_w[__popcll(kept & ((1ull << lane) - 1ull))] = cp;      // kept lanes < 32, so the shift is defined
     __syncthreads();
-    if (!active) return;
-    const int pc = spred[w][lane];                           // adapted prediction, character `lane` (-1 past its end)
+    pc = spred_w[lane];
+    return m;
+}
 
-    const int n = min(max(gt_len[b], 0), G);
+//   distance: Myers' bit-vector recurrence in Hyyro's form for the global (Levenshtein) distance, pattern = adapted prediction (m <= 32
+//            bits of a 64-bit word), text = ground truth.  The match mask of a text character is a 64-lane ballot, everything else is
+//            wave-uniform integer arithmetic: len(gt) short steps, unit costs, no transpositions (nltk.edit_distance defaults).
+//            Called by whole waves only (all 64 lanes take part in the ballots and shuffles); m and n are wave-uniform.
+static __device__ __forceinline__ int eval_row_distance(int pc, int m, const int* __restrict__ gt_row, int n, int lane) {
     int dist = n;                                            // empty prediction: n insertions
     if (m > 0) {
         unsigned long long Pv = (1ull << m) - 1ull, Mv = 0ull;      // m <= 32
         const unsigned long long top = 1ull << (m - 1);
         dist = m;
         for (int base = 0; base < n; base += 64) {
-            const int mine = (base + lane < n) ? gt[(size_t)b * G + base + lane] : -2;
+            const int mine = (base + lane < n) ? gt_row[base + lane] : -2;
             const int cnt = min(64, n - base);
             for (int i = 0; i < cnt; ++i) {
                 const int c = __shfl(mine, i, 64);
@@ -71,6 +67,23 @@ void eval_rows_kernel(const int* __restrict__ ids, const int* __restrict__ lengt
             }
         }
     }
+    return dist;
+}
+
+//   rows[b] = {m, n, distance, pred == gt};  row_ned[b] = distance / max(m, n, 1) in double, summed by eval_reduce_kernel.
+static __global__ __launch_bounds__(256)
+void eval_rows_kernel(const int* __restrict__ ids, const int* __restrict__ lengths, int B, int L, int C, const int* __restrict__ table,
+                      const int* __restrict__ gt, const int* __restrict__ gt_len, int G, int* __restrict__ rows, double* __restrict__ row_ned) {
+    __shared__ int spred[4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int b = blockIdx.x * 4 + w;
+    const bool active = b < B;                               // a wave past the batch only keeps the barrier company
+    const int plen = active ? min(max(lengths[b], 0), min(L, EVAL_MAX_PRED)) : 0;
+    int pc;
+    const int m = eval_adapt_row(ids + (size_t)(active ? b : 0) * L, plen, C, table, spred[w], lane, pc);
+    if (!active) return;
+    const int n = min(max(gt_len[b], 0), G);
+    const int dist = eval_row_distance(pc, m, gt + (size_t)b * G, n, lane);
     if (lane == 0) {
         int* r = rows + (size_t)b * 4;
         r[0] = m; r[1] = n; r[2] = dist; r[3] = dist == 0;

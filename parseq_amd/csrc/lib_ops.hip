@@ -1,6 +1,7 @@
 // libparseq_hip.so — input resize, post-process, and the per-kernel entry points the parity tests call.
 #include "lib_internal.h"
 #include "eval_metrics.h"
+#include "eval_beams.h"
 #include "rectify_mesh.h"
 
 // -------------------------------------------------------------------------------------------------------------------
@@ -551,6 +552,30 @@ extern "C" int parseq_eval_metrics(const float* logits, int batch, int L, int C,
     hipLaunchKernelGGL(eval_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, s, ids_out, lengths_out, batch, L, C, adapter_table, gt, gt_len, gt_width, rows_out, workspace);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(eval_reduce_kernel, dim3(1), dim3(256), 0, s, rows_out, workspace, confidence_out, batch, reinterpret_cast<EvalAccum*>(accum));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the same for an N-best (eval_beams.h): every refusal comes before any device work
+extern "C" int parseq_eval_beams(const int32_t* tokens, const float* scores, const int32_t* lengths, const float* conf_scores, int B, int W, int T, int C,
+                                 const int32_t* adapter_table, const int32_t* gt, const int32_t* gt_len, int G, int32_t* hyp_rows_out,
+                                 int32_t* image_rows_out, double* workspace, void* accum, void* stream) {
+    static_assert(EVAL_MAX_BEAMS == PARSEQ_EVAL_MAX_BEAMS && sizeof(BeamEvalAccum) == PARSEQ_EVAL_BEAMS_ACCUM_BYTES, "header and kernel limits must agree");
+    if (!tokens || !scores || !lengths || !conf_scores || !adapter_table || !gt || !gt_len || !hyp_rows_out || !image_rows_out || !workspace || !accum)
+        return fail(PARSEQ_E_INVALID, "eval_beams: null argument");
+    if (B < 1) return fail(PARSEQ_E_INVALID, "eval_beams: batch B = %d, it must be at least 1", B);
+    if (W < 1 || W > EVAL_MAX_BEAMS) return fail(PARSEQ_E_INVALID, "eval_beams: width W = %d, it must be in 1 .. %d", W, EVAL_MAX_BEAMS);
+    if (T < 1 || T > EVAL_MAX_PRED) return fail(PARSEQ_E_INVALID, "eval_beams: T = %d tokens per hypothesis, it must be in 1 .. %d", T, EVAL_MAX_PRED);
+    if (G < 1 || G > EVAL_MAX_GT) return fail(PARSEQ_E_INVALID, "eval_beams: ground truth of G = %d code points per row, it must be in 1 .. %d", G, EVAL_MAX_GT);
+    if (C < 1) return fail(PARSEQ_E_INVALID, "eval_beams: C = %d classes", C);
+    if (B > (1 << 26)) return fail(PARSEQ_E_INVALID, "eval_beams: batch B = %d, at most %d images per call", B, 1 << 26);
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = B * W;
+    hipLaunchKernelGGL(eval_beam_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, tokens, scores, lengths, rows, W, T, C, adapter_table, gt, gt_len, G,
+                       hyp_rows_out, workspace);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(eval_beam_images_kernel, dim3(1), dim3(256), 0, s, hyp_rows_out, workspace, scores, conf_scores, B, W, gt_len, G, image_rows_out,
+                       workspace + rows, reinterpret_cast<BeamEvalAccum*>(accum));
     HIPCHK(hipGetLastError());
     return 0;
 }

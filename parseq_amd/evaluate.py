@@ -21,13 +21,14 @@ Limits: a label of at most `MAX_GT` = 256 code points (the reference's dataset d
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from .system import BatchResult, eval_step
+from .system import BatchResult, edit_distance, eval_step
 
 MAX_GT = 256                 # PARSEQ_EVAL_MAX_GT
 
@@ -186,3 +187,241 @@ class Evaluator:
     def reduce(self, process_group=None) -> BatchResult:
         """`result()` summed over the ranks of `process_group`."""
         return reduce_result(self.result(), process_group)
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# N-best evaluation (DESIGN.md section 26)
+# -------------------------------------------------------------------------------------------------------------------
+MAX_BEAMS = 17               # PARSEQ_EVAL_MAX_BEAMS: the 16 candidates of a lexicon match plus the reading
+NO_HIT = -1                  # image row, word 4: no live hypothesis equals the label
+_BEAM_INTS = 8 + MAX_BEAMS   # int64 words of the accumulator; three float64 follow
+
+
+@dataclass
+class BeamEvalResult:
+    """Sums over the images of an N-best evaluation (the accumulator of `parseq_eval_beams`) and the quotients derived from them.
+    The top-1 of an image is its first live hypothesis; ranks are live ranks, counted from 0 (`first_hit[k]`: images whose first
+    exact hypothesis stands at rank k; `miss`: images without one).  The derived values are fractions, not percentages."""
+    num_samples: int = 0
+    correct: int = 0                     # images whose top-1 equals the label
+    label_length_sum: int = 0            # characters of the top-1s
+    top1_distance: int = 0               # edit distances of the top-1s
+    oracle_correct: int = 0              # images with the label anywhere in the list
+    oracle_distance: int = 0             # smallest edit distance over each image's list
+    live: int = 0                        # live hypotheses
+    miss: int = 0
+    first_hit: Tuple[int, ...] = (0,) * MAX_BEAMS
+    ned_sum: float = 0.0                 # normalised edit distances of the top-1s
+    confidence_sum: float = 0.0          # exp(log-probability) of the top-1s
+    oracle_ned_sum: float = 0.0          # smallest normalised edit distance over each image's list
+
+    def _mean(self, total) -> float:
+        return total / self.num_samples if self.num_samples else 0.0
+
+    @property
+    def accuracy(self) -> float:
+        return self._mean(self.correct)
+
+    @property
+    def ned(self) -> float:
+        """Mean normalised edit distance of the top-1 (the table prints 1 - this)."""
+        return self._mean(self.ned_sum)
+
+    @property
+    def confidence(self) -> float:
+        return self._mean(self.confidence_sum)
+
+    @property
+    def label_length(self) -> float:
+        return self._mean(self.label_length_sum)
+
+    def hit_at(self, k: int) -> float:
+        """Share of the images whose label is among their first `k` live hypotheses."""
+        return self._mean(sum(self.first_hit[:max(int(k), 0)]))
+
+    @property
+    def oracle_accuracy(self) -> float:
+        return self._mean(self.oracle_correct)
+
+    @property
+    def oracle_ned(self) -> float:
+        return self._mean(self.oracle_ned_sum)
+
+    @property
+    def mrr(self) -> float:
+        """Mean reciprocal rank of the label (0 for an image without it)."""
+        return self._mean(sum(c / (k + 1) for k, c in enumerate(self.first_hit)))
+
+    def _words(self):
+        ints = [self.num_samples, self.correct, self.label_length_sum, self.top1_distance, self.oracle_correct, self.oracle_distance, self.live, self.miss]
+        return ints + list(self.first_hit), [self.ned_sum, self.confidence_sum, self.oracle_ned_sum]
+
+    @classmethod
+    def _from_words(cls, ints, floats) -> 'BeamEvalResult':
+        ints = [int(v) for v in ints]
+        return cls(*ints[:8], tuple(ints[8:8 + MAX_BEAMS]), *(float(v) for v in floats))
+
+
+def host_beam_metrics(hypotheses, labels):
+    """The definitions of `parseq_eval_beams` on strings: `hypotheses[b]` is image b's slots in order, None for a dead slot, else
+    (adapted string, confidence score).  Returns (hypothesis rows [[m, n, distance, exact]], image rows, BeamEvalResult)."""
+    import math
+    hyp_rows, image_rows = [], []
+    ints, first_hit, floats = [0] * 8, [0] * MAX_BEAMS, [0.0, 0.0, 0.0]
+    for slots, gt in zip(hypotheses, labels):
+        n = len(gt)
+        top, hit, live, odist, oned, top_ned, conf = -1, NO_HIT, 0, n, n / max(n, 1), n / max(n, 1), 0.0
+        m, dist, exact = 0, n, 0
+        for w, slot in enumerate(slots):
+            if slot is None:
+                hyp_rows.append([-1, -1, -1, 0])
+                continue
+            s, score = slot
+            d = edit_distance(s, gt)
+            e = d / max(len(s), n, 1)
+            hyp_rows.append([len(s), n, d, int(d == 0)])
+            if live == 0:
+                top, odist, oned, top_ned, conf = w, d, e, e, math.exp(score)
+                m, dist, exact = len(s), d, int(d == 0)
+            else:
+                odist, oned = min(odist, d), min(oned, e)
+            if hit == NO_HIT and d == 0:
+                hit = live
+            live += 1
+        image_rows.append([m, n, dist, exact, hit, odist, live, top])
+        for i, v in enumerate((1, exact, m, dist, int(hit != NO_HIT), odist, live, int(hit == NO_HIT))):
+            ints[i] += v
+        if hit != NO_HIT:
+            first_hit[hit] += 1
+        floats[0] += top_ned; floats[1] += conf; floats[2] += oned
+    return hyp_rows, image_rows, BeamEvalResult._from_words(ints + first_hit, floats)
+
+
+def reduce_beam_result(result: BeamEvalResult, process_group=None) -> BeamEvalResult:
+    """The sums of `result` added over the ranks of `process_group` (None = the default group), as `reduce_result` does for the greedy
+    totals: the quotients are then those of the whole job.  Host tensors: works on gloo."""
+    import torch.distributed as dist
+    ints, floats = result._words()
+    ints, floats = torch.tensor(ints, dtype=torch.int64), torch.tensor(floats, dtype=torch.float64)
+    dist.all_reduce(ints, group=process_group)
+    dist.all_reduce(floats, group=process_group)
+    return BeamEvalResult._from_words(ints.tolist(), floats.tolist())
+
+
+class BeamEvaluator:
+    """Running totals of an evaluation of N-best decoding: `Evaluator` for `beam_search` / `lexicon_match` and everything they compose with.
+
+        ev = BeamEvaluator(model, beam_width=5, lexicon=lexicon)      # the search's own keywords
+        for images, labels in loader:
+            ev.update(images, labels)          # the search, then parseq_eval_beams: enqueues only
+        r = ev.result()                        # BeamEvalResult: the one copy
+
+    `match=N` evaluates `lexicon_match(images, lexicon, N, rescore=, keep_reading=, ignore_case=)` instead of a beam search.
+    `update_result(result, labels)` takes any BeamResult / LexiconBeamResult / LexiconMatchResult made elsewhere.  What is compared with
+    the label is the hypothesis' TOKENS through the test-charset adapter, also under a lexicon (not `lexicon.words[...]`' spelling).  The
+    confidence of an image is exp(score) of its first live hypothesis — `model_scores` where the result has them (a weighted automaton's
+    `scores` are fused values, no log-probabilities), `scores` otherwise.  The search's refusals pass through unchanged.  `host_path`:
+    as `Evaluator`'s, per batch through `decode_beams`."""
+
+    def __init__(self, system, beam_width: int = 5, lexicon=None, roots=None, automaton=None, alpha: float = 1.0, beta: float = 0.0,
+                 refine: Optional[str] = None, refine_iters: int = 1, match: Optional[int] = None, rescore: bool = True, keep_reading: bool = False,
+                 ignore_case: bool = False) -> None:
+        self.system = system
+        self.device = torch.device(system.device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('BeamEvaluator runs on the GPU (no CPU fallback); move the model to the device first')
+        if match is not None and lexicon is None:
+            raise ValueError('BeamEvaluator: match= needs a lexicon')
+        self.beam_width, self.match = beam_width, match
+        self._search = dict(lexicon=lexicon, roots=roots, automaton=automaton, alpha=alpha, beta=beta, refine=refine, refine_iters=refine_iters)
+        self._match = dict(rescore=rescore, keep_reading=keep_reading, ignore_case=ignore_case)
+        table = adapter_table(system.tokenizer, system.charset_adapter)
+        self.host_path = table is None
+        self._table = None if self.host_path else torch.from_numpy(table).to(self.device)
+        self.reset()
+
+    def reset(self) -> None:
+        self._host = BeamEvalResult()
+        self._last = None
+        if not self.host_path:
+            self._accum = torch.zeros(_BEAM_INTS + 3, dtype=torch.int64, device=self.device)      # 25 x int64, then 3 x float64 bit patterns
+
+    @torch.inference_mode()
+    def update(self, images: Tensor, labels: Sequence[str]) -> None:
+        if images.shape[0] != len(labels):
+            raise ValueError(f'{images.shape[0]} images but {len(labels)} labels')
+        if self.match is not None:
+            result = self.system.lexicon_match(images, self._search['lexicon'], self.match, **self._match)
+        else:
+            result = self.system.beam_search(images, self.beam_width, **self._search)
+        self.update_result(result, labels)
+
+    @torch.inference_mode()
+    def update_result(self, result, labels: Sequence[str]) -> None:
+        n = len(labels)
+        if result.tokens.dim() != 3 or result.tokens.shape[0] != n:
+            raise ValueError(f'a result of shape {tuple(result.tokens.shape)} but {n} labels')
+        if self.host_path:
+            self._update_host(result, labels)
+            return
+        from . import _native
+        dev = self.device
+        encoded = torch.from_numpy(encode_ground_truth(labels)).pin_memory().to(dev, non_blocking=True)
+        _, width, steps = result.tokens.shape
+        tokens = result.tokens.to(torch.int32).contiguous()
+        scores = result.scores.to(torch.float32).contiguous()
+        lengths = result.lengths.to(torch.int32).contiguous()
+        conf = scores if result.model_scores is None else result.model_scores.to(torch.float32).contiguous()
+        hyp_rows = torch.empty((n * width, 4), dtype=torch.int32, device=dev)
+        image_rows = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        ws = torch.empty((n * (width + 3),), dtype=torch.float64, device=dev)
+        gt_width = (encoded.numel() - n) // n if n else 0
+        with _native.guard(dev):
+            _native.check(_native.lib().parseq_eval_beams(
+                _native.ptr(tokens), _native.ptr(scores), _native.ptr(lengths), _native.ptr(conf), n, width, steps, self._table.numel(),
+                _native.ptr(self._table), _native.ptr(encoded[n:]), _native.ptr(encoded), gt_width, _native.ptr(hyp_rows), _native.ptr(image_rows),
+                _native.ptr(ws), _native.ptr(self._accum), _native.stream_ptr(dev)))
+        self._last = (hyp_rows, image_rows, width)
+
+    def _update_host(self, result, labels: Sequence[str]) -> None:
+        tokenizer, adapter = self.system.tokenizer, self.system.charset_adapter
+        beams = tokenizer.decode_beams(result)                   # the tokens' characters, live slots only, in order
+        packed = torch.stack([result.scores.float(), (result.scores if result.model_scores is None else result.model_scores).float()]).cpu()
+        live, conf = (packed[0] != float('-inf')).tolist(), packed[1].tolist()
+        hypotheses = []
+        for alts, live_row, conf_row in zip(beams, live, conf):
+            strings = iter(alts)
+            hypotheses.append([(adapter(next(strings)[0]), c) if on else None for on, c in zip(live_row, conf_row)])
+        hyp_rows, image_rows, r = host_beam_metrics(hypotheses, labels)
+        ints, floats = self._host._words()
+        more_ints, more_floats = r._words()
+        self._host = BeamEvalResult._from_words([a + b for a, b in zip(ints, more_ints)], [a + b for a, b in zip(floats, more_floats)])
+        self._last = (np.asarray(hyp_rows, dtype=np.int32).reshape(-1, 4), np.asarray(image_rows, dtype=np.int32).reshape(-1, 8), result.tokens.shape[1])
+
+    def result(self) -> BeamEvalResult:
+        """Totals so far: one copy of 224 bytes."""
+        if self.host_path:
+            return self._host
+        packed = self._accum.cpu()
+        return BeamEvalResult._from_words(packed[:_BEAM_INTS].tolist(), packed[_BEAM_INTS:].view(torch.float64).tolist())
+
+    def _rows(self, which: int, what: str):
+        if self._last is None:
+            raise RuntimeError(f'{what}() before the first update()')
+        rows = self._last[which]
+        return rows if isinstance(rows, np.ndarray) else rows.cpu().numpy()
+
+    def per_sample(self) -> np.ndarray:
+        """The last batch's image rows, int32 [B, 8]: length of the top-1 (the first live hypothesis), length of the label, their edit distance,
+        exact match, live rank of the first exact hypothesis (-1: none), smallest edit distance in the list, live hypotheses, the top-1's slot
+        (-1: every slot dead; the image then reads as the empty string)."""
+        return self._rows(1, 'per_sample')
+
+    def per_hypothesis(self) -> np.ndarray:
+        """The last batch's hypothesis rows, int32 [B, W, 4]: length of the adapted hypothesis, length of the label, edit distance, exact match;
+        a dead slot's row is [-1, -1, -1, 0]."""
+        return self._rows(0, 'per_hypothesis').reshape(-1, self._last[2], 4)
+
+    def reduce(self, process_group=None) -> BeamEvalResult:
+        """`result()` summed over the ranks of `process_group` (None = the default group).  Host tensors: works on gloo."""
+        return reduce_beam_result(self.result(), process_group)

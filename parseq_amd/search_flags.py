@@ -1,0 +1,193 @@
+"""The search flags of the command lines (read.py, test.py, tools/tune_fusion.py): what --beam / --lexicon / --priors / --lm / --pattern /
+--lm-weight / --char-bonus / --match / --refine-beams ask for, which of them go together, and the arguments of `beam_search` /
+`lexicon_match` / `BeamEvaluator` they turn into.  One set of composition and refusal rules for every command line: a contradiction ends
+in `parser.error`.  The resolvers read `args.nbest` and `args.boxes` too; a command line without those flags sets them (test.py: the
+N-best is the whole beam, no boxes)."""
+from collections import namedtuple
+
+LEXICON_BEAM = 8      # --beam under --lexicon when none is given
+MATCH_N = 8           # --match without a number
+LM_ORDER = 3          # --lm without --lm-order
+
+
+def load_word_list(path):
+    """The words of a lexicon file: one per line, surrounding white space and empty lines dropped."""
+    with open(path, encoding='utf-8') as fh:
+        return [w for w in (line.strip() for line in fh) if w]
+
+
+def load_word_counts(path):
+    """(words, counts) of a lexicon file with priors: per non-empty line a word and, after white space, its count (a number, not negative)."""
+    words, counts = [], []
+    with open(path, encoding='utf-8') as fh:
+        for number, line in enumerate(fh, 1):
+            fields = line.split()
+            if not fields:
+                continue
+            try:
+                if len(fields) != 2 or not float(fields[1]) >= 0 or float(fields[1]) == float('inf'):
+                    raise ValueError
+            except ValueError:
+                raise ValueError(f'{path}, line {number}: expected a word and its count, got {line.strip()!r}') from None
+            words.append(fields[0])
+            counts.append(float(fields[1]))
+    return words, counts
+
+
+def build_automaton(model, kind, args):
+    """The automaton of --priors / --lm / --pattern for the model's charset, on the device."""
+    from parseq_amd.automaton import Automaton
+    if kind == 'priors':
+        automaton = Automaton.from_lexicon(*load_word_counts(args.lexicon), model.tokenizer, fold_case=True)
+    elif kind == 'lm':
+        with open(args.lm, encoding='utf-8') as fh:
+            texts = [line.rstrip('\r\n') for line in fh]
+            automaton = Automaton.ngram([t for t in texts if t.strip()], args.lm_order or LM_ORDER, model.tokenizer, fold_case=True)      # (blank lines separate, they are no empty sequences)
+    else:
+        automaton = Automaton.pattern(args.pattern, model.tokenizer)
+    return automaton.to(args.device)
+
+
+def resolve_refine(parser, args, list_flag='--nbest N'):
+    """(mode, iterations) of --refine-beams, (None, 1) for none; a contradiction ends in parser.error.  `list_flag`: how the command line that
+    asks names the flag that makes `args.nbest` positive."""
+    if args.refine_beams is None:
+        if args.refine_iters is not None:
+            parser.error('--refine-iters needs --refine-beams')
+        return None, 1
+    if args.lexicon is None and args.nbest <= 0:
+        parser.error(f'--refine-beams needs {list_flag} or --lexicon FILE')
+    iters = 1 if args.refine_iters is None else args.refine_iters
+    if iters < 1:
+        parser.error('--refine-iters must be at least 1')
+    if args.refine_beams == 'score' and iters != 1:
+        parser.error('--refine-beams score runs once: --refine-iters must be 1')
+    if args.refine_beams == 'edit' and args.lexicon is not None:
+        parser.error('--refine-beams edit is not allowed with --lexicon (an edited reading can leave the list); use score')
+    return args.refine_beams, iters
+
+
+def resolve_match(parser, args):
+    """N of --match, None without it; a contradiction ends in parser.error."""
+    if args.match is None:
+        return None
+    if args.lexicon is None:
+        parser.error('--match needs --lexicon FILE')
+    if args.beam is not None:
+        parser.error('--match is not a beam search: not with --beam')
+    if args.refine_beams == 'edit':
+        parser.error('--match with --refine-beams edit: an edited reading can leave the list (the candidates of --match are rescored already)')
+    if not 1 <= args.match <= 16:
+        parser.error('--match N must be in [1, 16]')
+    if args.nbest > args.match:
+        parser.error('--nbest must be at most --match N')
+    return args.match
+
+
+def resolve_automaton(parser, args):
+    """(kind, alpha, beta) of the weighted automaton the flags ask for — 'priors', 'lm' or 'pattern', None for none; a contradiction ends in
+    parser.error."""
+    import math
+    kinds = [k for k, on in (('priors', args.priors), ('lm', args.lm is not None), ('pattern', args.pattern is not None)) if on]
+    if len(kinds) > 1:
+        parser.error('--priors, --lm and --pattern are one automaton each: give one of them')
+    if args.priors and args.lexicon is None:
+        parser.error('--priors needs --lexicon FILE')
+    if args.lm_order is not None and args.lm is None:
+        parser.error('--lm-order needs --lm FILE')
+    if args.lm_order is not None and not 1 <= args.lm_order <= 4:
+        parser.error('--lm-order must be in [1, 4]')
+    if not kinds:
+        if args.lm_weight is not None or args.char_bonus is not None:
+            parser.error('--lm-weight and --char-bonus need --priors, --lm or --pattern')
+        return None, 1.0, 0.0
+    if args.lexicon is not None and not args.priors:
+        parser.error(f'--{kinds[0]} with --lexicon: the search walks one table (--lexicon FILE --priors makes the list the prior)')
+    if args.refine_beams is not None or args.match is not None:
+        parser.error(f'--{kinds[0]} with --refine-beams or --match: refinement under a weighted automaton is not defined')
+    if args.boxes:
+        parser.error(f'--{kinds[0]} is a beam search: not with --boxes')
+    alpha = 1.0 if args.lm_weight is None else args.lm_weight
+    beta = 0.0 if args.char_bonus is None else args.char_bonus
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        parser.error('--lm-weight and --char-bonus must be finite')
+    return kinds[0], alpha, beta
+
+
+def resolve_search(parser, args):
+    """(beam width, N) of the search the flags ask for, (None, 0) for none; a contradiction ends in parser.error."""
+    if args.lexicon is not None or args.lm is not None or args.pattern is not None:
+        nbest = args.nbest if args.nbest > 0 else 1
+        beam = args.beam if args.beam is not None else max(LEXICON_BEAM, nbest)
+        if beam < nbest:
+            parser.error('--beam must be at least --nbest')
+        return beam, nbest
+    if args.beam is not None and (args.nbest <= 0 or args.beam < args.nbest):
+        parser.error('--beam needs --nbest N with N <= the beam width')
+    return args.beam, args.nbest
+
+
+SearchFlags = namedtuple('SearchFlags', 'kind alpha beta match beam nbest refine refine_iters')
+
+
+def resolve_flags(parser, args, list_flag='--nbest N'):
+    """All of the above in the order their refusals take precedence: SearchFlags(kind, alpha, beta, match, beam, nbest, refine, refine_iters)."""
+    kind, alpha, beta = resolve_automaton(parser, args)
+    match = resolve_match(parser, args)
+    beam, nbest = resolve_search(parser, args)
+    refine, refine_iters = resolve_refine(parser, args, list_flag)
+    return SearchFlags(kind, alpha, beta, match, beam, nbest, refine, refine_iters)
+
+
+def add_evaluation_flags(parser):
+    """The search flags of a command line that evaluates (test.py, tools/tune_fusion.py), named as read.py names them; there is no --nbest
+    (the whole beam is evaluated) and no --boxes."""
+    parser.add_argument('--beam', type=int, default=None, metavar='W',
+                        help=f'Evaluate a beam search of this width and its W-best list (default under --lexicon / --lm / --pattern: {LEXICON_BEAM})')
+    parser.add_argument('--lexicon', default=None, metavar='FILE', help='One word list (one word per line) for every dataset: the search is constrained to it')
+    parser.add_argument('--priors', action='store_true', help='With --lexicon: a second column holds counts, the words are a prior')
+    parser.add_argument('--lm', default=None, metavar='FILE', help='Fuse a character n-gram model counted from this text file into the search')
+    parser.add_argument('--lm-order', type=int, default=None, dest='lm_order', metavar='N', help=f'Order of --lm, 1 to 4 (default {LM_ORDER})')
+    parser.add_argument('--pattern', default=None, metavar='REGEX', help='Read only what fully matches this regular expression')
+    parser.add_argument('--lm-weight', type=float, default=None, dest='lm_weight', metavar='A', help='Weight of the prior of --priors / --lm / --pattern (default 1)')
+    parser.add_argument('--char-bonus', type=float, default=None, dest='char_bonus', metavar='B', help='Added per character read, with --priors / --lm / --pattern (default 0)')
+    parser.add_argument('--match', type=int, nargs='?', const=MATCH_N, default=None, metavar='N',
+                        help=f'With --lexicon: read freely, then let the model choose among the N (default {MATCH_N}) nearest words of the list')
+    parser.add_argument('--refine-beams', default=None, choices=['edit', 'score'], dest='refine_beams', help="Refine the alternatives with the model's cloze pass and rank them again")
+    parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
+
+
+def search_requested(args) -> bool:
+    """Whether any search flag was given: without one an evaluation stays the greedy one."""
+    return (args.beam is not None or args.lexicon is not None or args.priors or args.lm is not None or args.lm_order is not None or args.pattern is not None
+            or args.lm_weight is not None or args.char_bonus is not None or args.match is not None or args.refine_beams is not None or args.refine_iters is not None)
+
+
+def resolve_evaluation_flags(parser, args):
+    """SearchFlags of a command line made with `add_evaluation_flags`, None without a search flag: read.py's rules with the N-best = the beam."""
+    if not search_requested(args):
+        return None
+    if args.beam is not None and args.beam < 1:
+        parser.error('--beam must be at least 1')
+    args.nbest, args.boxes = (args.beam if args.beam is not None and args.match is None else 0), False
+    return resolve_flags(parser, args, list_flag='--beam W')
+
+
+def evaluator_arguments(model, args, flags):
+    """The keywords of `BeamEvaluator(model, ...)` for resolved `flags`: the tables (lexicon, automaton) are built once and serve every dataset."""
+    if flags.kind is not None:
+        return dict(beam_width=flags.beam, automaton=build_automaton(model, flags.kind, args), alpha=flags.alpha, beta=flags.beta)
+    kwargs = {}
+    if args.lexicon is not None:
+        from parseq_amd.lexicon import Lexicon
+        kwargs['lexicon'] = Lexicon(load_word_list(args.lexicon), model.tokenizer, fold_case=True, max_label_length=model.model.max_label_length).to(args.device)
+    if flags.match is not None:
+        return dict(kwargs, match=flags.match)
+    if flags.refine is not None:
+        kwargs.update(refine=flags.refine, refine_iters=flags.refine_iters)
+    return dict(kwargs, beam_width=flags.beam)
+
+
+def evaluation_width(flags) -> int:
+    """Hypotheses per image of the search `flags` ask for: the W of the table's Hit@W."""
+    return flags.match if flags.match is not None else flags.beam

@@ -26,6 +26,8 @@ from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.preprocess import resize_batch
+from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, build_automaton, load_word_counts, load_word_list, resolve_automaton,  # noqa: F401
+                                      resolve_flags, resolve_match, resolve_refine, resolve_search)
 
 
 @torch.inference_mode()
@@ -196,17 +198,6 @@ def read_regions(model, files, region_files, beam=None, nbest=0, words=None, lis
     return lines
 
 
-LEXICON_BEAM = 8      # --beam under --lexicon when none is given
-MATCH_N = 8           # --match without a number
-LM_ORDER = 3          # --lm without --lm-order
-
-
-def load_word_list(path):
-    """The words of a lexicon file: one per line, surrounding white space and empty lines dropped."""
-    with open(path, encoding='utf-8') as fh:
-        return [w for w in (line.strip() for line in fh) if w]
-
-
 @torch.inference_mode()
 def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, device='cuda', refine=None):
     """[(file, [(word, log-probability)] best first, at most `nbest`)]: one beam search of width `beam_width` constrained to `words`
@@ -223,38 +214,6 @@ def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, de
     search = {} if refine is None else {'refine': refine}
     beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width, lexicon=lexicon, **search), lexicon)
     return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
-
-
-def load_word_counts(path):
-    """(words, counts) of a lexicon file with priors: per non-empty line a word and, after white space, its count (a number, not negative)."""
-    words, counts = [], []
-    with open(path, encoding='utf-8') as fh:
-        for number, line in enumerate(fh, 1):
-            fields = line.split()
-            if not fields:
-                continue
-            try:
-                if len(fields) != 2 or not float(fields[1]) >= 0 or float(fields[1]) == float('inf'):
-                    raise ValueError
-            except ValueError:
-                raise ValueError(f'{path}, line {number}: expected a word and its count, got {line.strip()!r}') from None
-            words.append(fields[0])
-            counts.append(float(fields[1]))
-    return words, counts
-
-
-def build_automaton(model, kind, args):
-    """The automaton of --priors / --lm / --pattern for the model's charset, on the device."""
-    from parseq_amd.automaton import Automaton
-    if kind == 'priors':
-        automaton = Automaton.from_lexicon(*load_word_counts(args.lexicon), model.tokenizer, fold_case=True)
-    elif kind == 'lm':
-        with open(args.lm, encoding='utf-8') as fh:
-            texts = [line.rstrip('\r\n') for line in fh]
-            automaton = Automaton.ngram([t for t in texts if t.strip()], args.lm_order or LM_ORDER, model.tokenizer, fold_case=True)      # (blank lines separate, they are no empty sequences)
-    else:
-        automaton = Automaton.pattern(args.pattern, model.tokenizer)
-    return automaton.to(args.device)
 
 
 def automaton_batch(model, batch, beam_width, automaton, alpha, beta):
@@ -352,84 +311,6 @@ def build_parser():
     return parser
 
 
-def resolve_refine(parser, args):
-    """(mode, iterations) of --refine-beams, (None, 1) for none; a contradiction ends in parser.error."""
-    if args.refine_beams is None:
-        if args.refine_iters is not None:
-            parser.error('--refine-iters needs --refine-beams')
-        return None, 1
-    if args.lexicon is None and args.nbest <= 0:
-        parser.error('--refine-beams needs --nbest N or --lexicon FILE')
-    iters = 1 if args.refine_iters is None else args.refine_iters
-    if iters < 1:
-        parser.error('--refine-iters must be at least 1')
-    if args.refine_beams == 'score' and iters != 1:
-        parser.error('--refine-beams score runs once: --refine-iters must be 1')
-    if args.refine_beams == 'edit' and args.lexicon is not None:
-        parser.error('--refine-beams edit is not allowed with --lexicon (an edited reading can leave the list); use score')
-    return args.refine_beams, iters
-
-
-def resolve_match(parser, args):
-    """N of --match, None without it; a contradiction ends in parser.error."""
-    if args.match is None:
-        return None
-    if args.lexicon is None:
-        parser.error('--match needs --lexicon FILE')
-    if args.beam is not None:
-        parser.error('--match is not a beam search: not with --beam')
-    if args.refine_beams == 'edit':
-        parser.error('--match with --refine-beams edit: an edited reading can leave the list (the candidates of --match are rescored already)')
-    if not 1 <= args.match <= 16:
-        parser.error('--match N must be in [1, 16]')
-    if args.nbest > args.match:
-        parser.error('--nbest must be at most --match N')
-    return args.match
-
-
-def resolve_automaton(parser, args):
-    """(kind, alpha, beta) of the weighted automaton the flags ask for — 'priors', 'lm' or 'pattern', None for none; a contradiction ends in
-    parser.error."""
-    import math
-    kinds = [k for k, on in (('priors', args.priors), ('lm', args.lm is not None), ('pattern', args.pattern is not None)) if on]
-    if len(kinds) > 1:
-        parser.error('--priors, --lm and --pattern are one automaton each: give one of them')
-    if args.priors and args.lexicon is None:
-        parser.error('--priors needs --lexicon FILE')
-    if args.lm_order is not None and args.lm is None:
-        parser.error('--lm-order needs --lm FILE')
-    if args.lm_order is not None and not 1 <= args.lm_order <= 4:
-        parser.error('--lm-order must be in [1, 4]')
-    if not kinds:
-        if args.lm_weight is not None or args.char_bonus is not None:
-            parser.error('--lm-weight and --char-bonus need --priors, --lm or --pattern')
-        return None, 1.0, 0.0
-    if args.lexicon is not None and not args.priors:
-        parser.error(f'--{kinds[0]} with --lexicon: the search walks one table (--lexicon FILE --priors makes the list the prior)')
-    if args.refine_beams is not None or args.match is not None:
-        parser.error(f'--{kinds[0]} with --refine-beams or --match: refinement under a weighted automaton is not defined')
-    if args.boxes:
-        parser.error(f'--{kinds[0]} is a beam search: not with --boxes')
-    alpha = 1.0 if args.lm_weight is None else args.lm_weight
-    beta = 0.0 if args.char_bonus is None else args.char_bonus
-    if not (math.isfinite(alpha) and math.isfinite(beta)):
-        parser.error('--lm-weight and --char-bonus must be finite')
-    return kinds[0], alpha, beta
-
-
-def resolve_search(parser, args):
-    """(beam width, N) of the search the flags ask for, (None, 0) for none; a contradiction ends in parser.error."""
-    if args.lexicon is not None or args.lm is not None or args.pattern is not None:
-        nbest = args.nbest if args.nbest > 0 else 1
-        beam = args.beam if args.beam is not None else max(LEXICON_BEAM, nbest)
-        if beam < nbest:
-            parser.error('--beam must be at least --nbest')
-        return beam, nbest
-    if args.beam is not None and (args.nbest <= 0 or args.beam < args.nbest):
-        parser.error('--beam needs --nbest N with N <= the beam width')
-    return args.beam, args.nbest
-
-
 def main(argv=None):
     parser = build_parser()
     args, unknown = parser.parse_known_args(argv)
@@ -438,10 +319,7 @@ def main(argv=None):
 
     if args.boxes and (args.nbest > 0 or args.lexicon is not None):
         parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
-    kind, alpha, beta = resolve_automaton(parser, args)
-    match = resolve_match(parser, args)
-    beam, nbest = resolve_search(parser, args)
-    refine, refine_iters = resolve_refine(parser, args)
+    kind, alpha, beta, match, beam, nbest, refine, refine_iters = resolve_flags(parser, args)
     files = args.images or []
     if args.regions is not None and args.polygons is not None:
         parser.error('--polygons and --regions are two ways to cut the same scenes: give one of them')

@@ -4,6 +4,9 @@
 
     ./test.py pretrained=parseq --data_root data [--batch_size 512] [--cased] [--punctuation] [--rotation 90] [name:type=value ...]
     ./test.py path/to/lightning.ckpt --data_root data refine_iters:int=2
+    ./test.py pretrained=parseq --data_root data --beam 5     a beam search instead of the greedy decode: the table gains Hit@5, Oracle 1 - NED, MRR
+    ./test.py pretrained=parseq --data_root data --lexicon words.txt [--beam 8] [--match [N]] [--priors] [--refine-beams score]
+    ./test.py pretrained=parseq --data_root data --lm corpus.txt [--lm-order 3] [--lm-weight 0.3] [--char-bonus 0.5]     or --pattern REGEX
 
 A dataset is a sub-directory of `--data_root` that holds a `gt.txt`: one sample per line, the image path (relative to that
 sub-directory) and the label separated by the first run of whitespace — the input format of the reference's
@@ -16,13 +19,19 @@ dropped if longer than `max_label_length`, mapped into the test charset, dropped
 host (PIL) and uploaded as they are; the rotation of `--rotation` (`img.rotate(rotation, expand=True)` of the reference transform,
 `strhub/data/module.py:72-73`), the bicubic resize, the model and the metrics (parseq_amd.evaluate.Evaluator, one per dataset) run on
 the device with no copy back until a dataset is done.
+
+With a search flag (the flags, their composition and their refusals are read.py's: parseq_amd/search_flags.py) a dataset is evaluated by
+`parseq_amd.evaluate.BeamEvaluator` instead: the five columns then describe the first hypothesis of the list, and
+three more say how often the label is anywhere in the W hypotheses, how near the nearest of them comes, and the mean reciprocal rank.
+ONE lexicon / language model / pattern serves every dataset; per-image lexicons (the 50-word protocol of IIIT5k / SVT) are out of scope.
+Without a search flag the table and the log are what they were.
 """
 import argparse
 import os
 import string
 import sys
 from dataclasses import dataclass
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -30,8 +39,9 @@ from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.data import parse_gt_line, preprocess_label, read_gt  # noqa: F401  (the first two keep their names here)
-from parseq_amd.evaluate import Evaluator
+from parseq_amd.evaluate import BeamEvaluator, Evaluator
 from parseq_amd.preprocess import resize_batch
+from parseq_amd.search_flags import add_evaluation_flags, evaluation_width, evaluator_arguments, resolve_evaluation_flags
 from parseq_amd.tokenizer import CharsetAdapter  # noqa: F401
 
 
@@ -43,6 +53,14 @@ class Result:
     ned: float
     confidence: float
     label_length: float
+
+
+@dataclass
+class BeamTableResult(Result):
+    """A row of the extended table: the reference's five columns for the first hypothesis, then the N-best's."""
+    hit: float = 0.0             # 100 * share of the images whose label is among the W hypotheses
+    oracle_ned: float = 0.0      # 100 * (1 - mean smallest normalised edit distance over the list)
+    mrr: float = 0.0             # mean reciprocal rank of the label
 
 
 def read_dataset(root: str, name: str, charset_test: str, max_label_length: int) -> List[Tuple[str, str]]:
@@ -59,16 +77,21 @@ def load_crops(files, device):
     return [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
 
 
-def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0) -> Result:
+def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0, search: Optional[dict] = None, width: int = 0) -> Result:
+    """One dataset's row.  `search`: the keywords of `BeamEvaluator` (a beam search or a lexicon match instead of the greedy decode); the row is
+    then a `BeamTableResult` whose Hit column counts the first `width` hypotheses per image (`search_flags.evaluation_width`)."""
     hp = model.hparams
     samples = read_dataset(root, name, hp.charset_test, hp.max_label_length)
-    evaluator = Evaluator(model)
+    evaluator = Evaluator(model) if search is None else BeamEvaluator(model, **search)
     for at in range(0, len(samples), batch_size):
         chunk = samples[at:at + batch_size]
         images = resize_batch(load_crops([f for f, _ in chunk], model.device), tuple(hp.img_size), rotation=rotation)      # uint8 [N, 3, H, W]
         evaluator.update(images, [label for _, label in chunk])
     r = evaluator.result()
     n = r.num_samples
+    if search is not None:
+        return BeamTableResult(name, n, 100 * r.accuracy, 100 * (1 - r.ned) if n else 0.0, 100 * r.confidence, r.label_length, 100 * r.hit_at(width),
+                               100 * (1 - r.oracle_ned) if n else 0.0, r.mrr)
     if not n:
         return Result(name, 0, 0.0, 0.0, 0.0, 0.0)
     return Result(name, n, 100 * r.correct / n, 100 * (1 - r.ned / n), 100 * r.confidence / n, r.label_length / n)
@@ -95,6 +118,27 @@ def print_results_table(results: List[Result], file=None) -> None:
     print(row(Result('Combined', total, mean('accuracy'), mean('ned'), mean('confidence'), mean('label_length'))), file=file)
 
 
+def print_beam_results_table(results: List[BeamTableResult], width: int, file=None) -> None:
+    """The table of an N-best evaluation: the reference's columns, then Hit@W, Oracle 1 - NED and MRR; the same layout and `Combined` row."""
+    name_width = max([len(r.dataset) for r in results] + [len('Combined')])
+    heads = ('# samples', 'Accuracy', '1 - NED', 'Confidence', 'Label Length', f'Hit@{width}', 'Oracle 1 - NED', 'MRR')
+    fields = ('accuracy', 'ned', 'confidence', 'label_length', 'hit', 'oracle_ned', 'mrr')
+
+    def row(r: BeamTableResult) -> str:
+        cells = [f'{r.num_samples:d}'] + [f'{getattr(r, f):.2f}' for f in fields[:-1]] + [f'{r.mrr:.4f}']
+        return ' | '.join(['| ' + r.dataset.ljust(name_width)] + [c.rjust(w) for c, w in zip(cells, widths)]) + ' |'
+
+    widths = [max(len(h), 6) for h in heads]             # '100.00' and '0.1234' fit under the short heads too
+    print(' | '.join(['| ' + 'Dataset'.ljust(name_width)] + [h.rjust(w) for h, w in zip(heads, widths)]) + ' |', file=file)
+    print('|:' + '-' * name_width + ':|' + '|'.join('-' * (w + 1) + ':' for w in widths) + '|', file=file)
+    total = sum(r.num_samples for r in results)
+    for r in results:
+        print(row(r), file=file)
+    means = [sum(r.num_samples * getattr(r, f) for r in results) / total if total else 0.0 for f in fields]
+    print('|-' + '-' * name_width + '-|' + '|'.join('-' * (w + 2) for w in widths) + '|', file=file)
+    print(row(BeamTableResult('Combined', total, *means)), file=file)
+
+
 @torch.inference_mode()
 def main(argv=None) -> List[Result]:
     parser = argparse.ArgumentParser()
@@ -105,8 +149,10 @@ def main(argv=None) -> List[Result]:
     parser.add_argument('--punctuation', action='store_true', default=False, help='Check punctuation')
     parser.add_argument('--rotation', type=int, default=0, help='Angle of rotation (counter clockwise) in degrees.')
     parser.add_argument('--device', default='cuda')
+    add_evaluation_flags(parser)
     args, unknown = parser.parse_known_args(argv)
     kwargs = parse_model_args(unknown)
+    flags = resolve_evaluation_flags(parser, args)
 
     charset_test = string.digits + string.ascii_lowercase
     if args.cased:
@@ -117,12 +163,17 @@ def main(argv=None) -> List[Result]:
     print(f'Additional keyword arguments: {kwargs}')
 
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
-    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation) for name in find_datasets(args.data_root)]
+    search = evaluator_arguments(model, args, flags) if flags is not None else None
+    width = evaluation_width(flags) if flags is not None else 0
+    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width) for name in find_datasets(args.data_root)]
     if not results:
         raise SystemExit(f'no dataset (a sub-directory with a gt.txt) under {args.data_root!r}')
     with open(args.checkpoint + '.log.txt', 'w') as log:
         for out in (log, sys.stdout):
-            print_results_table(results, out)
+            if flags is not None:
+                print_beam_results_table(results, width, out)
+            else:
+                print_results_table(results, out)
     return results
 
 
