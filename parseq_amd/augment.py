@@ -40,7 +40,7 @@ import torch
 from torch import Tensor
 
 from . import _native
-from .preprocess import MAX_SIDE, ROTATE_90, ROTATE_180, ROTATE_270, _checked
+from .preprocess import MAX_SIDE, ROTATE_90, ROTATE_180, ROTATE_270, _checked, _workspace
 
 BILINEAR, BICUBIC = 2, 3                                 # Pillow's Image.Resampling values (PARSEQ_AUG_BILINEAR / _BICUBIC)
 OP_TABLE, OP_AUTOCONTRAST, OP_EQUALIZE, OP_CONTRAST, OP_COLOR, OP_AFFINE, OP_TURN = range(1, 8)      # PARSEQ_AUG_*
@@ -235,24 +235,10 @@ def _descs(images, chains):
     return descs, sizes
 
 
-def _workspace(lib, descs, n, dev):
-    need = lib.parseq_augment_workspace_bytes(descs, n)
-    if not need:
-        _native.check(-1)
-    return torch.empty((need,), dtype=torch.uint8, device=dev), need
-
-
-def _checked_gpu(images, what):
-    for im in images:
-        if not im.is_cuda:
-            raise RuntimeError(f'{what} runs on the GPU (no CPU fallback); move the decoded images to the device first')
-    return _checked(images)
-
-
 def apply_batch(images: Sequence[Tensor], chains) -> list:
     """images: CUDA uint8 tensors [H_i, W_i, 3]; chains[i]: at most three (name, *args) tuples.  Returns the augmented uint8
     [H'_i, W'_i, 3] tensors, each bit for bit what the Pillow calls of the module docstring give (parseq_op_augment, one chain per call)."""
-    keep = _checked_gpu(images, 'apply_batch')
+    keep = _checked(images, 'apply_batch')
     dev = keep[0].device
     lib = _native.lib()
     outs, hold = [], []
@@ -262,7 +248,8 @@ def apply_batch(images: Sequence[Tensor], chains) -> list:
             raise ValueError(f'{len(chains)} chains for {len(keep)} images')
         for im, chain in zip(keep, chains):
             descs, sizes = _descs([im], [chain])
-            ws, need = _workspace(lib, descs, 1, dev)
+            need = lib.parseq_augment_workspace_bytes(descs, 1)
+            ws = _workspace(need, dev)
             out = torch.empty(sizes[0] + (3,), dtype=torch.uint8, device=dev)
             _native.check(lib.parseq_op_augment(descs, _native.ptr(out), _native.ptr(ws), need, _native.stream_ptr(dev)))
             outs.append(out)
@@ -274,14 +261,15 @@ def apply_batch(images: Sequence[Tensor], chains) -> list:
 def augment_resize_batch(images: Sequence[Tensor], chains, size=(32, 128)) -> Tensor:
     """images: CUDA uint8 tensors [H_i, W_i, 3] (sizes may differ); chains as for `apply_batch`.  Returns uint8 [N, 3, size[0], size[1]]:
     every image augmented, then resized as `resize_batch` resizes it, in one call (one launch per chain stage, then the resize kernel)."""
-    keep = _checked_gpu(images, 'augment_resize_batch')
+    keep = _checked(images, 'augment_resize_batch')
     dev = keep[0].device
     n = len(keep)
     descs, _ = _descs(keep, chains)
     lib = _native.lib()
     out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
     with _native.guard(dev):
-        ws, need = _workspace(lib, descs, n, dev)
+        need = lib.parseq_augment_workspace_bytes(descs, n)
+        ws = _workspace(need, dev)
         _native.check(lib.parseq_augment_resize_bicubic(descs, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), need, _native.stream_ptr(dev)))
     torch.cuda.current_stream(dev).synchronize()         # the descriptor array is host memory read by an asynchronous copy
     return out

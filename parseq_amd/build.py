@@ -3,7 +3,7 @@
 The shared library is the product: there is no pure-Python or CPU execution path.  It is built in-tree so that it
 travels with the repository snapshot to the GPU box (it is git-ignored, not gpurun-ignored).
 
-The library is eight translation units (UNITS) compiled in parallel and linked once; a unit is recompiled when the
+The library is nine translation units (UNITS) compiled in parallel and linked once; a unit is recompiled when the
 SHA-256 of its source, of every header under csrc/, of include/parseq_hip.h and of the compiler flags differs from the one
 recorded beside its object file (content, not mtime: a fresh checkout with an up-to-date library does not rebuild, an
 edited header always does).  Wall time of a full build on 8 cores: under a minute (the longest unit ≈ 45 s); the single
@@ -24,7 +24,7 @@ LIB_DIR = os.path.join(HERE, 'lib')
 OBJ_DIR = os.path.join(LIB_DIR, 'obj')          # git-ignored AND gpurun-ignored (as are the obj_<suffix> of A/B builds): only .so files travel
 LIB_PATH = os.path.join(LIB_DIR, 'libparseq_hip.so')
 STAMP_PATH = LIB_PATH + '.sha256'
-UNITS = ['lib_model', 'lib_encode', 'lib_decode', 'lib_train', 'lib_ops', 'kern_enc_blocks', 'kern_enc_blocks_x3', 'kern_enc_blocks_x3w']
+UNITS = ['lib_model', 'lib_encode', 'lib_decode', 'lib_train', 'lib_input', 'lib_ops', 'kern_enc_blocks', 'kern_enc_blocks_x3', 'kern_enc_blocks_x3w']
 SOURCES = [u + '.hip' for u in UNITS]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith('.h')) + [os.path.join('..', '..', 'include', 'parseq_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-pass-failed']

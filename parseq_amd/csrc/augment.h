@@ -24,14 +24,12 @@
 // LDS and applied in the same launch.  An image of more than one tile gathers its statistics once per tile (each workgroup reads
 // the whole image, at most AUG_MAX_TILES times, from L2) — no grid-wide synchronisation, no second launch.
 // Image.blend computes in SINGLE precision, the affine map and its taps in DOUBLE; both without contraction.  The *_rn intrinsics do
-// not give that — hipcc defines __dmul_rn(a, b) as a * b, carrying the `contract` flag, and fuses it with a following add once
-// inlined (AutoContrast's int(ix * scale + offset) was one off on an MI355X that way) — so every function below that does
-// floating-point arithmetic opens with AUG_NO_CONTRACT and uses plain operators: none of its operations carries the flag, wherever
-// they end up inlined (checked in the unit's LLVM IR: no fmul / fadd of augment_stage_kernel has `contract`).
+// not give that (AutoContrast's int(ix * scale + offset) was one off on an MI355X that way), so every function below that does
+// floating-point arithmetic opens with AUG_NO_CONTRACT and uses the plain-operator macros of resize.h, where the reason is told: none of
+// its operations carries the `contract` flag, wherever they end up inlined (checked in the unit's LLVM IR: no fmul / fadd of
+// augment_stage_kernel has `contract`).
 #pragma once
 #include "resize.h"
-
-#define AUG_NO_CONTRACT _Pragma("clang fp contract(off)")
 
 namespace pq {
 
@@ -116,10 +114,6 @@ __device__ __forceinline__ int aug_luma(const unsigned char* p) {
     return (int)(((unsigned)p[0] * 19595u + (unsigned)p[1] * 38470u + (unsigned)p[2] * 7471u + 0x8000u) >> 16);
 }
 
-// plain operators, not __dmul_rn / __dadd_rn: the pragma reaches the operations written in the function, not those of a callee
-#define AUG_MUL(a, b) ((a) * (b))
-#define AUG_ADD(a, b) ((a) + (b))
-
 // Pillow's BICUBIC(v, v1, v2, v3, v4, d) of Geometry.c, in its order of operations
 __device__ __forceinline__ double aug_cubic(double v1, double v2, double v3, double v4, double d) {
     AUG_NO_CONTRACT
@@ -162,17 +156,27 @@ __device__ __forceinline__ void aug_bicubic_taps(const unsigned char* src, long 
     }
 }
 
+// Where the source position (sx, sy) of an Image.transform map falls in an h x w image: false outside (written so that NaN is outside), where the
+// fill stays; else the pixel (*fx, *fy) = the floor of the position half a pixel back, and the fractions (*dx, *dy) beyond it
+__device__ __forceinline__ bool aug_source_pixel(double sx, double sy, int h, int w, int* fx, int* fy, double* dx, double* dy) {
+    AUG_NO_CONTRACT
+    if (!(sx >= 0.0 && sx < (double)w && sy >= 0.0 && sy < (double)h)) return false;
+    sx = AUG_ADD(sx, -0.5); sy = AUG_ADD(sy, -0.5);
+    *fx = (int)floor(sx); *fy = (int)floor(sy);
+    *dx = AUG_ADD(sx, -(double)*fx); *dy = AUG_ADD(sy, -(double)*fy);
+    return true;
+}
+
 // one output pixel of Image.transform(AFFINE): false where the fill colour stays
 __device__ __forceinline__ bool aug_affine_pixel(const unsigned char* src, long long stride, int h, int w, const double* a, int resample,
                                                  int x, int y, unsigned char* out) {
     AUG_NO_CONTRACT
     const double xin = (double)x + 0.5, yin = (double)y + 0.5;
-    double sx = AUG_ADD(AUG_ADD(AUG_MUL(a[0], xin), AUG_MUL(a[1], yin)), a[2]);
-    double sy = AUG_ADD(AUG_ADD(AUG_MUL(a[3], xin), AUG_MUL(a[4], yin)), a[5]);
-    if (!(sx >= 0.0 && sx < (double)w && sy >= 0.0 && sy < (double)h)) return false;
-    sx = AUG_ADD(sx, -0.5); sy = AUG_ADD(sy, -0.5);
-    const int fx = (int)floor(sx), fy = (int)floor(sy);
-    const double dx = AUG_ADD(sx, -(double)fx), dy = AUG_ADD(sy, -(double)fy);
+    const double sx = AUG_ADD(AUG_ADD(AUG_MUL(a[0], xin), AUG_MUL(a[1], yin)), a[2]);
+    const double sy = AUG_ADD(AUG_ADD(AUG_MUL(a[3], xin), AUG_MUL(a[4], yin)), a[5]);
+    int fx, fy;
+    double dx, dy;
+    if (!aug_source_pixel(sx, sy, h, w, &fx, &fy, &dx, &dy)) return false;
     if (resample == AUG_BILINEAR) {
         const size_t x0 = (size_t)aug_clampi(fx, w) * 3, x1 = (size_t)aug_clampi(fx + 1, w) * 3;
         const unsigned char* r0 = src + (size_t)aug_clampi(fy, h) * stride;
@@ -438,9 +442,5 @@ void augment_stage_kernel(const AugDesc* __restrict__ descs, const size_t* __res
         }
     }
 }
-
-#undef AUG_MUL
-#undef AUG_ADD
-#undef AUG_NO_CONTRACT
 
 }  // namespace pq

@@ -1,8 +1,9 @@
 // lib_internal.h — what the translation units of libparseq_hip.so share: error reporting, the device guard, the per-family
 // event profiler, the model / plan objects behind include/parseq_hip.h and the launch helpers of the generic kernels.
 // The library is split into lib_model.hip (model + plan objects), lib_encode.hip / lib_decode.hip (encode; decode / forward),
-// lib_train.hip (training step) and lib_ops.hip (per-kernel test entry points, resize, post-process) so that build() compiles
-// them in parallel; kernels are templates or file-local (`static __global__`), so every unit carries the instantiations it launches.
+// lib_train.hip (training step), lib_input.hip (the input path: resize, rotate, augment, rectify) and lib_ops.hip (post-process,
+// evaluation, per-kernel test entry points) so that build() compiles them in parallel; kernels are templates or file-local
+// (`static __global__`), so every unit carries the instantiations it launches.
 #pragma once
 #include "../../include/parseq_hip.h"
 
@@ -21,7 +22,6 @@
 #include "common.h"
 #include "decoder_attn.h"
 #include "decoder_step.h"
-#include "resize.h"
 #include "encoder_attn.h"
 #include "encoder_panel.h"
 #include "encoder_mlp.h"

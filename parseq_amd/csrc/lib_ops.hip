@@ -1,512 +1,7 @@
-// libparseq_hip.so — input resize, post-process, and the per-kernel entry points the parity tests call.
+// libparseq_hip.so — post-process, evaluation, and the per-kernel entry points the parity tests call.
 #include "lib_internal.h"
 #include "eval_metrics.h"
 #include "eval_beams.h"
-#include "rectify_mesh.h"
-
-// -------------------------------------------------------------------------------------------------------------------
-static int resize_taps(int in_size, int out_size) {
-    const double scale = (double)in_size / (double)out_size;
-    const double support = 2.0 * (scale < 1.0 ? 1.0 : scale);
-    return (int)ceil(support) * 2 + 1;
-}
-
-extern "C" size_t parseq_resize_workspace_bytes(int batch) { return batch > 0 ? (size_t)batch * sizeof(ImageDesc) : 0; }
-
-extern "C" int parseq_resize_bicubic(const parseq_image_desc* images, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
-                                     void* stream) {
-    static_assert(sizeof(parseq_image_desc) == sizeof(ImageDesc), "descriptor layouts must match");
-    if (!images || !out || !workspace) return fail(PARSEQ_E_INVALID, "null images / out / workspace");
-    if (batch <= 0 || out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, output %dx%d", batch, out_h, out_w);
-    int ksh = 1, ksv = 1;
-    for (int i = 0; i < batch; ++i) {
-        const parseq_image_desc& d = images[i];
-        if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
-            return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
-        ksh = std::max(ksh, resize_taps(d.width, out_w));
-        ksv = std::max(ksv, resize_taps(d.height, out_h));
-    }
-    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
-    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "an image is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(workspace, images, (size_t)batch * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(batch), dim3(256), lds, s, reinterpret_cast<const ImageDesc*>(workspace), out_h, out_w, ksh, ksv, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// rotate, then resize: the first two steps of the reference's evaluation transform (strhub/data/module.py:72-77) in one launch
-static int check_rotated(const parseq_rotated_image_desc& d, int i) {
-    if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
-        return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
-    const bool turned = d.mode == PARSEQ_ROTATE_90 || d.mode == PARSEQ_ROTATE_270;
-    switch (d.mode) {
-        case PARSEQ_ROTATE_NONE: case PARSEQ_ROTATE_90: case PARSEQ_ROTATE_180: case PARSEQ_ROTATE_270:
-            if (d.rot_height != (turned ? d.width : d.height) || d.rot_width != (turned ? d.height : d.width))
-                return fail(PARSEQ_E_INVALID, "image %d: mode %d turns %dx%d into %dx%d, not %dx%d", i, d.mode, d.height, d.width,
-                            turned ? d.width : d.height, turned ? d.height : d.width, d.rot_height, d.rot_width);
-            break;
-        case PARSEQ_ROTATE_AFFINE:
-            if (d.rot_height <= 0 || d.rot_width <= 0) return fail(PARSEQ_E_INVALID, "image %d: rotated size %dx%d", i, d.rot_height, d.rot_width);
-            break;
-        default: return fail(PARSEQ_E_INVALID, "image %d: unknown rotation mode %d", i, d.mode);
-    }
-    if (std::max(std::max(d.height, d.width), std::max(d.rot_height, d.rot_width)) > PARSEQ_ROTATE_MAX_SIDE)
-        return fail(PARSEQ_E_INVALID, "image %d: %dx%d rotated to %dx%d, a side is above %d (the map is 32-bit fixed point)", i, d.height, d.width,
-                    d.rot_height, d.rot_width, PARSEQ_ROTATE_MAX_SIDE);
-    return 0;
-}
-
-extern "C" size_t parseq_rotate_resize_workspace_bytes(int batch) { return batch > 0 ? (size_t)batch * sizeof(RotatedImageDesc) : 0; }
-
-extern "C" int parseq_rotate_resize_bicubic(const parseq_rotated_image_desc* images, int batch, int out_h, int out_w, uint8_t* out,
-                                            void* workspace, void* stream) {
-    static_assert(sizeof(parseq_rotated_image_desc) == sizeof(RotatedImageDesc) && offsetof(parseq_rotated_image_desc, a) == offsetof(RotatedImageDesc, a) &&
-                  PARSEQ_ROTATE_AFFINE == ROT_AFFINE && PARSEQ_ROTATE_MAX_SIDE == ROT_MAX_SIDE, "descriptor layouts must match");
-    if (!images || !out || !workspace) return fail(PARSEQ_E_INVALID, "null images / out / workspace");
-    if (batch <= 0 || out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: batch %d, output %dx%d", batch, out_h, out_w);
-    int ksh = 1, ksv = 1;
-    for (int i = 0; i < batch; ++i) {
-        CHK(check_rotated(images[i], i));
-        ksh = std::max(ksh, resize_taps(images[i].rot_width, out_w));
-        ksv = std::max(ksv, resize_taps(images[i].rot_height, out_h));
-    }
-    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
-    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "a rotated image is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
-    hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpyAsync(workspace, images, (size_t)batch * sizeof(RotatedImageDesc), hipMemcpyHostToDevice, s));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(rotate_resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(rotate_resize_bicubic_kernel, dim3(batch), dim3(256), lds, s, reinterpret_cast<const RotatedImageDesc*>(workspace), out_h, out_w, ksh,
-                       ksv, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int parseq_op_rotate(const parseq_rotated_image_desc* image, uint8_t* out, void* stream) {
-    if (!image || !out) return fail(PARSEQ_E_INVALID, "null image / out");
-    CHK(check_rotated(*image, 0));
-    RotatedImageDesc im;
-    memcpy(&im, image, sizeof(im));
-    const long long pixels = (long long)im.rot_height * im.rot_width;
-    hipLaunchKernelGGL(rotate_kernel, dim3((unsigned)std::min<long long>((pixels + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, im, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// -------------------------------------------------------------------------------------------------------------------
-// training augmentation (augment.h): chains of Pillow-exact RandAugment operators, then the resize above
-// -------------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(parseq_augment_op) == sizeof(AugOp) && offsetof(parseq_augment_op, arg) == offsetof(AugOp, arg) &&
-              sizeof(parseq_augment_desc) == sizeof(AugDesc) && offsetof(parseq_augment_desc, ops) == offsetof(AugDesc, ops) &&
-              PARSEQ_AUGMENT_MAX_OPS == AUG_MAX_OPS && PARSEQ_AUG_TURN == AUG_TURN && PARSEQ_AUG_TABLE == AUG_TABLE &&
-              PARSEQ_AUG_BICUBIC == AUG_BICUBIC && PARSEQ_AUG_GAUSSIAN_BLUR == AUG_GAUSSIAN_BLUR && PARSEQ_AUG_POISSON_NOISE == AUG_POISSON_NOISE &&
-              sizeof(parseq_augment_op) == 16 + 256 && offsetof(parseq_augment_op, arg.blur.fw) == offsetof(AugOp, arg.blur.fw) &&
-              offsetof(parseq_augment_op, arg.noise.lam) == offsetof(AugOp, arg.noise.lam), "descriptor layouts must match");
-
-static bool aug_side_ok(int v) { return v >= 1 && v <= PARSEQ_ROTATE_MAX_SIDE; }
-
-static int check_augment(const parseq_augment_desc& d, int i) {
-    if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
-        return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
-    if (!aug_side_ok(d.height) || !aug_side_ok(d.width))
-        return fail(PARSEQ_E_INVALID, "image %d: %dx%d, a side is above %d", i, d.height, d.width, PARSEQ_ROTATE_MAX_SIDE);
-    if (d.num_ops < 0 || d.num_ops > PARSEQ_AUGMENT_MAX_OPS)
-        return fail(PARSEQ_E_INVALID, "image %d: %d operators, a chain holds at most %d", i, d.num_ops, PARSEQ_AUGMENT_MAX_OPS);
-    int h = d.height, w = d.width;
-    for (int k = 0; k < d.num_ops; ++k) {
-        const parseq_augment_op& op = d.ops[k];
-        if (!aug_side_ok(op.out_height) || !aug_side_ok(op.out_width))
-            return fail(PARSEQ_E_INVALID, "image %d, operator %d: output of %dx%d, each side must be in 1 .. %d", i, k, op.out_height, op.out_width,
-                        PARSEQ_ROTATE_MAX_SIDE);
-        const bool same = op.out_height == h && op.out_width == w;
-        switch (op.op) {
-            case PARSEQ_AUG_TABLE: case PARSEQ_AUG_AUTOCONTRAST: case PARSEQ_AUG_EQUALIZE: break;
-            case PARSEQ_AUG_CONTRAST: case PARSEQ_AUG_COLOR:
-                if (!(std::isfinite(op.arg.factor) && op.arg.factor >= 0.1f))
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: factor %g is out of range (finite, >= 0.1)", i, k, (double)op.arg.factor);
-                break;
-            case PARSEQ_AUG_AFFINE:
-                if (op.mode != PARSEQ_AUG_BILINEAR && op.mode != PARSEQ_AUG_BICUBIC)
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: resample %d is out of range (2 bilinear, 3 bicubic)", i, k, op.mode);
-                for (int t = 0; t < 6; ++t)
-                    if (!std::isfinite(op.arg.coef[t]))
-                        return fail(PARSEQ_E_INVALID, "image %d, operator %d: coefficient %d is out of range (not finite)", i, k, t);
-                break;
-            case PARSEQ_AUG_TURN: {
-                if (op.mode != PARSEQ_ROTATE_90 && op.mode != PARSEQ_ROTATE_180 && op.mode != PARSEQ_ROTATE_270)
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: turn %d is out of range (1, 2 or 3 quarter turns)", i, k, op.mode);
-                const bool swap = op.mode != PARSEQ_ROTATE_180;
-                if (op.out_height != (swap ? w : h) || op.out_width != (swap ? h : w))
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: turn %d makes %dx%d of %dx%d, not %dx%d", i, k, op.mode, swap ? w : h, swap ? h : w,
-                                h, w, op.out_height, op.out_width);
-                break;
-            }
-            case PARSEQ_AUG_GAUSSIAN_BLUR: {
-                if (op.arg.blur.r < 0 || op.arg.blur.r > AUG_BLUR_MAX_R)
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: blur radius r %d is out of range (0 .. %d)", i, k, op.arg.blur.r, AUG_BLUR_MAX_R);
-                const unsigned long long sum = (2ull * (unsigned)op.arg.blur.r + 1) * op.arg.blur.ww + 2ull * op.arg.blur.fw;
-                if (sum > (1ull << 24))
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: blur weights ww %u, fw %u are out of range ((2 r + 1) ww + 2 fw = %llu, above 2^24)",
-                                i, k, op.arg.blur.ww, op.arg.blur.fw, sum);
-                break;
-            }
-            case PARSEQ_AUG_POISSON_NOISE:
-                if (op.arg.noise.lam < 1 || op.arg.noise.lam > AUG_NOISE_MAX_LAM)
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: noise lam %d is out of range (1 .. %d)", i, k, op.arg.noise.lam, AUG_NOISE_MAX_LAM);
-                if (!(std::isfinite(op.arg.noise.p0) && op.arg.noise.p0 > 0.0 && op.arg.noise.p0 < 1.0))
-                    return fail(PARSEQ_E_INVALID, "image %d, operator %d: noise p0 %g is out of range (exp(-lam): finite, in (0, 1))", i, k, op.arg.noise.p0);
-                break;
-            default: return fail(PARSEQ_E_INVALID, "image %d, operator %d: unknown operator %d", i, k, op.op);
-        }
-        if (op.op != PARSEQ_AUG_AFFINE && op.op != PARSEQ_AUG_TURN && !same)
-            return fail(PARSEQ_E_INVALID, "image %d, operator %d: operator %d keeps the size, %dx%d stated for %dx%d", i, k, op.op, op.out_height,
-                        op.out_width, h, w);
-        h = op.out_height; w = op.out_width;
-    }
-    return 0;
-}
-
-struct AugLayout { size_t descs, offsets, finals, regions, total; };
-
-static size_t aug_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static AugLayout aug_layout(const parseq_augment_desc* descs, int batch) {
-    AugLayout l;
-    l.descs = 0;
-    l.offsets = aug_align((size_t)batch * sizeof(AugDesc));
-    l.finals = l.offsets + aug_align((size_t)batch * sizeof(size_t));
-    l.regions = l.finals + aug_align((size_t)batch * sizeof(ImageDesc));
-    l.total = l.regions;
-    for (int i = 0; i < batch; ++i) l.total += 2 * aug_region_bytes(descs[i]);
-    return l;
-}
-
-extern "C" size_t parseq_augment_workspace_bytes(const parseq_augment_desc* descs, int batch) {
-    if (!descs || batch <= 0) { fail(PARSEQ_E_INVALID, "null descriptors / batch %d", batch); return 0; }
-    for (int i = 0; i < batch; ++i)
-        if (check_augment(descs[i], i)) return 0;
-    return aug_layout(descs, batch).total;
-}
-
-// validates, copies the descriptors, plans the regions and runs every stage on `s`
-static int augment_run(const parseq_augment_desc* descs, int batch, void* workspace, size_t workspace_bytes, hipStream_t s, AugLayout* layout) {
-    if (!descs || !workspace) return fail(PARSEQ_E_INVALID, "null descriptors / workspace");
-    if (batch <= 0) return fail(PARSEQ_E_INVALID, "bad shape: batch %d", batch);
-    for (int i = 0; i < batch; ++i) CHK(check_augment(descs[i], i));
-    const AugLayout l = aug_layout(descs, batch);
-    if (workspace_bytes < l.total)
-        return fail(PARSEQ_E_INVALID, "workspace of %zu bytes, %zu needed (parseq_augment_workspace_bytes)", workspace_bytes, l.total);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    const AugDesc* dd = reinterpret_cast<const AugDesc*>(ws + l.descs);
-    size_t* offsets = reinterpret_cast<size_t*>(ws + l.offsets);
-    HIPCHK(hipMemcpyAsync(ws + l.descs, descs, (size_t)batch * sizeof(AugDesc), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(augment_plan_kernel, dim3(1), dim3(256), 0, s, dd, batch, ws + l.regions, offsets, reinterpret_cast<ImageDesc*>(ws + l.finals));
-    HIPCHK(hipGetLastError());
-    for (int k = 0; k < PARSEQ_AUGMENT_MAX_OPS; ++k) {
-        int tiles = 0;
-        for (int i = 0; i < batch; ++i)
-            if (descs[i].num_ops > k) tiles = std::max(tiles, aug_tiles((long long)descs[i].ops[k].out_height * descs[i].ops[k].out_width));
-        if (!tiles) break;                                   // chains are dense: no image has an operator k + 1 without an operator k
-        hipLaunchKernelGGL(augment_stage_kernel, dim3(batch, tiles), dim3(256), 0, s, dd, offsets, ws + l.regions, k);
-        HIPCHK(hipGetLastError());
-    }
-    *layout = l;
-    return 0;
-}
-
-extern "C" int parseq_augment_resize_bicubic(const parseq_augment_desc* descs, int batch, int out_h, int out_w, uint8_t* out, void* workspace,
-                                             size_t workspace_bytes, void* stream) {
-    if (!out) return fail(PARSEQ_E_INVALID, "null out");
-    if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
-    if (!descs || batch <= 0) return fail(PARSEQ_E_INVALID, "null descriptors / batch %d", batch);
-    int ksh = 1, ksv = 1;
-    for (int i = 0; i < batch; ++i) {
-        CHK(check_augment(descs[i], i));
-        const parseq_augment_desc& d = descs[i];
-        ksh = std::max(ksh, resize_taps(d.num_ops ? d.ops[d.num_ops - 1].out_width : d.width, out_w));
-        ksv = std::max(ksv, resize_taps(d.num_ops ? d.ops[d.num_ops - 1].out_height : d.height, out_h));
-    }
-    const size_t lds = sizeof(int) * ((size_t)out_w * ksh + (size_t)out_h * ksv + 2 * (size_t)(out_w + out_h));
-    if (lds > 150 * 1024) return fail(PARSEQ_E_INVALID, "an augmented image is too large for the on-chip weight tables (%zu bytes of LDS needed)", lds);
-    hipStream_t s = (hipStream_t)stream;
-    AugLayout l;
-    CHK(augment_run(descs, batch, workspace, workspace_bytes, s, &l));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(batch), dim3(256), lds, s,
-                       reinterpret_cast<const ImageDesc*>(static_cast<unsigned char*>(workspace) + l.finals), out_h, out_w, ksh, ksv, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int parseq_op_augment(const parseq_augment_desc* desc, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!desc || !out) return fail(PARSEQ_E_INVALID, "null descriptor / out");
-    hipStream_t s = (hipStream_t)stream;
-    AugLayout l;
-    CHK(augment_run(desc, 1, workspace, workspace_bytes, s, &l));
-    const int n = desc->num_ops;
-    const int h = n ? desc->ops[n - 1].out_height : desc->height, w = n ? desc->ops[n - 1].out_width : desc->width;
-    const unsigned char* last = n ? static_cast<unsigned char*>(workspace) + l.regions + (size_t)((n - 1) & 1) * aug_region_bytes(*desc) : desc->data;
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)w * 3, last, n ? (size_t)w * 3 : (size_t)desc->row_stride, (size_t)w * 3, (size_t)h, hipMemcpyDeviceToDevice, s));
-    return 0;
-}
-
-// -------------------------------------------------------------------------------------------------------------------
-// rectification of quadrilateral regions (rectify.h), alone and ahead of the resize above
-// -------------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(parseq_region_desc) == sizeof(RegionDesc) && offsetof(parseq_region_desc, coef) == offsetof(RegionDesc, coef) &&
-              offsetof(parseq_region_desc, width) == offsetof(RegionDesc, width), "descriptor layouts must match");
-
-// `strips`: the strip table of polygon regions (rectify_mesh.h), empty for quadrilaterals
-struct RectLayout { size_t regions, strips, images, tiles, dst, finals, outs, slots, total; long long n_tiles; };
-
-template <class Region>
-static int check_region_size(const Region& r, int i) {
-    if (!aug_side_ok(r.height) || !aug_side_ok(r.width))
-        return fail(PARSEQ_E_INVALID, "region %d: size %dx%d, each side must be in 1 .. %d", i, r.height, r.width, PARSEQ_ROTATE_MAX_SIDE);
-    return 0;
-}
-
-// sizes only: what parseq_rectify_workspace_bytes can know
-template <class Region>
-static RectLayout rect_layout(const Region* regions, int n, int n_images, int n_strips = 0) {
-    RectLayout l;
-    l.regions = 0;
-    l.strips = l.regions + aug_align((size_t)n * sizeof(Region));
-    l.images = l.strips + aug_align((size_t)n_strips * sizeof(MeshStrip));
-    l.tiles = l.images + aug_align((size_t)n_images * sizeof(ImageDesc));
-    l.dst = l.tiles + aug_align((size_t)(n + 1) * sizeof(int));
-    l.finals = l.dst + aug_align((size_t)n * sizeof(unsigned char*));
-    l.outs = l.finals + aug_align((size_t)n * sizeof(ImageDesc));
-    l.slots = l.outs + aug_align((size_t)n * sizeof(unsigned char*));
-    l.total = l.slots;
-    l.n_tiles = 0;
-    for (int i = 0; i < n; ++i) {
-        l.total += rect_slot_bytes(regions[i].height, regions[i].width);
-        l.n_tiles += rect_tiles(regions[i].height, regions[i].width);
-    }
-    return l;
-}
-
-extern "C" size_t parseq_rectify_workspace_bytes(const parseq_region_desc* regions, int n_regions, int n_images) {
-    if (!regions || n_regions <= 0 || n_images <= 0) { fail(PARSEQ_E_INVALID, "null regions / %d regions / %d images", n_regions, n_images); return 0; }
-    for (int i = 0; i < n_regions; ++i)
-        if (check_region_size(regions[i], i)) return 0;
-    return rect_layout(regions, n_regions, n_images).total;
-}
-
-// the source images of a rectification, quadrilaterals or strips
-static int check_rect_images(const parseq_image_desc* images, int n_images) {
-    for (int i = 0; i < n_images; ++i) {
-        const parseq_image_desc& d = images[i];
-        if (!d.data || d.height <= 0 || d.width <= 0 || d.row_stride < (int64_t)d.width * 3)
-            return fail(PARSEQ_E_INVALID, "image %d: bad descriptor (%dx%d, row stride %lld)", i, d.height, d.width, (long long)d.row_stride);
-        if (d.row_stride > INT32_MAX / d.height)
-            return fail(PARSEQ_E_INVALID, "image %d: %d rows of %lld bytes do not fit 31 bits", i, d.height, (long long)d.row_stride);
-    }
-    return 0;
-}
-
-static int check_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n) {
-    if (!images || !regions) return fail(PARSEQ_E_INVALID, "null images / regions");
-    if (n_images <= 0 || n <= 0) return fail(PARSEQ_E_INVALID, "bad shape: %d images, %d regions", n_images, n);
-    CHK(check_rect_images(images, n_images));
-    for (int i = 0; i < n; ++i) {
-        const parseq_region_desc& r = regions[i];
-        if (r.image < 0 || r.image >= n_images) return fail(PARSEQ_E_INVALID, "region %d: image index %d is outside 0 .. %d", i, r.image, n_images - 1);
-        CHK(check_region_size(r, i));
-        for (int t = 0; t < 8; ++t)
-            if (!std::isfinite(r.coef[t])) return fail(PARSEQ_E_INVALID, "region %d: coefficient %d is not finite", i, t);
-        const double w = r.width, h = r.height;
-        const double corners[4][2] = {{0.0, 0.0}, {w, 0.0}, {w, h}, {0.0, h}};
-        for (const auto& c : corners) {
-            const double den = r.coef[6] * c[0] + r.coef[7] * c[1] + 1.0;
-            if (!(den > 0.0))
-                return fail(PARSEQ_E_INVALID, "region %d: the denominator is %g at output corner (%g, %g), it must be > 0 over the output", i, den, c[0], c[1]);
-        }
-    }
-    return 0;
-}
-
-// copies images, regions (and outs, if any) into the workspace, plans and rectifies on `s`: ONE launch for all regions after the plan
-static int rectify_run(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n, uint8_t* const* outs, void* workspace,
-                       size_t workspace_bytes, hipStream_t s, RectLayout* layout) {
-    if (!workspace) return fail(PARSEQ_E_INVALID, "null workspace");
-    const RectLayout l = rect_layout(regions, n, n_images);
-    if (workspace_bytes < l.total)
-        return fail(PARSEQ_E_INVALID, "workspace of %zu bytes, %zu needed (parseq_rectify_workspace_bytes)", workspace_bytes, l.total);
-    if (l.n_tiles > RECT_MAX_TILES)                      // 256 work-items each: the launch holds fewer than 2^32 of them
-        return fail(PARSEQ_E_INVALID, "%lld tiles of %dx%d pixels in one call, at most %d", l.n_tiles, RECT_TILE, RECT_TILE, RECT_MAX_TILES);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    const RegionDesc* rr = reinterpret_cast<const RegionDesc*>(ws + l.regions);
-    const ImageDesc* ii = reinterpret_cast<const ImageDesc*>(ws + l.images);
-    int* tile_start = reinterpret_cast<int*>(ws + l.tiles);
-    unsigned char** dst = reinterpret_cast<unsigned char**>(ws + l.dst);
-    unsigned char** douts = nullptr;
-    HIPCHK(hipMemcpyAsync(ws + l.regions, regions, (size_t)n * sizeof(RegionDesc), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ws + l.images, images, (size_t)n_images * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
-    if (outs) {
-        douts = reinterpret_cast<unsigned char**>(ws + l.outs);
-        HIPCHK(hipMemcpyAsync(douts, outs, (size_t)n * sizeof(unsigned char*), hipMemcpyHostToDevice, s));
-    }
-    hipLaunchKernelGGL(rectify_plan_kernel<RegionDesc>, dim3(1), dim3(256), 0, s, rr, n, douts, ws + l.slots, tile_start, dst, reinterpret_cast<ImageDesc*>(ws + l.finals));
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(rectify_kernel, dim3((unsigned)l.n_tiles), dim3(256), 0, s, ii, n_images, rr, n, tile_start, dst);
-    HIPCHK(hipGetLastError());
-    *layout = l;
-    return 0;
-}
-
-extern "C" int parseq_rectify(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions, uint8_t* const* outs,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    static_assert(sizeof(parseq_image_desc) == sizeof(ImageDesc), "descriptor layouts must match");
-    CHK(check_rectify(images, n_images, regions, n_regions));
-    if (!outs) return fail(PARSEQ_E_INVALID, "null outs");
-    for (int i = 0; i < n_regions; ++i)
-        if (!outs[i]) return fail(PARSEQ_E_INVALID, "region %d: null output", i);
-    RectLayout l;
-    return rectify_run(images, n_images, regions, n_regions, outs, workspace, workspace_bytes, (hipStream_t)stream, &l);
-}
-
-// the resize behind a rectification: the taps and the LDS its regions need (before any device work), then resize_bicubic_kernel on the
-// ImageDesc array the plan kernel wrote
-struct RectResize { int ksh, ksv; size_t lds; };
-
-template <class Region>
-static int rect_resize_plan(const Region* regions, int n, int out_h, int out_w, RectResize* z) {
-    z->ksh = z->ksv = 1;
-    for (int i = 0; i < n; ++i) {
-        z->ksh = std::max(z->ksh, resize_taps(regions[i].width, out_w));
-        z->ksv = std::max(z->ksv, resize_taps(regions[i].height, out_h));
-    }
-    z->lds = sizeof(int) * ((size_t)out_w * z->ksh + (size_t)out_h * z->ksv + 2 * (size_t)(out_w + out_h));
-    if (z->lds > 150 * 1024)
-        return fail(PARSEQ_E_INVALID, "a rectified region is too large for the on-chip weight tables (%zu bytes of LDS needed)", z->lds);
-    return 0;
-}
-
-static int rect_resize_run(const unsigned char* finals, int n, const RectResize& z, int out_h, int out_w, uint8_t* out, hipStream_t s) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(resize_bicubic_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)z.lds));
-    hipLaunchKernelGGL(resize_bicubic_kernel, dim3(n), dim3(256), z.lds, s, reinterpret_cast<const ImageDesc*>(finals), out_h, out_w, z.ksh, z.ksv, out);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int parseq_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_region_desc* regions, int n_regions,
-                                             int out_h, int out_w, uint8_t* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!out) return fail(PARSEQ_E_INVALID, "null out");
-    if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
-    CHK(check_rectify(images, n_images, regions, n_regions));
-    RectResize z;
-    CHK(rect_resize_plan(regions, n_regions, out_h, out_w, &z));
-    hipStream_t s = (hipStream_t)stream;
-    RectLayout l;
-    CHK(rectify_run(images, n_images, regions, n_regions, nullptr, workspace, workspace_bytes, s, &l));
-    return rect_resize_run(static_cast<unsigned char*>(workspace) + l.finals, n_regions, z, out_h, out_w, out, s);
-}
-
-// -------------------------------------------------------------------------------------------------------------------
-// rectification of polygon regions as strips (rectify_mesh.h): the same plan, workspace and resize, one more table
-// -------------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(parseq_mesh_strip) == sizeof(MeshStrip) && offsetof(parseq_mesh_strip, coef) == offsetof(MeshStrip, coef) &&
-              sizeof(parseq_mesh_region_desc) == sizeof(MeshRegionDesc) && offsetof(parseq_mesh_region_desc, n_strips) == offsetof(MeshRegionDesc, n_strips) &&
-              PARSEQ_MESH_MAX_STRIPS == MESH_MAX_STRIPS, "descriptor layouts must match");
-
-extern "C" size_t parseq_mesh_rectify_workspace_bytes(const parseq_mesh_region_desc* regions, int n_regions, const parseq_mesh_strip* strips, int n_strips,
-                                                      int n_images) {
-    if (!regions || !strips || n_regions <= 0 || n_strips <= 0 || n_images <= 0) {
-        fail(PARSEQ_E_INVALID, "null regions / strips / %d regions / %d strips / %d images", n_regions, n_strips, n_images);
-        return 0;
-    }
-    for (int i = 0; i < n_regions; ++i)
-        if (check_region_size(regions[i], i)) return 0;
-    return rect_layout(regions, n_regions, n_images, n_strips).total;
-}
-
-static int check_mesh(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n, const parseq_mesh_strip* strips,
-                      int n_strips) {
-    if (!images || !regions || !strips) return fail(PARSEQ_E_INVALID, "null images / regions / strips");
-    if (n_images <= 0 || n <= 0 || n_strips <= 0) return fail(PARSEQ_E_INVALID, "bad shape: %d images, %d regions, %d strips", n_images, n, n_strips);
-    CHK(check_rect_images(images, n_images));
-    for (int i = 0; i < n; ++i) {
-        const parseq_mesh_region_desc& r = regions[i];
-        if (r.image < 0 || r.image >= n_images) return fail(PARSEQ_E_INVALID, "region %d: image index %d is outside 0 .. %d", i, r.image, n_images - 1);
-        CHK(check_region_size(r, i));
-        if (r.n_strips < 1 || r.n_strips > PARSEQ_MESH_MAX_STRIPS)
-            return fail(PARSEQ_E_INVALID, "region %d: %d strips, a region has 1 .. %d", i, r.n_strips, PARSEQ_MESH_MAX_STRIPS);
-        if (r.first_strip < 0 || r.first_strip > n_strips - r.n_strips)
-            return fail(PARSEQ_E_INVALID, "region %d: strips %d .. %d are outside the strips array of %d", i, r.first_strip, r.first_strip + r.n_strips - 1, n_strips);
-        int at = 0;
-        for (int k = 0; k < r.n_strips; ++k) {
-            const parseq_mesh_strip& s = strips[r.first_strip + k];
-            if (s.x0 != at || s.x1 <= s.x0 || s.x1 > r.width)
-                return fail(PARSEQ_E_INVALID, "region %d: strip %d covers columns %d .. %d where %d begins: the strips must tile 0 .. %d in order", i, k, s.x0,
-                            s.x1, at, r.width);
-            at = s.x1;
-            for (int t = 0; t < 8; ++t)
-                if (!std::isfinite(s.coef[t])) return fail(PARSEQ_E_INVALID, "region %d: strip %d: coefficient %d is not finite", i, k, t);
-        }
-        if (at != r.width) return fail(PARSEQ_E_INVALID, "region %d: the strips end at column %d: they must tile 0 .. %d", i, at, r.width);
-    }
-    return 0;
-}
-
-// rectify_run with the strip table: ONE launch for all regions after the plan
-static int mesh_run(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n, const parseq_mesh_strip* strips, int n_strips,
-                    uint8_t* const* outs, void* workspace, size_t workspace_bytes, hipStream_t s, RectLayout* layout) {
-    if (!workspace) return fail(PARSEQ_E_INVALID, "null workspace");
-    const RectLayout l = rect_layout(regions, n, n_images, n_strips);
-    if (workspace_bytes < l.total)
-        return fail(PARSEQ_E_INVALID, "workspace of %zu bytes, %zu needed (parseq_mesh_rectify_workspace_bytes)", workspace_bytes, l.total);
-    if (l.n_tiles > RECT_MAX_TILES)
-        return fail(PARSEQ_E_INVALID, "%lld tiles of %dx%d pixels in one call, at most %d", l.n_tiles, RECT_TILE, RECT_TILE, RECT_MAX_TILES);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    const MeshRegionDesc* rr = reinterpret_cast<const MeshRegionDesc*>(ws + l.regions);
-    const MeshStrip* ss = reinterpret_cast<const MeshStrip*>(ws + l.strips);
-    const ImageDesc* ii = reinterpret_cast<const ImageDesc*>(ws + l.images);
-    int* tile_start = reinterpret_cast<int*>(ws + l.tiles);
-    unsigned char** dst = reinterpret_cast<unsigned char**>(ws + l.dst);
-    unsigned char** douts = nullptr;
-    HIPCHK(hipMemcpyAsync(ws + l.regions, regions, (size_t)n * sizeof(MeshRegionDesc), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ws + l.strips, strips, (size_t)n_strips * sizeof(MeshStrip), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(ws + l.images, images, (size_t)n_images * sizeof(ImageDesc), hipMemcpyHostToDevice, s));
-    if (outs) {
-        douts = reinterpret_cast<unsigned char**>(ws + l.outs);
-        HIPCHK(hipMemcpyAsync(douts, outs, (size_t)n * sizeof(unsigned char*), hipMemcpyHostToDevice, s));
-    }
-    hipLaunchKernelGGL(rectify_plan_kernel<MeshRegionDesc>, dim3(1), dim3(256), 0, s, rr, n, douts, ws + l.slots, tile_start, dst,
-                       reinterpret_cast<ImageDesc*>(ws + l.finals));
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(mesh_rectify_kernel, dim3((unsigned)l.n_tiles), dim3(256), 0, s, ii, n_images, rr, n, ss, tile_start, dst);
-    HIPCHK(hipGetLastError());
-    *layout = l;
-    return 0;
-}
-
-extern "C" int parseq_mesh_rectify(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n_regions,
-                                   const parseq_mesh_strip* strips, int n_strips, uint8_t* const* outs, void* workspace, size_t workspace_bytes,
-                                   void* stream) {
-    CHK(check_mesh(images, n_images, regions, n_regions, strips, n_strips));
-    if (!outs) return fail(PARSEQ_E_INVALID, "null outs");
-    for (int i = 0; i < n_regions; ++i)
-        if (!outs[i]) return fail(PARSEQ_E_INVALID, "region %d: null output", i);
-    RectLayout l;
-    return mesh_run(images, n_images, regions, n_regions, strips, n_strips, outs, workspace, workspace_bytes, (hipStream_t)stream, &l);
-}
-
-extern "C" int parseq_mesh_rectify_resize_bicubic(const parseq_image_desc* images, int n_images, const parseq_mesh_region_desc* regions, int n_regions,
-                                                  const parseq_mesh_strip* strips, int n_strips, int out_h, int out_w, uint8_t* out, void* workspace,
-                                                  size_t workspace_bytes, void* stream) {
-    if (!out) return fail(PARSEQ_E_INVALID, "null out");
-    if (out_h <= 0 || out_w <= 0) return fail(PARSEQ_E_INVALID, "bad shape: output %dx%d", out_h, out_w);
-    CHK(check_mesh(images, n_images, regions, n_regions, strips, n_strips));
-    RectResize z;
-    CHK(rect_resize_plan(regions, n_regions, out_h, out_w, &z));
-    hipStream_t s = (hipStream_t)stream;
-    RectLayout l;
-    CHK(mesh_run(images, n_images, regions, n_regions, strips, n_strips, nullptr, workspace, workspace_bytes, s, &l));
-    return rect_resize_run(static_cast<unsigned char*>(workspace) + l.finals, n_regions, z, out_h, out_w, out, s);
-}
 
 // -------------------------------------------------------------------------------------------------------------------
 // post-processing

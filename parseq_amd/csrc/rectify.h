@@ -16,13 +16,6 @@
 #pragma once
 #include "augment.h"
 
-// as in augment.h: plain operators under the pragma, not the *_rn intrinsics, so that no operation carries the `contract` flag; the
-// division of doubles is the correctly rounded one (no fast-math in this build)
-#define AUG_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define AUG_MUL(a, b) ((a) * (b))
-#define AUG_ADD(a, b) ((a) + (b))
-#define AUG_DIV(a, b) ((a) / (b))
-
 namespace pq {
 
 constexpr int RECT_TILE = 16;                        // 16 x 16 output pixels = the 256 work-items of a workgroup
@@ -75,11 +68,10 @@ void rectify_plan_kernel(const Region* __restrict__ regions, int n, unsigned cha
 
 // the tail every Image.transform map shares: the inside test and the bicubic taps around the source position (sx, sy); false where the fill stays
 __device__ __forceinline__ bool rect_sample(const unsigned char* src, long long stride, int h, int w, double sx, double sy, unsigned char* out) {
-    AUG_NO_CONTRACT
-    if (!(sx >= 0.0 && sx < (double)w && sy >= 0.0 && sy < (double)h)) return false;
-    sx = AUG_ADD(sx, -0.5); sy = AUG_ADD(sy, -0.5);
-    const int fx = (int)floor(sx), fy = (int)floor(sy);
-    aug_bicubic_taps(src, stride, h, w, fx, fy, AUG_ADD(sx, -(double)fx), AUG_ADD(sy, -(double)fy), out);
+    int fx, fy;
+    double dx, dy;
+    if (!aug_source_pixel(sx, sy, h, w, &fx, &fy, &dx, &dy)) return false;
+    aug_bicubic_taps(src, stride, h, w, fx, fy, dx, dy, out);
     return true;
 }
 
@@ -93,39 +85,47 @@ __device__ __forceinline__ bool rect_pixel(const unsigned char* src, long long s
     return rect_sample(src, stride, h, w, sx, sy, out);
 }
 
-// grid = tile_start[n] workgroups.  Region i is written HWC, tight, at dst[i].
-static __global__ __launch_bounds__(256)
-void rectify_kernel(const ImageDesc* __restrict__ images, int n_images, const RegionDesc* __restrict__ regions, int n,
-                    const int* __restrict__ tile_start, unsigned char* const* __restrict__ dst) {
-    AUG_NO_CONTRACT
+// The front of every rectification kernel: workgroup blockIdx.x is a tile of region *region (bisection in tile_start), the work-item is pixel
+// (*x, *y) of that region.  False for a workgroup beyond the tiles and for a pixel outside the region's size.
+template <class Region>
+__device__ __forceinline__ bool rect_locate(const Region* __restrict__ regions, int n, const int* __restrict__ tile_start, int* region, int* x, int* y) {
     const int b = blockIdx.x;
-    if (b >= tile_start[n]) return;
+    if (b >= tile_start[n]) return false;
     int lo = 0, hi = n;                                                    // tile_start[lo] <= b < tile_start[hi]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
         if (tile_start[mid] <= b) lo = mid; else hi = mid;
     }
-    const RegionDesc& r = regions[lo];
-    const int oh = r.height, ow = r.width, image = r.image;
-    if ((unsigned)image >= (unsigned)n_images) return;                     // never, for descriptors the host accepted
+    const int oh = regions[lo].height, ow = regions[lo].width;
     const int t = b - tile_start[lo];
     const int across = (ow + RECT_TILE - 1) / RECT_TILE;
     const int ty = t / across, tx = t - ty * across;
-    const int x = tx * RECT_TILE + (int)(threadIdx.x % RECT_TILE), y = ty * RECT_TILE + (int)(threadIdx.x / RECT_TILE);
-    if (x >= ow || y >= oh) return;
-    const ImageDesc im = images[image];
+    *region = lo;
+    *x = tx * RECT_TILE + (int)(threadIdx.x % RECT_TILE); *y = ty * RECT_TILE + (int)(threadIdx.x / RECT_TILE);
+    return *x < ow && *y < oh;
+}
+
+// their tail: pixel (x, y) of a region ow wide, HWC and tight at `out`: v, or 0 where the fill stays
+__device__ __forceinline__ void rect_store(unsigned char* out, int ow, int x, int y, bool inside, const unsigned char* v) {
+    unsigned char* o = out + ((size_t)y * (size_t)ow + (size_t)x) * 3;
+    o[0] = inside ? v[0] : 0; o[1] = inside ? v[1] : 0; o[2] = inside ? v[2] : 0;
+}
+
+// grid = tile_start[n] workgroups.  Region i is written HWC, tight, at dst[i].
+static __global__ __launch_bounds__(256)
+void rectify_kernel(const ImageDesc* __restrict__ images, int n_images, const RegionDesc* __restrict__ regions, int n,
+                    const int* __restrict__ tile_start, unsigned char* const* __restrict__ dst) {
+    int i, x, y;
+    if (!rect_locate(regions, n, tile_start, &i, &x, &y)) return;
+    const RegionDesc& r = regions[i];
+    if ((unsigned)r.image >= (unsigned)n_images) return;                   // never, for descriptors the host accepted
+    const ImageDesc im = images[r.image];
     double a[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) a[k] = r.coef[k];
     unsigned char v[3];
-    if (!rect_pixel(im.data, im.row_stride, im.height, im.width, a, x, y, v)) v[0] = v[1] = v[2] = 0;
-    unsigned char* o = dst[lo] + ((size_t)y * (size_t)ow + (size_t)x) * 3;
-    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+    const bool inside = rect_pixel(im.data, im.row_stride, im.height, im.width, a, x, y, v);
+    rect_store(dst[i], r.width, x, y, inside, v);
 }
 
 }  // namespace pq
-
-#undef AUG_DIV
-#undef AUG_MUL
-#undef AUG_ADD
-#undef AUG_NO_CONTRACT

@@ -20,10 +20,6 @@
 #pragma once
 #include "rectify.h"
 
-#define AUG_NO_CONTRACT _Pragma("clang fp contract(off)")
-#define AUG_MUL(a, b) ((a) * (b))
-#define AUG_ADD(a, b) ((a) + (b))
-
 namespace pq {
 
 constexpr int MESH_MAX_STRIPS = 64;                  // PARSEQ_MESH_MAX_STRIPS
@@ -44,41 +40,27 @@ __device__ __forceinline__ bool mesh_pixel(const unsigned char* src, long long s
 static __global__ __launch_bounds__(256)
 void mesh_rectify_kernel(const ImageDesc* __restrict__ images, int n_images, const MeshRegionDesc* __restrict__ regions, int n,
                          const MeshStrip* __restrict__ strips, const int* __restrict__ tile_start, unsigned char* const* __restrict__ dst) {
-    AUG_NO_CONTRACT
-    const int b = blockIdx.x;
-    if (b >= tile_start[n]) return;
-    int lo = 0, hi = n;                                                    // tile_start[lo] <= b < tile_start[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tile_start[mid] <= b) lo = mid; else hi = mid;
-    }
-    const MeshRegionDesc r = regions[lo];
-    const int oh = r.height, ow = r.width, image = r.image, ns = r.n_strips;
-    if ((unsigned)image >= (unsigned)n_images || ns < 1 || ns > MESH_MAX_STRIPS) return;      // never, for descriptors the host accepted
-    const int t = b - tile_start[lo];
-    const int across = (ow + RECT_TILE - 1) / RECT_TILE;
-    const int ty = t / across, tx = t - ty * across;
+    int i, x, y;
+    if (!rect_locate(regions, n, tile_start, &i, &x, &y)) return;
+    const MeshRegionDesc r = regions[i];
+    const int ns = r.n_strips;
+    if ((unsigned)r.image >= (unsigned)n_images || ns < 1 || ns > MESH_MAX_STRIPS) return;    // never, for descriptors the host accepted
     const MeshStrip* st = strips + r.first_strip;
+    // the tile's first column: the same for every lane, and taken from the first so that the bisection below runs on scalar loads
+    const int tile_x = __builtin_amdgcn_readfirstlane(x) / RECT_TILE * RECT_TILE;
     int k = 0, kh = ns;                                                    // st[k].x0 <= the tile's first column < st[kh].x0 (st[ns].x0 = ow)
     while (kh - k > 1) {
         const int mid = (k + kh) >> 1;
-        if (st[mid].x0 <= tx * RECT_TILE) k = mid; else kh = mid;
+        if (st[mid].x0 <= tile_x) k = mid; else kh = mid;
     }
-    const int x = tx * RECT_TILE + (int)(threadIdx.x % RECT_TILE), y = ty * RECT_TILE + (int)(threadIdx.x / RECT_TILE);
-    if (x >= ow || y >= oh) return;
     while (k + 1 < ns && x >= st[k].x1) ++k;
-    const ImageDesc im = images[image];
+    const ImageDesc im = images[r.image];
     double a[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) a[c] = st[k].coef[c];
     unsigned char v[3];
-    if (!mesh_pixel(im.data, im.row_stride, im.height, im.width, a, x - st[k].x0, y, v)) v[0] = v[1] = v[2] = 0;
-    unsigned char* o = dst[lo] + ((size_t)y * (size_t)ow + (size_t)x) * 3;
-    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+    const bool inside = mesh_pixel(im.data, im.row_stride, im.height, im.width, a, x - st[k].x0, y, v);
+    rect_store(dst[i], r.width, x, y, inside, v);
 }
 
 }  // namespace pq
-
-#undef AUG_MUL
-#undef AUG_ADD
-#undef AUG_NO_CONTRACT

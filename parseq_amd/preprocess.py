@@ -64,13 +64,14 @@ def rotation_map(h: int, w: int, angle):
                                    fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5))
 
 
-def _checked(images: Sequence[Tensor]):
+def _checked(images: Sequence[Tensor], what: str):
+    """`images` as the library reads them (uint8 [H, W, 3] on the device, pixels packed), for the public function `what`."""
     if len(images) == 0:
         raise ValueError('empty batch')
     keep = []
     for i, im in enumerate(images):
         if not im.is_cuda:
-            raise RuntimeError('resize_batch runs on the GPU (no CPU fallback); move the decoded images to the device first')
+            raise RuntimeError(f'{what} runs on the GPU (no CPU fallback); move the decoded images to the device first')
         if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
             raise ValueError(f'image {i}: expected uint8 [H, W, 3], got {im.dtype} {list(im.shape)}')
         if im.stride(2) != 1 or im.stride(1) != 3:
@@ -86,6 +87,21 @@ def _angles(rotation, n: int):
     if len(angles) != n:
         raise ValueError(f'{len(angles)} rotations for {n} images')
     return angles
+
+
+def _workspace(need: int, dev) -> Tensor:
+    """The workspace a *_workspace_bytes function asked for; 0 means the library refused the descriptors: its message is raised."""
+    if need == 0:
+        _native.check(-1)
+    return torch.empty((need,), dtype=torch.uint8, device=dev)
+
+
+def _image_descs(keep):
+    images = (_native.ImageDesc * len(keep))()
+    for d, im in zip(images, keep):
+        d.data = im.data_ptr()
+        d.height, d.width, d.row_stride = im.shape[0], im.shape[1], im.stride(0)
+    return images
 
 
 def _rotated_descs(images, angles):
@@ -106,7 +122,7 @@ def rotate_batch(images: Sequence[Tensor], angle) -> list:
     """images: CUDA uint8 tensors [H_i, W_i, 3]; angle: degrees counter clockwise, one value or one per image.  Returns the uint8
     [nh_i, nw_i, 3] tensors PIL's Image.rotate(angle, expand=True) gives (parseq_op_rotate, one launch per image: the rotation on
     its own is the kernel tests' view of the map — `resize_batch(..., rotation=)` never materialises these)."""
-    keep = _checked(images)
+    keep = _checked(images, 'rotate_batch')
     dev = keep[0].device
     descs, sizes = _rotated_descs(keep, _angles(angle, len(keep)))
     lib = _native.lib()
@@ -121,25 +137,19 @@ def resize_batch(images: Sequence[Tensor], size=(32, 128), rotation=0) -> Tensor
     """images: CUDA uint8 tensors [H_i, W_i, 3] (sizes may differ).  Returns uint8 [N, 3, size[0], size[1]].
     rotation: degrees counter clockwise (int or float), or one value per image: each image is first turned as PIL's
     Image.rotate(rotation, expand=True) turns it, inside the same launch."""
-    keep = _checked(images)
+    keep = _checked(images, 'resize_batch')
     dev = keep[0].device
     n = len(keep)
     angles = _angles(rotation, n)
-    plain = all(a % 360.0 == 0 for a in angles)          # nothing turns: the resize alone, as before there was a rotation
-    descs = (_native.ImageDesc * n)() if plain else _rotated_descs(keep, angles)[0]
     lib = _native.lib()
-    out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
-    if plain:
-        for d, im in zip(descs, keep):
-            d.data = im.data_ptr()
-            d.height, d.width, d.row_stride = im.shape[0], im.shape[1], im.stride(0)
-        ws = torch.empty((lib.parseq_resize_workspace_bytes(n),), dtype=torch.uint8, device=dev)
-        with _native.guard(dev):
-            _native.check(lib.parseq_resize_bicubic(descs, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), _native.stream_ptr(dev)))
+    if all(a % 360.0 == 0 for a in angles):              # nothing turns: the resize alone, as before there was a rotation
+        descs, query, call = _image_descs(keep), lib.parseq_resize_workspace_bytes, lib.parseq_resize_bicubic
     else:
-        ws = torch.empty((lib.parseq_rotate_resize_workspace_bytes(n),), dtype=torch.uint8, device=dev)
-        with _native.guard(dev):
-            _native.check(lib.parseq_rotate_resize_bicubic(descs, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), _native.stream_ptr(dev)))
+        descs, query, call = _rotated_descs(keep, angles)[0], lib.parseq_rotate_resize_workspace_bytes, lib.parseq_rotate_resize_bicubic
+    out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
+    ws = torch.empty((query(n),), dtype=torch.uint8, device=dev)
+    with _native.guard(dev):
+        _native.check(call(descs, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), _native.stream_ptr(dev)))
     # the descriptor array is host memory read by an asynchronous copy: keep it (and the inputs) alive until the stream has passed
     torch.cuda.current_stream(dev).synchronize()
     return out
@@ -227,9 +237,9 @@ def map_to_source(coeffs, size, img_size, points):
     return out
 
 
-def region_descs(regions, sizes=None, n_images=None):
-    """[(image_index, (h, w), coeffs)] of `regions`: each (image_index, quad) — sized by `sizes[i]` or `region_size` — or
-    (image_index, coeffs8, (h, w)) verbatim.  Everything the library would refuse is a ValueError here."""
+def _described(regions, sizes, n_images, verbatim, from_shape, default_size):
+    """[(image_index, (h, w), map)] of `regions`, quadrilaterals or polygons alike: each is (image_index, shape) — sized by `sizes[i]` or
+    `default_size(shape)`, its map `from_shape(shape, h, w)` — or (image_index, map, (h, w)) verbatim, its map `verbatim(map, h, w)`."""
     regions = list(regions)
     if len(regions) == 0:
         raise ValueError('no regions')
@@ -237,20 +247,18 @@ def region_descs(regions, sizes=None, n_images=None):
         raise ValueError(f'{len(sizes)} sizes for {len(regions)} regions')
     out = []
     for i, region in enumerate(regions):
+        given = sizes[i] if sizes is not None else None
         try:
             if len(region) == 3:
-                index, coeffs, (h, w) = region
-                if sizes is not None and sizes[i] is not None:
-                    h, w = sizes[i]
-                h, w = int(h), int(w)
-                coeffs = check_coeffs(coeffs, h, w)
+                index, described, (h, w) = region
+                h, w = (int(v) for v in (given if given is not None else (h, w)))
+                described = verbatim(described, h, w)
             else:
-                index, quad = region
-                h, w = sizes[i] if sizes is not None and sizes[i] is not None else region_size(quad)
-                h, w = int(h), int(w)
+                index, shape = region
+                h, w = (int(v) for v in (given if given is not None else default_size(shape)))
                 if h < 1 or w < 1:
                     raise ValueError(f'size {h} x {w}: each side must be at least 1')
-                coeffs = quad_coeffs(quad, h, w)
+                described = from_shape(shape, h, w)
         except ValueError as e:
             raise ValueError(f'region {i}: {e}') from None
         index = int(index)
@@ -258,16 +266,14 @@ def region_descs(regions, sizes=None, n_images=None):
             raise ValueError(f'region {i}: image index {index} is outside 0 .. {n_images - 1}')
         if h > MAX_SIDE or w > MAX_SIDE:
             raise ValueError(f'region {i}: size {h} x {w}, each side must be at most {MAX_SIDE}')
-        out.append((index, (h, w), coeffs))
+        out.append((index, (h, w), described))
     return out
 
 
-def _image_descs(keep):
-    images = (_native.ImageDesc * len(keep))()
-    for d, im in zip(images, keep):
-        d.data = im.data_ptr()
-        d.height, d.width, d.row_stride = im.shape[0], im.shape[1], im.stride(0)
-    return images
+def region_descs(regions, sizes=None, n_images=None):
+    """[(image_index, (h, w), coeffs)] of `regions`: each (image_index, quad) — sized by `sizes[i]` or `region_size` — or
+    (image_index, coeffs8, (h, w)) verbatim.  Everything the library would refuse is a ValueError here."""
+    return _described(regions, sizes, n_images, check_coeffs, quad_coeffs, region_size)
 
 
 def _native_regions(keep, described):
@@ -279,8 +285,32 @@ def _native_regions(keep, described):
     return images, regions
 
 
-def _slot(h, w):
-    return (3 * h * w + 255) & ~255
+def _region_call(keep, described, arrays, query, call, size=None):
+    """One library call over the regions `described` of the scenes `keep`.  `arrays`: the descriptor arrays (images, regions and, for
+    polygons, strips); `query`: the call's *_workspace_bytes function; `call`: the library function.
+    With `size` the regions are resized into one uint8 [N, 3, size[0], size[1]] tensor, which is returned; without, they are
+    returned themselves: uint8 [h_i, w_i, 3] views of one buffer, each on a 256-byte boundary."""
+    dev = keep[0].device
+    n, n_images = len(described), len(keep)
+    images, *others = arrays
+    counted = [v for a in others for v in (a, len(a))]            # regions, n[, strips, n_strips]
+    if size is None:
+        offsets, total = [], 0
+        for _, (h, w), _ in described:
+            offsets.append(total)
+            total += (3 * h * w + 255) & ~255
+        flat = torch.empty((total,), dtype=torch.uint8, device=dev)
+        result = [flat[o:o + 3 * h * w].view(h, w, 3) for o, (_, (h, w), _) in zip(offsets, described)]
+        target = ((_native.C.c_void_p * n)(*[flat.data_ptr() + o for o in offsets]),)
+    else:
+        result = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
+        target = (size[0], size[1], _native.ptr(result))
+    need = query(*counted, n_images)
+    ws = _workspace(need, dev)
+    with _native.guard(dev):
+        _native.check(call(images, n_images, *counted, *target, _native.ptr(ws), need, _native.stream_ptr(dev)))
+    torch.cuda.current_stream(dev).synchronize()          # the host arrays are read by asynchronous copies
+    return result
 
 
 def rectify_batch(images: Sequence[Tensor], regions, sizes=None) -> list:
@@ -288,48 +318,19 @@ def rectify_batch(images: Sequence[Tensor], regions, sizes=None) -> list:
     [h_i, w_i, 3] crops PIL's Image.transform((w, h), PERSPECTIVE, quad_coeffs(quad, h, w), BICUBIC) cuts out of them, all in one launch
     (parseq_rectify; views of one buffer).  The crops on their own are the kernel tests' view of the map — `rectify_resize_batch` never
     hands them out."""
-    keep = _checked(images)
-    dev = keep[0].device
+    keep = _checked(images, 'rectify_batch')
     described = region_descs(regions, sizes, len(keep))
-    image_descs, region_array = _native_regions(keep, described)
     lib = _native.lib()
-    n = len(described)
-    offsets, total = [], 0
-    for _, (h, w), _ in described:
-        offsets.append(total)
-        total += _slot(h, w)
-    flat = torch.empty((total,), dtype=torch.uint8, device=dev)
-    outs = [flat[o:o + 3 * h * w].view(h, w, 3) for o, (_, (h, w), _) in zip(offsets, described)]
-    pointers = (_native.C.c_void_p * n)(*[flat.data_ptr() + o for o in offsets])
-    need = lib.parseq_rectify_workspace_bytes(region_array, n, len(keep))
-    if need == 0:
-        _native.check(-1)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    with _native.guard(dev):
-        _native.check(lib.parseq_rectify(image_descs, len(keep), region_array, n, pointers, _native.ptr(ws), need, _native.stream_ptr(dev)))
-    torch.cuda.current_stream(dev).synchronize()          # the three host arrays are read by asynchronous copies
-    return outs
+    return _region_call(keep, described, _native_regions(keep, described), lib.parseq_rectify_workspace_bytes, lib.parseq_rectify)
 
 
 def rectify_resize_batch(images: Sequence[Tensor], regions, size=(32, 128), sizes=None) -> Tensor:
     """`resize_batch(rectify_batch(images, regions, sizes), size)` without the crops ever leaving the library's workspace: uint8
     [N, 3, size[0], size[1]], one row per region, the model's input."""
-    keep = _checked(images)
-    dev = keep[0].device
+    keep = _checked(images, 'rectify_resize_batch')
     described = region_descs(regions, sizes, len(keep))
-    image_descs, region_array = _native_regions(keep, described)
     lib = _native.lib()
-    n = len(described)
-    out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
-    need = lib.parseq_rectify_workspace_bytes(region_array, n, len(keep))
-    if need == 0:
-        _native.check(-1)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    with _native.guard(dev):
-        _native.check(lib.parseq_rectify_resize_bicubic(image_descs, len(keep), region_array, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), need,
-                                                        _native.stream_ptr(dev)))
-    torch.cuda.current_stream(dev).synchronize()
-    return out
+    return _region_call(keep, described, _native_regions(keep, described), lib.parseq_rectify_workspace_bytes, lib.parseq_rectify_resize_bicubic, size)
 
 
 # ---- polygon regions of a scene (DESIGN.md section 25) --------------------------------------------------------------------------------
@@ -455,34 +456,7 @@ def mesh_to_source(strips, size, img_size, points):
 def polygon_descs(regions, sizes=None, n_images=None):
     """[(image_index, (h, w), strips)] of `regions`: each (image_index, polygon) — sized by `sizes[i]` or `polygon_size` — or
     (image_index, strips, (h, w)) verbatim.  Everything the library would refuse is a ValueError here, naming the region."""
-    regions = list(regions)
-    if len(regions) == 0:
-        raise ValueError('no regions')
-    if sizes is not None and len(sizes) != len(regions):
-        raise ValueError(f'{len(sizes)} sizes for {len(regions)} regions')
-    out = []
-    for i, region in enumerate(regions):
-        try:
-            if len(region) == 3:
-                index, strips, (h, w) = region
-                if sizes is not None and sizes[i] is not None:
-                    h, w = sizes[i]
-                h, w = int(h), int(w)
-                strips = check_strips(strips, h, w)
-            else:
-                index, polygon = region
-                h, w = sizes[i] if sizes is not None and sizes[i] is not None else polygon_size(polygon)
-                h, w = int(h), int(w)
-                strips = polygon_mesh(polygon, h, w)
-        except ValueError as e:
-            raise ValueError(f'region {i}: {e}') from None
-        index = int(index)
-        if n_images is not None and not 0 <= index < n_images:
-            raise ValueError(f'region {i}: image index {index} is outside 0 .. {n_images - 1}')
-        if h > MAX_SIDE or w > MAX_SIDE:
-            raise ValueError(f'region {i}: size {h} x {w}, each side must be at most {MAX_SIDE}')
-        out.append((index, (h, w), strips))
-    return out
+    return _described(regions, sizes, n_images, check_strips, polygon_mesh, polygon_size)
 
 
 def _native_mesh(keep, described):
@@ -503,46 +477,17 @@ def mesh_rectify_batch(images: Sequence[Tensor], regions, sizes=None) -> list:
     """images: CUDA uint8 tensors [H_i, W_i, 3], the scenes; regions: (image_index, polygon) each (see `polygon_descs`).  Returns the uint8
     [h_i, w_i, 3] crops PIL's Image.transform((w, h), MESH, the boxes and quads of polygon_mesh(polygon, h, w), BICUBIC) cuts out of them, all
     in one launch (parseq_mesh_rectify; views of one buffer), as `rectify_batch` does for quadrilaterals."""
-    keep = _checked(images)
-    dev = keep[0].device
+    keep = _checked(images, 'mesh_rectify_batch')
     described = polygon_descs(regions, sizes, len(keep))
-    image_descs, region_array, strip_array = _native_mesh(keep, described)
     lib = _native.lib()
-    n = len(described)
-    offsets, total = [], 0
-    for _, (h, w), _ in described:
-        offsets.append(total)
-        total += _slot(h, w)
-    flat = torch.empty((total,), dtype=torch.uint8, device=dev)
-    outs = [flat[o:o + 3 * h * w].view(h, w, 3) for o, (_, (h, w), _) in zip(offsets, described)]
-    pointers = (_native.C.c_void_p * n)(*[flat.data_ptr() + o for o in offsets])
-    need = lib.parseq_mesh_rectify_workspace_bytes(region_array, n, strip_array, len(strip_array), len(keep))
-    if need == 0:
-        _native.check(-1)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    with _native.guard(dev):
-        _native.check(lib.parseq_mesh_rectify(image_descs, len(keep), region_array, n, strip_array, len(strip_array), pointers, _native.ptr(ws), need,
-                                              _native.stream_ptr(dev)))
-    torch.cuda.current_stream(dev).synchronize()          # the four host arrays are read by asynchronous copies
-    return outs
+    return _region_call(keep, described, _native_mesh(keep, described), lib.parseq_mesh_rectify_workspace_bytes, lib.parseq_mesh_rectify)
 
 
 def mesh_rectify_resize_batch(images: Sequence[Tensor], regions, size=(32, 128), sizes=None) -> Tensor:
     """`resize_batch(mesh_rectify_batch(images, regions, sizes), size)` without the crops ever leaving the library's workspace: uint8
     [N, 3, size[0], size[1]], one row per region, the model's input."""
-    keep = _checked(images)
-    dev = keep[0].device
+    keep = _checked(images, 'mesh_rectify_resize_batch')
     described = polygon_descs(regions, sizes, len(keep))
-    image_descs, region_array, strip_array = _native_mesh(keep, described)
     lib = _native.lib()
-    n = len(described)
-    out = torch.empty((n, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
-    need = lib.parseq_mesh_rectify_workspace_bytes(region_array, n, strip_array, len(strip_array), len(keep))
-    if need == 0:
-        _native.check(-1)
-    ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    with _native.guard(dev):
-        _native.check(lib.parseq_mesh_rectify_resize_bicubic(image_descs, len(keep), region_array, n, strip_array, len(strip_array), size[0], size[1],
-                                                             _native.ptr(out), _native.ptr(ws), need, _native.stream_ptr(dev)))
-    torch.cuda.current_stream(dev).synchronize()
-    return out
+    return _region_call(keep, described, _native_mesh(keep, described), lib.parseq_mesh_rectify_workspace_bytes, lib.parseq_mesh_rectify_resize_bicubic,
+                        size)

@@ -160,6 +160,43 @@ def test_no_rotation_is_the_plain_resize():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('target', [(32, 128), (16, 64)])
+def test_skipped_passes_through_both_resize_kernels(target):
+    """A pass whose size does not change is skipped: canvases with the target's height, its width, or both, through the plain kernel and
+    through the rotating one — as its unrotated mode and as a turn whose CANVAS has the side (the last image of the batch turns)."""
+    from parseq_amd.preprocess import resize_batch, rotation_map
+    cases = [((32, 128), 0), ((32, 77), 0), ((50, 128), 0), ((16, 64), 0), ((16, 40), 0), ((9, 64), 0),
+             ((128, 32), 90), ((77, 32), 90), ((128, 50), 270), ((32, 128), 180)]
+    assert [rotation_map(h, w, a)[1:3] for (h, w), a in cases[6:]] == [(32, 128), (32, 77), (50, 128), (32, 128)]
+    rng = np.random.default_rng(54)
+    imgs = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for (h, w), _ in cases]
+    canvases = [rotate_u8(img, angle) for img, (_, angle) in zip(imgs, cases)]
+    want = np.stack([resize_bicubic_u8(canvas, *target).transpose(2, 0, 1) for canvas in canvases])
+    skipped = {(c.shape[0] == target[0], c.shape[1] == target[1]) for c in canvases}
+    assert skipped == {(True, True), (True, False), (False, True), (False, False)}
+    plain = resize_batch([torch.from_numpy(c).cuda() for c in canvases], target).cpu().numpy()
+    turned = resize_batch([torch.from_numpy(i).cuda() for i in imgs], target, rotation=[a for _, a in cases]).cpu().numpy()
+    for i, case in enumerate(cases):
+        assert np.array_equal(plain[i], want[i]), ('plain', case)
+        assert np.array_equal(turned[i], want[i]), ('rotating', case)
+
+
+@pytest.mark.gpu
+def test_region_of_the_target_size_skips_both_passes_behind_a_rectification():
+    """An integer axis-aligned 32 x 128 box rectified and resized to (32, 128): the map is the identity shifted, both resize passes are
+    skipped, the result is the slice; the same box as a 4-point polygon comes out of the resize as it came out of the mesh."""
+    from parseq_amd.preprocess import mesh_rectify_batch, mesh_rectify_resize_batch, rectify_resize_batch
+    scene = torch.from_numpy(np.random.default_rng(55).integers(0, 256, (60, 200, 3), dtype=np.uint8)).cuda()
+    left, top = 7, 5
+    box = [(left, top), (left + 128, top), (left + 128, top + 32), (left, top + 32)]
+    got = rectify_resize_batch([scene], [(0, box)], (32, 128))
+    assert np.array_equal(got[0].cpu().numpy(), scene[top:top + 32, left:left + 128].permute(2, 0, 1).cpu().numpy())
+    crop = mesh_rectify_batch([scene], [(0, box)], sizes=[(32, 128)])[0]
+    got = mesh_rectify_resize_batch([scene], [(0, box)], (32, 128), sizes=[(32, 128)])
+    assert tuple(crop.shape) == (32, 128, 3) and np.array_equal(got[0].cpu().numpy(), crop.permute(2, 0, 1).cpu().numpy())
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize('rotation', [90, 15])
 def test_evaluate_dataset_rotates_on_the_device(rotation, tmp_path):
     """test.py --rotation: the same Result as the unrotated evaluation of files PIL rotated beforehand."""
