@@ -942,6 +942,12 @@ int parseq_op_mlp_variant(float* x, const float* gamma, const float* beta, const
  * out [bh / heads * 128, heads * 64] in `dtype`.  dtype = PARSEQ_BF16X3: f32 tensors, split-bf16 products. */
 int parseq_op_encoder_attention(const void* q, const void* k, const void* vt, void* out, int dtype, int bh, int heads,
                                 void* stream);
+/* The AR cross-attention on 24-bit K / V rows alone, embed_dim 384 (12 heads of 32), 128 memory tokens, one query per image: qc fp32
+ * [batch, 384] (unscaled); kmem, vmem: the u16 plane [batch, 12, 128, 32] (bits 31..16 of each f32) with the u8 plane (bits 15..8) of the
+ * same shape plane_elems * 2 bytes behind its start; out fp32 [batch, 384].  tile = 0: one workgroup per image (what a forward alone on the
+ * device runs); tile = 1: one workgroup per 16 images (the in-flight AR decode's form).  Bit-identical outputs. */
+int parseq_op_cross_attention_ar24(const float* qc, const void* kmem, const void* vmem, int64_t plane_elems, int batch, int tile, float* out,
+                                   void* stream);
 /* (ABI 10) The training step's encoder self-attention alone, fp32 (exact products): `tokens` tokens of `heads` heads of width 64;
  * qkv [batch * tokens, 3 E] (q | k | v per row, E = 64 heads), o [batch * tokens, E]; backward: d_o like o, dqkv like qkv (written).
  * Past 128 tokens (up to 256) the key-streaming kernels run: the forward writes lse [batch, heads, tokens] (each query row's

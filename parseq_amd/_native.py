@@ -262,6 +262,7 @@ SIGNATURES = {
                                           C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_op_encoder_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                               C.c_void_p]),
+    'parseq_op_cross_attention_ar24': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'parseq_op_train_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     'parseq_op_train_gemm': (C.c_int, [C.POINTER(TrainGemmDesc), C.POINTER(GemmRoute), C.c_void_p]),

@@ -343,14 +343,16 @@ __device__ __forceinline__ void f24_unpack8(const u32x4& hi, const uint2& lo, fl
     }
 }
 
-// dec_cross_attn_ar_kernel on 24-bit rows: lane (kl = lane / 4, dl = lane % 4) takes elements 8 dl .. 8 dl + 7 of key row 16 c + kl —
-// one 16-byte and one 8-byte load per piece, a KiB and half a KiB contiguous per wave load; all 32 loads of a head in flight first.
-template <int E, bool QSPLIT = false>
-__global__ __launch_bounds__(E)
-void dec_cross_attn_ar24_kernel(const float* __restrict__ qc, const QAsm qa, const unsigned char* __restrict__ kmem, const unsigned char* __restrict__ vmem,
-                                size_t plane_elems, float scale, float* __restrict__ out) {
-    constexpr int H = E / DEC_HD, NK = 128, LPR = 4, KPL = 16, NL = 8;
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = E / 64, b = blockIdx.x;
+// One (image, head) pair of the AR cross-attention on 24-bit rows by one wave: lane (kl = lane / 4, dl = lane % 4) takes elements
+// 8 dl .. 8 dl + 7 of key row 16 c + kl — one 16-byte and one 8-byte load per piece, a KiB and half a KiB contiguous per wave load; all
+// 32 loads of the head in flight first.  `bh` = image * H + head; `qh` (LDS) the head's 32 scaled query values, read only after
+// `between()` has run behind the loads (where the one-image kernel finishes and parks its query); acc[i] (all lanes) = element 8 dl + i of the
+// head's output.  Both the one-image kernel and the tile-owner forms below call this one body: their results are bit-identical.
+template <typename Between>
+__device__ __forceinline__ void ca24_pair(const unsigned char* __restrict__ kmem, const unsigned char* __restrict__ vmem, size_t plane_elems, size_t bh,
+                                          const float* qh, float (&acc)[8], Between&& between) {
+    constexpr int NK = 128, LPR = 4, KPL = 16, NL = 8;
+    const int lane = threadIdx.x & 63;
     const int kl = lane / LPR, dl = lane % LPR;
     auto over_keys_sum = [](float v) {
         v = dpp_add<0x124>(v);     // row_ror:4
@@ -366,68 +368,119 @@ void dec_cross_attn_ar24_kernel(const float* __restrict__ qc, const QAsm qa, con
         v = fmaxf(v, __shfl_xor(v, 32, 64));
         return v;
     };
+    const size_t at = (bh * NK + kl) * DEC_HD + dl * 8;
+    const unsigned char* kh = kmem + at * 2; const unsigned char* kq = kmem + plane_elems * 2 + at;
+    const unsigned char* vh = vmem + at * 2; const unsigned char* vq = vmem + plane_elems * 2 + at;
+    u32x4 khi[NL], vhi[NL];
+    uint2 klo[NL], vlo[NL];
+#pragma unroll
+    for (int c = 0; c < NL; ++c) khi[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kh + (size_t)c * KPL * DEC_HD * 2));
+#pragma unroll
+    for (int c = 0; c < NL; ++c) { const unsigned long long t = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(kq + (size_t)c * KPL * DEC_HD)); klo[c] = make_uint2((unsigned)t, (unsigned)(t >> 32)); }
+#pragma unroll
+    for (int c = 0; c < NL; ++c) vhi[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vh + (size_t)c * KPL * DEC_HD * 2));
+#pragma unroll
+    for (int c = 0; c < NL; ++c) { const unsigned long long t = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(vq + (size_t)c * KPL * DEC_HD)); vlo[c] = make_uint2((unsigned)t, (unsigned)(t >> 32)); }
+    __builtin_amdgcn_sched_barrier(0);                 // every load of the head is in flight before the first is waited for
+    between();
+    float qv[8];
+#pragma unroll
+    for (int i = 0; i < 8; i += 4) {
+        const float4 v4 = *reinterpret_cast<const float4*>(qh + dl * 8 + i);
+        qv[i] = v4.x; qv[i + 1] = v4.y; qv[i + 2] = v4.z; qv[i + 3] = v4.w;
+    }
+    float s[NL], mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < NL; ++c) {
+        float kv[8];
+        f24_unpack8(khi[c], klo[c], kv);
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d = fmaf(qv[i], kv[i], d);
+        d = dpp_add<0xB1>(d);                              // quad: the four lanes of one key row
+        d = dpp_add<0x4E>(d);
+        s[c] = d;
+        mx = fmaxf(mx, d);
+    }
+    mx = over_keys_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < NL; ++c) { s[c] = expf(s[c] - mx); sum += s[c]; }
+    const float inv = 1.0f / over_keys_sum(sum);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NL; ++c) {
+        const float pc = s[c] * inv;
+        float vv[8];
+        f24_unpack8(vhi[c], vlo[c], vv);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(pc, vv[i], acc[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = over_keys_sum(acc[i]);
+}
+
+// dec_cross_attn_ar_kernel on 24-bit rows: one workgroup per image, two heads per wave.
+template <int E, bool QSPLIT = false>
+__global__ __launch_bounds__(E)
+void dec_cross_attn_ar24_kernel(const float* __restrict__ qc, const QAsm qa, const unsigned char* __restrict__ kmem, const unsigned char* __restrict__ vmem,
+                                size_t plane_elems, float scale, float* __restrict__ out) {
+    constexpr int H = E / DEC_HD;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = E / 64, b = blockIdx.x;
+    const int kl = lane / 4, dl = lane % 4;
     __shared__ __attribute__((aligned(16))) float qs[E];
     QOne<QSPLIT> q1;
     q_issue<QSPLIT>(qa, qc, b, E, (int)threadIdx.x, q1);
     bool first = true;
     for (int h = wid; h < H; h += nw) {              // exactly two heads per wave (H = 2 nw): the barrier below is uniform
-        const size_t at = (((size_t)b * H + h) * NK + kl) * DEC_HD + dl * 8;
-        const unsigned char* kh = kmem + at * 2; const unsigned char* kq = kmem + plane_elems * 2 + at;
-        const unsigned char* vh = vmem + at * 2; const unsigned char* vq = vmem + plane_elems * 2 + at;
-        u32x4 khi[NL], vhi[NL];
-        uint2 klo[NL], vlo[NL];
-#pragma unroll
-        for (int c = 0; c < NL; ++c) khi[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kh + (size_t)c * KPL * DEC_HD * 2));
-#pragma unroll
-        for (int c = 0; c < NL; ++c) { const unsigned long long t = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(kq + (size_t)c * KPL * DEC_HD)); klo[c] = make_uint2((unsigned)t, (unsigned)(t >> 32)); }
-#pragma unroll
-        for (int c = 0; c < NL; ++c) vhi[c] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vh + (size_t)c * KPL * DEC_HD * 2));
-#pragma unroll
-        for (int c = 0; c < NL; ++c) { const unsigned long long t = __builtin_nontemporal_load(reinterpret_cast<const unsigned long long*>(vq + (size_t)c * KPL * DEC_HD)); vlo[c] = make_uint2((unsigned)t, (unsigned)(t >> 32)); }
-        __builtin_amdgcn_sched_barrier(0);                 // every load of the head is in flight before the first is waited for
-        if (first) {
-            qs[threadIdx.x] = q_finish<QSPLIT>(qa, q1, scale);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            first = false;
-        }
-        float qv[8];
-#pragma unroll
-        for (int i = 0; i < 8; i += 4) {
-            const float4 v4 = *reinterpret_cast<const float4*>(qs + h * DEC_HD + dl * 8 + i);
-            qv[i] = v4.x; qv[i + 1] = v4.y; qv[i + 2] = v4.z; qv[i + 3] = v4.w;
-        }
-        float s[NL], mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < NL; ++c) {
-            float kv[8];
-            f24_unpack8(khi[c], klo[c], kv);
-            float d = 0.f;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) d = fmaf(qv[i], kv[i], d);
-            d = dpp_add<0xB1>(d);                              // quad: the four lanes of one key row
-            d = dpp_add<0x4E>(d);
-            s[c] = d;
-            mx = fmaxf(mx, d);
-        }
-        mx = over_keys_max(mx);
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < NL; ++c) { s[c] = expf(s[c] - mx); sum += s[c]; }
-        const float inv = 1.0f / over_keys_sum(sum);
         float acc[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = 0.f;
-#pragma unroll
-        for (int c = 0; c < NL; ++c) {
-            const float pc = s[c] * inv;
-            float vv[8];
-            f24_unpack8(vhi[c], vlo[c], vv);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i] = fmaf(pc, vv[i], acc[i]);
+        ca24_pair(kmem, vmem, plane_elems, (size_t)b * H + h, qs + h * DEC_HD, acc, [&] {
+            if (first) {
+                qs[threadIdx.x] = q_finish<QSPLIT>(qa, q1, scale);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                first = false;
+            }
+        });
+        if (kl == 0) {
+            float* o = out + (size_t)b * E + h * DEC_HD + dl * 8;
+            *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+            *reinterpret_cast<float4*>(o + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
         }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = over_keys_sum(acc[i]);
+    }
+}
+
+// Tile-owner form (the in-flight AR decode, decoder_tile_loop.h): a 512-thread workgroup owns DS_ROWS = 16 images, its 8 waves take the
+// 16 H (image, head) pairs round-robin.  32 workgroups at batch 512 instead of 512: each compute unit it holds pulls what one compute
+// unit can (tools/microbench/l2_fill.hip), instead of the whole chip waiting on 22 GB/s per compute unit.  qc fp32 [B][E]; out fp32 [B][E].
+constexpr int CA_TILE = 16, CA_TILE_NW = 8;
+template <int E>
+__global__ __launch_bounds__(64 * CA_TILE_NW)
+void dec_cross_attn_ar24_tile_kernel(const float* __restrict__ qc, const unsigned char* __restrict__ kmem, const unsigned char* __restrict__ vmem,
+                                     size_t plane_elems, float scale, float* __restrict__ out, int B) {
+    constexpr int H = E / DEC_HD;
+    static_assert(H > CA_TILE_NW && (CA_TILE * H) % CA_TILE_NW == 0, "every wave's first pair is of the tile's first image; equal pairs per wave");
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int kl = lane / 4, dl = lane % 4;
+    const int row0 = blockIdx.x * CA_TILE;
+    __shared__ __attribute__((aligned(16))) float qs[CA_TILE * E];
+    bool first = true;
+    for (int pr = wid; pr < CA_TILE * H; pr += CA_TILE_NW) {
+        const int img = pr / H, h = pr - img * H, b = row0 + img;
+        if (b >= B) break;                             // wave-uniform, and never on a wave's first pair (image row0 exists)
+        float acc[8];
+        ca24_pair(kmem, vmem, plane_elems, (size_t)b * H + h, qs + img * E + h * DEC_HD, acc, [&] {
+            if (first) {                               // the tile's queries, scaled, behind the first pair's loads
+                for (int i = threadIdx.x; i < CA_TILE * (E / 4); i += 64 * CA_TILE_NW) {
+                    const int row = i / (E / 4), c = (i - row * (E / 4)) * 4;
+                    const float4 v = *reinterpret_cast<const float4*>(qc + (size_t)min(row0 + row, B - 1) * E + c);
+                    *reinterpret_cast<float4*>(qs + row * E + c) = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+                }
+                __syncthreads();
+                first = false;
+            }
+        });
         if (kl == 0) {
             float* o = out + (size_t)b * E + h * DEC_HD + dl * 8;
             *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);

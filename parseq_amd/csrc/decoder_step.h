@@ -19,6 +19,12 @@
 // W fragments (lane l's 16 bytes land at slot + 16 l, exactly where lane l reads its MFMA operand back) while the wave
 // multiplies — no block-level barrier inside a GEMM, only counted `s_waitcnt vmcnt`.
 // Rounding points are the generic path's (lib_decode.hip decoder_pass): bf16 GEMM operands, fp32 accumulation, fp32 residual stream.
+//
+// Three arrangements are built from the pieces of this header (ds_prefetch, ds_wave_gemm, ds_layernorm_rows, ds_self_attn_rows, the
+// parameter staging): the pre / post pair above (single-query passes of the decode entry points), the mid / mlp pair further down (the AR
+// loop of parseq_forward, three launches per step), and decoder_tile_loop.h — the whole AR loop of a batch in flight as one launch, in
+// which the workgroup that owns 16 rows also runs their cross-attention and all six hidden slices (bf16x3, embed_dim 384, 24-bit K / V
+// rows; bit-identical to the mid / mlp pair on one workgroup per tile).
 #pragma once
 #include "common.h"
 #include "decoder_attn.h"

@@ -1,5 +1,6 @@
 // libparseq_hip.so — launch orchestration of the decoder passes, the AR loop, refinement and parseq_forward.
 #include "lib_internal.h"
+#include "decoder_tile_loop.h"
 #include "beam.h"
 #include "beam_refine.h"
 #include "attn_map.h"
@@ -95,13 +96,18 @@ struct DecPass {
 // widths parseq_model_create admits (192, 384, 768) that leaves 192 and 384, the two the step kernels are built for; forward_impl
 // and decoder_pass ask E <= 384 at compile time and keep the per-operation step otherwise.
 // The step kernels' head holds up to 128 classes.  `qsplit`: the mid kernel's start half on DS_QS workgroups per row tile, see ar_loop_fused.
+// `tile_loop`: the whole AR loop of parseq_forward as one launch in which a workgroup owns 16 images (decoder_tile_loop.h) — batches in
+// flight (no PARSEQ_FLAG_LATENCY) of at least p->tile_loop_min images, in the one geometry that kernel is built for: bf16x3, embed_dim 384,
+// 128 memory tokens held as 24-bit K / V rows (asked after the encoder has run: p->kv24 is what this call's encoder left).
 enum DecStep { STEP_DEEP, STEP_FUSED, STEP_PER_OP };
-struct DecRoute { DecStep step; bool qsplit; };
-static DecRoute dec_route(const parseq_plan* p, bool latency) {
+struct DecRoute { DecStep step; bool qsplit; bool tile_loop; };
+static DecRoute dec_route(const parseq_plan* p, bool latency, int batch = 0) {
     const parseq_model* m = p->m;
-    if (m->cfg.dec_depth > 1) return {STEP_DEEP, false};
-    if (!(p->wstep[0] && p->fused_step && m->classes <= 128)) return {STEP_PER_OP, false};
-    return {STEP_FUSED, latency && p->qsplit && m->tokens == 128 && m->cfg.max_label_length + 1 >= DS_QS + 2};
+    if (m->cfg.dec_depth > 1) return {STEP_DEEP, false, false};
+    if (!(p->wstep[0] && p->fused_step && m->classes <= 128)) return {STEP_PER_OP, false, false};
+    const bool tile_loop = !latency && p->tile_loop && p->precision == PARSEQ_BF16X3 && m->cfg.embed_dim == 384 && m->tokens == 128 && p->kv24 &&
+                           batch >= p->tile_loop_min;
+    return {STEP_FUSED, latency && p->qsplit && m->tokens == 128 && m->cfg.max_label_length + 1 >= DS_QS + 2, tile_loop};
 }
 
 static float dec_scale() { return sqrtf(1.0f / (float)DEC_HD); }
@@ -411,6 +417,29 @@ static int ar_loop_fused(parseq_plan* p, hipStream_t s, const DecW<TS>& w, int B
     return 0;
 }
 
+// The whole AR loop as one launch of decoder_tile_loop.h (dec_route: tile_loop): logits, p->tok and the EOS bookkeeping as ar_loop_fused leaves them,
+// bit for bit.
+template <int E>
+static int ar_tile_loop(parseq_plan* p, hipStream_t s, const DecW<float>& w, int B, int num_steps, float* logits, bool testing) {
+    const parseq_config& c = p->m->cfg;
+    const DecLayerW<float>& y = w.layer[0];
+    ArTileArgs a{};
+    a.M = B; a.num_steps = num_steps; a.C = p->m->classes; a.testing = testing ? 1 : 0; a.eos_id = c.eos_id; a.ldt = LDT; a.ntok = c.num_tokens;
+    a.npos = c.max_label_length + 1; a.eps = c.dec_ln_eps; a.scale = dec_scale();
+    a.b2 = y.lin2_b; a.lnf_w = w.norm.g; a.lnf_b = w.norm.b; a.bh = w.head_b; a.Wh = p->wstep[5];
+    a.logits = logits; a.eos_seen = p->eos_seen; a.eos_rows = p->counters; a.ar_len = p->counters + 1; a.ar_last = p->counters + 2;
+    a.stab = p->stab; a.kvtab = reinterpret_cast<const float*>(p->kvtab); a.tok = p->tok;
+    a.Wo = p->wstep[0]; a.Wq = p->wstep[1]; a.bo = y.sa_out_b; a.pos_queries = w.pos_queries; a.ln1_w = y.norm1.g; a.ln1_b = y.norm1.b; a.bq = y.ca_in_b;
+    a.kmem = reinterpret_cast<const unsigned char*>(p->kmem); a.vmem = reinterpret_cast<const unsigned char*>(p->vmem); a.plane_elems = p->kv_plane_elems;
+    a.Wco = p->wstep[2]; a.W1 = p->wstep[3]; a.W2 = p->wstep[4]; a.bco = y.ca_out_b; a.ln2_w = y.norm2.g; a.ln2_b = y.norm2.b; a.b1 = y.lin1_b;
+    static LdsAttr attr_;
+    HIPCHK(attr_.ensure(reinterpret_cast<const void*>(dec_ar_tile_loop_kernel<E, true>), dec_ar_tile_loop_lds<E>()));
+    ProfScope ps_(&p->prof, T_DEC_LOOP, s);
+    hipLaunchKernelGGL((dec_ar_tile_loop_kernel<E, true>), dim3((B + DS_ROWS - 1) / DS_ROWS), dim3(64 * DS_NW), dec_ar_tile_loop_lds<E>(), s, a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // The cloze pass of a refinement iteration (model.py:154-167) over rows x L positions: every position queried against the whole content
 // in p->tok under the cloze mask, key padding in p->kpm.  `logits` [rows][L][C], or null for the attention map's pass (DecPass::logits).
 // dec_depth > 1: the content stream runs under the same cloze-edited mask (model.py:117, 157: tgt_mask and query_mask are one tensor) over
@@ -440,14 +469,21 @@ static int forward_impl(parseq_plan* p, int B, int flags, int refine_iters, int 
     const parseq_config& c = p->m->cfg;
     const bool ar = flags & PARSEQ_FLAG_DECODE_AR, testing = flags & PARSEQ_FLAG_TESTING;
     const DecW<T> w = dec_weights<T>(p);
-    const DecRoute route = dec_route(p, flags & PARSEQ_FLAG_LATENCY);
+    const DecRoute route = dec_route(p, flags & PARSEQ_FLAG_LATENCY, B);
     DecPass a; a.B = B; a.logits = logits; a.Ltot = num_steps; a.fused_step_allowed = route.step == STEP_FUSED;
-    CHK(launch(ar_init_kernel, dim3((B * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, B, c.bos_id, c.pad_id, p->eos_seen, p->counters, 2, num_steps));
+    CHK(launch(ar_init_kernel, dim3((B * LDT + 255) / 256), dim3(256), 0, s, p->tok, LDT, B, c.bos_id, c.pad_id, p->eos_seen, p->counters, 3, num_steps));
     // model.py:119-147.  All num_steps steps are always run (no per-step host sync); the step at which the reference
     // would have stopped is recorded on the device and only truncates the returned view.
     bool stepwise = ar;      // one decoder_pass per AR step, unless the fused loop runs them all
     if constexpr (E <= 384) {
-        if (ar && route.step == STEP_FUSED) { CHK((ar_loop_fused<E, sizeof(T) == 4>(p, s, w, B, num_steps, logits, testing, route.qsplit))); stepwise = false; }
+        if (ar && route.step == STEP_FUSED) {
+            bool looped = false;
+            if constexpr (E == 384 && sizeof(T) == 4) {
+                if (route.tile_loop) { CHK((ar_tile_loop<E>(p, s, w, B, num_steps, logits, testing))); looped = true; }
+            }
+            if (!looped) CHK((ar_loop_fused<E, sizeof(T) == 4>(p, s, w, B, num_steps, logits, testing, route.qsplit)));
+            stepwise = false;
+        }
     }
     for (int i = 0; stepwise && i < num_steps; ++i) {
         // greedy pick of position i into tok[:, i + 1] (+ EOS bookkeeping) rides on the step; the last step needs none

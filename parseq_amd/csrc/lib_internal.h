@@ -92,10 +92,10 @@ struct SplitScope {
 // -------------------------------------------------------------------------------------------------------------------
 // optional per-kernel-family timing with HIP events on the caller's stream (bench.py's roofline leg)
 // -------------------------------------------------------------------------------------------------------------------
-enum ProfTag { T_PATCH, T_LN, T_QKV, T_ATTN, T_PROJ, T_FC1, T_FC2, T_MLP, T_ATTNF, T_BLOCKS, T_KVMEM, T_DEC_SA, T_DEC_GEMM, T_DEC_CA, T_DEC_LN, T_DEC_MISC, T_DEC_PRE, T_DEC_POST, T_COUNT };
+enum ProfTag { T_PATCH, T_LN, T_QKV, T_ATTN, T_PROJ, T_FC1, T_FC2, T_MLP, T_ATTNF, T_BLOCKS, T_KVMEM, T_DEC_SA, T_DEC_GEMM, T_DEC_CA, T_DEC_LN, T_DEC_MISC, T_DEC_PRE, T_DEC_POST, T_DEC_LOOP, T_COUNT };
 static const char* const kProfNames[T_COUNT] = {"enc.patch_embed_gemm", "enc.layernorm", "enc.qkv_gemm", "enc.attention", "enc.proj_gemm",
                                                 "enc.fc1_gelu_gemm", "enc.fc2_gemm", "enc.mlp_fused", "enc.attn_fused", "enc.blocks_fused", "dec.memory_kv_gemm", "dec.self_attention", "dec.gemm",
-                                                "dec.cross_attention", "dec.layernorm", "dec.misc", "dec.step_pre", "dec.step_post"};
+                                                "dec.cross_attention", "dec.layernorm", "dec.misc", "dec.step_pre", "dec.step_post", "dec.ar_tile_loop"};
 struct Profiler {
     bool enabled = false;
     std::vector<hipEvent_t> pool;          // events, used pairwise
@@ -283,7 +283,7 @@ struct parseq_plan {
     unsigned char* eos_seen = nullptr;
     unsigned char* cloze = nullptr;  // [npos][LDT]
     unsigned char* qmask_user = nullptr;  // [npos][LDT] staging for parseq_decode_logits
-    int* counters = nullptr;       // [0] rows that have seen an EOS, [1] step at which the reference would have stopped (ar_len)
+    int* counters = nullptr;       // [0] rows that have seen an EOS, [1] step at which the reference would have stopped (ar_len), [2] the tile loop's running maximum of the rows' first-EOS steps
     // dec_depth > 1 (sized at plan creation; null at depth 1): layer l's memory K / V (kmem_l[0] / vmem_l[0] are kmem / vmem), the
     // self-attention K | V rows of every layer's content input [max_batch][npos][2E] in T (the AR loop's per-layer cache), the content
     // stream [max_batch * npos][E] f32 (updated in place layer by layer) and the staging of a caller's content mask [npos][LDT]
@@ -300,6 +300,13 @@ struct parseq_plan {
     bool fused_step = getenv("PARSEQ_NO_FUSED_STEP") == nullptr;   // diagnostics: fall back to the per-op AR step
     float* qfold = nullptr;        // [wbar E | cq E | bq2 E | c0 npos] of the split mid kernel (decoder_step.h dec_qfold_kernel), per weight set
     bool qsplit = getenv("PARSEQ_NO_QSPLIT") == nullptr;         // diagnostics: the mid kernel's start half on one workgroup per row tile
+    // The in-flight AR decode as one launch, a workgroup per 16 images (decoder_tile_loop.h; lib_decode.hip dec_route).  PARSEQ_NO_TILE_LOOP=1 keeps the
+    // three launches per step (A/B on one build, and the reference of tests/test_ar_tile_loop.py: the two are bit-identical); PARSEQ_TILE_LOOP_MIN=<n>
+    // moves the batch size from which the route is taken (profiles/ar_tile_loop.md, three batches in flight: +1.7-2 % at batch 512, nothing at 384, -5 % at
+    // 256, -19 % at 128, where the batches in flight no longer hide the decode chain, 4.5 ms in this form against 1.7 ms).  A caller that says `in flight`
+    // (no PARSEQ_FLAG_LATENCY) but keeps ONE batch of 512 or more in flight gets that longer chain with nothing to hide it behind.
+    bool tile_loop = getenv("PARSEQ_NO_TILE_LOOP") == nullptr;
+    int tile_loop_min = [] { const char* e = getenv("PARSEQ_TILE_LOOP_MIN"); const int v = e ? atoi(e) : 512; return v < 1 ? 1 : v; }();
     bool fused_blocks = getenv("PARSEQ_NO_FUSED_BLOCKS") == nullptr;   // diagnostics: one launch per branch instead of encoder_blocks.h
     bool fused_x3 = getenv("PARSEQ_NO_FUSED_X3") == nullptr;
          // diagnostics: bf16x3 encoder through the per-op kernels instead of encoder_blocks_x3.h

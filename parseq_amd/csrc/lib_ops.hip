@@ -390,3 +390,17 @@ extern "C" int parseq_op_encoder_attention(const void* q, const void* k, const v
     return run_enc_attention<float>((hipStream_t)stream, (const float*)q, (const float*)k, (const float*)vt, (float*)out, bh, heads);
 }
 
+// The AR cross-attention on 24-bit K / V rows alone (decoder_attn.h; PARSeq-S geometry: embed_dim 384, 128 memory tokens): tile = 0 the
+// one-workgroup-per-image kernel, tile = 1 the kernel in which a workgroup owns 16 images.  One body, bit-identical outputs.
+extern "C" int parseq_op_cross_attention_ar24(const float* qc, const void* kmem, const void* vmem, int64_t plane_elems, int batch, int tile, float* out, void* stream) {
+    CHK(check_arch());
+    if (!qc || !kmem || !vmem || !out) return fail(PARSEQ_E_INVALID, "cross_attention_ar24: null argument");
+    if (batch < 1) return fail(PARSEQ_E_INVALID, "cross_attention_ar24: batch %d", batch);
+    if (plane_elems < (int64_t)batch * 384 * 128) return fail(PARSEQ_E_INVALID, "cross_attention_ar24: planes of %lld elements hold fewer than %d images", (long long)plane_elems, batch);
+    if (tile != 0 && tile != 1) return fail(PARSEQ_E_INVALID, "cross_attention_ar24: tile %d (0 or 1)", tile);
+    const unsigned char* k = reinterpret_cast<const unsigned char*>(kmem); const unsigned char* v = reinterpret_cast<const unsigned char*>(vmem);
+    const float scale = sqrtf(1.0f / (float)DEC_HD);
+    if (tile) return launch(dec_cross_attn_ar24_tile_kernel<384>, dim3((batch + CA_TILE - 1) / CA_TILE), dim3(64 * CA_TILE_NW), 0, (hipStream_t)stream, qc, k, v,
+                            (size_t)plane_elems, scale, out, batch);
+    return launch(dec_cross_attn_ar24_kernel<384, false>, dim3(batch), dim3(384), 0, (hipStream_t)stream, qc, QAsm{}, k, v, (size_t)plane_elems, scale, out);
+}

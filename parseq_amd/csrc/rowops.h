@@ -204,7 +204,8 @@ void refine_prep_kernel(const float* __restrict__ logits, int L, int C, int* __r
     }
 }
 
-// counters: ncounters ints, pairs (rows that hold an EOS, step count the reference would have returned) per AR chain
+// counters: ncounters ints (parseq_plan::counters).  Even slots start at 0 — [0] the rows that hold an EOS, [2] the tile loop's running maximum of
+// the rows' first-EOS steps (decoder_tile_loop.h) — and odd slots at num_steps: [1] the step count the reference would have returned.
 static __global__ void ar_init_kernel(int* __restrict__ tok, int ldt, int B, int bos_id, int pad_id, unsigned char* __restrict__ eos_seen,
                                int* __restrict__ counters, int ncounters, int num_steps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -648,7 +648,11 @@ class PARSeq(_NativeBacked):
         with the encoder of the next).  The default (`slot=None`) is the reference's behaviour: one call at a time,
         stream-ordered, on workspace 0 — and it tells the library so (PARSEQ_FLAG_LATENCY): with the device to itself the AR step
         spreads over more compute units, a shorter dependent chain.  An explicit slot (0 included) says other batches are in flight
-        and keeps the narrower step, whose compute units they need; the two forms differ by rounding only."""
+        and keeps the narrower step, whose compute units they need; the two forms differ by rounding only.  In `bf16x3` at 512 crops or
+        more per call (PARSEQ_TILE_LOOP_MIN) an explicit slot goes further: the whole AR loop is one launch in which a workgroup owns 16
+        crops (csrc/decoder_tile_loop.h) — a third of the compute-unit time, but a decode chain of about 4.5 ms instead of 1.7 ms, so it
+        pays only with other batches in flight; a caller that passes a slot but keeps one batch in flight should not (or sets
+        PARSEQ_NO_TILE_LOOP=1)."""
         testing = max_length is None
         num_steps = self._num_steps(max_length)
         images = self._check_images(images)
