@@ -955,6 +955,43 @@ int parseq_op_cross_attention_ar24(const float* qc, const void* kmem, const void
  * fewer the step's resident kernels run and neither is touched.  *route (may be NULL): 1 for the key-streaming kernels, 0 otherwise. */
 int parseq_op_train_attention(const float* qkv, float* o, float* lse, const float* d_o, float* dqkv, float* dsum, int batch, int tokens,
                               int heads, int backward, int* route, void* stream);
+/* One call of the training step's train_attn(), whichever kernel it takes (tests/test_train_attn.py; additive, no ABI bump).  The
+ * descriptor carries every field of the step's own argument block (parseq_amd/csrc/train_attn.h TrainAttnArgs, which documents the
+ * layouts and the pass rules) and what the step takes from its context: the head width, the operand mode as a precision constant
+ * (PARSEQ_F32, PARSEQ_BF16 or PARSEQ_BF16X3, anything else is refused) and the dropout as (dropout_p in [0, 1), seed), from which the
+ * hook derives threshold and scale as parseq_train_decoder does.  All pointers are device pointers; strides in elements. */
+enum parseq_train_attn_route {     /* which kernel family a call took (or would have taken, when it is refused) */
+    PARSEQ_TRAIN_ATTN_DEC_BF16 = 0,    /* train_attn_dec_bf16_kernel: bf16 operands, head width 32, <= 32 queries, <= 128 keys (two instantiations: <= 32 keys, more) */
+    PARSEQ_TRAIN_ATTN_ENC_BF16 = 1,    /* train_attn_bf16_kernel: bf16 operands, 128 x 128 tokens, head width 64 */
+    PARSEQ_TRAIN_ATTN_MFMA = 2,        /* train_attn_mfma_kernel: exact fp32 products on the matrix cores, head width 64 */
+    PARSEQ_TRAIN_ATTN_WIDE = 3,        /* train_attn_wide_*_kernel: key-streaming, 129..256 tokens, head width 64 */
+    PARSEQ_TRAIN_ATTN_HD32 = 4,        /* train_attn_kernel<*, 32> */
+    PARSEQ_TRAIN_ATTN_HD64 = 5,        /* train_attn_kernel<*, 64> */
+    PARSEQ_TRAIN_ATTN_NONE = 6         /* no kernel */
+};
+typedef struct parseq_train_attn_desc {
+    const float* q; int64_t q_bstride; int32_t ldq;                /* q_bstride = 0: one set of queries for the whole batch */
+    const float* k; const float* v; int32_t ldkv;
+    const uint8_t* qmask; const uint8_t* kmask; int32_t ldkm;      /* [Lq, Lk] per pass and [images of a pass, ldkm]; non-zero = masked; NULL: none */
+    float* o; int32_t ldo;
+    void* o16; void* dq16; void* dk16; void* dv16;                 /* bf16 outputs INSTEAD of o / dq / dk + dv (the 128 x 128 bf16 kernel alone) */
+    const float* d_o;
+    float* dq; int32_t lddq;
+    float* dk; float* dv; int32_t lddkv;
+    int32_t kv_accumulate;
+    int32_t Lq, Lk, H;
+    float scale;
+    uint32_t drop_site;
+    int32_t pass_B; int64_t qmask_pstride; uint32_t site_pstride; int32_t kv_shared;
+    int32_t pass_loop;
+    float* lse; float* dsum;                                       /* [batch, H, Lq], the key-streaming route alone */
+    int32_t head_dim;
+    int32_t bf16_ops;
+    float dropout_p; uint64_t seed;
+} parseq_train_attn_desc;
+/* batch: images over all passes.  backward == 0: o (or o16) is written; otherwise dq / dk / dv (or their bf16 twins).  *route (may be
+ * NULL) receives an enum parseq_train_attn_route, also when the call is refused (non-zero return, nothing written). */
+int parseq_op_train_attention_desc(const parseq_train_attn_desc* desc, int batch, int backward, int32_t* route, void* stream);
 
 /* (ABI 13) The rotation alone, for one image (tests/test_rotate.py compares it with Pillow): out = device uint8
  * [rot_height, rot_width, 3], dense.  image: HOST descriptor, read before the call returns. */

@@ -117,6 +117,22 @@ GEMM_KERNELS = ('valu', 'mfma_f32', 'bf16_kk', 'bf16_kn', 'bf16_nk', 'bf16_nn', 
 GEMM_KERNELS_X3 = {13: 'x3_kk', 14: 'x3_kn', 15: 'x3_nk', 16: 'x3_nn'}
 
 
+class TrainAttnDesc(C.Structure):
+    """parseq_train_attn_desc: one call of the training step's train_attn() (parseq_op_train_attention_desc)."""
+    _fields_ = [('q', C.c_void_p), ('q_bstride', C.c_int64), ('ldq', C.c_int32), ('k', C.c_void_p), ('v', C.c_void_p), ('ldkv', C.c_int32),
+                ('qmask', C.c_void_p), ('kmask', C.c_void_p), ('ldkm', C.c_int32), ('o', C.c_void_p), ('ldo', C.c_int32),
+                ('o16', C.c_void_p), ('dq16', C.c_void_p), ('dk16', C.c_void_p), ('dv16', C.c_void_p), ('d_o', C.c_void_p),
+                ('dq', C.c_void_p), ('lddq', C.c_int32), ('dk', C.c_void_p), ('dv', C.c_void_p), ('lddkv', C.c_int32),
+                ('kv_accumulate', C.c_int32), ('Lq', C.c_int32), ('Lk', C.c_int32), ('H', C.c_int32), ('scale', C.c_float),
+                ('drop_site', C.c_uint32), ('pass_B', C.c_int32), ('qmask_pstride', C.c_int64), ('site_pstride', C.c_uint32),
+                ('kv_shared', C.c_int32), ('pass_loop', C.c_int32), ('lse', C.c_void_p), ('dsum', C.c_void_p), ('head_dim', C.c_int32),
+                ('bf16_ops', C.c_int32), ('dropout_p', C.c_float), ('seed', C.c_uint64)]
+
+
+# enum parseq_train_attn_route, by value
+TRAIN_ATTN_ROUTES = ('dec_bf16', 'enc_bf16', 'mfma', 'wide', 'hd32', 'hd64', 'none')
+
+
 class NativeError(RuntimeError):
     """A libparseq_hip entry point returned a non-zero status."""
 
@@ -265,6 +281,7 @@ SIGNATURES = {
     'parseq_op_cross_attention_ar24': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'parseq_op_train_attention': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_int, C.POINTER(C.c_int), C.c_void_p]),
+    'parseq_op_train_attention_desc': (C.c_int, [C.POINTER(TrainAttnDesc), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_void_p]),
     'parseq_op_train_gemm': (C.c_int, [C.POINTER(TrainGemmDesc), C.POINTER(GemmRoute), C.c_void_p]),
     'parseq_op_train_linear': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -363,20 +363,57 @@ static int train_attn(const TrainCtx& cx, const TrainAttnArgs& a, int B, bool ba
     return launch(train_attn_wide_dkv_kernel, p.grid, dim3(p.threads), 0, cx.s, a);
 }
 
-// The training step's encoder attention on its own (the kernels' unit test): the self-attention of `tokens` tokens, `heads` heads of 64,
-// q | k | v interleaved in qkv [batch * tokens, 3 E] (E = 64 heads), o [batch * tokens, E], fp32, exact products.
+// The dropout of a step as its kernels take it: keep an element iff its hash >= dropout_p * 2^32, kept elements times 1 / (1 - dropout_p)
+static DropSpec drop_spec(float dropout_p, uint64_t seed) {
+    DropSpec drop{(unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), 0u, 1.0f};
+    if (dropout_p > 0.f) { drop.thresh = (unsigned)((double)dropout_p * 4294967296.0); drop.scale = 1.0f / (1.0f - dropout_p); }
+    return drop;
+}
+static bool dropout_p_ok(float dropout_p) { return dropout_p >= 0.f && dropout_p < 1.f; }
+
+// One call of train_attn() from a descriptor (the kernels' unit test, tests/test_train_attn.py): the descriptor is TrainAttnArgs field
+// by field plus what the step takes from its context (head width, operand mode, dropout as probability and seed).
+static_assert((int)PARSEQ_TRAIN_ATTN_DEC_BF16 == TA_DEC_BF16 && (int)PARSEQ_TRAIN_ATTN_ENC_BF16 == TA_ENC_BF16 && (int)PARSEQ_TRAIN_ATTN_MFMA == TA_MFMA &&
+              (int)PARSEQ_TRAIN_ATTN_WIDE == TA_WIDE && (int)PARSEQ_TRAIN_ATTN_HD32 == TA_HD32 && (int)PARSEQ_TRAIN_ATTN_HD64 == TA_HD64 &&
+              (int)PARSEQ_TRAIN_ATTN_NONE == TA_NONE, "the public route enum restates TrainAttnRoute");
+extern "C" int parseq_op_train_attention_desc(const parseq_train_attn_desc* d, int batch, int backward, int32_t* route, void* stream) {
+    if (route) *route = TA_NONE;
+    CHK(check_arch());
+    if (!d || !d->q || !d->k || !d->v || batch <= 0 || d->Lq <= 0 || d->Lk <= 0 || d->H <= 0 || d->pass_B < 0 || d->pass_loop < 0 ||
+        (backward ? (!d->d_o || !(d->dq || d->dq16) || !((d->dk && d->dv) || d->dk16 || d->dv16)) : !(d->o || d->o16)))
+        return fail(PARSEQ_E_INVALID, "bad argument");
+    if (!train_ops_ok(d->bf16_ops)) return fail(PARSEQ_E_INVALID, "operand mode %d", d->bf16_ops);
+    if (!dropout_p_ok(d->dropout_p)) return fail(PARSEQ_E_INVALID, "dropout_p %g outside [0, 1)", d->dropout_p);
+    TrainAttnArgs a{};
+    a.q = d->q; a.q_bstride = (long)d->q_bstride; a.ldq = d->ldq; a.k = d->k; a.v = d->v; a.ldkv = d->ldkv;
+    a.qmask = d->qmask; a.kmask = d->kmask; a.ldkm = d->ldkm;
+    a.o = d->o; a.ldo = d->ldo; a.o16 = static_cast<bf16_t*>(d->o16);
+    a.dq16 = static_cast<bf16_t*>(d->dq16); a.dk16 = static_cast<bf16_t*>(d->dk16); a.dv16 = static_cast<bf16_t*>(d->dv16);
+    a.d_o = d->d_o; a.dq = d->dq; a.lddq = d->lddq; a.dk = d->dk; a.dv = d->dv; a.lddkv = d->lddkv; a.kv_accumulate = d->kv_accumulate;
+    a.Lq = d->Lq; a.Lk = d->Lk; a.H = d->H; a.scale = d->scale; a.drop = drop_spec(d->dropout_p, d->seed); a.drop_site = d->drop_site;
+    a.pass_B = d->pass_B; a.qmask_pstride = (long)d->qmask_pstride; a.site_pstride = d->site_pstride; a.kv_shared = d->kv_shared;
+    a.pass_loop = d->pass_loop; a.lse = d->lse; a.dsum = d->dsum;
+    const TrainCtx cx{(hipStream_t)stream, nullptr, d->bf16_ops, 0};
+    TrainAttnRoute took = TA_NONE;
+    const int rc = train_attn(cx, a, batch, backward != 0, d->head_dim, &took);
+    if (route) *route = (int32_t)took;
+    return rc;
+}
+
+// The training step's encoder attention on its own: the self-attention of `tokens` tokens, `heads` heads of 64, q | k | v interleaved in
+// qkv [batch * tokens, 3 E] (E = 64 heads), o [batch * tokens, E], fp32, exact products.  A caller of the descriptor hook.
 extern "C" int parseq_op_train_attention(const float* qkv, float* o, float* lse, const float* d_o, float* dqkv, float* dsum, int batch, int tokens,
                                          int heads, int backward, int* route, void* stream) {
     CHK(check_arch());
     if (!qkv || !o || batch <= 0 || tokens <= 0 || heads <= 0 || (backward && (!d_o || !dqkv))) return fail(PARSEQ_E_INVALID, "bad argument");
     const int E = heads * TW_HD;
-    TrainAttnArgs a{};
-    a.q = qkv; a.q_bstride = (long)tokens * 3 * E; a.ldq = 3 * E; a.k = qkv + E; a.v = qkv + 2 * E; a.ldkv = 3 * E;
-    a.o = o; a.ldo = E; a.d_o = d_o; a.dq = dqkv; a.lddq = 3 * E; a.dk = dqkv ? dqkv + E : nullptr; a.dv = dqkv ? dqkv + 2 * E : nullptr;
-    a.lddkv = 3 * E; a.Lq = tokens; a.Lk = tokens; a.H = heads; a.scale = 1.0f / sqrtf((float)TW_HD); a.lse = lse; a.dsum = dsum;
-    const TrainCtx cx{(hipStream_t)stream, nullptr, PARSEQ_F32, 0};
-    TrainAttnRoute took = TA_NONE;
-    const int rc = train_attn(cx, a, batch, backward != 0, TW_HD, &took);
+    parseq_train_attn_desc d{};
+    d.q = qkv; d.q_bstride = (int64_t)tokens * 3 * E; d.ldq = 3 * E; d.k = qkv + E; d.v = qkv + 2 * E; d.ldkv = 3 * E;
+    d.o = o; d.ldo = E; d.d_o = d_o; d.dq = dqkv; d.lddq = 3 * E; d.dk = dqkv ? dqkv + E : nullptr; d.dv = dqkv ? dqkv + 2 * E : nullptr;
+    d.lddkv = 3 * E; d.Lq = tokens; d.Lk = tokens; d.H = heads; d.scale = 1.0f / sqrtf((float)TW_HD); d.lse = lse; d.dsum = dsum;
+    d.head_dim = TW_HD; d.bf16_ops = PARSEQ_F32;
+    int32_t took = TA_NONE;
+    const int rc = parseq_op_train_attention_desc(&d, batch, backward, &took, stream);
     if (route) *route = took == TA_WIDE ? 1 : 0;
     return rc;
 }
@@ -582,15 +619,14 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     const int B = batch, L = ctx_len, K = num_perms;
     if (B <= 0 || L < 2 || L > m->cfg.max_label_length + 1 || K <= 0 || total_targets <= 0)
         return fail(PARSEQ_E_INVALID, "bad shape: batch %d, ctx_len %d (2..%d), %d permutations, %d targets", B, L, m->cfg.max_label_length + 1, K, total_targets);
-    if (!(dropout_p >= 0.f && dropout_p < 1.f)) return fail(PARSEQ_E_INVALID, "dropout_p %g outside [0, 1)", dropout_p);
+    if (!dropout_p_ok(dropout_p)) return fail(PARSEQ_E_INVALID, "dropout_p %g outside [0, 1)", dropout_p);
     const TrainDecRoute route = train_dec_route(m, L, K);
     const TrainDecoderLayout o = train_decoder_layout(m, B, L, K, route);
     if (workspace_bytes < o.total * sizeof(float)) return fail(PARSEQ_E_INVALID, "workspace: %zu bytes given, %zu needed", workspace_bytes, o.total * sizeof(float));
     hipStream_t s = (hipStream_t)stream;
     const int E = m->cfg.embed_dim, F = E * m->cfg.dec_mlp_ratio, S = m->tokens, C = m->classes, H = m->cfg.dec_heads, M = B * L, MS = B * S;
     const float eps = m->cfg.dec_ln_eps, scale = 1.0f / sqrtf(32.0f), sqrtE = sqrtf((float)E);
-    DropSpec drop{(unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), 0u, 1.0f};
-    if (dropout_p > 0.f) { drop.thresh = (unsigned)((double)dropout_p * 4294967296.0); drop.scale = 1.0f / (1.0f - dropout_p); }
+    const DropSpec drop = drop_spec(dropout_p, seed);
     float* w = reinterpret_cast<float*>(workspace);
     const TrainDecW W = train_dec_weights(m, grads);
     // the in-projections by their rows: [0, E) the queries, [E, 3E) k | v
@@ -628,6 +664,14 @@ extern "C" int parseq_train_decoder(parseq_model* m, const float* memory, const 
     // the route (and with it the layout, which then has no per-pass copies) chose the pass-walking kernel; the kernel's own preconditions must agree
     TrainAttnPlan ca_plan;      // consulted for its route alone (pass_loop is set per batch below); a refusal by the plan is answered with the message here
     if (ca_loop && (train_attn_plan(cx, ca, 32, KP * B, true, &ca_plan) != 0 || ca_plan.route != TA_DEC_BF16)) return fail(PARSEQ_E_STATE, "training decoder: the workspace was laid out for the pass-walking cross-attention, which this call cannot run (its operands are not aligned for it)");
+    // Both attentions are planned in both directions BEFORE the passes start (only the workspace has been written so far): the backward holds more in LDS than the forward
+    // (train_attn_lds_floats: at 32 queries of width 32 the forward fits up to 256 keys, the backward up to 223), so without this a step in
+    // the fp32 mode over 224..256 memory tokens would run its forward and be refused in the middle of its backward, gradients half written.
+    // Planned as the arguments stand here: sa.qmask is still null and ca.pass_loop still 0 (both are set per batch below).  At head width 32 no
+    // route asks whether a mask is present, and pass_loop only adds a condition on pass_B, kv_shared and the batch size that the per-batch
+    // call meets by construction (pass_loop = kp, batch = kp * B) — a route that came to depend on either would have to be planned with them set.
+    for (const TrainAttnArgs* at : {&sa, &ca})
+        for (const bool bw : {false, true}) { TrainAttnPlan pl; CHK(train_attn_plan(cx, *at, 32, KP * B, bw, &pl)); }
     enum { S_CONTENT, S_QUERY, S_SA_PROB, S_SA_OUT, S_CA_PROB, S_CA_OUT, S_FF_HIDDEN, S_FF_OUT };      // dropout sites of one pass
 
     for (int i0 = 0; i0 < K; i0 += KP) {
