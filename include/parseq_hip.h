@@ -413,6 +413,44 @@ int parseq_forward_lexicon_match(parseq_plan* p, const void* images, int images_
                                  uint8_t* finished_out, int32_t* words_out, int32_t* distances_out, int32_t* reading_tokens_out,
                                  int32_t* reading_lengths_out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- orientation-robust reading (pure additions under ABI 15; DESIGN.md section 27 defines it) ----------------------- */
+
+/* The best of K turned views of every crop, chosen on the device.  Rows b K .. b K + K - 1 of `logits` (fp32 [batch * views, L, C]) are the
+ * views of crop b.  parseq_postprocess' kernel runs on all rows; the key of a view is, in fp64 and with n = min(length + 1, L),
+ *   s = sum_{i < n} log((double)p_i) added in position order (p_i the fp32 probability parseq_postprocess gives position i),
+ *   PARSEQ_ORIENT_SUM: s (the log of the confidence's product)      PARSEQ_ORIENT_MEAN: s / n
+ * plus (double)prior[k] when prior (device fp32 [views]) is not NULL; a NaN key counts as -inf and is stored as -inf.  The winner is the
+ * first view of the largest key (view 0 when every key is -inf).
+ *   images, images_out   NULL together, or device [batch * views, image_elems] and [batch, image_elems] of images_dtype (PARSEQ_F32,
+ *                        PARSEQ_BF16 or PARSEQ_U8): the winner's crop is copied beside its logits; no alignment is asked of either
+ *   view_out             int32 [batch]              keys_out   fp64 [batch, views]
+ *   logits_out           fp32 [batch, L, C]: the winner's rows, bit for bit
+ *   ids_out, lengths_out, confidence_out   int32 [batch, L], int32 [batch], fp32 [batch]: exactly what parseq_postprocess writes for the winner
+ *   workspace            device, parseq_op_orient_select_workspace_bytes(batch, views, L) bytes (0: a shape outside the ranges), 16-byte aligned
+ * Two launches, no host synchronisation.  Refused with PARSEQ_E_INVALID before any device work, outputs untouched: views outside
+ * 1 .. PARSEQ_ORIENT_MAX_VIEWS, L outside 1 .. 64, batch * views above 2^26, an eos_id outside [0, C), an unknown criterion, only one of images
+ * and images_out, a NULL output, a short or misaligned workspace. */
+#define PARSEQ_ORIENT_MAX_VIEWS 8
+enum parseq_orient_criterion { PARSEQ_ORIENT_MEAN = 0, PARSEQ_ORIENT_SUM = 1 };
+size_t parseq_op_orient_select_workspace_bytes(int batch, int views, int L);
+int parseq_op_orient_select(const float* logits, int batch, int views, int L, int C, int eos_id, const void* images, int images_dtype,
+                            int64_t image_elems, int criterion, const float* prior, int32_t* view_out, double* keys_out, float* logits_out,
+                            int32_t* ids_out, int32_t* lengths_out, float* confidence_out, void* images_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* parseq_forward's body on the batch * views rows of `images` (crop-major: row b * views + k is view k of crop b), then the op above on its
+ * logits — one call, no host synchronisation, no allocation.  flags: PARSEQ_FLAG_DECODE_AR, PARSEQ_FLAG_LATENCY; all num_steps positions
+ * are computed and the early exit never applies (a reading is cut at its <eos>, so readings and confidences are the same without it).
+ * images_out (NULL: not wanted) [batch, 3, img_h, img_w] of images_dtype.  workspace: parseq_forward_oriented_workspace_bytes(p, batch,
+ * views, num_steps) device bytes (0: refused, parseq_last_error says why), 16-byte aligned.  Afterwards the plan's cached memory K / V are
+ * those of the batch * views rows.  Refused with PARSEQ_E_INVALID before any device work, outputs untouched: a ViTSTR model (run
+ * parseq_vitstr_forward, then the op), batch * views above the plan's max_batch, views outside 1 .. PARSEQ_ORIENT_MAX_VIEWS, an unknown
+ * criterion, whatever parseq_forward refuses, a NULL output, a short or misaligned workspace. */
+size_t parseq_forward_oriented_workspace_bytes(const parseq_plan* p, int batch, int views, int num_steps);
+int parseq_forward_oriented(parseq_plan* p, const void* images, int images_dtype, int batch, int views, int flags, int refine_iters,
+                            int num_steps, int criterion, const float* prior, int32_t* view_out, double* keys_out, float* logits_out,
+                            int32_t* ids_out, int32_t* lengths_out, float* confidence_out, void* images_out, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ---- beam search over a weighted automaton (pure additions under ABI 15; DESIGN.md section 24 defines it) ------------ */
 
 /* parseq_forward_beam_lexicon with a weight on every arc of the table, which then need not be a tree (cycles and shared states are

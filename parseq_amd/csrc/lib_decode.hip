@@ -5,6 +5,7 @@
 #include "beam_refine.h"
 #include "attn_map.h"
 #include "lexicon_match.h"
+#include "orient.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -1271,4 +1272,99 @@ extern "C" int parseq_forward_lexicon_match(parseq_plan* p, const void* images, 
     CHK(encode_dispatch(p, images, images_dtype, batch, ws.memory, s));      // (without rescoring ws.memory is null: nothing reads the memory again)
     const LexMatchOut out{tokens_out, scores_out, lengths_out, finished_out, words_out, distances_out, reading_tokens_out, reading_lengths_out};
     return dispatch_te(p, [&](auto te) { return lexmatch_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, flags, refine_iters, args, ws, out, s); });
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// orientation-robust reading (orient.h): the best of K turned views of every crop
+// -------------------------------------------------------------------------------------------------------------------
+// What postprocess_kernel leaves for the batch * views rows.
+struct OrientWs { int *ids, *lens; float *probs, *confs; size_t total; };
+static OrientWs orient_ws(int batch, int views, int L, void* workspace = nullptr) {
+    const size_t rows = (size_t)batch * views;
+    Carver cv{reinterpret_cast<unsigned char*>(workspace)};
+    OrientWs o{};
+    o.ids = cv.take<int>(rows * L); o.probs = cv.take<float>(rows * L); o.lens = cv.take<int>(rows); o.confs = cv.take<float>(rows);
+    o.total = cv.off;
+    return o;
+}
+
+static int orient_shape_check(int batch, int views, int L) {
+    if (views < 1 || views > ORIENT_MAX_VIEWS) return fail(PARSEQ_E_INVALID, "orient: %d views, it must be in 1 .. %d", views, ORIENT_MAX_VIEWS);
+    if (batch < 1 || (long long)batch * views > (1 << 26)) return fail(PARSEQ_E_INVALID, "orient: batch %d x %d views outside (0, %d]", batch, views, 1 << 26);
+    if (L < 1 || L > 64) return fail(PARSEQ_E_INVALID, "orient: L = %d positions, it must be in 1 .. 64", L);
+    return 0;
+}
+
+extern "C" size_t parseq_op_orient_select_workspace_bytes(int batch, int views, int L) {
+    if (orient_shape_check(batch, views, L) != 0) return 0;
+    return orient_ws(batch, views, L).total;
+}
+
+extern "C" int parseq_op_orient_select(const float* logits, int batch, int views, int L, int C, int eos_id, const void* images, int images_dtype,
+                                       int64_t image_elems, int criterion, const float* prior, int32_t* view_out, double* keys_out, float* logits_out,
+                                       int32_t* ids_out, int32_t* lengths_out, float* confidence_out, void* images_out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    static_assert(ORIENT_MAX_VIEWS == PARSEQ_ORIENT_MAX_VIEWS && ORIENT_MEAN == PARSEQ_ORIENT_MEAN && ORIENT_SUM == PARSEQ_ORIENT_SUM, "header and kernel must agree");
+    CHK(orient_shape_check(batch, views, L));
+    if (C < 1 || eos_id < 0 || eos_id >= C) return fail(PARSEQ_E_INVALID, "orient: C = %d classes, eos_id %d", C, eos_id);
+    if (criterion != PARSEQ_ORIENT_MEAN && criterion != PARSEQ_ORIENT_SUM) return fail(PARSEQ_E_INVALID, "orient: unknown criterion %d", criterion);
+    if (!logits || !view_out || !keys_out || !logits_out || !ids_out || !lengths_out || !confidence_out || !workspace)
+        return fail(PARSEQ_E_INVALID, "orient: null logits / output / workspace");
+    size_t image_bytes = 0;
+    if (images || images_out) {
+        if (!images || !images_out) return fail(PARSEQ_E_INVALID, "orient: images and images_out go together");
+        if (images_dtype != PARSEQ_F32 && images_dtype != PARSEQ_BF16 && images_dtype != PARSEQ_U8) return fail(PARSEQ_E_INVALID, "orient: images_dtype %d", images_dtype);
+        if (image_elems < 1 || image_elems > (int64_t)1 << 32) return fail(PARSEQ_E_INVALID, "orient: %lld elements per crop", (long long)image_elems);
+        image_bytes = (size_t)image_elems * (images_dtype == PARSEQ_F32 ? 4 : images_dtype == PARSEQ_BF16 ? 2 : 1);
+    }
+    const OrientWs ws = orient_ws(batch, views, L, workspace);
+    if (workspace_bytes < ws.total) return fail(PARSEQ_E_INVALID, "orient workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "orient workspace not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int rows = batch * views;
+    CHK(launch(postprocess_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, rows, L, C, eos_id, ws.ids, ws.lens, ws.probs, ws.confs));
+    return launch(orient_select_kernel, dim3(batch), dim3(ORIENT_THREADS), 0, s, logits, (const int*)ws.ids, (const int*)ws.lens, (const float*)ws.probs,
+                  (const float*)ws.confs, images, image_bytes, views, L, C, criterion, prior, view_out, keys_out, logits_out, ids_out, lengths_out,
+                  confidence_out, images_out);
+}
+
+// The whole call's workspace: the logits of the batch * views rows, then the op's.
+static int orient_forward_check(const parseq_plan* p, int batch, int views, int num_steps, int criterion) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    if (p->m->vitstr) return fail(PARSEQ_E_INVALID, "parseq_forward_oriented on a ViTSTR model: parseq_vitstr_forward, then parseq_op_orient_select");
+    const int npos = p->m->cfg.max_label_length + 1;
+    if (num_steps < 1 || num_steps > npos) return fail(PARSEQ_E_INVALID, "num_steps %d outside [1, %d]", num_steps, npos);
+    CHK(orient_shape_check(batch, views, num_steps));
+    if ((long long)batch * views > p->max_batch) return fail(PARSEQ_E_INVALID, "orient: batch %d x %d views outside (0, %d]", batch, views, p->max_batch);
+    if (criterion != PARSEQ_ORIENT_MEAN && criterion != PARSEQ_ORIENT_SUM) return fail(PARSEQ_E_INVALID, "orient: unknown criterion %d", criterion);
+    return 0;
+}
+
+extern "C" size_t parseq_forward_oriented_workspace_bytes(const parseq_plan* p, int batch, int views, int num_steps) {
+    if (orient_forward_check(p, batch, views, num_steps, PARSEQ_ORIENT_MEAN) != 0) return 0;
+    size_t off = 0;
+    carve(off, (size_t)batch * views * num_steps * p->m->classes * sizeof(float));
+    return off + orient_ws(batch, views, num_steps).total;
+}
+
+extern "C" int parseq_forward_oriented(parseq_plan* p, const void* images, int images_dtype, int batch, int views, int flags, int refine_iters,
+                                       int num_steps, int criterion, const float* prior, int32_t* view_out, double* keys_out, float* logits_out,
+                                       int32_t* ids_out, int32_t* lengths_out, float* confidence_out, void* images_out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    CHK(orient_forward_check(p, batch, views, num_steps, criterion));
+    if (!view_out || !keys_out || !logits_out || !ids_out || !lengths_out || !confidence_out || !workspace) return fail(PARSEQ_E_INVALID, "orient: null output / workspace");
+    const size_t need = parseq_forward_oriented_workspace_bytes(p, batch, views, num_steps);
+    if (workspace_bytes < need) return fail(PARSEQ_E_INVALID, "orient workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "orient workspace not 16-byte aligned");
+    const parseq_config& c = p->m->cfg;
+    const int rows = batch * views;
+    size_t off = 0;
+    carve(off, (size_t)rows * num_steps * p->m->classes * sizeof(float));
+    float* all = reinterpret_cast<float*>(workspace);
+    // every position of every view: the early exit only truncates what parseq_forward returns, and a reading is cut at its <eos> anyway
+    CHK(parseq_forward(p, images, images_dtype, rows, flags & ~PARSEQ_FLAG_TESTING, refine_iters, num_steps, all, nullptr, stream));
+    DevGuard dg(p->m->device);
+    return parseq_op_orient_select(all, batch, views, num_steps, p->m->classes, c.eos_id, images_out ? images : nullptr, images_dtype,
+                                   (int64_t)3 * c.img_h * c.img_w, criterion, prior, view_out, keys_out, logits_out, ids_out, lengths_out, confidence_out,
+                                   images_out, static_cast<unsigned char*>(workspace) + off, workspace_bytes - off, stream);
 }

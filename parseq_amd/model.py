@@ -136,6 +136,72 @@ def check_labels(labels, max_label_length: int):
             raise ValueError(f'localize: label {y!r} has {len(y)} characters, the model reads at most max_label_length = {max_label_length}')
 
 
+@dataclass
+class OrientedResult:
+    """What `orient` returns, on the device: of the K turned views of every crop, the one the model reads best."""
+    view: Tensor                         # int32 [B] the winner: the first view of the largest key
+    keys: Tensor                         # fp64 [B, K] every view's key (a NaN key is stored as -inf)
+    logits: Tensor                       # fp32 [B, L, C] the winner's logits, bit for bit (`tokenizer.decode_logits` reads them)
+    ids: Tensor                          # int32 [B, L], int32 [B], fp32 [B]: what parseq_postprocess writes for the winner
+    lengths: Tensor
+    confidence: Tensor
+    images: Tensor                       # [B, 3, H, W] the winner's crop, in the dtype of the views
+
+
+def check_orient(shape, criterion, prior):
+    """The refusals of `orient` that need no device; returns (B, K, the prior as K floats or None)."""
+    if len(shape) != 5:
+        raise ValueError(f'orient: views must be [B, K, 3, H, W], got {list(shape)}')
+    B, K = int(shape[0]), int(shape[1])
+    if B < 1:
+        raise ValueError('orient: empty batch')
+    if not 1 <= K <= _native.ORIENT_MAX_VIEWS:
+        raise ValueError(f'orient: {K} views per crop, there must be 1 .. {_native.ORIENT_MAX_VIEWS}')
+    if criterion not in _native.ORIENT_CRITERIA:
+        raise ValueError(f"orient: criterion must be 'mean' or 'sum', got {criterion!r}")
+    if prior is not None:
+        prior = [float(v) for v in (prior.tolist() if isinstance(prior, Tensor) else prior)]
+        if len(prior) != K:
+            raise ValueError(f'orient: a prior of {len(prior)} values for {K} views')
+        if any(math.isnan(v) or v == math.inf for v in prior):
+            raise ValueError(f'orient: the prior {prior} must hold numbers below +inf (-inf rules a view out)')
+    return B, K, prior
+
+
+def orient_select(logits: Tensor, views: int, eos_id: int, images: Optional[Tensor] = None, criterion: str = 'mean', prior=None) -> OrientedResult:
+    """The choice alone (parseq_op_orient_select) on logits [B * K, L, C] whose rows b K .. b K + K - 1 are the K = `views` views of crop b,
+    and optionally their crops `images` [B * K, ...]: two launches, no host synchronisation."""
+    if logits.dim() != 3 or logits.dtype != torch.float32 or not logits.is_cuda or logits.shape[0] % views:
+        raise ValueError(f'orient_select: logits must be CUDA fp32 [B * {views}, L, C], got {logits.dtype} {list(logits.shape)}')
+    logits = logits.contiguous()
+    rows, L, C = logits.shape
+    B, dev = rows // views, logits.device
+    _, _, prior = check_orient((B, views, 0, 0, 0), criterion, prior)
+    images_out, elems, code = None, 0, 0
+    if images is not None:
+        if images.shape[0] != rows or images.device != dev:
+            raise ValueError(f'orient_select: images must hold {rows} crops on {dev}, got {list(images.shape)} on {images.device}')
+        images = images.contiguous()
+        code = _native.dtype_code(images.dtype)
+        elems = images[0].numel()
+        images_out = torch.empty((B,) + tuple(images.shape[1:]), dtype=images.dtype, device=dev)
+    pr = torch.tensor(prior, dtype=torch.float32).to(dev) if prior is not None else None
+    res = OrientedResult(torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, views, dtype=torch.float64, device=dev),
+                         torch.empty(B, L, C, dtype=torch.float32, device=dev), torch.empty(B, L, dtype=torch.int32, device=dev),
+                         torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float32, device=dev), images_out)
+    lib = _native.lib()
+    need = lib.parseq_op_orient_select_workspace_bytes(B, views, L)
+    if need == 0:
+        raise ValueError(f'orient_select: {B} crops of {views} views and {L} positions: the library takes 1 .. 64 positions and at most 2^26 rows')
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    with _native.guard(dev):
+        _native.check(lib.parseq_op_orient_select(_native.ptr(logits), B, views, L, C, int(eos_id), _native.ptr(images), code, elems,
+                                                  _native.ORIENT_CRITERIA[criterion], _native.ptr(pr), _native.ptr(res.view), _native.ptr(res.keys),
+                                                  _native.ptr(res.logits), _native.ptr(res.ids), _native.ptr(res.lengths), _native.ptr(res.confidence),
+                                                  _native.ptr(images_out), _native.ptr(ws), need, _native.stream_ptr(dev)))
+    return res
+
+
 def init_weights(module: nn.Module, name: str = '', exclude: Sequence[str] = ()):
     """Initialisation scheme of the reference (`strhub/models/utils.py:107-125`): trunc-normal(0.02) Linear / Embedding
     weights, zero biases, unit LayerNorm, Kaiming-normal(fan_out) convolutions.  This is a deliberate statement-for-statement
@@ -797,6 +863,34 @@ class PARSeq(_NativeBacked):
                                                        _native.ptr(res.tokens), _native.ptr(res.scores), _native.ptr(res.lengths), _native.ptr(res.finished),
                                                        _native.ptr(res.words), _native.ptr(res.distances), _native.ptr(res.reading_tokens),
                                                        _native.ptr(res.reading_lengths), _native.ptr(ws), ws.numel(), _native.stream_ptr(self._device)))
+        return res
+
+    def orient(self, tokenizer: Tokenizer, views: Tensor, criterion: str = 'mean', prior=None, max_length: Optional[int] = None,
+               slot: Optional[int] = None) -> OrientedResult:
+        """Orientation-robust reading: `views` [B, K, 3, H, W] holds K turned views of every crop
+        (`preprocess.orientation_views` makes them); all B * K rows go through one `forward` — every position, the early exit never applies —
+        and of each crop the view with the largest key wins: the length-normalised log-probability of its reading ('mean'), or its sum
+        ('sum', the log of the reference's confidence), plus `prior[k]` (K values in nats).  Ties go to the lowest view.  One library call,
+        no host synchronisation; everything stays on the device.  `max_length` and `slot` as in `forward`."""
+        B, K, prior = check_orient(tuple(getattr(views, 'shape', ())), criterion, prior)
+        num_steps = self._num_steps(max_length)
+        images = self._check_images(views.flatten(0, 1))
+        plan = self._plan(B * K, 0 if slot is None else slot)
+        self._memory_replaced(plan)
+        self._check_tokenizer(tokenizer)
+        dev, C_ = images.device, self._cfg['num_tokens'] - 2
+        pr = torch.tensor(prior, dtype=torch.float32).to(dev) if prior is not None else None
+        res = OrientedResult(torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, K, dtype=torch.float64, device=dev),
+                             torch.empty(B, num_steps, C_, dtype=torch.float32, device=dev), torch.empty(B, num_steps, dtype=torch.int32, device=dev),
+                             torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+                             torch.empty((B,) + tuple(images.shape[1:]), dtype=images.dtype, device=dev))
+        lib = _native.lib()
+        ws = self._workspace(lib.parseq_forward_oriented_workspace_bytes, plan, B, K, num_steps)
+        flags = (_native.FLAG_DECODE_AR if self.decode_ar else 0) | (_native.FLAG_LATENCY if slot is None else 0)
+        _native.check(lib.parseq_forward_oriented(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, K, flags, int(self.refine_iters), num_steps,
+                                                  _native.ORIENT_CRITERIA[criterion], _native.ptr(pr), _native.ptr(res.view), _native.ptr(res.keys),
+                                                  _native.ptr(res.logits), _native.ptr(res.ids), _native.ptr(res.lengths), _native.ptr(res.confidence),
+                                                  _native.ptr(res.images), _native.ptr(ws), ws.numel(), _native.stream_ptr(self._device)))
         return res
 
     def _check_localizable(self, what: str) -> None:

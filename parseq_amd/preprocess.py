@@ -491,3 +491,86 @@ def mesh_rectify_resize_batch(images: Sequence[Tensor], regions, size=(32, 128),
     lib = _native.lib()
     return _region_call(keep, described, _native_mesh(keep, described), lib.parseq_mesh_rectify_workspace_bytes, lib.parseq_mesh_rectify_resize_bicubic,
                         size)
+
+
+# ---- turned views of a crop -------------------------------------------------------------------------------------
+# A reader that does not know which way up a crop is reads it in a few quarter turns and keeps the reading the model trusts most
+# (`model.orient`).  The views are made here: Pillow-exact quarter turns fused into the resize, every source uploaded once.
+ORIENTATION_MODES = ('flip', 'auto', 'all')
+
+
+def orientation_angles(sizes, mode: str, tall: float = 1.5):
+    """The angles (degrees counter clockwise, as `resize_batch(rotation=)` takes them) of the views of crops of `sizes` [(h, w)]: one
+    tuple per crop, the upright guess first.  'flip': (0, 180); 'all': (0, 90, 180, 270); 'auto': (90, 270) for a crop with h > tall * w
+    — vertical text — and (0, 180) otherwise, so every crop has two views."""
+    if mode not in ORIENTATION_MODES:
+        raise ValueError(f'orientation mode must be one of {ORIENTATION_MODES}, got {mode!r}')
+    if not (isinstance(tall, numbers.Real) and math.isfinite(tall) and tall > 0):
+        raise ValueError(f'tall must be a positive number, got {tall!r}')
+    if mode == 'flip':
+        return [(0, 180) for _ in sizes]
+    if mode == 'all':
+        return [(0, 90, 180, 270) for _ in sizes]
+    return [(90, 270) if h > tall * w else (0, 180) for h, w in sizes]
+
+
+def orientation_views(images: Sequence[Tensor], mode: str = 'flip', size=(32, 128), tall: float = 1.5, rotation=0):
+    """images: CUDA uint8 tensors [H_i, W_i, 3].  Returns (views uint8 [B, K, 3, size[0], size[1]], angles): view k of crop b is
+    `resize_batch([images[b]], size, rotation=rotation + angles[b][k])`.  One parseq_rotate_resize_bicubic launch over B * K descriptors;
+    the K descriptors of a crop point at the one copy of its pixels.  `rotation` (degrees, one value; test.py --rotation) turns every crop
+    before its views are taken: each view is ONE Pillow rotation by the sum of the two angles, and 'auto' judges the turned crop's shape."""
+    keep = _checked(images, 'orientation_views')
+    dev = keep[0].device
+    angles = orientation_angles([rotation_map(im.shape[0], im.shape[1], rotation)[1:3] for im in keep], mode, tall)
+    K = len(angles[0])
+    n = len(keep) * K
+    descs, _ = _rotated_descs([im for im in keep for _ in range(K)], [rotation + a for per_crop in angles for a in per_crop])
+    lib = _native.lib()
+    out = torch.empty((len(keep), K, 3, size[0], size[1]), dtype=torch.uint8, device=dev)
+    ws = torch.empty((lib.parseq_rotate_resize_workspace_bytes(n),), dtype=torch.uint8, device=dev)
+    with _native.guard(dev):
+        _native.check(lib.parseq_rotate_resize_bicubic(descs, n, size[0], size[1], _native.ptr(out), _native.ptr(ws), _native.stream_ptr(dev)))
+    torch.cuda.current_stream(dev).synchronize()          # the descriptor array is host memory read by an asynchronous copy
+    return out, angles
+
+
+def rotated_size(angle, size):
+    """(h, w) of an image of `size` = (h, w) turned by a multiple of 90 degrees."""
+    return (size[1], size[0]) if angle % 180 == 90 else (size[0], size[1])
+
+
+def unrotate_points(angle, size, points):
+    """The way back from a turned image to its source: `points` (x, y) in pixels of the image Image.rotate(angle, expand=True) makes of a
+    source of `size` = (h, w), angle a multiple of 90 degrees, as [(x, y)] in pixels of the source.  A pixel's area maps onto the area of
+    the pixel it was copied from: (x' + 0.5, y' + 0.5) goes to the centre of the source pixel of (x', y')."""
+    h, w = size
+    angle = angle % 360
+    if angle not in (0, 90, 180, 270):
+        raise ValueError(f'unrotate_points: {angle} degrees is not a multiple of 90')
+    if angle == 0:
+        return [(x, y) for x, y in points]
+    if angle == 90:
+        return [(w - y, x) for x, y in points]
+    if angle == 180:
+        return [(w - x, h - y) for x, y in points]
+    return [(y, h - x) for x, y in points]
+
+
+def shift_quad(quad, k: int):
+    """View k of a quadrilateral: its corner list shifted cyclically by k, so that corner k becomes the text's top-left.  The rectified
+    crop of shift k is the crop of shift 0 turned by 90 k degrees counter clockwise (shift 1: what was the top-right corner is now the
+    top-left), and `region_size` swaps height and width under an odd shift."""
+    quad = list(quad)
+    if len(quad) != 4:
+        raise ValueError(f'a quadrilateral has 4 points, got {len(quad)}')
+    k %= 4
+    return quad[k:] + quad[:k]
+
+
+def orientation_regions(regions, mode: str = 'flip', tall: float = 1.5):
+    """The views of quadrilateral regions [(image_index, quad)] for `rectify_resize_batch`: (regions of all views, crop-major; the shifts of
+    every region).  The shifts are the angles of `orientation_angles` on the `region_size` of each quad, divided by 90."""
+    regions = [(index, list(quad)) for index, quad in regions]
+    angles = orientation_angles([region_size(quad) for _, quad in regions], mode, tall)
+    shifts = [tuple(a // 90 for a in per_region) for per_region in angles]
+    return [(index, shift_quad(quad, k)) for (index, quad), per_region in zip(regions, shifts) for k in per_region], shifts

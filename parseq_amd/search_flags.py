@@ -2,7 +2,8 @@
 --lm-weight / --char-bonus / --match / --refine-beams ask for, which of them go together, and the arguments of `beam_search` /
 `lexicon_match` / `BeamEvaluator` they turn into.  One set of composition and refusal rules for every command line: a contradiction ends
 in `parser.error`.  The resolvers read `args.nbest` and `args.boxes` too; a command line without those flags sets them (test.py: the
-N-best is the whole beam, no boxes)."""
+N-best is the whole beam, no boxes).  --auto-rotate / --upright-bias have their rules at the end of the module: they
+choose the crops every other flag then works on, so they compose with all of them but --polygons."""
 from collections import namedtuple
 
 LEXICON_BEAM = 8      # --beam under --lexicon when none is given
@@ -191,3 +192,33 @@ def evaluator_arguments(model, args, flags):
 def evaluation_width(flags) -> int:
     """Hypotheses per image of the search `flags` ask for: the W of the table's Hit@W."""
     return flags.match if flags.match is not None else flags.beam
+
+
+# ---- --auto-rotate (DESIGN.md section 27) -----------------------------------------------------------------------------------------------
+def add_orientation_flags(parser):
+    """--auto-rotate / --upright-bias, for read.py and test.py alike."""
+    parser.add_argument('--auto-rotate', default=None, choices=['flip', 'auto', 'all'], dest='auto_rotate', metavar='MODE',
+                        help="Read every crop in several quarter turns and keep the one the model reads best: 'flip' tries 0 and 180 degrees, "
+                             "'all' 0, 90, 180 and 270, 'auto' 90 and 270 for a crop more than 1.5 times as high as wide and 0 and 180 otherwise")
+    parser.add_argument('--upright-bias', type=float, default=None, dest='upright_bias', metavar='X',
+                        help="With --auto-rotate: a prior of X nats on every crop's first view (default 0)")
+
+
+def resolve_orientation(parser, args):
+    """(mode, bias) of --auto-rotate, None without it; a contradiction ends in parser.error.  Reads `args.polygons` where the command line has it."""
+    import math
+    if args.auto_rotate is None:
+        if args.upright_bias is not None:
+            parser.error('--upright-bias needs --auto-rotate MODE')
+        return None
+    if getattr(args, 'polygons', None) is not None:
+        parser.error('--auto-rotate with --polygons: a polygon has no corner order to shift; cut the regions as quadrilaterals (--regions)')
+    bias = 0.0 if args.upright_bias is None else args.upright_bias
+    if not math.isfinite(bias):
+        parser.error('--upright-bias must be finite')
+    return args.auto_rotate, bias
+
+
+def orientation_prior(bias: float, views: int):
+    """The prior of `orient` for --upright-bias: `bias` on the first view, None for no bias."""
+    return None if bias == 0.0 else [bias] + [0.0] * (views - 1)

@@ -283,6 +283,13 @@ class PARSeq(nn.Module):
         `self.tokenizer.decode_localization(result)` turns it into strings and per-character boxes.  uint8 images as in `forward`."""
         return self.model.localize(self.tokenizer, images, labels)
 
+    def orient(self, views: Tensor, criterion: str = 'mean', prior=None, max_length: Optional[int] = None, slot: Optional[int] = None):
+        """Of K turned views of every crop, `views` [B, K, 3, H, W] (`preprocess.orientation_views`), the one the model reads best
+        (model.PARSeq.orient): an `OrientedResult` on the device — the winner's index, every view's key, and the
+        winner's logits, ids, lengths, confidence and crop.  `self.tokenizer.decode_logits(result.logits)` turns it into strings, and
+        `result.images` goes into any other call (`beam_search`, `lexicon_match`, `localize`) as upright crops."""
+        return self.model.orient(self.tokenizer, views, criterion=criterion, prior=prior, max_length=max_length, slot=slot)
+
     # ---- evaluation glue used by the reference's test.py:121-126 ------------------------------------------------
     def _eval_step(self, batch, validation: bool):
         return eval_step(self, batch, validation)

@@ -144,6 +144,15 @@ class ViTSTR(nn.Module):
     def localize(self, images: Tensor, labels=None):
         raise ValueError('localize: ViTSTR has no decoder, hence no cross-attention over the patch tokens; use a PARSeq model')
 
+    def orient(self, views: Tensor, criterion: str = 'mean', prior=None, max_length: Optional[int] = None, slot: Optional[int] = None):
+        """As `PARSeq.orient`: `forward` on the B * K rows of `views` [B, K, 3, H, W], then the choice on the device
+        (parseq_op_orient_select).  No host synchronisation."""
+        from .model import check_orient, orient_select
+        check_orient(tuple(getattr(views, 'shape', ())), criterion, prior)
+        images = self.model._check_images(views.flatten(0, 1))      # the dtype the model reads is the dtype the winner's crop comes back in
+        logits = self.forward(images, max_length, 0 if slot is None else slot)
+        return orient_select(logits, views.shape[1], self.eos_id, images, criterion, prior)
+
     def _eval_step(self, batch, validation: bool):
         return eval_step(self, batch, validation)
 

@@ -13,6 +13,7 @@
     ./read.py pretrained=parseq --images a.png --boxes     a second line per image: every character with its box in the image's own pixels
     ./read.py pretrained=parseq --images scene.jpg --regions scene.txt [--boxes]     read every quadrilateral of the file (x1,y1,..,x4,y4 per line)
     ./read.py pretrained=parseq --images scene.jpg --polygons scene.txt [--boxes]     read every polygon of the file (x1,y1,..,xK,yK per line): curved text
+    ./read.py pretrained=parseq --images a.png --auto-rotate flip [--upright-bias 0.1]     read every crop upright and upside down, keep the better reading
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -25,35 +26,58 @@ import torch
 from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
-from parseq_amd.preprocess import resize_batch
-from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, build_automaton, load_word_counts, load_word_list, resolve_automaton,  # noqa: F401
-                                      resolve_flags, resolve_match, resolve_refine, resolve_search)
+from parseq_amd.preprocess import resize_batch, rotated_size, unrotate_points
+from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, add_orientation_flags, build_automaton, load_word_counts, load_word_list,  # noqa: F401
+                                      orientation_prior, resolve_automaton, resolve_flags, resolve_match, resolve_orientation, resolve_refine, resolve_search)
+
+
+def turned_name(name, angle):
+    """How --auto-rotate names a reading: the name itself for a crop read as it came, `name@angle` for one read turned by `angle` degrees
+    counter clockwise."""
+    return name if angle % 360 == 0 else f'{name}@{angle % 360}'
+
+
+def crop_batch(model, crops, orient=None):
+    """(batch, angles, result): the model's input for `crops`.  Without `orient` the resized crops, angles all 0 and no result; with
+    `orient` = (mode, bias) of --auto-rotate the view of every crop that the model reads best, the angle it was
+    turned by, and the `OrientedResult` of that choice."""
+    img_size = tuple(model.hparams.img_size)
+    if orient is None:
+        return resize_batch(crops, img_size), [0] * len(crops), None
+    from parseq_amd.preprocess import orientation_views
+    views, angles = orientation_views(crops, orient[0], img_size)
+    result = model.orient(views, prior=orientation_prior(orient[1], views.shape[1]))
+    return result.images, [a[k] for a, k in zip(angles, result.view.cpu().tolist())], result
 
 
 @torch.inference_mode()
-def read_files(model, files, device='cuda'):
-    """[(file, label, confidence)] for image files, one batched forward."""
+def read_files(model, files, device='cuda', orient=None):
+    """[(file, label, confidence)] for image files, one batched forward.  `orient`: see `crop_batch`; a turned crop is named `file@angle`."""
     import numpy as np
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     if not crops:
         return []
+    if orient is not None:
+        _, angles, result = crop_batch(model, crops, orient)
+        labels, confidences = model.tokenizer.read(result.logits)
+        return list(zip([turned_name(f, a) for f, a in zip(files, angles)], labels, confidences.tolist()))
     batch = resize_batch(crops, tuple(model.hparams.img_size))          # uint8 [N, 3, H, W], Pillow-exact bicubic
     labels, confidences = model.tokenizer.read(model(batch))             # normalisation happens inside the patch embedding
     return list(zip(files, labels, confidences.tolist()))
 
 
 @torch.inference_mode()
-def read_files_nbest(model, files, nbest, beam_width=None, device='cuda', refine=None, refine_iters=1):
+def read_files_nbest(model, files, nbest, beam_width=None, device='cuda', refine=None, refine_iters=1, orient=None):
     """[(file, [(label, log-probability)] best first, at most `nbest`)] through one beam search of width `beam_width` (default `nbest`);
     `refine` ('edit' / 'score') refines the alternatives on the device and ranks them by their refined scores."""
     import numpy as np
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     if not crops:
         return []
-    batch = resize_batch(crops, tuple(model.hparams.img_size))
+    batch, angles, _ = crop_batch(model, crops, orient)
     search = {} if refine is None else {'refine': refine, 'refine_iters': refine_iters}
     beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width or nbest, **search))
-    return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
+    return [(turned_name(f, a), alts[:nbest]) for f, a, alts in zip(files, angles, beams)]
 
 
 def scale_box(box, img_size, size):
@@ -63,18 +87,26 @@ def scale_box(box, img_size, size):
     return (box[0] * sx, box[1] * sy, box[2] * sx, box[3] * sy)
 
 
+def unturned_box(box, angle, size):
+    """A box (x0, y0, x1, y1) in pixels of a crop of `size` = (h, w) turned by `angle` (a multiple of 90 degrees), in pixels of the crop itself."""
+    (xa, ya), (xb, yb) = unrotate_points(angle, size, ((box[0], box[1]), (box[2], box[3])))
+    return (min(xa, xb), min(ya, yb), max(xa, xb), max(ya, yb))
+
+
 @torch.inference_mode()
-def read_files_boxes(model, files, device='cuda'):
+def read_files_boxes(model, files, device='cuda', orient=None):
     """[(file, label, [(character, (x0, y0, x1, y1))])]: the greedy reading of every file and where each of its characters is (DESIGN.md
-    section 21), boxes in pixels of the file's own image.  One batched call."""
+    section 21), boxes in pixels of the file's own image.  One batched call.  With `orient` the boxes of a turned crop are led back through
+    `unrotate_points`."""
     import numpy as np
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     if not crops:
         return []
     img_size = tuple(model.hparams.img_size)
-    batch = resize_batch(crops, img_size)
+    batch, angles, _ = crop_batch(model, crops, orient)
     labels, chars = model.tokenizer.decode_localization(model.localize(batch))
-    return [(f, label, [(ch, scale_box(box, img_size, crop.shape[:2])) for ch, box in row]) for f, label, row, crop in zip(files, labels, chars, crops)]
+    return [(turned_name(f, a), label, [(ch, unturned_box(scale_box(box, img_size, rotated_size(a, crop.shape[:2])), a, crop.shape[:2])) for ch, box in row])
+            for f, a, label, row, crop in zip(files, angles, labels, chars, crops)]
 
 
 def load_regions(path):
@@ -127,14 +159,17 @@ def load_polygons(path):
 
 
 @torch.inference_mode()
-def load_region_batch(model, files, region_files, device='cuda', polygons=False):
+def load_region_batch(model, files, region_files, device='cuda', polygons=False, orient=None):
     """The regions of `region_files[i]` cut out of `files[i]` and straightened, as one batch for the model: every
     scene is decoded and uploaded once, all regions of all scenes go through ONE rectify-and-resize call.  Returns (names, batch, back):
     `file#k` per region, k counting from 0 within its file; uint8 [N, 3, H, W] (None without regions); per region the (coefficients, (h, w))
     with which `map_to_source` leads from the model's input back into the scene.  With `polygons` the files hold polygons (`load_polygons`),
-    straightened strip by strip (section 25), and `back` holds per region the (strips, (h, w)) of `mesh_to_source`."""
+    straightened strip by strip (section 25), and `back` holds per region the (strips, (h, w)) of `mesh_to_source`.
+    With `orient` = (mode, bias) of --auto-rotate every quadrilateral is cut in the views of `orientation_regions` — its corner list shifted —
+    still in ONE rectify-and-resize call; the batch is the view of every region the model reads best, `back` that view's map, and a region
+    read at a shift k other than 0 is named `file#i@angle`, angle = 90 k."""
     import numpy as np
-    from parseq_amd.preprocess import mesh_rectify_resize_batch, polygon_descs, rectify_resize_batch, region_descs
+    from parseq_amd.preprocess import mesh_rectify_resize_batch, orientation_regions, polygon_descs, rectify_resize_batch, region_descs
     load, describe, rectify = (load_polygons, polygon_descs, mesh_rectify_resize_batch) if polygons else (load_regions, region_descs, rectify_resize_batch)
     names, regions = [], []
     for i, (f, rf) in enumerate(zip(files, region_files)):
@@ -143,21 +178,31 @@ def load_region_batch(model, files, region_files, device='cuda', polygons=False)
             regions.append((i, quad))
     if not regions:
         return [], None, []
+    shifts = None
+    if orient is not None:
+        regions, shifts = orientation_regions(regions, orient[0])
     described = describe(regions, n_images=len(files))
     scenes = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     batch = rectify(scenes, [(index, coeffs, size) for index, size, coeffs in described], tuple(model.hparams.img_size))
+    if shifts is not None:
+        K = len(shifts[0])
+        result = model.orient(batch.view(len(names), K, *batch.shape[1:]), prior=orientation_prior(orient[1], K))
+        view = result.view.cpu().tolist()
+        names = [turned_name(name, 90 * per_region[k]) for name, per_region, k in zip(names, shifts, view)]
+        batch, described = result.images, [described[i * K + k] for i, k in enumerate(view)]
     return names, batch, [(coeffs, size) for _, size, coeffs in described]
 
 
 @torch.inference_mode()
 def read_regions(model, files, region_files, beam=None, nbest=0, words=None, list_words=False, refine=None, refine_iters=1, boxes=False, device='cuda',
-                 match=None, prior=None, polygons=False):
+                 match=None, prior=None, polygons=False, orient=None):
     """The lines `--regions` prints, for the same flags as the whole-crop readings above, on the batch of `load_region_batch`: `words` is the
     list of --lexicon (its alternatives are listed only with `list_words`), `boxes` adds every character's quadrilateral in the scene, `match`
-    the N of --match, `prior` the (automaton, alpha, beta) of --priors / --lm / --pattern; `polygons` makes the files those of --polygons."""
+    the N of --match, `prior` the (automaton, alpha, beta) of --priors / --lm / --pattern; `polygons` makes the files those of --polygons; `orient` is the (mode, bias) of
+    --auto-rotate (`load_region_batch`)."""
     from parseq_amd.preprocess import map_to_source, mesh_to_source
     to_source = mesh_to_source if polygons else map_to_source
-    names, batch, back = load_region_batch(model, files, region_files, device, polygons)
+    names, batch, back = load_region_batch(model, files, region_files, device, polygons, orient)
     if not names:
         return []
     lines = []
@@ -199,7 +244,7 @@ def read_regions(model, files, region_files, beam=None, nbest=0, words=None, lis
 
 
 @torch.inference_mode()
-def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, device='cuda', refine=None):
+def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, device='cuda', refine=None, orient=None):
     """[(file, [(word, log-probability)] best first, at most `nbest`)]: one beam search of width `beam_width` constrained to `words`
     (DESIGN.md section 19).  A finished reading is a word of the list in the list's spelling; case is folded when the model's charset has
     only one.  A crop for which no word of the list finishes keeps its unfinished prefixes, or nothing.  `refine='score'` ranks the words by
@@ -210,10 +255,10 @@ def read_files_lexicon(model, files, words, nbest=1, beam_width=LEXICON_BEAM, de
     if not crops:
         return []
     lexicon = Lexicon(words, model.tokenizer, fold_case=True, max_label_length=model.model.max_label_length).to(device)
-    batch = resize_batch(crops, tuple(model.hparams.img_size))
+    batch, angles, _ = crop_batch(model, crops, orient)
     search = {} if refine is None else {'refine': refine}
     beams = model.tokenizer.decode_beams(model.beam_search(batch, beam_width, lexicon=lexicon, **search), lexicon)
-    return [(f, alts[:nbest]) for f, alts in zip(files, beams)]
+    return [(turned_name(f, a), alts[:nbest]) for f, a, alts in zip(files, angles, beams)]
 
 
 def automaton_batch(model, batch, beam_width, automaton, alpha, beta):
@@ -232,13 +277,14 @@ def automaton_lines(name, alts, list_all):
 
 
 @torch.inference_mode()
-def read_files_automaton(model, files, automaton, beam_width=8, alpha=1.0, beta=0.0, device='cuda'):
+def read_files_automaton(model, files, automaton, beam_width=8, alpha=1.0, beta=0.0, device='cuda', orient=None):
     """[(file, [(label, fused score, model log-probability, prior)] best first)] for image files: one batched search over `automaton`."""
     import numpy as np
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     if not crops:
         return []
-    return list(zip(files, automaton_batch(model, resize_batch(crops, tuple(model.hparams.img_size)), beam_width, automaton, alpha, beta)))
+    batch, angles, _ = crop_batch(model, crops, orient)
+    return list(zip([turned_name(f, a) for f, a in zip(files, angles)], automaton_batch(model, batch, beam_width, automaton, alpha, beta)))
 
 
 def match_batch(model, batch, words, n, device='cuda'):
@@ -259,13 +305,14 @@ def match_lines(name, alts, list_all):
 
 
 @torch.inference_mode()
-def read_files_match(model, files, words, n=MATCH_N, device='cuda'):
+def read_files_match(model, files, words, n=MATCH_N, device='cuda', orient=None):
     """[(file, [(word, pseudo-log-likelihood, distance)] best first)] for image files: one batched `lexicon_match` call."""
     import numpy as np
     crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
     if not crops:
         return []
-    return list(zip(files, match_batch(model, resize_batch(crops, tuple(model.hparams.img_size)), words, n, device)))
+    batch, angles, _ = crop_batch(model, crops, orient)
+    return list(zip([turned_name(f, a) for f, a in zip(files, angles)], match_batch(model, batch, words, n, device)))
 
 
 def build_parser():
@@ -308,6 +355,7 @@ def build_parser():
     parser.add_argument('--char-bonus', type=float, default=None, dest='char_bonus', metavar='B',
                         help='Added to the ranking per character read, with --priors / --lm / --pattern (default 0)')
     parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
+    add_orientation_flags(parser)      # --auto-rotate MODE [--upright-bias X]: a crop read turned is printed as file@angle
     return parser
 
 
@@ -324,6 +372,7 @@ def main(argv=None):
     if args.regions is not None and args.polygons is not None:
         parser.error('--polygons and --regions are two ways to cut the same scenes: give one of them')
     polygons = args.polygons is not None
+    orient = resolve_orientation(parser, args)
     region_files = args.polygons if polygons else args.regions
     if region_files is not None and len(region_files) != len(files):
         parser.error(f'--{"polygons" if polygons else "regions"} takes one file per image, in order: {len(region_files)} files for {len(files)} images')
@@ -332,9 +381,9 @@ def main(argv=None):
         automaton = build_automaton(model, kind, args)
         if region_files is not None:
             lines = read_regions(model, files, region_files, beam, nbest, list_words=args.nbest > 0, device=args.device, prior=(automaton, alpha, beta),
-                                 polygons=polygons)
+                                 polygons=polygons, orient=orient)
         else:
-            lines = [line for fname, alts in read_files_automaton(model, files, automaton, beam, alpha, beta, args.device)
+            lines = [line for fname, alts in read_files_automaton(model, files, automaton, beam, alpha, beta, args.device, orient)
                      for line in automaton_lines(fname, alts[:nbest], args.nbest > 0)]
         for line in lines:
             print(line)
@@ -342,28 +391,28 @@ def main(argv=None):
     if region_files is not None:
         words = load_word_list(args.lexicon) if args.lexicon is not None else None
         for line in read_regions(model, files, region_files, beam, nbest, words, args.nbest > 0, refine, refine_iters, args.boxes, args.device, match,
-                                 polygons=polygons):
+                                 polygons=polygons, orient=orient):
             print(line)
         return
     if match is not None:
-        for fname, alts in read_files_match(model, files, load_word_list(args.lexicon), match, args.device):
+        for fname, alts in read_files_match(model, files, load_word_list(args.lexicon), match, args.device, orient):
             for line in match_lines(fname, alts[:nbest], args.nbest > 0):
                 print(line)
         return
     if args.lexicon is not None:
         # the best word of the list where the greedy reading goes; the alternatives only where --nbest asks for them
-        for fname, alts in read_files_lexicon(model, files, load_word_list(args.lexicon), nbest, beam, args.device, refine):
+        for fname, alts in read_files_lexicon(model, files, load_word_list(args.lexicon), nbest, beam, args.device, refine, orient):
             print(f'{fname}: {alts[0][0] if alts else ""}')
             for label, logp in (alts if args.nbest > 0 else []):
                 print(f'    {logp:9.4f}  {label}')
         return
     if args.boxes:
-        for fname, pred, chars in read_files_boxes(model, files, args.device):
+        for fname, pred, chars in read_files_boxes(model, files, args.device, orient):
             print(f'{fname}: {pred}')
             print('    ' + ' '.join(f'{ch}[{x0:.1f},{y0:.1f},{x1:.1f},{y1:.1f}]' for ch, (x0, y0, x1, y1) in chars))
         return
-    alternatives = dict(read_files_nbest(model, files, args.nbest, args.beam, args.device, refine, refine_iters)) if args.nbest > 0 else {}
-    for fname, pred, _ in read_files(model, files, args.device):
+    alternatives = dict(read_files_nbest(model, files, args.nbest, args.beam, args.device, refine, refine_iters, orient)) if args.nbest > 0 else {}
+    for fname, pred, _ in read_files(model, files, args.device, orient):
         print(f'{fname}: {pred}')
         for label, logp in alternatives.get(fname, []):
             print(f'    {logp:9.4f}  {label}')

@@ -7,6 +7,7 @@
     ./test.py pretrained=parseq --data_root data --beam 5     a beam search instead of the greedy decode: the table gains Hit@5, Oracle 1 - NED, MRR
     ./test.py pretrained=parseq --data_root data --lexicon words.txt [--beam 8] [--match [N]] [--priors] [--refine-beams score]
     ./test.py pretrained=parseq --data_root data --lm corpus.txt [--lm-order 3] [--lm-weight 0.3] [--char-bonus 0.5]     or --pattern REGEX
+    ./test.py pretrained=parseq --data_root data --rotation 180 --auto-rotate flip [--upright-bias 0.1]     read every crop in several quarter turns, score the best
 
 A dataset is a sub-directory of `--data_root` that holds a `gt.txt`: one sample per line, the image path (relative to that
 sub-directory) and the label separated by the first run of whitespace — the input format of the reference's
@@ -25,6 +26,10 @@ With a search flag (the flags, their composition and their refusals are read.py'
 three more say how often the label is anywhere in the W hypotheses, how near the nearest of them comes, and the mean reciprocal rank.
 ONE lexicon / language model / pattern serves every dataset; per-image lexicons (the 50-word protocol of IIIT5k / SVT) are out of scope.
 Without a search flag the table and the log are what they were.
+
+With `--auto-rotate MODE` every crop, after `--rotation`, is read in the quarter turns of MODE in one forward, the
+view the model reads best is chosen on the device, and its logits go to the same `Evaluator`; one more line per dataset says how many
+crops were read turned.  It does not combine with a search flag.  Without the flag nothing changes.
 """
 import argparse
 import os
@@ -40,8 +45,9 @@ from PIL import Image
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.data import parse_gt_line, preprocess_label, read_gt  # noqa: F401  (the first two keep their names here)
 from parseq_amd.evaluate import BeamEvaluator, Evaluator
-from parseq_amd.preprocess import resize_batch
-from parseq_amd.search_flags import add_evaluation_flags, evaluation_width, evaluator_arguments, resolve_evaluation_flags
+from parseq_amd.preprocess import orientation_views, resize_batch
+from parseq_amd.search_flags import (add_evaluation_flags, add_orientation_flags, evaluation_width, evaluator_arguments, orientation_prior, resolve_evaluation_flags,
+                                      resolve_orientation)
 from parseq_amd.tokenizer import CharsetAdapter  # noqa: F401
 
 
@@ -77,17 +83,51 @@ def load_crops(files, device):
     return [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
 
 
-def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0, search: Optional[dict] = None, width: int = 0) -> Result:
+class UprightReader:
+    """What the unchanged `Evaluator` sees of a model under --auto-rotate: a system whose `forward` takes the views
+    [B, K, 3, H, W] of `orientation_views`, chooses every crop's best view on the device (`orient`) and returns the chosen logits.
+    `note(angles)` hands over the angles of the next batch's views; `turned` counts, on the device, the crops whose chosen view was not at
+    0 degrees."""
+
+    def __init__(self, model, bias: float = 0.0) -> None:
+        self._model, self._bias, self._angles = model, bias, None
+        self.turned = torch.zeros((), dtype=torch.int64, device=model.device)
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+    def note(self, angles) -> None:
+        self._angles = torch.tensor(angles, dtype=torch.int32).to(self._model.device) % 360
+
+    def forward(self, views):
+        result = self._model.orient(views, prior=orientation_prior(self._bias, views.shape[1]))
+        self.turned += (self._angles.gather(1, result.view.long().unsqueeze(1)) != 0).sum()
+        return result.logits
+
+
+def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0, search: Optional[dict] = None, width: int = 0,
+                     orient=None) -> Result:
     """One dataset's row.  `search`: the keywords of `BeamEvaluator` (a beam search or a lexicon match instead of the greedy decode); the row is
-    then a `BeamTableResult` whose Hit column counts the first `width` hypotheses per image (`search_flags.evaluation_width`)."""
+    then a `BeamTableResult` whose Hit column counts the first `width` hypotheses per image (`search_flags.evaluation_width`).  `orient`: the
+    (mode, bias) of --auto-rotate: every crop — turned by `rotation` first — is read in the views of that mode, the best view is what the
+    evaluator scores, and the share of crops read turned is printed under the dataset's name."""
     hp = model.hparams
     samples = read_dataset(root, name, hp.charset_test, hp.max_label_length)
-    evaluator = Evaluator(model) if search is None else BeamEvaluator(model, **search)
+    system = model if orient is None else UprightReader(model, orient[1])
+    evaluator = Evaluator(system) if search is None else BeamEvaluator(model, **search)
     for at in range(0, len(samples), batch_size):
         chunk = samples[at:at + batch_size]
-        images = resize_batch(load_crops([f for f, _ in chunk], model.device), tuple(hp.img_size), rotation=rotation)      # uint8 [N, 3, H, W]
+        crops = load_crops([f for f, _ in chunk], model.device)
+        if orient is None:
+            images = resize_batch(crops, tuple(hp.img_size), rotation=rotation)      # uint8 [N, 3, H, W]
+        else:
+            images, angles = orientation_views(crops, orient[0], tuple(hp.img_size), rotation=rotation)      # uint8 [N, K, 3, H, W]
+            system.note(angles)
         evaluator.update(images, [label for _, label in chunk])
     r = evaluator.result()
+    if orient is not None:
+        turned = int(system.turned)
+        print(f'{name}: {turned} of {len(samples)} crops read turned ({100 * turned / max(len(samples), 1):.2f} %)')
     n = r.num_samples
     if search is not None:
         return BeamTableResult(name, n, 100 * r.accuracy, 100 * (1 - r.ned) if n else 0.0, 100 * r.confidence, r.label_length, 100 * r.hit_at(width),
@@ -150,9 +190,13 @@ def main(argv=None) -> List[Result]:
     parser.add_argument('--rotation', type=int, default=0, help='Angle of rotation (counter clockwise) in degrees.')
     parser.add_argument('--device', default='cuda')
     add_evaluation_flags(parser)
+    add_orientation_flags(parser)
     args, unknown = parser.parse_known_args(argv)
     kwargs = parse_model_args(unknown)
     flags = resolve_evaluation_flags(parser, args)
+    orient = resolve_orientation(parser, args)
+    if orient is not None and flags is not None:
+        parser.error('--auto-rotate scores the greedy reading of the chosen view: not with a search flag')
 
     charset_test = string.digits + string.ascii_lowercase
     if args.cased:
@@ -165,7 +209,7 @@ def main(argv=None) -> List[Result]:
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     search = evaluator_arguments(model, args, flags) if flags is not None else None
     width = evaluation_width(flags) if flags is not None else 0
-    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width) for name in find_datasets(args.data_root)]
+    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width, orient) for name in find_datasets(args.data_root)]
     if not results:
         raise SystemExit(f'no dataset (a sub-directory with a gt.txt) under {args.data_root!r}')
     with open(args.checkpoint + '.log.txt', 'w') as log:
