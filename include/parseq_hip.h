@@ -759,6 +759,39 @@ int parseq_eval_beams(const int32_t* tokens, const float* scores, const int32_t*
                       const int32_t* adapter_table, const int32_t* gt, const int32_t* gt_len, int G, int32_t* hyp_rows_out,
                       int32_t* image_rows_out, double* workspace, void* accum, void* stream);
 
+/* Error analysis: HOW the greedy readings are wrong.  For every sample the canonical edit script between the adapted
+ * prediction p[0..m) (ids cut at `lengths`, mapped through adapter_table, dropped characters removed: what parseq_eval_metrics compares) and
+ * the label g[0..n), and integer tables summed over the batch.  One launch on the caller's stream, no allocation, no synchronisation.
+ *   ids, lengths   device int32 [batch, L], int32 [batch]: what parseq_eval_metrics or parseq_postprocess wrote; 1 <= L <= 32.  Lengths
+ *                  are clamped to [0, L], ids outside [0, C) are dropped
+ *   adapter_table  device int32 [C], as parseq_eval_metrics takes it
+ *   symbols        device int32 [num_symbols], STRICTLY ASCENDING (the caller's contract: the table lies in device memory and is not
+ *                  checked): the distinct non-negative code points of adapter_table, T = num_symbols of them.  Index T stands for a label
+ *                  code point outside the set ("other"), T + 1 for the missing side of an insertion or a deletion ("none")
+ *   gt, gt_len, gt_width   as parseq_eval_metrics takes them
+ *   script_out     int8 [batch, PARSEQ_EVAL_SCRIPT_WIDTH]: the script in forward order, padded with -1.  Codes: 0 match, 1 substitution,
+ *                  2 insertion (a predicted character that answers to no label character), 3 deletion (a label character nothing was
+ *                  predicted for).  With D the unit-cost Levenshtein table (D[i][0] = i, D[0][j] = j) the script is read from (m, n) back
+ *                  to (0, 0), at (i, j) by the first rule that holds: (1) i, j > 0 and D[i-1][j-1] + (p[i-1] != g[j-1]) == D[i][j]: match
+ *                  or substitution, to (i-1, j-1); (2) i > 0 and D[i-1][j] + 1 == D[i][j]: insertion, to (i-1, j); (3) deletion, to (i, j-1)
+ *   script_len_out int32 [batch]: codes of each script (at most m + n)
+ *   rows_out       int32 [batch, 4]: {m, n, distance, exact}, equal to parseq_eval_metrics' rows for the same input
+ *   accum          device, parseq_eval_errors_accum_bytes(num_symbols) bytes of int64, ACCUMULATED into (zero it to start):
+ *                  head[8] = {samples, matches, substitutions, insertions, deletions, exact, 0, 0};
+ *                  by_length[33][4], row min(n, 32) = {samples, exact, distance, label characters};
+ *                  by_position[33][4], row min(j, 32) with j the label characters before the operation = {label characters at that
+ *                  position, substitutions, deletions, insertions};
+ *                  confusion[T + 2][T + 2], row = label symbol (or none), column = predicted symbol (or none); matches lie on the diagonal.
+ *                  Integer atomic adds only: equal inputs give bit-identical totals in any order, on any stream.
+ * PARSEQ_E_INVALID, before any device work and with outputs and accumulator untouched: a null pointer, batch < 1, L outside 1 .. 32, C < 1,
+ * gt_width outside 1 .. PARSEQ_EVAL_MAX_GT, num_symbols outside 1 .. PARSEQ_EVAL_MAX_SYMBOLS. */
+#define PARSEQ_EVAL_MAX_SYMBOLS 512
+#define PARSEQ_EVAL_SCRIPT_WIDTH 288 /* PARSEQ_EVAL_MAX_GT + 32 */
+size_t parseq_eval_errors_accum_bytes(int num_symbols); /* 0 outside 1 .. PARSEQ_EVAL_MAX_SYMBOLS */
+int parseq_eval_errors(const int32_t* ids, const int32_t* lengths, int batch, int L, int C, const int32_t* adapter_table,
+                       const int32_t* symbols, int num_symbols, const int32_t* gt, const int32_t* gt_len, int gt_width,
+                       int8_t* script_out, int32_t* script_len_out, int32_t* rows_out, void* accum, void* stream);
+
 /* ---- "next" row N3: training step, decoder side (strhub/models/parseq/system.py:168-199 + loss.backward()) ---------- */
 
 /* Offset (in floats) of parameter `index` inside a gradient buffer, and the buffer's length: gradients are laid out like

@@ -178,6 +178,9 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_eval_beams': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'parseq_eval_errors_accum_bytes': (C.c_size_t, [C.c_int]),
+    'parseq_eval_errors': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_plan_set_profiling': (C.c_int, [C.c_void_p, C.c_int]),
     'parseq_plan_get_profile': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     'parseq_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -387,7 +390,7 @@ def stream_ptr(device=None) -> C.c_void_p:
 
 def guard(device):
     """Context manager making `device` (torch.device or tensor) current: for the raw-pointer entry points (parseq_op_*,
-    parseq_postprocess, parseq_eval_metrics, parseq_eval_beams, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_rectify, parseq_rectify_resize_bicubic, parseq_mesh_rectify, parseq_mesh_rectify_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
+    parseq_postprocess, parseq_eval_metrics, parseq_eval_beams, parseq_eval_errors, parseq_resize_bicubic, parseq_rotate_resize_bicubic, parseq_augment_resize_bicubic, parseq_rectify, parseq_rectify_resize_bicubic, parseq_mesh_rectify, parseq_mesh_rectify_resize_bicubic, parseq_cross_entropy, parseq_grad_norm, parseq_op_weights_average), which launch on the current device."""
     import torch
     if hasattr(device, 'device'):
         device = device.device

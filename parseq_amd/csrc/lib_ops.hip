@@ -2,6 +2,7 @@
 #include "lib_internal.h"
 #include "eval_metrics.h"
 #include "eval_beams.h"
+#include "eval_errors.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // post-processing
@@ -71,6 +72,31 @@ extern "C" int parseq_eval_beams(const int32_t* tokens, const float* scores, con
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(eval_beam_images_kernel, dim3(1), dim3(256), 0, s, hyp_rows_out, workspace, scores, conf_scores, B, W, gt_len, G, image_rows_out,
                        workspace + rows, reinterpret_cast<BeamEvalAccum*>(accum));
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// error analysis (eval_errors.h): edit scripts and integer tables from the ids and lengths parseq_eval_metrics /
+// parseq_postprocess wrote.  One launch; every refusal comes before any device work.  `symbols` lies in device memory, so that it is
+// strictly ascending is the caller's contract (parseq_amd.evaluate.symbol_table builds it so)
+extern "C" size_t parseq_eval_errors_accum_bytes(int num_symbols) {
+    if (num_symbols < 1 || num_symbols > EVAL_MAX_SYMBOLS) return 0;
+    return eval_errors_accum_words(num_symbols) * sizeof(long long);
+}
+
+extern "C" int parseq_eval_errors(const int32_t* ids, const int32_t* lengths, int batch, int L, int C, const int32_t* adapter_table,
+                                  const int32_t* symbols, int num_symbols, const int32_t* gt, const int32_t* gt_len, int gt_width,
+                                  int8_t* script_out, int32_t* script_len_out, int32_t* rows_out, void* accum, void* stream) {
+    static_assert(EVAL_MAX_SYMBOLS == PARSEQ_EVAL_MAX_SYMBOLS && EVAL_SCRIPT_WIDTH == PARSEQ_EVAL_SCRIPT_WIDTH, "header and kernel limits must agree");
+    if (!ids || !lengths || !adapter_table || !symbols || !gt || !gt_len || !script_out || !script_len_out || !rows_out || !accum)
+        return fail(PARSEQ_E_INVALID, "eval_errors: null argument");
+    if (batch < 1) return fail(PARSEQ_E_INVALID, "eval_errors: batch = %d, it must be at least 1", batch);
+    if (L < 1 || L > EVAL_MAX_PRED) return fail(PARSEQ_E_INVALID, "eval_errors: L = %d positions per prediction, it must be in 1 .. %d", L, EVAL_MAX_PRED);
+    if (C < 1) return fail(PARSEQ_E_INVALID, "eval_errors: C = %d classes", C);
+    if (gt_width < 1 || gt_width > EVAL_MAX_GT) return fail(PARSEQ_E_INVALID, "eval_errors: ground truth of gt_width = %d code points per row, it must be in 1 .. %d", gt_width, EVAL_MAX_GT);
+    if (num_symbols < 1 || num_symbols > EVAL_MAX_SYMBOLS) return fail(PARSEQ_E_INVALID, "eval_errors: num_symbols = %d, it must be in 1 .. %d", num_symbols, EVAL_MAX_SYMBOLS);
+    hipLaunchKernelGGL(eval_errors_kernel, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, ids, lengths, batch, L, C, adapter_table, symbols, num_symbols,
+                       gt, gt_len, gt_width, reinterpret_cast<signed char*>(script_out), script_len_out, rows_out, reinterpret_cast<long long*>(accum));
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -16,6 +16,10 @@ once, when the `Evaluator` is built:
 For such a model `adapter_table` returns None and the `Evaluator` runs `eval_step` per batch and sums on the host (`host_path`
 is True): same totals, the parent path's speed.
 
+`ErrorAnalysis` says HOW the readings are wrong: `parseq_eval_errors` (csrc/eval_errors.h) takes the ids and lengths
+the metrics kernel just wrote and the labels already uploaded, and keeps per-sample edit scripts and integer tables (operation totals,
+accuracy by label length, errors by position, a confusion matrix) on the device; `ErrorReport` is the one copy.
+
 Limits: a label of at most `MAX_GT` = 256 code points (the reference's dataset drops labels longer than `max_label_length`,
 25 by default, before they get here: strhub/data/dataset.py:111-113); predictions of at most 32 positions (DEC_MAXL).
 """
@@ -101,10 +105,11 @@ class Evaluator:
         totals = ev.result()                   # BatchResult of sums: the one copy
 
     The system must be on the GPU when the Evaluator is built (there is no CPU path: RuntimeError otherwise).  `host_path` tells
-    whether this model's charsets forced the per-batch host loop (see the module docstring)."""
+    whether this model's charsets forced the per-batch host loop (see the module docstring).  `errors`: an `ErrorAnalysis` of the same
+    system; every `update` then hands it the ids and lengths the metrics kernel wrote and the uploaded labels, `reset` resets it too."""
 
-    def __init__(self, system, validation: bool = False) -> None:
-        self.system, self.validation = system, validation
+    def __init__(self, system, validation: bool = False, errors: Optional['ErrorAnalysis'] = None) -> None:
+        self.system, self.validation, self.errors = system, validation, errors
         self.device = torch.device(system.device)
         if self.device.type != 'cuda':
             raise RuntimeError('Evaluator runs on the GPU (no CPU fallback); move the model to the device first')
@@ -117,6 +122,8 @@ class Evaluator:
     def reset(self) -> None:
         self._host = [0, 0, 0, 0.0, 0.0, 0.0, 0]          # host path: samples, correct, label_length, ned, confidence, loss * numel, numel
         self._last_rows = None
+        if self.errors is not None:
+            self.errors.reset()
         if not self.host_path:
             self._accum = torch.zeros(5, dtype=torch.int64, device=self.device)          # 3 x int64, then 2 x float64 bit patterns
             self._loss_sum = torch.zeros(1, dtype=torch.float64, device=self.device)
@@ -154,9 +161,31 @@ class Evaluator:
                 _native.ptr(encoded), width, _native.ptr(ids), _native.ptr(lengths), _native.ptr(conf), _native.ptr(rows), _native.ptr(ws),
                 _native.ptr(self._accum), _native.stream_ptr(dev)))
         self._last_rows = rows
+        if self.errors is not None:
+            self.errors.update_ids(ids, lengths, encoded)
+
+    def _eval_step_with_errors(self, images: Tensor, labels: Sequence[str]) -> BatchResult:
+        """`eval_step` (system.py) with the ids kept for the error analysis: the same forward, the same sums in the same order."""
+        from .system import forward_logits_loss
+        if self.validation:
+            logits, loss, loss_numel = forward_logits_loss(self.system, images, labels)
+        else:
+            logits, loss, loss_numel = self.system.forward(images), None, None
+        tokenizer = self.system.tokenizer
+        ids, lengths, _, conf = tokenizer._postprocess(logits)
+        self.errors.update_ids(ids, lengths, labels)
+        correct = label_length = 0
+        ned = confidence = 0.0
+        for row, k, c, gt in zip(ids.cpu().numpy(), lengths.cpu().tolist(), conf.cpu().tolist(), labels):
+            confidence += c
+            pred = self.system.charset_adapter(tokenizer._ids2tok(row[:k].tolist()))
+            ned += edit_distance(pred, gt) / max(len(pred), len(gt), 1)
+            correct += int(pred == gt)
+            label_length += len(pred)
+        return BatchResult(len(labels), correct, ned, confidence, label_length, loss, loss_numel)
 
     def _update_host(self, images: Tensor, labels: Sequence[str]) -> None:
-        r = eval_step(self.system, (images, labels), self.validation)['output']
+        r = eval_step(self.system, (images, labels), self.validation)['output'] if self.errors is None else self._eval_step_with_errors(images, labels)
         h = self._host
         h[0] += r.num_samples; h[1] += r.correct; h[2] += r.label_length; h[3] += r.ned; h[4] += r.confidence
         if self.validation:
@@ -425,3 +454,291 @@ class BeamEvaluator:
     def reduce(self, process_group=None) -> BeamEvalResult:
         """`result()` summed over the ranks of `process_group` (None = the default group).  Host tensors: works on gloo."""
         return reduce_beam_result(self.result(), process_group)
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# Error analysis (DESIGN.md section 28)
+# -------------------------------------------------------------------------------------------------------------------
+MAX_SYMBOLS = 512            # PARSEQ_EVAL_MAX_SYMBOLS
+SCRIPT_WIDTH = MAX_GT + 32   # PARSEQ_EVAL_SCRIPT_WIDTH
+LEN_BINS = 33                # rows of by_length / by_position: 0 .. 31, then "32 and more"
+MATCH, SUBSTITUTION, INSERTION, DELETION = range(4)      # the codes of an edit script
+_HEAD, _BY_LENGTH, _BY_POSITION, _CONFUSION = 0, 8, 8 + LEN_BINS * 4, 8 + 2 * LEN_BINS * 4      # int64 words of the accumulator
+OTHER, NONE = '<other>', '<none>'                        # what `ErrorReport` calls symbol T and symbol T + 1
+
+
+def symbol_table(adapter_table) -> np.ndarray:
+    """int32, strictly ascending: the distinct code points a prediction can consist of under `adapter_table`."""
+    table = np.asarray(adapter_table)
+    return np.unique(table[table >= 0]).astype(np.int32)
+
+
+def host_edit_script(pred: str, gt: str) -> List[int]:
+    """The canonical edit script of DESIGN.md section 28 in forward order: 0 match, 1 substitution, 2 insertion (a character of `pred` that
+    answers to none of `gt`), 3 deletion (a character of `gt` nothing was predicted for).  Plain Python over the full table."""
+    m, n = len(pred), len(gt)
+    table = [list(range(n + 1))]
+    for i in range(1, m + 1):
+        above, row = table[-1], [i]
+        for j in range(1, n + 1):
+            row.append(min(above[j - 1] + (pred[i - 1] != gt[j - 1]), above[j] + 1, row[j - 1] + 1))
+        table.append(row)
+    script, i, j = [], m, n
+    while i or j:
+        if i and j and table[i - 1][j - 1] + (pred[i - 1] != gt[j - 1]) == table[i][j]:
+            script.append(SUBSTITUTION if pred[i - 1] != gt[j - 1] else MATCH)
+            i, j = i - 1, j - 1
+        elif i and table[i - 1][j] + 1 == table[i][j]:
+            script.append(INSERTION)
+            i -= 1
+        else:
+            script.append(DELETION)
+            j -= 1
+    return script[::-1]
+
+
+def _accumulate_script(words: np.ndarray, index: dict, script: Sequence[int], pred: str, gt: str) -> None:
+    """One sample into the flat int64 accumulator `words` (the layout of `parseq_eval_errors`); `index`: character -> symbol index."""
+    t = len(index)
+    confusion = words[_CONFUSION:].reshape(t + 2, t + 2)
+    by_position = words[_BY_POSITION:_CONFUSION].reshape(LEN_BINS, 4)
+    i = j = 0
+    for code in script:
+        at = by_position[min(j, LEN_BINS - 1)]
+        row = t + 1 if code == INSERTION else index.get(gt[j], t)
+        col = t + 1 if code == DELETION else index.get(pred[i], t)
+        confusion[row, col] += 1
+        words[_HEAD + 1 + code] += 1
+        if code != INSERTION:
+            at[0] += 1
+        if code:
+            at[{SUBSTITUTION: 1, DELETION: 2, INSERTION: 3}[code]] += 1
+        i += code != DELETION
+        j += code != INSERTION
+    distance = sum(1 for code in script if code)
+    words[_HEAD] += 1
+    words[_HEAD + 5] += distance == 0
+    words[_BY_LENGTH:_BY_POSITION].reshape(LEN_BINS, 4)[min(len(gt), LEN_BINS - 1)] += (1, distance == 0, distance, len(gt))
+
+
+def host_error_tables(preds: Sequence[str], labels: Sequence[str], symbols: Sequence[str]) -> 'ErrorReport':
+    """The tables of `parseq_eval_errors` for adapted predictions and labels given as strings: `host_edit_script` per pair."""
+    index = {ch: i for i, ch in enumerate(symbols)}
+    words = np.zeros(_CONFUSION + (len(index) + 2) ** 2, dtype=np.int64)
+    for pred, gt in zip(preds, labels):
+        _accumulate_script(words, index, host_edit_script(pred, gt), pred, gt)
+    return ErrorReport._from_words(symbols, words)
+
+
+@dataclass
+class ErrorReport:
+    """The tables of an error analysis as numpy int64 arrays, and the symbols they are indexed by as characters.
+    `head` = [samples, matches, substitutions, insertions, deletions, exact, 0, 0]; `by_length[min(n, 32)]` = [samples, exact, distance,
+    label characters] of the labels of n characters; `by_position[min(j, 32)]` = [label characters at position j, substitutions, deletions,
+    insertions] (an insertion's position is the number of label characters before it); `confusion[label][predicted]` over the T symbols,
+    then `OTHER` (a label character outside them) and `NONE` (the missing side of an insertion or deletion)."""
+    symbols: List[str]
+    head: np.ndarray
+    by_length: np.ndarray
+    by_position: np.ndarray
+    confusion: np.ndarray
+
+    @classmethod
+    def _from_words(cls, symbols: Sequence[str], words) -> 'ErrorReport':
+        words, t = np.asarray(words, dtype=np.int64), len(symbols)
+        return cls(list(symbols), words[:_BY_LENGTH].copy(), words[_BY_LENGTH:_BY_POSITION].reshape(LEN_BINS, 4).copy(),
+                   words[_BY_POSITION:_CONFUSION].reshape(LEN_BINS, 4).copy(), words[_CONFUSION:].reshape(t + 2, t + 2).copy())
+
+    def _words(self) -> np.ndarray:
+        return np.concatenate([self.head.ravel(), self.by_length.ravel(), self.by_position.ravel(), self.confusion.ravel()]).astype(np.int64)
+
+    samples = property(lambda self: int(self.head[0]))
+    matches = property(lambda self: int(self.head[1]))
+    substitutions = property(lambda self: int(self.head[2]))
+    insertions = property(lambda self: int(self.head[3]))
+    deletions = property(lambda self: int(self.head[4]))
+    exact = property(lambda self: int(self.head[5]))
+
+    def __add__(self, other: 'ErrorReport') -> 'ErrorReport':
+        if self.symbols != other.symbols:
+            raise ValueError('reports over different symbol sets do not add')
+        return ErrorReport._from_words(self.symbols, self._words() + other._words())
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, ErrorReport) and self.symbols == other.symbols and np.array_equal(self._words(), other._words())
+
+    def name(self, index: int) -> str:
+        t = len(self.symbols)
+        return self.symbols[index] if index < t else OTHER if index == t else NONE
+
+    def _top(self, cells: np.ndarray, k: int):
+        """(flat index, count) of the `k` largest positive cells, ties in index order."""
+        flat = cells.ravel()
+        order = np.argsort(-flat, kind='stable')[:max(int(k), 0)]
+        return [(int(i), int(flat[i])) for i in order if flat[i] > 0]
+
+    def top_confusions(self, k: int) -> List[Tuple[str, str, int]]:
+        """(label character, predicted character, count) of the `k` most frequent substitutions; ties by (label, predicted) index."""
+        t = len(self.symbols)
+        cells = self.confusion[:t + 1, :t + 1].copy()
+        cells[np.arange(t), np.arange(t)] = 0
+        return [(self.name(i // (t + 1)), self.name(i % (t + 1)), c) for i, c in self._top(cells, k)]
+
+    def top_deleted(self, k: int) -> List[Tuple[str, int]]:
+        """(label character, count) of the `k` label characters most often left unread."""
+        t = len(self.symbols)
+        return [(self.name(i), c) for i, c in self._top(self.confusion[:t + 1, t + 1], k)]
+
+    def top_inserted(self, k: int) -> List[Tuple[str, int]]:
+        """(predicted character, count) of the `k` characters most often read where the label has none."""
+        t = len(self.symbols)
+        return [(self.name(i), c) for i, c in self._top(self.confusion[t + 1, :t + 1], k)]
+
+    def accuracy_by_length(self) -> List[Tuple[int, int, float]]:
+        """(label length, samples, share read exactly) for every length that occurs; the last row, 32, holds every longer label."""
+        return [(n, int(r[0]), int(r[1]) / int(r[0])) for n, r in enumerate(self.by_length) if r[0]]
+
+    def error_rate_by_position(self) -> List[Tuple[int, int, float, int]]:
+        """(position, label characters there, share of them substituted or deleted, insertions in front of that position) for every
+        position that occurs; the last row, 32, holds every later one."""
+        return [(j, int(r[0]), (int(r[1]) + int(r[2])) / int(r[0]) if r[0] else 0.0, int(r[3])) for j, r in enumerate(self.by_position) if r[0] or r[3]]
+
+    def to_dict(self) -> dict:
+        return dict(symbols=list(self.symbols), head=self.head.tolist(), by_length=self.by_length.tolist(), by_position=self.by_position.tolist(),
+                    confusion=self.confusion.tolist())
+
+    @classmethod
+    def from_dict(cls, d: dict) -> 'ErrorReport':
+        return cls(list(d['symbols']), *(np.asarray(d[key], dtype=np.int64) for key in ('head', 'by_length', 'by_position', 'confusion')))
+
+    def to_json(self) -> str:
+        import json
+        return json.dumps(self.to_dict(), ensure_ascii=False)
+
+    @classmethod
+    def from_json(cls, text: str) -> 'ErrorReport':
+        import json
+        return cls.from_dict(json.loads(text))
+
+
+def reduce_report(report: ErrorReport, process_group=None) -> ErrorReport:
+    """The tables of `report` added over the ranks of `process_group` (None = the default group), as `reduce_result` does for the totals.
+    One int64 all-reduce of a host tensor: works on gloo.  The ranks must analyse the same symbol set."""
+    import torch.distributed as dist
+    words = torch.from_numpy(report._words())
+    dist.all_reduce(words, group=process_group)
+    return ErrorReport._from_words(report.symbols, words.numpy())
+
+
+def _host_symbols(tokenizer, charset_adapter) -> List[str]:
+    """The characters a prediction can consist of when the adapter is no per-character map (the host path): whatever it makes of each
+    train character alone and doubled (a doubled 'Σ' lower-cases to both of its forms)."""
+    classes = len(tokenizer) - 2
+    chars = set()
+    for token_id in range(classes):
+        if token_id != tokenizer.eos_id:
+            ch = tokenizer._itos[token_id]
+            chars.update(charset_adapter(ch), charset_adapter(ch + ch))
+    return sorted(chars)
+
+
+class ErrorAnalysis:
+    """Running edit scripts and error tables of an evaluation, beside `Evaluator`'s totals:
+
+        errors = ErrorAnalysis(model)
+        ev = Evaluator(model, errors=errors)
+        for images, labels in loader:
+            ev.update(images, labels)          # the metrics, then parseq_eval_errors on the ids they wrote: enqueues only
+        report = errors.result()               # ErrorReport: the one copy
+
+    `update_ids(ids, lengths, labels)` takes the device tensors of any greedy decode (`parseq_postprocess`) directly.  A model whose
+    charsets select `host_path` (see the module docstring) is analysed by `host_edit_script` per sample: the same tables."""
+
+    def __init__(self, system) -> None:
+        self.system = system
+        self.device = torch.device(system.device)
+        if self.device.type != 'cuda':
+            raise RuntimeError('ErrorAnalysis runs on the GPU (no CPU fallback); move the model to the device first')
+        table = adapter_table(system.tokenizer, system.charset_adapter)
+        self.host_path = table is None
+        self.symbols = _host_symbols(system.tokenizer, system.charset_adapter) if self.host_path else [chr(c) for c in symbol_table(table)]
+        if not 1 <= len(self.symbols) <= MAX_SYMBOLS:
+            raise ValueError(f'{len(self.symbols)} symbols: the error analysis takes 1 to {MAX_SYMBOLS}')
+        self._words = _CONFUSION + (len(self.symbols) + 2) ** 2
+        if self.host_path:
+            self._index = {ch: i for i, ch in enumerate(self.symbols)}
+        else:
+            self._table = torch.from_numpy(table).to(self.device)
+            self._symbols = torch.tensor([ord(ch) for ch in self.symbols], dtype=torch.int32).to(self.device)
+        self.reset()
+
+    def reset(self) -> None:
+        self._last = None
+        if self.host_path:
+            self._host = np.zeros(self._words, dtype=np.int64)
+        else:
+            self._accum = torch.zeros(self._words, dtype=torch.int64, device=self.device)
+
+    @torch.inference_mode()
+    def update_ids(self, ids: Tensor, lengths: Tensor, labels) -> None:
+        """`ids` int32 [B, L] and `lengths` int32 [B] on the device, as `parseq_postprocess` / `parseq_eval_metrics` write them; `labels`:
+        the strings, or the device tensor `encode_ground_truth` made of them (what `Evaluator` has uploaded already)."""
+        n, length = ids.shape
+        if lengths.shape[0] != n:
+            raise ValueError(f'{n} rows of ids but {lengths.shape[0]} lengths')
+        if isinstance(labels, Tensor):
+            if n == 0 or labels.numel() % n or labels.numel() < 2 * n:
+                raise ValueError(f'an encoded label tensor of {labels.numel()} words for {n} samples')
+        elif len(labels) != n:
+            raise ValueError(f'{n} rows of ids but {len(labels)} labels')
+        if self.host_path:
+            self._update_host(ids, lengths, labels)
+            return
+        from . import _native
+        dev = self.device
+        encoded = labels if isinstance(labels, Tensor) else torch.from_numpy(encode_ground_truth(labels)).pin_memory().to(dev, non_blocking=True)
+        encoded = encoded.to(device=dev, dtype=torch.int32).contiguous()
+        ids, lengths = ids.to(device=dev, dtype=torch.int32).contiguous(), lengths.to(device=dev, dtype=torch.int32).contiguous()
+        width = (encoded.numel() - n) // n
+        scripts = torch.empty((n, SCRIPT_WIDTH), dtype=torch.int8, device=dev)
+        script_len = torch.empty((n,), dtype=torch.int32, device=dev)
+        rows = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        with _native.guard(dev):
+            _native.check(_native.lib().parseq_eval_errors(
+                _native.ptr(ids), _native.ptr(lengths), n, length, self._table.numel(), _native.ptr(self._table), _native.ptr(self._symbols),
+                len(self.symbols), _native.ptr(encoded[n:]), _native.ptr(encoded), width, _native.ptr(scripts), _native.ptr(script_len), _native.ptr(rows),
+                _native.ptr(self._accum), _native.stream_ptr(dev)))
+        self._last = (scripts, script_len, rows)
+
+    def _update_host(self, ids: Tensor, lengths: Tensor, labels) -> None:
+        tokenizer, adapter = self.system.tokenizer, self.system.charset_adapter
+        if isinstance(labels, Tensor):
+            labels = decode_ground_truth(labels.cpu().numpy(), ids.shape[0])
+        classes = len(tokenizer) - 2
+        n, length = ids.shape
+        scripts = np.full((n, SCRIPT_WIDTH), -1, dtype=np.int8)
+        script_len, rows = np.zeros(n, dtype=np.int32), np.zeros((n, 4), dtype=np.int32)
+        for b, (row, k, gt) in enumerate(zip(ids.cpu().numpy(), lengths.cpu().tolist(), labels)):
+            kept = [int(i) for i in row[:min(max(k, 0), length)] if 0 <= i < classes and i != tokenizer.eos_id]
+            pred = adapter(tokenizer._ids2tok(kept))
+            script = host_edit_script(pred, gt)
+            _accumulate_script(self._host, self._index, script, pred, gt)
+            distance = sum(1 for code in script if code)
+            scripts[b, :len(script)] = script
+            script_len[b], rows[b] = len(script), (len(pred), len(gt), distance, distance == 0)
+        self._last = (scripts, script_len, rows)
+
+    def result(self) -> ErrorReport:
+        """The tables so far: one copy of 8 * (272 + (T + 2) ** 2) bytes."""
+        return ErrorReport._from_words(self.symbols, self._host if self.host_path else self._accum.cpu().numpy())
+
+    def per_sample(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The last batch's (scripts int8 [B, 288] in forward order, padded with -1; script lengths int32 [B]; rows int32 [B, 4] = length of the
+        adapted prediction, length of the label, edit distance, exact match)."""
+        if self._last is None:
+            raise RuntimeError('per_sample() before the first update_ids()')
+        return tuple(t if isinstance(t, np.ndarray) else t.cpu().numpy() for t in self._last)
+
+    def reduce(self, process_group=None) -> ErrorReport:
+        """`result()` summed over the ranks of `process_group`."""
+        return reduce_report(self.result(), process_group)

@@ -8,6 +8,7 @@
     ./test.py pretrained=parseq --data_root data --lexicon words.txt [--beam 8] [--match [N]] [--priors] [--refine-beams score]
     ./test.py pretrained=parseq --data_root data --lm corpus.txt [--lm-order 3] [--lm-weight 0.3] [--char-bonus 0.5]     or --pattern REGEX
     ./test.py pretrained=parseq --data_root data --rotation 180 --auto-rotate flip [--upright-bias 0.1]     read every crop in several quarter turns, score the best
+    ./test.py pretrained=parseq --data_root data --analyse [K]     after the table: which characters are confused, dropped or made up, and at which label lengths
 
 A dataset is a sub-directory of `--data_root` that holds a `gt.txt`: one sample per line, the image path (relative to that
 sub-directory) and the label separated by the first run of whitespace — the input format of the reference's
@@ -30,8 +31,15 @@ Without a search flag the table and the log are what they were.
 With `--auto-rotate MODE` every crop, after `--rotation`, is read in the quarter turns of MODE in one forward, the
 view the model reads best is chosen on the device, and its logits go to the same `Evaluator`; one more line per dataset says how many
 crops were read turned.  It does not combine with a search flag.  Without the flag nothing changes.
+
+With `--analyse [K]` (K = 20 by default) every dataset's `Evaluator` carries an `ErrorAnalysis`: the edit scripts between
+readings and labels are made on the device beside the metrics.  After the table — which, like the log, is what it is without the flag — the
+operation totals, the accuracy by label length and the K most frequent confusions, deletions and insertions are printed per dataset and for
+all datasets together, and every table is written to `<checkpoint>.errors.json`.  It composes with --cased, --punctuation, --rotation and
+--auto-rotate; the analysis of an N-best is out of scope, so with a search flag it is refused.
 """
 import argparse
+import json
 import os
 import string
 import sys
@@ -44,7 +52,7 @@ from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.data import parse_gt_line, preprocess_label, read_gt  # noqa: F401  (the first two keep their names here)
-from parseq_amd.evaluate import BeamEvaluator, Evaluator
+from parseq_amd.evaluate import BeamEvaluator, ErrorAnalysis, ErrorReport, Evaluator
 from parseq_amd.preprocess import orientation_views, resize_batch
 from parseq_amd.search_flags import (add_evaluation_flags, add_orientation_flags, evaluation_width, evaluator_arguments, orientation_prior, resolve_evaluation_flags,
                                       resolve_orientation)
@@ -106,15 +114,17 @@ class UprightReader:
 
 
 def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0, search: Optional[dict] = None, width: int = 0,
-                     orient=None) -> Result:
+                     orient=None, reports: Optional[dict] = None) -> Result:
     """One dataset's row.  `search`: the keywords of `BeamEvaluator` (a beam search or a lexicon match instead of the greedy decode); the row is
     then a `BeamTableResult` whose Hit column counts the first `width` hypotheses per image (`search_flags.evaluation_width`).  `orient`: the
     (mode, bias) of --auto-rotate: every crop — turned by `rotation` first — is read in the views of that mode, the best view is what the
-    evaluator scores, and the share of crops read turned is printed under the dataset's name."""
+    evaluator scores, and the share of crops read turned is printed under the dataset's name.  `reports`: a dict that receives this dataset's
+    `ErrorReport` under `name` (--analyse; greedy evaluation only)."""
     hp = model.hparams
     samples = read_dataset(root, name, hp.charset_test, hp.max_label_length)
     system = model if orient is None else UprightReader(model, orient[1])
-    evaluator = Evaluator(system) if search is None else BeamEvaluator(model, **search)
+    errors = ErrorAnalysis(model) if reports is not None and search is None else None
+    evaluator = Evaluator(system, errors=errors) if search is None else BeamEvaluator(model, **search)
     for at in range(0, len(samples), batch_size):
         chunk = samples[at:at + batch_size]
         crops = load_crops([f for f, _ in chunk], model.device)
@@ -125,6 +135,8 @@ def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotatio
             system.note(angles)
         evaluator.update(images, [label for _, label in chunk])
     r = evaluator.result()
+    if errors is not None:
+        reports[name] = errors.result()
     if orient is not None:
         turned = int(system.turned)
         print(f'{name}: {turned} of {len(samples)} crops read turned ({100 * turned / max(len(samples), 1):.2f} %)')
@@ -179,8 +191,39 @@ def print_beam_results_table(results: List[BeamTableResult], width: int, file=No
     print(row(BeamTableResult('Combined', total, *means)), file=file)
 
 
-@torch.inference_mode()
-def main(argv=None) -> List[Result]:
+def print_error_report(name: str, report: ErrorReport, top: int, file=None) -> None:
+    """What --analyse prints for one dataset (or for all of them together): the four operation totals, the accuracy by label length, and the
+    `top` most frequent confusions, deletions and insertions."""
+    print(f'\n{name}: {report.samples} samples, {report.exact} read exactly; {report.matches} matches, {report.substitutions} substitutions, '
+          f'{report.insertions} insertions, {report.deletions} deletions', file=file)
+    print('| Label length | # samples | Accuracy |', file=file)
+    print('|-------------:|----------:|---------:|', file=file)
+    for length, samples, share in report.accuracy_by_length():
+        print(f"| {str(length) + ('+' if length == 32 else ''):>12} | {samples:>9d} | {100 * share:>8.2f} |", file=file)
+    for title, rows in (('confusions (label -> read)', [(f'{a!r} -> {b!r}', c) for a, b, c in report.top_confusions(top)]),
+                        ('deletions (label characters not read)', [(repr(a), c) for a, c in report.top_deleted(top)]),
+                        ('insertions (characters read that the label lacks)', [(repr(a), c) for a, c in report.top_inserted(top)])):
+        print(f'Most frequent {title}: ' + (', '.join(f'{what} x {count}' for what, count in rows) if rows else 'none'), file=file)
+
+
+def add_analysis_flag(parser) -> None:
+    parser.add_argument('--analyse', type=int, nargs='?', const=20, default=None, metavar='K',
+                        help='After the table: operation totals, accuracy by label length and the K (default 20) most frequent confusions, deletions '
+                             'and insertions per dataset; every table goes to <checkpoint>.errors.json')
+
+
+def resolve_analysis(parser, args, flags) -> Optional[int]:
+    """K of --analyse, None without it; a contradiction ends in parser.error."""
+    if args.analyse is None:
+        return None
+    if args.analyse < 1:
+        parser.error('--analyse K must be at least 1')
+    if flags is not None:
+        parser.error('--analyse describes the greedy reading: not with a search flag (the analysis of an N-best is out of scope)')
+    return args.analyse
+
+
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser()
     parser.add_argument('checkpoint', help="Model checkpoint (or 'pretrained=<model_id>')")
     parser.add_argument('--data_root', default='data')
@@ -191,12 +234,21 @@ def main(argv=None) -> List[Result]:
     parser.add_argument('--device', default='cuda')
     add_evaluation_flags(parser)
     add_orientation_flags(parser)
+    add_analysis_flag(parser)
+    return parser
+
+
+@torch.inference_mode()
+def main(argv=None) -> List[Result]:
+    parser = build_parser()
     args, unknown = parser.parse_known_args(argv)
     kwargs = parse_model_args(unknown)
     flags = resolve_evaluation_flags(parser, args)
     orient = resolve_orientation(parser, args)
     if orient is not None and flags is not None:
         parser.error('--auto-rotate scores the greedy reading of the chosen view: not with a search flag')
+    top = resolve_analysis(parser, args, flags)
+    reports = {} if top is not None else None
 
     charset_test = string.digits + string.ascii_lowercase
     if args.cased:
@@ -209,7 +261,7 @@ def main(argv=None) -> List[Result]:
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     search = evaluator_arguments(model, args, flags) if flags is not None else None
     width = evaluation_width(flags) if flags is not None else 0
-    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width, orient) for name in find_datasets(args.data_root)]
+    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width, orient, reports) for name in find_datasets(args.data_root)]
     if not results:
         raise SystemExit(f'no dataset (a sub-directory with a gt.txt) under {args.data_root!r}')
     with open(args.checkpoint + '.log.txt', 'w') as log:
@@ -218,6 +270,14 @@ def main(argv=None) -> List[Result]:
                 print_beam_results_table(results, width, out)
             else:
                 print_results_table(results, out)
+    if reports is not None:
+        combined = None
+        for name, report in reports.items():
+            print_error_report(name, report, top)
+            combined = report if combined is None else combined + report
+        print_error_report('All datasets', combined, top)
+        with open(args.checkpoint + '.errors.json', 'w', encoding='utf-8') as f:
+            json.dump({'top': top, 'datasets': {name: report.to_dict() for name, report in reports.items()}, 'combined': combined.to_dict()}, f, ensure_ascii=False)
     return results
 
 
