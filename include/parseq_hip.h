@@ -451,6 +451,49 @@ int parseq_forward_oriented(parseq_plan* p, const void* images, int images_dtype
                             int32_t* ids_out, int32_t* lengths_out, float* confidence_out, void* images_out, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ---- long text lines (pure additions under ABI 15; DESIGN.md section 29 defines it) ---------------------------------- */
+
+/* A text line wider than the model's input is read as overlapping windows, every window one row of a batch, and stitched by position.
+ * Rows line_first[l] .. line_first[l + 1] - 1 are the windows of line l, left to right; win[row] = (x0, ww, h): the window is the columns
+ * x0 .. x0 + ww - 1 of a source line h pixels high.  In fp64, every product and sum rounded on its own:
+ *   X = (double)x0 + (double)cx * ((double)ww / (double)img_w)      Y = (double)cy * ((double)h / (double)img_h)
+ *   cut c_k = ((double)x0_{k+1} + (double)(x0_k + ww_k)) / 2        delta = min_sep[l] / 2
+ *   1  position i of window k is a candidate when i < clamp(lengths[row], 0, L) and 0 <= tokens[row][i] < C
+ *   2  it is kept iff lo_k <= X < hi_k: lo_0 = -inf, hi_{K-1} = +inf, else lo_k = c_{k-1} - delta, hi_k = c_k + delta (a NaN X is dropped)
+ *   3  per seam (k, k + 1), on the lists of step 2: the kept characters b of window k + 1 in position order are matched to the kept, not yet
+ *      matched character a of window k of the same token and the smallest |X_a - X_b| < min_sep (ties: the lowest position); of a matched
+ *      pair b is dropped if !(p_b > p_a), else a; a character is dropped if any seam drops it; min_sep = 0 matches nothing
+ *   4  the survivors in (window, position) order
+ *   5  confidence = (float)((((1.0 q_0) q_1) .. q_{K-1}) p_eos), q_k the product of window k's surviving probabilities in position order
+ *      from 1.0, p_eos the last window's probability at position n = clamp(lengths, 0, L) when n < L, else 1.0
+ * Inputs, device: tokens int32 [rows, L], lengths int32 [rows], probs fp32 [rows, L], centres fp32 [rows, L, 2] and boxes fp32 [rows, L, 4]
+ * in pixels of the model's input (img_h x img_w), win int32 [rows, 3], line_first int32 [lines + 1], min_sep fp64 [lines].
+ * Outputs, device, max_out slots per line: len_out int32 [lines] the true number of survivors (stores stop at max_out); tokens_out int32
+ * (padding -1), probs_out fp32, boxes_out fp32 [.., 4] and x_out fp64 in source pixels (padding 0), src_out int32 [.., 2] = (window index in
+ * the line, position) (padding -1); confidence_out fp32 [lines].
+ * One launch, a workgroup per line, no atomics: bit-identical on any stream.  That line_first ascends with 1 .. PARSEQ_LINE_MAX_WINDOWS
+ * windows per line inside [0, rows] and that x0 increases within a line is the caller's contract; a table that breaks it is clamped so that
+ * every index stays in bounds.  Refused with PARSEQ_E_INVALID before any device work, outputs untouched: a NULL argument, L outside 1 .. 32,
+ * lines < 1, rows < lines, max_out outside 1 .. PARSEQ_LINE_MAX_OUT, C < 1, img_h or img_w < 1. */
+#define PARSEQ_LINE_MAX_WINDOWS 64
+#define PARSEQ_LINE_MAX_OUT 2048
+int parseq_op_stitch_lines(const int32_t* tokens, const int32_t* lengths, const float* probs, const float* centres, const float* boxes, int rows,
+                           int L, int C, const int32_t* win, int img_h, int img_w, const int32_t* line_first, int lines, const double* min_sep,
+                           int max_out, int32_t* len_out, int32_t* tokens_out, float* probs_out, float* boxes_out, double* x_out,
+                           int32_t* src_out, float* confidence_out, void* stream);
+/* Read, localise and stitch in one call, no host synchronisation, no allocation: parseq_localize's body with tokens_in NULL on the `rows`
+ * windows of `images`, parseq_postprocess' kernel on the logits that leaves in the workspace (probs_out), then the op above.  The per-window
+ * outputs tokens_out int32 [rows, L], lengths_out int32 [rows], centres_out, boxes_out are parseq_localize's, probs_out fp32 [rows, L] is
+ * parseq_postprocess'; the line_* outputs are the op's.  workspace: parseq_read_lines_workspace_bytes(p, rows) device bytes (0: refused,
+ * parseq_last_error says why), 16-byte aligned.  Refusals: parseq_localize's (a ViTSTR model, dec_depth > 1, more than 256 memory tokens, rows
+ * above the plan's max_batch, a NULL output, a short or misaligned workspace) and the op's, all before any device work. */
+size_t parseq_read_lines_workspace_bytes(const parseq_plan* p, int rows);
+int parseq_read_lines(parseq_plan* p, const void* images, int images_dtype, int rows, int flags, int refine_iters, const int32_t* win,
+                      const int32_t* line_first, int lines, const double* min_sep, int max_out, int32_t* tokens_out, int32_t* lengths_out,
+                      float* probs_out, float* centres_out, float* boxes_out, int32_t* line_len_out, int32_t* line_tokens_out,
+                      float* line_probs_out, float* line_boxes_out, double* line_x_out, int32_t* line_src_out, float* line_confidence_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- beam search over a weighted automaton (pure additions under ABI 15; DESIGN.md section 24 defines it) ------------ */
 
 /* parseq_forward_beam_lexicon with a weight on every arc of the table, which then need not be a tree (cycles and shared states are

@@ -19,6 +19,7 @@ FLAG_DECODE_AR, FLAG_TESTING, FLAG_LATENCY = 1, 2, 4
 ABI_VERSION = 15
 ORIENT_MAX_VIEWS = 8                                  # PARSEQ_ORIENT_MAX_VIEWS
 ORIENT_CRITERIA = {'mean': 0, 'sum': 1}               # enum parseq_orient_criterion
+LINE_MAX_WINDOWS, LINE_MAX_OUT = 64, 2048             # PARSEQ_LINE_MAX_WINDOWS, PARSEQ_LINE_MAX_OUT
 
 
 class ParseqConfig(C.Structure):
@@ -228,6 +229,13 @@ SIGNATURES = {
     'parseq_forward_oriented_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     'parseq_forward_oriented': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_op_stitch_lines': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    'parseq_read_lines_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int]),
+    'parseq_read_lines': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'parseq_beam_automaton_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     'parseq_forward_beam_automaton': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(BeamTrace), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,

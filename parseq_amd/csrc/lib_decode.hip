@@ -6,6 +6,7 @@
 #include "attn_map.h"
 #include "lexicon_match.h"
 #include "orient.h"
+#include "line_stitch.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -1367,4 +1368,80 @@ extern "C" int parseq_forward_oriented(parseq_plan* p, const void* images, int i
     return parseq_op_orient_select(all, batch, views, num_steps, p->m->classes, c.eos_id, images_out ? images : nullptr, images_dtype,
                                    (int64_t)3 * c.img_h * c.img_w, criterion, prior, view_out, keys_out, logits_out, ids_out, lengths_out, confidence_out,
                                    images_out, static_cast<unsigned char*>(workspace) + off, workspace_bytes - off, stream);
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// long text lines (line_stitch.h): overlapping windows of a line, stitched by position
+// -------------------------------------------------------------------------------------------------------------------
+static int stitch_check(int rows, int L, int C, int img_h, int img_w, int lines, int max_out) {
+    static_assert(LINE_MAX_WINDOWS == PARSEQ_LINE_MAX_WINDOWS && LINE_MAX_OUT == PARSEQ_LINE_MAX_OUT && LINE_MAX_L == DEC_MAXL, "header and kernel must agree");
+    if (L < 1 || L > LINE_MAX_L) return fail(PARSEQ_E_INVALID, "lines: L = %d positions, it must be in 1 .. %d", L, LINE_MAX_L);
+    if (lines < 1 || rows < lines) return fail(PARSEQ_E_INVALID, "lines: %d lines over %d rows: there must be a line, and a row for each", lines, rows);
+    if (max_out < 1 || max_out > LINE_MAX_OUT) return fail(PARSEQ_E_INVALID, "lines: max_out %d, it must be in 1 .. %d", max_out, LINE_MAX_OUT);
+    if (C < 1 || img_h < 1 || img_w < 1) return fail(PARSEQ_E_INVALID, "lines: C = %d classes, input of %d x %d", C, img_h, img_w);
+    return 0;
+}
+
+extern "C" int parseq_op_stitch_lines(const int32_t* tokens, const int32_t* lengths, const float* probs, const float* centres, const float* boxes, int rows,
+                                      int L, int C, const int32_t* win, int img_h, int img_w, const int32_t* line_first, int lines, const double* min_sep,
+                                      int max_out, int32_t* len_out, int32_t* tokens_out, float* probs_out, float* boxes_out, double* x_out,
+                                      int32_t* src_out, float* confidence_out, void* stream) {
+    if (!tokens || !lengths || !probs || !centres || !boxes || !win || !line_first || !min_sep || !len_out || !tokens_out || !probs_out || !boxes_out ||
+        !x_out || !src_out || !confidence_out)
+        return fail(PARSEQ_E_INVALID, "lines: null argument");
+    CHK(stitch_check(rows, L, C, img_h, img_w, lines, max_out));
+    const LineStitchArgs a{tokens, lengths, probs, centres, boxes, rows, L, C, win, img_h, img_w, line_first, min_sep, max_out,
+                           len_out, tokens_out, probs_out, boxes_out, x_out, src_out, confidence_out};
+    return launch(line_stitch_kernel, dim3(lines), dim3(LINE_THREADS), 0, (hipStream_t)stream, a);
+}
+
+// parseq_read_lines' workspace: parseq_localize's (the logits, at the start), then what the call keeps to itself — the maps, their peaks and
+// what postprocess_kernel leaves beside the probabilities.
+struct ReadLinesWs { size_t localize; float* attn; int* peak; float* peak_mass; int* ids; int* lens; size_t total; };
+static ReadLinesWs read_lines_ws(const parseq_plan* p, int rows, size_t localize, void* workspace = nullptr) {
+    const size_t L = p->m->cfg.max_label_length + 1;
+    Carver cv{reinterpret_cast<unsigned char*>(workspace)};
+    cv.off = localize;
+    ReadLinesWs w{};
+    w.localize = localize;
+    w.attn = cv.take<float>((size_t)rows * L * p->m->tokens);
+    w.peak = cv.take<int>((size_t)rows * L); w.peak_mass = cv.take<float>((size_t)rows * L);
+    w.ids = cv.take<int>((size_t)rows * L); w.lens = cv.take<int>(rows);
+    w.total = cv.off;
+    return w;
+}
+
+extern "C" size_t parseq_read_lines_workspace_bytes(const parseq_plan* p, int rows) {
+    const size_t localize = parseq_localize_workspace_bytes(p, rows);
+    if (localize == 0) return 0;
+    return read_lines_ws(p, rows, localize).total;
+}
+
+extern "C" int parseq_read_lines(parseq_plan* p, const void* images, int images_dtype, int rows, int flags, int refine_iters, const int32_t* win,
+                                 const int32_t* line_first, int lines, const double* min_sep, int max_out, int32_t* tokens_out, int32_t* lengths_out,
+                                 float* probs_out, float* centres_out, float* boxes_out, int32_t* line_len_out, int32_t* line_tokens_out,
+                                 float* line_probs_out, float* line_boxes_out, double* line_x_out, int32_t* line_src_out, float* line_confidence_out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    const int L = p->m->cfg.max_label_length + 1;
+    CHK(attention_check(p, L));
+    if (!win || !line_first || !min_sep || !probs_out || !line_len_out || !line_tokens_out || !line_probs_out || !line_boxes_out || !line_x_out ||
+        !line_src_out || !line_confidence_out)
+        return fail(PARSEQ_E_INVALID, "lines: null argument");
+    const parseq_config& c = p->m->cfg;
+    CHK(stitch_check(rows, L, p->m->classes, c.img_h, c.img_w, lines, max_out));
+    const size_t localize = parseq_localize_workspace_bytes(p, rows);
+    if (localize == 0) return PARSEQ_E_INVALID;
+    const ReadLinesWs ws = read_lines_ws(p, rows, localize, workspace);
+    if (workspace && workspace_bytes < ws.total) return fail(PARSEQ_E_INVALID, "lines workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
+    // the windows are rows of an ordinary batch: read and localise them (its own refusals come before any device work, too)
+    CHK(parseq_localize(p, images, images_dtype, rows, nullptr, flags, refine_iters, tokens_out, lengths_out, ws.attn, centres_out, boxes_out, ws.peak,
+                        ws.peak_mass, workspace, localize, stream));
+    DevGuard dg(p->m->device);
+    hipStream_t s = (hipStream_t)stream;
+    const float* logits = reinterpret_cast<const float*>(workspace);
+    CHK(launch(postprocess_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, logits, rows, L, p->m->classes, c.eos_id, ws.ids, ws.lens, probs_out, (float*)nullptr));
+    return parseq_op_stitch_lines(tokens_out, lengths_out, probs_out, centres_out, boxes_out, rows, L, p->m->classes, win, c.img_h, c.img_w, line_first,
+                                  lines, min_sep, max_out, line_len_out, line_tokens_out, line_probs_out, line_boxes_out, line_x_out, line_src_out,
+                                  line_confidence_out, stream);
 }

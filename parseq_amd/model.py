@@ -202,6 +202,80 @@ def orient_select(logits: Tensor, views: int, eos_id: int, images: Optional[Tens
     return res
 
 
+@dataclass
+class LineWindows:
+    """The windows a `LineResult` was stitched from, on the device: R = all windows of all lines, rows of one batch."""
+    tokens: Tensor                       # int32 [R, L], int32 [R], fp32 [R, L, 2], fp32 [R, L, 4]: what `localize` gives for the window batch
+    lengths: Tensor
+    centres: Tensor
+    boxes: Tensor
+    probs: Tensor                        # fp32 [R, L]: what parseq_postprocess gives for `forward`'s logits of the window batch
+    win: Tensor                          # int32 [R, 3]: (x0, ww, h) of every window
+    line_first: Tensor                   # int32 [N + 1]: line l is rows line_first[l] .. line_first[l + 1] - 1
+    images: Tensor                       # uint8 [R, 3, H, W]: the window batch itself
+
+
+@dataclass
+class LineResult:
+    """What `read_lines` returns, on the device: N lines of at most M = max_chars characters, in (window, position)
+    order; coordinates are pixels of the line's own image."""
+    lengths: Tensor                      # int32 [N] the characters that survived the stitch (may exceed M: only M are stored)
+    tokens: Tensor                       # int32 [N, M], -1 past the reading
+    probs: Tensor                        # fp32 [N, M]
+    boxes: Tensor                        # fp32 [N, M, 4] (x0, y0, x1, y1)
+    x: Tensor                            # fp64 [N, M] the centres the stitch compared
+    src: Tensor                          # int32 [N, M, 2] (window index in its line, position in the window), -1 past the reading
+    confidence: Tensor                   # fp32 [N]
+    windows: LineWindows
+
+
+def check_lines(overlap, aspect, min_sep, max_chars, max_batch):
+    """The refusals of `read_lines` that need neither an image nor a device (`preprocess.line_windows` has the plan's own)."""
+    if not 0.0 <= overlap <= 0.75:
+        raise ValueError(f'read_lines: overlap must be in [0, 0.75], got {overlap!r}')
+    if not 0.25 <= aspect <= 4.0:
+        raise ValueError(f'read_lines: aspect must be in [0.25, 4], got {aspect!r}')
+    if not (isinstance(min_sep, (int, float)) and 0.0 <= min_sep < math.inf):
+        raise ValueError(f'read_lines: min_sep must be a finite fraction of the line height, at least 0, got {min_sep!r}')
+    if max_chars is not None and not (isinstance(max_chars, int) and 1 <= max_chars <= _native.LINE_MAX_OUT):
+        raise ValueError(f'read_lines: max_chars must be an integer in [1, {_native.LINE_MAX_OUT}], got {max_chars!r}')
+    if not (isinstance(max_batch, int) and max_batch >= 1):
+        raise ValueError(f'read_lines: max_batch must be a positive integer, got {max_batch!r}')
+
+
+def chunk_lines(line_first, max_batch: int):
+    """[(first line, end line)] of the calls `read_lines` makes: lines in order, as many whole lines per call as fit in `max_batch` rows.
+    ValueError for a line that does not fit on its own."""
+    chunks, start = [], 0
+    for l in range(len(line_first) - 1):
+        k = line_first[l + 1] - line_first[l]
+        if k > max_batch:
+            raise ValueError(f'read_lines: line {l} has {k} windows, more than max_batch = {max_batch} rows of one call')
+        if line_first[l + 1] - line_first[start] > max_batch:
+            chunks.append((start, l))
+            start = l
+    return chunks + [(start, len(line_first) - 1)]
+
+
+def stitch_lines(tokens: Tensor, lengths: Tensor, probs: Tensor, centres: Tensor, boxes: Tensor, win: Tensor, line_first: Tensor, min_sep: Tensor,
+                 C_: int, img_size, max_out: int):
+    """The stitch alone (parseq_op_stitch_lines) on caller tensors — as `LineWindows` holds them; `min_sep` fp64 [N] in source pixels.
+    Returns (lengths, tokens, probs, boxes, x, src, confidence).  One launch, no host synchronisation."""
+    dev = tokens.device
+    rows, L = tokens.shape
+    n = line_first.numel() - 1
+    out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, max_out, dtype=torch.int32, device=dev),
+           torch.empty(n, max_out, dtype=torch.float32, device=dev), torch.empty(n, max_out, 4, dtype=torch.float32, device=dev),
+           torch.empty(n, max_out, dtype=torch.float64, device=dev), torch.empty(n, max_out, 2, dtype=torch.int32, device=dev),
+           torch.empty(n, dtype=torch.float32, device=dev))
+    with _native.guard(dev):
+        _native.check(_native.lib().parseq_op_stitch_lines(
+            _native.ptr(tokens.contiguous()), _native.ptr(lengths.contiguous()), _native.ptr(probs.contiguous()), _native.ptr(centres.contiguous()),
+            _native.ptr(boxes.contiguous()), rows, L, int(C_), _native.ptr(win.contiguous()), int(img_size[0]), int(img_size[1]),
+            _native.ptr(line_first.contiguous()), n, _native.ptr(min_sep.contiguous()), int(max_out), *[_native.ptr(t) for t in out], _native.stream_ptr(dev)))
+    return out
+
+
 def init_weights(module: nn.Module, name: str = '', exclude: Sequence[str] = ()):
     """Initialisation scheme of the reference (`strhub/models/utils.py:107-125`): trunc-normal(0.02) Linear / Embedding
     weights, zero biases, unit LayerNorm, Kaiming-normal(fan_out) convolutions.  This is a deliberate statement-for-statement
@@ -957,6 +1031,56 @@ class PARSeq(_NativeBacked):
                                           _native.ptr(loc.boxes), _native.ptr(loc.peak), _native.ptr(loc.peak_mass), _native.ptr(ws), ws.numel(),
                                           _native.stream_ptr(self._device)))
         return loc
+
+    def read_lines(self, tokenizer: Tokenizer, images, overlap: float = 0.25, aspect: float = 1.0, min_sep: float = 0.25,
+                   max_chars: Optional[int] = None, max_batch: int = 512) -> LineResult:
+        """Whole text lines: `images` is a list of uint8 [H, W, 3] device tensors of any width.  Every line is cut
+        into the overlapping windows of `preprocess.line_windows(H, W, img_size, overlap, aspect)`; all windows of all lines are column
+        slices resized in ONE `resize_batch` launch; every call of parseq_read_lines then reads, localises and stitches as many whole lines
+        as fit in `max_batch` rows, without a host synchronisation.  Two readings of one character in neighbouring windows are told apart
+        from a doubled letter by position: centres closer than `min_sep` line heights are the same character.  `max_chars`: the slots per
+        line (default: what the windows of the longest line could hold, at most 2048)."""
+        from . import preprocess
+        self._check_localizable('read_lines')
+        check_lines(overlap, aspect, min_sep, max_chars, max_batch)
+        images = preprocess._checked(list(images), 'read_lines')
+        img_size = self._cfg['img_size']
+        win, first = preprocess.line_plan([(im.shape[0], im.shape[1]) for im in images], img_size, overlap, aspect)
+        chunks = chunk_lines(first, max_batch)
+        N, R, L, dev = len(images), len(win), self.max_label_length + 1, images[0].device
+        if max_chars is None:
+            max_chars = min(_native.LINE_MAX_OUT, max(first[l + 1] - first[l] for l in range(N)) * self.max_label_length)
+        batch = self._check_images(preprocess.resize_batch(preprocess.line_views(images, win, first), img_size))
+        plan = self._plan(max(first[b] - first[a] for a, b in chunks))
+        self._memory_replaced()
+        self._check_tokenizer(tokenizer)
+        # one upload: the window table, every call's own line_first (counted from the call's first row) and the separations
+        firsts = [first[l] - first[a] for a, b in chunks for l in range(a, b + 1)]
+        table = torch.tensor([v for row in win for v in row] + firsts, dtype=torch.int32).to(dev)
+        sep = torch.tensor([float(min_sep) * im.shape[0] for im in images], dtype=torch.float64).to(dev)
+        win_d, firsts_d = table[:3 * R].view(R, 3), table[3 * R:]
+        w = LineWindows(torch.empty(R, L, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.int32, device=dev),
+                        torch.empty(R, L, 2, dtype=torch.float32, device=dev), torch.empty(R, L, 4, dtype=torch.float32, device=dev),
+                        torch.empty(R, L, dtype=torch.float32, device=dev), win_d, torch.tensor(first, dtype=torch.int32).to(dev), batch)
+        M = max_chars
+        res = LineResult(torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, M, dtype=torch.int32, device=dev),
+                         torch.empty(N, M, dtype=torch.float32, device=dev), torch.empty(N, M, 4, dtype=torch.float32, device=dev),
+                         torch.empty(N, M, dtype=torch.float64, device=dev), torch.empty(N, M, 2, dtype=torch.int32, device=dev),
+                         torch.empty(N, dtype=torch.float32, device=dev), w)
+        lib = _native.lib()
+        flags = (_native.FLAG_DECODE_AR if self.decode_ar else 0) | _native.FLAG_LATENCY
+        pos = 0
+        for a, b in chunks:
+            r0, rows = first[a], first[b] - first[a]
+            ws = self._workspace(lib.parseq_read_lines_workspace_bytes, plan, rows)
+            _native.check(lib.parseq_read_lines(
+                plan, _native.ptr(batch[r0:]), _native.dtype_code(batch.dtype), rows, flags, int(self.refine_iters), _native.ptr(win_d[r0:]),
+                _native.ptr(firsts_d[pos:]), b - a, _native.ptr(sep[a:]), M, _native.ptr(w.tokens[r0:]), _native.ptr(w.lengths[r0:]), _native.ptr(w.probs[r0:]),
+                _native.ptr(w.centres[r0:]), _native.ptr(w.boxes[r0:]), _native.ptr(res.lengths[a:]), _native.ptr(res.tokens[a:]), _native.ptr(res.probs[a:]),
+                _native.ptr(res.boxes[a:]), _native.ptr(res.x[a:]), _native.ptr(res.src[a:]), _native.ptr(res.confidence[a:]), _native.ptr(ws), ws.numel(),
+                _native.stream_ptr(self._device)))
+            pos += b - a + 1
+        return res
 
     # ---- native plumbing ---------------------------------------------------------------------------------------
     def _special_ids(self, tokenizer):

@@ -574,3 +574,48 @@ def orientation_regions(regions, mode: str = 'flip', tall: float = 1.5):
     angles = orientation_angles([region_size(quad) for _, quad in regions], mode, tall)
     shifts = [tuple(a // 90 for a in per_region) for per_region in angles]
     return [(index, shift_quad(quad, k)) for (index, quad), per_region in zip(regions, shifts) for k in per_region], shifts
+
+
+# ---- long text lines (DESIGN.md section 29) -------------------------------------------------------------------------------------------
+# A line wider than the model's input is read as overlapping windows of the width the model was made for; `model.read_lines` reads them as
+# one batch and stitches the characters by position on the device.  The plan is made here, on the host, in float64 and integers.
+LINE_MAX_WINDOWS = _native.LINE_MAX_WINDOWS          # PARSEQ_LINE_MAX_WINDOWS
+
+
+def line_windows(h: int, w: int, img_size=(32, 128), overlap: float = 0.25, aspect: float = 1.0):
+    """[(x0, ww)] — the windows of a line of `h` x `w` pixels, left to right: window k is the columns x0 .. x0 + ww - 1.  The width
+    ww = max(1, floor(h img_w / img_h aspect + 1/2)) is what the resize maps onto the model's input without distortion (`aspect` stretches
+    it); a line no wider than that is one window (0, w), the crop as `resize_batch` reads it.  Otherwise neighbours share
+    ov = floor(ww overlap + 1/2) columns: the stride is s = max(1, ww - ov), there are ceil((w - ww) / s) + 1 windows, and the last one is
+    right-aligned.  ValueError: sizes below 1, `overlap` outside [0, 0.75], `aspect` outside [0.25, 4], more than LINE_MAX_WINDOWS windows."""
+    h, w, img_h, img_w = int(h), int(w), int(img_size[0]), int(img_size[1])
+    if h < 1 or w < 1 or img_h < 1 or img_w < 1:
+        raise ValueError(f'line_windows: a line of {h} x {w} for an input of {img_h} x {img_w}: every side must be at least 1')
+    if not 0.0 <= overlap <= 0.75:
+        raise ValueError(f'line_windows: overlap must be in [0, 0.75], got {overlap!r}')
+    if not 0.25 <= aspect <= 4.0:
+        raise ValueError(f'line_windows: aspect must be in [0.25, 4], got {aspect!r}')
+    ww = max(1, math.floor(h * img_w / img_h * aspect + 0.5))
+    if w <= ww:
+        return [(0, w)]
+    ov = math.floor(ww * overlap + 0.5)
+    s = max(1, ww - ov)
+    K = -(-(w - ww) // s) + 1
+    if K > LINE_MAX_WINDOWS:
+        raise ValueError(f'line_windows: a line of {h} x {w} gives {K} windows of {ww} columns, the limit is {LINE_MAX_WINDOWS}; raise `aspect` or cut the line')
+    return [(min(k * s, w - ww), ww) for k in range(K)]
+
+
+def line_plan(sizes, img_size=(32, 128), overlap: float = 0.25, aspect: float = 1.0):
+    """The window table of the lines of `sizes` = [(h, w)]: (win, line_first) as lists — win[row] = (x0, ww, h) for every window of every
+    line in order, line_first[l] the first row of line l, with one entry more for the end."""
+    win, first = [], [0]
+    for h, w in sizes:
+        win += [(x0, ww, int(h)) for x0, ww in line_windows(h, w, img_size, overlap, aspect)]
+        first.append(len(win))
+    return win, first
+
+
+def line_views(images: Sequence[Tensor], win, line_first):
+    """The windows of `line_plan` as views of the uploaded lines: image l's columns x0 .. x0 + ww - 1 per row of `win`.  No copy."""
+    return [images[l][:, x0:x0 + ww] for l in range(len(images)) for x0, ww, _ in win[line_first[l]:line_first[l + 1]]]

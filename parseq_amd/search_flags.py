@@ -219,6 +219,44 @@ def resolve_orientation(parser, args):
     return args.auto_rotate, bias
 
 
+# ---- --lines ------------------------------------------------------------------------------------------------------
+LINE_OVERLAP, LINE_SEP = 0.25, 0.25
+
+
+def add_line_flags(parser):
+    """--lines [--line-overlap F] [--line-sep F] of read.py."""
+    parser.add_argument('--lines', action='store_true',
+                        help='Every image (or region of --regions) is a whole text line: read it as overlapping windows stitched by character position; '
+                             'composes with --boxes and --regions only')
+    parser.add_argument('--line-overlap', type=float, default=None, dest='line_overlap', metavar='F',
+                        help=f'With --lines: the share of a window its neighbour repeats, 0 to 0.75 (default {LINE_OVERLAP})')
+    parser.add_argument('--line-sep', type=float, default=None, dest='line_sep', metavar='F',
+                        help=f'With --lines: two readings of a character closer than F line heights are one character (default {LINE_SEP}; 0 keeps both)')
+
+
+def resolve_lines(parser, args):
+    """(overlap, sep) of --lines, None without it; a contradiction ends in parser.error.  The greedy reading of a line composes with --boxes
+    and --regions; a search, a rotation or --polygons does not reach across windows."""
+    import math
+    if not args.lines:
+        if args.line_overlap is not None or args.line_sep is not None:
+            parser.error('--line-overlap and --line-sep need --lines')
+        return None
+    if search_requested(args) or args.nbest > 0:
+        parser.error('--lines reads greedily: not with --nbest, --beam, --lexicon, --match, --priors, --lm, --pattern or --refine-beams')
+    if args.auto_rotate is not None or args.upright_bias is not None:
+        parser.error('--lines does not turn its windows: not with --auto-rotate')
+    if getattr(args, 'polygons', None) is not None:
+        parser.error('--lines with --polygons: cut the lines as quadrilaterals (--regions)')
+    overlap = LINE_OVERLAP if args.line_overlap is None else args.line_overlap
+    sep = LINE_SEP if args.line_sep is None else args.line_sep
+    if not 0.0 <= overlap <= 0.75:
+        parser.error('--line-overlap must be in [0, 0.75]')
+    if not (math.isfinite(sep) and sep >= 0.0):
+        parser.error('--line-sep must be finite and at least 0')
+    return overlap, sep
+
+
 def orientation_prior(bias: float, views: int):
     """The prior of `orient` for --upright-bias: `bias` on the first view, None for no bias."""
     return None if bias == 0.0 else [bias] + [0.0] * (views - 1)

@@ -290,6 +290,14 @@ class PARSeq(nn.Module):
         `result.images` goes into any other call (`beam_search`, `lexicon_match`, `localize`) as upright crops."""
         return self.model.orient(self.tokenizer, views, criterion=criterion, prior=prior, max_length=max_length, slot=slot)
 
+    def read_lines(self, images, overlap: float = 0.25, aspect: float = 1.0, min_sep: float = 0.25, max_chars: Optional[int] = None, max_batch: int = 512):
+        """Whole text lines, far wider than `img_size` and longer than `max_label_length` (model.PARSeq.read_lines):
+        `images` is a list of uint8 [H, W, 3] device tensors.  Every line is read as overlapping windows (`overlap` of a window's width,
+        windows `aspect` times as wide as the model's input is at the line's height) and the windows' characters are stitched by their
+        positions on the device — two readings of a character less than `min_sep` line heights apart are one.  A `LineResult` on the device;
+        `self.tokenizer.decode_lines(result)` turns it into strings.  Calls hold at most `max_batch` windows; a line never splits."""
+        return self.model.read_lines(self.tokenizer, images, overlap=overlap, aspect=aspect, min_sep=min_sep, max_chars=max_chars, max_batch=max_batch)
+
     # ---- evaluation glue used by the reference's test.py:121-126 ------------------------------------------------
     def _eval_step(self, batch, validation: bool):
         return eval_step(self, batch, validation)

@@ -178,3 +178,20 @@ class Tokenizer(BaseTokenizer):
         boxes = packed[:, length + 1:].contiguous().view(torch.float32).reshape(b, length, 4).tolist()
         labels = [self._ids2tok(row[:k].tolist()) for row, k in zip(ids, lengths)]
         return labels, [[(ch, tuple(boxes[i][j])) for j, ch in enumerate(label)] for i, label in enumerate(labels)]
+
+    def decode_lines(self, result, boxes: bool = False):
+        """A `LineResult` as strings: (labels, confidences), and with `boxes` a third list — per line the
+        (character, (x0, y0, x1, y1)) of every character in reading order, in pixels of the line's own image.  A line that holds more
+        characters than the result has slots is cut at the slots.  One copy to the host."""
+        n, m = result.tokens.shape
+        parts = [result.tokens, result.lengths.reshape(n, 1).to(torch.int32), result.confidence.reshape(n, 1).contiguous().view(torch.int32)]
+        if boxes:
+            parts.append(result.boxes.reshape(n, m * 4).contiguous().view(torch.int32))
+        packed = torch.cat(parts, dim=1).cpu()
+        ids, lengths = packed[:, :m].numpy(), packed[:, m].tolist()
+        conf = packed[:, m + 1].contiguous().view(torch.float32).tolist()
+        labels = [self._ids2tok(row[:min(k, m)].tolist()) for row, k in zip(ids, lengths)]
+        if not boxes:
+            return labels, conf
+        bx = packed[:, m + 2:].contiguous().view(torch.float32).reshape(n, m, 4).tolist()
+        return labels, conf, [[(ch, tuple(bx[i][j])) for j, ch in enumerate(label)] for i, label in enumerate(labels)]

@@ -144,6 +144,9 @@ class ViTSTR(nn.Module):
     def localize(self, images: Tensor, labels=None):
         raise ValueError('localize: ViTSTR has no decoder, hence no cross-attention over the patch tokens; use a PARSeq model')
 
+    def read_lines(self, images, overlap: float = 0.25, aspect: float = 1.0, min_sep: float = 0.25, max_chars: Optional[int] = None, max_batch: int = 512):
+        raise ValueError('read_lines: ViTSTR has no decoder, hence no character positions to stitch windows by; use a PARSeq model')
+
     def orient(self, views: Tensor, criterion: str = 'mean', prior=None, max_length: Optional[int] = None, slot: Optional[int] = None):
         """As `PARSeq.orient`: `forward` on the B * K rows of `views` [B, K, 3, H, W], then the choice on the device
         (parseq_op_orient_select).  No host synchronisation."""

@@ -14,6 +14,7 @@
     ./read.py pretrained=parseq --images scene.jpg --regions scene.txt [--boxes]     read every quadrilateral of the file (x1,y1,..,x4,y4 per line)
     ./read.py pretrained=parseq --images scene.jpg --polygons scene.txt [--boxes]     read every polygon of the file (x1,y1,..,xK,yK per line): curved text
     ./read.py pretrained=parseq --images a.png --auto-rotate flip [--upright-bias 0.1]     read every crop upright and upside down, keep the better reading
+    ./read.py pretrained=parseq --images line.png --lines [--line-overlap 0.25] [--line-sep 0.25] [--boxes]     read a whole text line as stitched windows
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -27,8 +28,8 @@ from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.preprocess import resize_batch, rotated_size, unrotate_points
-from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, add_orientation_flags, build_automaton, load_word_counts, load_word_list,  # noqa: F401
-                                      orientation_prior, resolve_automaton, resolve_flags, resolve_match, resolve_orientation, resolve_refine, resolve_search)
+from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, add_line_flags, add_orientation_flags, build_automaton, load_word_counts, load_word_list,  # noqa: F401
+                                      orientation_prior, resolve_lines, resolve_automaton, resolve_flags, resolve_match, resolve_orientation, resolve_refine, resolve_search)
 
 
 def turned_name(name, angle):
@@ -315,6 +316,41 @@ def read_files_match(model, files, words, n=MATCH_N, device='cuda', orient=None)
     return list(zip([turned_name(f, a) for f, a in zip(files, angles)], match_batch(model, batch, words, n, device)))
 
 
+@torch.inference_mode()
+def read_lines_lines(model, files, lines, region_files=None, boxes=False, device='cuda'):
+    """The lines `--lines` prints: every file — or, with `region_files`, every quadrilateral of every file, cut out
+    at its own size by `rectify_batch` and named `file#k` — is one text line, read by `model.read_lines` with `lines` = (overlap, sep).
+    `boxes` adds every character's box in the file's own pixels; a region's boxes are led back through `map_to_source` as quadrilaterals."""
+    import numpy as np
+    from parseq_amd.preprocess import map_to_source, rectify_batch, region_descs
+    scenes = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+    names, crops, back = list(files), scenes, None
+    if region_files is not None:
+        names, regions = [], []
+        for i, (f, rf) in enumerate(zip(files, region_files)):
+            for k, quad in enumerate(load_regions(rf)):
+                names.append(f'{f}#{k}')
+                regions.append((i, quad))
+        if regions:
+            described = region_descs(regions, n_images=len(files))
+            crops = rectify_batch(scenes, [(index, coeffs, size) for index, size, coeffs in described])
+            back = [(coeffs, size) for _, size, coeffs in described]
+    if not names:
+        return []
+    result = model.read_lines(crops, overlap=lines[0], min_sep=lines[1])
+    decoded = model.tokenizer.decode_lines(result, boxes=boxes)
+    out = []
+    for i, (name, label) in enumerate(zip(names, decoded[0])):
+        out.append(f'{name}: {label}')
+        if boxes and back is None:
+            out.append('    ' + ' '.join(f'{ch}[{x0:.1f},{y0:.1f},{x1:.1f},{y1:.1f}]' for ch, (x0, y0, x1, y1) in decoded[2][i]))
+        elif boxes:
+            coeffs, size = back[i]       # the boxes are in pixels of the rectified region already: no stretch to undo
+            quads = [(ch, map_to_source(coeffs, size, size, ((x0, y0), (x1, y0), (x1, y1), (x0, y1)))) for ch, (x0, y0, x1, y1) in decoded[2][i]]
+            out.append('    ' + ' '.join(f'{ch}[' + ','.join(f'{v:.1f}' for p in quad for v in p) + ']' for ch, quad in quads))
+    return out
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('checkpoint', help="Model checkpoint (or 'pretrained=<model_id>')")
@@ -356,6 +392,7 @@ def build_parser():
                         help='Added to the ranking per character read, with --priors / --lm / --pattern (default 0)')
     parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
     add_orientation_flags(parser)      # --auto-rotate MODE [--upright-bias X]: a crop read turned is printed as file@angle
+    add_line_flags(parser)             # --lines [--line-overlap F] [--line-sep F]: every image is a whole text line
     return parser
 
 
@@ -367,6 +404,7 @@ def main(argv=None):
 
     if args.boxes and (args.nbest > 0 or args.lexicon is not None):
         parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
+    lines = resolve_lines(parser, args)
     kind, alpha, beta, match, beam, nbest, refine, refine_iters = resolve_flags(parser, args)
     files = args.images or []
     if args.regions is not None and args.polygons is not None:
@@ -377,6 +415,10 @@ def main(argv=None):
     if region_files is not None and len(region_files) != len(files):
         parser.error(f'--{"polygons" if polygons else "regions"} takes one file per image, in order: {len(region_files)} files for {len(files)} images')
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
+    if lines is not None:
+        for line in read_lines_lines(model, files, lines, region_files, args.boxes, args.device):
+            print(line)
+        return
     if kind is not None:
         automaton = build_automaton(model, kind, args)
         if region_files is not None:
