@@ -494,6 +494,51 @@ int parseq_read_lines(parseq_plan* p, const void* images, int images_dtype, int 
                       float* line_probs_out, float* line_boxes_out, double* line_x_out, int32_t* line_src_out, float* line_confidence_out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- scoring given readings (pure additions under ABI 15; DESIGN.md section 30 defines it) -------------------------- */
+
+/* How likely is THIS string for this crop?  Rows b n .. b n + n - 1 are the candidates of crop b.  A candidate of len characters is the
+ * int32 row c_0 .. c_{len-1}, <eos>, then <pad> to L = num_steps entries; a first entry of <pad> is an absent candidate.  A row is invalid
+ * when a token before its <eos> lies outside [0, C), when anything but <pad> follows the <eos>, or when it holds no <eos>; the staging
+ * kernel turns absent and invalid rows into <bos>, <pad> .. before the decoder sees them, so no table is indexed out of range.
+ * The decoder input of a row is <bos>, c_0 .. c_{len-1}, <pad> .., its key padding the <pad> slots, its targets the row itself.  For each of
+ * `orders` decoding orders, query_masks (device uint8 [orders, L, L], 1 = masked: generate_attn_masks(perm)[1] of the reference) is the
+ * attention mask of the query stream of one teacher-forced decoder pass over all batch * n rows, and with lp = log_softmax(logits):
+ *   char_logprobs_out  fp32 [batch, n, orders, L] (NULL: not wanted): lp[i][c_i] for i <= len (i = len: the <eos>), 0 past it and in rows
+ *                      that are not valid
+ *   order_scores_out   fp32 [batch, n, orders]: the fp32 sum of those terms from 0 in ascending i, the <eos> term always included; a sum
+ *                      that is not a number is -inf
+ *   scores_out         fp32 [batch, n]: in fp64 with k ascending, PARSEQ_SCORE_MIX: m + log(sum_k exp(s_k - m)) - log(orders), m = max_k s_k
+ *                      (the mixture of the orders, a probability); PARSEQ_SCORE_MEAN: (sum_k s_k) / orders.  orders = 1: the order's bits.
+ *                      -inf for rows that are not valid
+ *   rank_out           int32 [batch, n]: the candidates of a crop best first — the higher key, then the lower index; the key is the score,
+ *                      under PARSEQ_SCORE_LENGTH_NORM (double)score / (len + 1).  Rows of score -inf come last.  A permutation of 0 .. n-1
+ *   lengths_out, valid_out   int32, uint8 [batch, n]: len and 1, or 0 and 0 for an absent or invalid row
+ * The log-soft-max is the expression of parseq_op_beam_refine's statistics, (x - max) - logf(sum expf(x - max)) with the same lane-strided
+ * partial sums: given the same logits the terms have the same bits.  No atomics: bit-identical on any stream.
+ * parseq_score: encode once, replicate the memory n-fold, then `orders` x (decoder pass, row kernel), then the rank — no allocation, no host
+ * synchronisation.  workspace: parseq_score_workspace_bytes(p, batch, n, num_steps, orders) device bytes (0: refused, parseq_last_error says
+ * why), 16-byte aligned.  Afterwards the plan's cached memory K / V are the replicated batch's.  Refused with PARSEQ_E_INVALID before any
+ * device work, outputs untouched: a NULL argument (char_logprobs_out may be NULL), a ViTSTR model, dec_depth > 1, n outside
+ * 1 .. PARSEQ_SCORE_MAX_CANDIDATES, orders outside 1 .. PARSEQ_SCORE_MAX_ORDERS, batch * n above the plan's max_batch, num_steps outside
+ * [2, max_label_length + 1], a short or misaligned workspace, unknown flags. */
+#define PARSEQ_SCORE_MAX_CANDIDATES 16
+#define PARSEQ_SCORE_MAX_ORDERS 16
+enum parseq_score_flags { PARSEQ_SCORE_MIX = 0, PARSEQ_SCORE_MEAN = 1, PARSEQ_SCORE_LENGTH_NORM = 2 };
+size_t parseq_score_workspace_bytes(const parseq_plan* p, int batch, int n, int num_steps, int orders);
+int parseq_score(parseq_plan* p, const void* images, int images_dtype, int batch, const int32_t* candidates, int n, int num_steps,
+                 const uint8_t* query_masks, int orders, int flags, float* scores_out, float* order_scores_out, float* char_logprobs_out,
+                 int32_t* rank_out, int32_t* lengths_out, uint8_t* valid_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The two kernels after the decoder pass, on the caller's tensors.  parseq_op_score_rows: order `order` of `orders` from logits fp32
+ * [rows, L, C] (any C), targets int32 [rows, L] (a summed target outside [0, C) gives a term of -inf), lengths int32 [rows] (positions
+ * 0 .. lengths are summed), valid uint8 [rows]; it writes order_scores [rows, orders] and char_logprobs [rows, orders, L] (may be NULL) at
+ * that order.  parseq_op_score_rank: scores_out and rank_out from order_scores [batch, n, orders], lengths and valid [batch, n]; a NaN in
+ * order_scores counts as -inf.  One launch each.  Refused: a NULL argument, L outside 1 .. 64, rows, n or orders outside their ranges, an
+ * order outside [0, orders), unknown flags. */
+int parseq_op_score_rows(const float* logits, int rows, int L, int C, const int32_t* targets, const int32_t* lengths, const uint8_t* valid,
+                         int orders, int order, float* order_scores, float* char_logprobs, void* stream);
+int parseq_op_score_rank(const float* order_scores, const int32_t* lengths, const uint8_t* valid, int batch, int n, int orders, int flags,
+                         float* scores_out, int32_t* rank_out, void* stream);
+
 /* ---- beam search over a weighted automaton (pure additions under ABI 15; DESIGN.md section 24 defines it) ------------ */
 
 /* parseq_forward_beam_lexicon with a weight on every arc of the table, which then need not be a tree (cycles and shared states are

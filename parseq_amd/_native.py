@@ -20,6 +20,8 @@ ABI_VERSION = 15
 ORIENT_MAX_VIEWS = 8                                  # PARSEQ_ORIENT_MAX_VIEWS
 ORIENT_CRITERIA = {'mean': 0, 'sum': 1}               # enum parseq_orient_criterion
 LINE_MAX_WINDOWS, LINE_MAX_OUT = 64, 2048             # PARSEQ_LINE_MAX_WINDOWS, PARSEQ_LINE_MAX_OUT
+SCORE_MAX_CANDIDATES, SCORE_MAX_ORDERS = 16, 16       # PARSEQ_SCORE_MAX_CANDIDATES, PARSEQ_SCORE_MAX_ORDERS
+SCORE_MIX, SCORE_MEAN, SCORE_LENGTH_NORM = 0, 1, 2    # enum parseq_score_flags
 
 
 class ParseqConfig(C.Structure):
@@ -229,6 +231,12 @@ SIGNATURES = {
     'parseq_forward_oriented_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     'parseq_forward_oriented': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_score_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'parseq_score': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'parseq_op_score_rows': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    'parseq_op_score_rank': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     'parseq_op_stitch_lines': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),

@@ -7,6 +7,7 @@
 #include "lexicon_match.h"
 #include "orient.h"
 #include "line_stitch.h"
+#include "score.h"
 
 // -------------------------------------------------------------------------------------------------------------------
 // what a call runs on: storage type and width, the decoder's parameters, the pass, the route of the single-query step
@@ -1444,4 +1445,114 @@ extern "C" int parseq_read_lines(parseq_plan* p, const void* images, int images_
     return parseq_op_stitch_lines(tokens_out, lengths_out, probs_out, centres_out, boxes_out, rows, L, p->m->classes, win, c.img_h, c.img_w, line_first,
                                   lines, min_sep, max_out, line_len_out, line_tokens_out, line_probs_out, line_boxes_out, line_x_out, line_src_out,
                                   line_confidence_out, stream);
+}
+
+// -------------------------------------------------------------------------------------------------------------------
+// scoring of given readings (score.h): joint log-probabilities of candidates in any decoding order
+// -------------------------------------------------------------------------------------------------------------------
+static_assert(SCORE_MAX_N == PARSEQ_SCORE_MAX_CANDIDATES && SCORE_MAX_ORDERS == PARSEQ_SCORE_MAX_ORDERS && SCORE_MEAN == PARSEQ_SCORE_MEAN &&
+              SCORE_LENGTH_NORM == PARSEQ_SCORE_LENGTH_NORM && PARSEQ_SCORE_MIX == 0 && LDT <= SCORE_MAX_L, "header and kernel must agree");
+
+static int score_op_check(int batch, int n, int L, int orders, int flags) {
+    if (n < 1 || n > SCORE_MAX_N) return fail(PARSEQ_E_INVALID, "score: %d candidates per crop, it must be in 1 .. %d", n, SCORE_MAX_N);
+    if (orders < 1 || orders > SCORE_MAX_ORDERS) return fail(PARSEQ_E_INVALID, "score: %d orders, it must be in 1 .. %d", orders, SCORE_MAX_ORDERS);
+    if (batch < 1 || (long long)batch * n > (1 << 26)) return fail(PARSEQ_E_INVALID, "score: batch %d x %d candidates outside (0, %d]", batch, n, 1 << 26);
+    if (L < 1 || L > SCORE_MAX_L) return fail(PARSEQ_E_INVALID, "score: L = %d positions, it must be in 1 .. %d", L, SCORE_MAX_L);
+    if (flags & ~(PARSEQ_SCORE_MEAN | PARSEQ_SCORE_LENGTH_NORM)) return fail(PARSEQ_E_INVALID, "score: unknown flags 0x%x", flags);
+    return 0;
+}
+
+extern "C" int parseq_op_score_rows(const float* logits, int rows, int L, int C, const int32_t* targets, const int32_t* lengths, const uint8_t* valid,
+                                    int orders, int order, float* order_scores, float* char_logprobs, void* stream) {
+    if (!logits || !targets || !lengths || !valid || !order_scores) return fail(PARSEQ_E_INVALID, "score: null argument");
+    if (rows < 1 || rows > (1 << 26) || C < 1) return fail(PARSEQ_E_INVALID, "score: %d rows of %d classes", rows, C);
+    if (L < 1 || L > SCORE_MAX_L) return fail(PARSEQ_E_INVALID, "score: L = %d positions, it must be in 1 .. %d", L, SCORE_MAX_L);
+    if (orders < 1 || orders > SCORE_MAX_ORDERS || order < 0 || order >= orders) return fail(PARSEQ_E_INVALID, "score: order %d of %d (1 .. %d)", order, orders, SCORE_MAX_ORDERS);
+    return launch(score_rows_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, logits, L, C, targets, lengths, valid, orders, order, order_scores, char_logprobs);
+}
+
+extern "C" int parseq_op_score_rank(const float* order_scores, const int32_t* lengths, const uint8_t* valid, int batch, int n, int orders, int flags,
+                                    float* scores_out, int32_t* rank_out, void* stream) {
+    if (!order_scores || !lengths || !valid || !scores_out || !rank_out) return fail(PARSEQ_E_INVALID, "score: null argument");
+    CHK(score_op_check(batch, n, 1, orders, flags));
+    return launch(score_rank_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, order_scores, lengths, valid, n, orders, flags, scores_out, rank_out);
+}
+
+// The caller's workspace: the encoder memory of the crops, its N-fold replication (set_memory_impl's operand), one order's logits of every
+// position and the targets the seed leaves.  The token rows and the key padding live in the plan, where the decoder reads them.
+struct ScoreWs { float *memory, *memory_rep, *logits; int* target; size_t total; };
+static ScoreWs score_ws(const parseq_plan* p, int batch, int n, int L, void* workspace = nullptr) {
+    const parseq_model* m = p->m;
+    const size_t rows = (size_t)batch * n, img = (size_t)m->tokens * m->cfg.embed_dim;
+    Carver cv{reinterpret_cast<unsigned char*>(workspace)};
+    ScoreWs o{};
+    o.memory = cv.take<float>(batch * img);
+    o.memory_rep = cv.take<float>(rows * img);
+    o.logits = cv.take<float>(rows * L * m->classes);
+    o.target = cv.take<int>(rows * L);
+    o.total = cv.off;
+    return o;
+}
+
+static int score_check(const parseq_plan* p, int batch, int n, int num_steps, int orders, int flags) {
+    if (!p) return fail(PARSEQ_E_INVALID, "null plan");
+    const parseq_model* m = p->m;
+    if (m->vitstr) return fail(PARSEQ_E_INVALID, "parseq_score on a ViTSTR model: it has no decoder to condition on a reading");
+    if (m->cfg.dec_depth > 1) return fail(PARSEQ_E_INVALID, "parseq_score at dec_depth %d: only dec_depth 1", m->cfg.dec_depth);
+    const int npos = m->cfg.max_label_length + 1;
+    if (num_steps < 2 || num_steps > npos) return fail(PARSEQ_E_INVALID, "score: num_steps %d outside [2, %d]", num_steps, npos);
+    CHK(score_op_check(batch, n, num_steps, orders, flags));
+    if ((long long)batch * n > p->max_batch) return fail(PARSEQ_E_INVALID, "score: batch %d x %d candidates outside (0, %d]", batch, n, p->max_batch);
+    return 0;
+}
+
+extern "C" size_t parseq_score_workspace_bytes(const parseq_plan* p, int batch, int n, int num_steps, int orders) {
+    if (score_check(p, batch, n, num_steps, orders, 0) != 0) return 0;
+    return score_ws(p, batch, n, num_steps).total;
+}
+
+template <typename T, int E>
+static int score_impl(parseq_plan* p, int B, int N, int L, const int32_t* candidates, const uint8_t* query_masks, int K, int flags, const ScoreWs& ws,
+                      float* scores_out, float* order_scores_out, float* char_logprobs_out, int32_t* rank_out, int32_t* lengths_out, uint8_t* valid_out,
+                      hipStream_t s) {
+    const parseq_config& c = p->m->cfg;
+    const int C = p->m->classes, rows = B * N;
+    // every candidate of a crop attends to that crop's memory: N copies through the projection every caller-supplied memory takes
+    const size_t per_img4 = (size_t)p->m->tokens * E / 4, total4 = per_img4 * rows;
+    CHK(launch(beam_replicate_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const float4*>(ws.memory),
+               reinterpret_cast<float4*>(ws.memory_rep), per_img4, N, total4));
+    CHK(set_memory_impl<T>(p, ws.memory_rep, rows, s));
+    CHK(launch(score_seed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, candidates, rows, L, C, c.bos_id, c.eos_id, c.pad_id, p->tok, LDT, p->kpm, LDT,
+               ws.target, lengths_out, valid_out));
+    const DecW<T> w = dec_weights<T>(p);
+    // the teacher-forced pass of training_step (system.py:183-189): every position queried against the whole context under the order's mask
+    DecPass a; a.B = rows; a.Lk = a.Lq = L; a.qmask = p->qmask_user; a.kpm = p->kpm; a.logits = ws.logits; a.Ltot = L;
+    for (int k = 0; k < K; ++k) {
+        HIPCHK(hipMemcpy2DAsync(p->qmask_user, LDT, query_masks + (size_t)k * L * L, L, L, L, hipMemcpyDeviceToDevice, s));
+        CHK((decoder_pass<T, E>(p, s, w, a)));
+        CHK(launch(score_rows_kernel, dim3(rows), dim3(256), 0, s, (const float*)ws.logits, L, C, (const int*)ws.target, (const int*)lengths_out,
+                   (const unsigned char*)valid_out, K, k, order_scores_out, char_logprobs_out));
+    }
+    return launch(score_rank_kernel, dim3(B), dim3(64), 0, s, (const float*)order_scores_out, (const int*)lengths_out, (const unsigned char*)valid_out, N, K,
+                  flags, scores_out, rank_out);
+}
+
+extern "C" int parseq_score(parseq_plan* p, const void* images, int images_dtype, int batch, const int32_t* candidates, int n, int num_steps,
+                            const uint8_t* query_masks, int orders, int flags, float* scores_out, float* order_scores_out, float* char_logprobs_out,
+                            int32_t* rank_out, int32_t* lengths_out, uint8_t* valid_out, void* workspace, size_t workspace_bytes, void* stream) {
+    CHK(score_check(p, batch, n, num_steps, orders, flags));
+    CHK(check_call(p, batch, images_dtype));
+    if (!images || !candidates || !query_masks || !scores_out || !order_scores_out || !rank_out || !lengths_out || !valid_out || !workspace)
+        return fail(PARSEQ_E_INVALID, "score: null images / candidates / query_masks / output / workspace");
+    const ScoreWs ws = score_ws(p, batch, n, num_steps, workspace);
+    if (workspace_bytes < ws.total) return fail(PARSEQ_E_INVALID, "score workspace of %zu bytes, %zu needed", workspace_bytes, ws.total);
+    if ((uintptr_t)workspace % 16) return fail(PARSEQ_E_INVALID, "score workspace not 16-byte aligned");
+    DevGuard dg(p->m->device);
+    SplitScope ss(p->precision == PARSEQ_BF16X3);
+    hipStream_t s = (hipStream_t)stream;
+    CHK(encode_dispatch(p, images, images_dtype, batch, ws.memory, s));
+    return dispatch_te(p, [&](auto te) {
+        return score_impl<typename decltype(te)::T, decltype(te)::E>(p, batch, n, num_steps, candidates, query_masks, orders, flags, ws, scores_out,
+                                                                     order_scores_out, char_logprobs_out, rank_out, lengths_out, valid_out, s);
+    });
 }

@@ -106,16 +106,20 @@ class Evaluator:
 
     The system must be on the GPU when the Evaluator is built (there is no CPU path: RuntimeError otherwise).  `host_path` tells
     whether this model's charsets forced the per-batch host loop (see the module docstring).  `errors`: an `ErrorAnalysis` of the same
-    system; every `update` then hands it the ids and lengths the metrics kernel wrote and the uploaded labels, `reset` resets it too."""
+    system; every `update` then hands it the ids and lengths the metrics kernel wrote and the uploaded labels, `reset` resets it too.
+    `audit`: a `LabelAudit` of the same system; every `update` then scores label and reading of the batch.  It needs
+    the device path (ValueError on a model whose charsets select `host_path`)."""
 
-    def __init__(self, system, validation: bool = False, errors: Optional['ErrorAnalysis'] = None) -> None:
-        self.system, self.validation, self.errors = system, validation, errors
+    def __init__(self, system, validation: bool = False, errors: Optional['ErrorAnalysis'] = None, audit: Optional['LabelAudit'] = None) -> None:
+        self.system, self.validation, self.errors, self.audit = system, validation, errors, audit
         self.device = torch.device(system.device)
         if self.device.type != 'cuda':
             raise RuntimeError('Evaluator runs on the GPU (no CPU fallback); move the model to the device first')
         table = adapter_table(system.tokenizer, system.charset_adapter)
         self.host_path = table is None
         self._table = None if self.host_path else torch.from_numpy(table).to(self.device)
+        if audit is not None and self.host_path:
+            raise ValueError('Evaluator(audit=) needs the device path; this model\'s charsets select the host path')
         self._last_rows = None
         self.reset()
 
@@ -124,6 +128,8 @@ class Evaluator:
         self._last_rows = None
         if self.errors is not None:
             self.errors.reset()
+        if self.audit is not None:
+            self.audit.reset()
         if not self.host_path:
             self._accum = torch.zeros(5, dtype=torch.int64, device=self.device)          # 3 x int64, then 2 x float64 bit patterns
             self._loss_sum = torch.zeros(1, dtype=torch.float64, device=self.device)
@@ -163,6 +169,8 @@ class Evaluator:
         self._last_rows = rows
         if self.errors is not None:
             self.errors.update_ids(ids, lengths, encoded)
+        if self.audit is not None:
+            self.audit.update_ids(images, labels, ids, lengths, rows[:, 3])
 
     def _eval_step_with_errors(self, images: Tensor, labels: Sequence[str]) -> BatchResult:
         """`eval_step` (system.py) with the ids kept for the error analysis: the same forward, the same sums in the same order."""
@@ -742,3 +750,128 @@ class ErrorAnalysis:
     def reduce(self, process_group=None) -> ErrorReport:
         """`result()` summed over the ranks of `process_group`."""
         return reduce_report(self.result(), process_group)
+
+
+# -------------------------------------------------------------------------------------------------------------------
+# label audit (DESIGN.md section 30)
+# -------------------------------------------------------------------------------------------------------------------
+@dataclass
+class AuditReport:
+    """What a `LabelAudit` has seen, on the host.  Per sample, in the order of the updates: the label, the raw reading (the training
+    charset's characters, before the test-charset adapter), whether the adapted reading differs from the label, and — where it does and
+    both strings can be scored — the two log-probabilities; `suspicion` = score(reading) - score(label), NaN elsewhere.  `unscorable`:
+    mismatching samples whose label the training charset cannot spell (or whose reading has no <eos>)."""
+    labels: List[str]
+    readings: List[str]
+    mismatch: np.ndarray           # bool [S]
+    label_scores: np.ndarray       # float32 [S]
+    reading_scores: np.ndarray     # float32 [S]
+    suspicion: np.ndarray          # float32 [S], NaN where nothing was compared
+    unscorable: int
+
+    def top(self, k: int) -> List[dict]:
+        """The `k` most suspicious samples: suspicion descending, then the sample index."""
+        idx = [i for i in range(len(self.labels)) if not np.isnan(self.suspicion[i])]
+        idx.sort(key=lambda i: (-float(self.suspicion[i]), i))
+        return [dict(index=i, label=self.labels[i], reading=self.readings[i], label_score=float(self.label_scores[i]),
+                     reading_score=float(self.reading_scores[i]), suspicion=float(self.suspicion[i])) for i in idx[:max(int(k), 0)]]
+
+
+class LabelAudit:
+    """Which labels does the model disagree with most?  Beside an `Evaluator`:
+
+        audit = LabelAudit(model)                      # orders / combine / normalize as `PARSeq.score` takes them
+        ev = Evaluator(model, audit=audit)
+        for images, labels in loader:
+            ev.update(images, labels)                  # the metrics, then ONE `score` call with N = 2 (label, raw reading): enqueues only
+        report = audit.result()                        # AuditReport: the one copy
+        report.top(20)
+
+    The score call covers the whole batch — which samples mismatch is known on the device only, and asking would be a host
+    synchronisation — and the suspicion of a sample whose adapted reading equals its label is masked to NaN there.  The candidates are
+    L = max_label_length + 1 wide whatever the batch holds, so one mask upload serves every update."""
+
+    def __init__(self, system, orders='forward', combine: str = 'mix', normalize: bool = False, seed: Optional[int] = None) -> None:
+        from . import score as _score
+        self.system = system
+        self._flags = _score.score_flags(combine, normalize)
+        self._T = system.model.max_label_length
+        self.perms = _score.parse_orders(orders, self._T, system, seed)
+        self._masks = None
+        self.reset()
+
+    def reset(self) -> None:
+        self._labels: List[str] = []
+        self._parts = []           # per update: (label score, reading score, mismatch & scorable, mismatch, reading ids, reading lengths)
+
+    def label_rows(self, labels: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+        """(int32 [B, L] candidate rows of the labels — an absent row for one the training charset cannot spell —, bool [B] scorable)."""
+        tok = self.system.tokenizer
+        L = self._T + 1
+        rows = np.full((len(labels), L), tok.pad_id, dtype=np.int32)
+        ok = np.zeros(len(labels), dtype=bool)
+        specials = (tok.BOS, tok.EOS, tok.PAD)
+        for b, y in enumerate(labels):
+            if len(y) <= self._T and all(ch in tok._stoi and ch not in specials for ch in y):
+                rows[b, :len(y)] = [tok._stoi[ch] for ch in y]
+                rows[b, len(y)] = tok.eos_id
+                ok[b] = True
+        return rows, ok
+
+    def reading_rows(self, ids: Tensor, lengths: Tensor) -> Tensor:
+        """The greedy readings (`ids` int32 [B, P], `lengths` int32 [B]: the index of the first <eos>, P without one) as candidate rows
+        int32 [B, L], with torch operations on whatever device holds them.  A reading without <eos> gives a row without one: invalid."""
+        tok = self.system.tokenizer
+        B, P = ids.shape
+        L = self._T + 1
+        pos = torch.arange(L, device=ids.device).unsqueeze(0)
+        n = lengths.to(torch.int64).clamp(0, P).unsqueeze(1)
+        body = torch.full((B, L), tok.pad_id, dtype=torch.int32, device=ids.device)
+        body[:, :min(P, L)] = ids[:, :L].to(torch.int32)
+        eos = torch.full_like(body, tok.eos_id)
+        pad = torch.full_like(body, tok.pad_id)
+        return torch.where(pos < n, body, torch.where(pos == n, eos, pad))
+
+    def add_scores(self, labels: Sequence[str], scores: Tensor, valid: Tensor, mismatch: Tensor, reading_ids: Tensor,
+                   reading_lengths: Tensor) -> None:
+        """The bookkeeping of one batch, no copy: `scores` fp32 [B, 2] and `valid` [B, 2] of the (label, reading) candidates, `mismatch` [B]
+        (the adapted reading differs from the label), on any one device."""
+        self._labels += list(labels)
+        both = (valid[:, 0] != 0) & (valid[:, 1] != 0)
+        mismatch = mismatch.to(torch.bool)
+        self._parts.append((scores[:, 0].float(), scores[:, 1].float(), mismatch & both, mismatch, reading_ids.to(torch.int32), reading_lengths.to(torch.int32)))
+
+    @torch.inference_mode()
+    def update_ids(self, images: Tensor, labels: Sequence[str], ids: Tensor, lengths: Tensor, exact: Tensor) -> None:
+        """`ids`, `lengths`: what the metrics kernel (or `parseq_postprocess`) wrote for `images`; `exact` [B]: non-zero where the adapted
+        reading equals the label.  One `score` call on (label, raw reading) per sample."""
+        from . import score as _score
+        dev = images.device
+        if self._masks is None or self._masks.device != dev:
+            self._masks = _score.query_masks(self.perms).to(dev)
+        rows, _ = self.label_rows(labels)
+        cand = torch.stack([torch.from_numpy(rows).pin_memory().to(dev, non_blocking=True), self.reading_rows(ids, lengths)], dim=1).contiguous()
+        scores, _, _, _, _, valid = self.system.model.score(self.system.tokenizer, images, cand, self._masks, self._flags, char_logprobs=False)
+        self.add_scores(labels, scores, valid, exact == 0, ids, lengths)
+
+    def result(self) -> AuditReport:
+        """Everything so far: one copy."""
+        tok = self.system.tokenizer
+        if not self._parts:
+            return AuditReport([], [], np.zeros(0, bool), np.zeros(0, np.float32), np.zeros(0, np.float32), np.zeros(0, np.float32), 0)
+        width = max(p[4].shape[1] for p in self._parts)
+        packed = torch.cat([torch.cat([p[0].view(-1, 1).contiguous().view(torch.int32), p[1].view(-1, 1).contiguous().view(torch.int32),
+                                       p[2].view(-1, 1).to(torch.int32), p[3].view(-1, 1).to(torch.int32), p[5].view(-1, 1),
+                                       torch.nn.functional.pad(p[4], (0, width - p[4].shape[1]), value=tok.pad_id)], dim=1) for p in self._parts]).cpu()
+        label_scores = packed[:, 0].contiguous().view(torch.float32).numpy()
+        reading_scores = packed[:, 1].contiguous().view(torch.float32).numpy()
+        compared, mismatch = packed[:, 2].numpy().astype(bool), packed[:, 3].numpy().astype(bool)
+        lengths, ids = packed[:, 4].tolist(), packed[:, 5:].numpy()
+        classes = len(tok) - 2
+        readings = [tok._ids2tok([int(i) for i in row[:min(max(k, 0), width)] if 0 <= i < classes and i != tok.eos_id]) for row, k in zip(ids, lengths)]
+        with np.errstate(invalid='ignore'):
+            suspicion = np.where(compared, reading_scores - label_scores, np.float32('nan')).astype(np.float32)
+        return AuditReport(list(self._labels), readings, mismatch, label_scores, reading_scores, suspicion, int((mismatch & ~compared).sum()))
+
+    def top(self, k: int) -> List[dict]:
+        return self.result().top(k)

@@ -967,6 +967,35 @@ class PARSeq(_NativeBacked):
                                                   _native.ptr(res.images), _native.ptr(ws), ws.numel(), _native.stream_ptr(self._device)))
         return res
 
+    def score(self, tokenizer: Tokenizer, images: Tensor, candidates: Tensor, masks: Tensor, flags: int = 0, char_logprobs: bool = True):
+        """The joint log-probability of given readings: `candidates` int32 [B, N, L] rows `c_0 .. c_{n-1}, <eos>,
+        <pad> ..` (a first <pad>: absent) and `masks` uint8 [K, L, L], the query mask of every decoding order, both on the device.  One
+        library call on a plan of B * N rows — encode once, K teacher-forced decoder passes, the combination and the rank — no host
+        synchronisation.  Returns (scores [B, N], order_scores [B, N, K], char_logprobs [B, N, K, L] or None, rank, lengths, valid)."""
+        self._check_localizable('score')
+        images = self._check_images(images)
+        B, dev = images.shape[0], images.device
+        if candidates.dtype != torch.int32 or candidates.ndim != 3 or candidates.shape[0] != B or not candidates.is_cuda:
+            raise ValueError(f'score: candidates must be device int32 [B = {B}, N, L], got {candidates.dtype} {tuple(candidates.shape)}')
+        N, L = candidates.shape[1], candidates.shape[2]
+        if masks.dtype != torch.uint8 or masks.ndim != 3 or tuple(masks.shape[1:]) != (L, L) or not masks.is_cuda:
+            raise ValueError(f'score: masks must be device uint8 [K, {L}, {L}], got {masks.dtype} {tuple(masks.shape)}')
+        K = masks.shape[0]
+        if not 1 <= N <= _native.SCORE_MAX_CANDIDATES or not 1 <= K <= _native.SCORE_MAX_ORDERS:
+            raise ValueError(f'score: N = {N} candidates (1 .. {_native.SCORE_MAX_CANDIDATES}), K = {K} orders (1 .. {_native.SCORE_MAX_ORDERS})')
+        candidates, masks = candidates.contiguous(), masks.contiguous()
+        plan = self._plan(B * N)
+        self._memory_replaced()
+        self._check_tokenizer(tokenizer)
+        out = (torch.empty(B, N, dtype=torch.float32, device=dev), torch.empty(B, N, K, dtype=torch.float32, device=dev),
+               torch.empty(B, N, K, L, dtype=torch.float32, device=dev) if char_logprobs else None, torch.empty(B, N, dtype=torch.int32, device=dev),
+               torch.empty(B, N, dtype=torch.int32, device=dev), torch.empty(B, N, dtype=torch.uint8, device=dev))
+        lib = _native.lib()
+        ws = self._workspace(lib.parseq_score_workspace_bytes, plan, B, N, L, K)
+        _native.check(lib.parseq_score(plan, _native.ptr(images), _native.dtype_code(images.dtype), B, _native.ptr(candidates), N, L, _native.ptr(masks), K,
+                                       int(flags), *[_native.ptr(t) for t in out], _native.ptr(ws), ws.numel(), _native.stream_ptr(self._device)))
+        return out
+
     def _check_localizable(self, what: str) -> None:
         if self._cfg['dec_depth'] != 1:
             raise ValueError(f"{what} needs dec_depth == 1, this model has dec_depth = {self._cfg['dec_depth']}")

@@ -3,7 +3,9 @@
 `lexicon_match` / `BeamEvaluator` they turn into.  One set of composition and refusal rules for every command line: a contradiction ends
 in `parser.error`.  The resolvers read `args.nbest` and `args.boxes` too; a command line without those flags sets them (test.py: the
 N-best is the whole beam, no boxes).  --auto-rotate / --upright-bias have their rules at the end of the module: they
-choose the crops every other flag then works on, so they compose with all of them but --polygons."""
+choose the crops every other flag then works on, so they compose with all of them but --polygons.  --candidates / --expect of read.py and
+--audit of test.py score given strings instead of searching for one: they refuse every search flag."""
+from argparse import SUPPRESS
 from collections import namedtuple
 
 LEXICON_BEAM = 8      # --beam under --lexicon when none is given
@@ -255,6 +257,115 @@ def resolve_lines(parser, args):
     if not (math.isfinite(sep) and sep >= 0.0):
         parser.error('--line-sep must be finite and at least 0')
     return overlap, sep
+
+
+# ---- --candidates / --expect / --audit ----------------------------------------------------------------------------
+AUDIT_TOP = 20
+
+
+def parse_orders_flag(text):
+    """--orders: 'forward', 'mirrored', 'both', or a number K of orderings drawn as training draws them."""
+    if text in ('forward', 'mirrored', 'both'):
+        return text
+    try:
+        k = int(text)
+    except ValueError:
+        raise ValueError(f"--orders must be forward, mirrored, both or a number, got {text!r}") from None
+    if not 1 <= k <= 16:
+        raise ValueError('--orders K must be in [1, 16]')
+    return k
+
+
+def _absent_flags(args, **defaults):
+    """The flags of this section stay out of the parsed namespace unless they are given (`argparse.SUPPRESS`): a command line without them
+    parses to exactly what it parsed to before.  The resolvers fill in what is absent."""
+    for name, value in defaults.items():
+        if not hasattr(args, name):
+            setattr(args, name, value)
+
+
+def add_score_flags(parser):
+    """--candidates FILE / --expect STRING .. [--orders O] [--length-norm] of read.py."""
+    parser.add_argument('--candidates', default=SUPPRESS, metavar='FILE',
+                        help='Score given readings instead of reading: one line per image (or region), its candidates separated by tabs (at most 16); '
+                             'prints them best first with their log-probabilities')
+    parser.add_argument('--expect', nargs='+', default=SUPPRESS, metavar='STRING',
+                        help='One expected string per image (or region): prints the free reading, then the log-probabilities of the expected string and of the reading')
+    add_order_flags(parser)
+
+
+def add_order_flags(parser):
+    parser.add_argument('--orders', default=SUPPRESS, metavar='O',
+                        help="With --candidates / --expect / --audit: the decoding orders a string is scored under — forward (default), mirrored, both, or a number K "
+                             'of orderings drawn as training draws them; the score is the log of their mixture')
+    parser.add_argument('--length-norm', action='store_true', default=SUPPRESS, dest='length_norm', help='With --candidates / --expect / --audit: rank by score / (length + 1)')
+
+
+def resolve_orders(parser, args, needs):
+    """(orders, normalize) of --orders / --length-norm; `needs`: whether a flag that uses them was given, and how the message names it."""
+    on, what = needs
+    _absent_flags(args, orders=None, length_norm=False)
+    if not on:
+        if args.orders is not None or args.length_norm:
+            parser.error(f'--orders and --length-norm need {what}')
+        return None
+    try:
+        return ('forward' if args.orders is None else parse_orders_flag(args.orders)), bool(args.length_norm)
+    except ValueError as e:
+        parser.error(str(e))
+
+
+ScoreFlags = namedtuple('ScoreFlags', 'candidates expect orders normalize')
+
+
+def resolve_score(parser, args):
+    """ScoreFlags of --candidates / --expect, None without them; a contradiction ends in parser.error.  Scoring replaces the reading: it
+    composes with --regions (and --polygons) only."""
+    _absent_flags(args, candidates=None, expect=None)
+    on = args.candidates is not None or args.expect is not None
+    picked = resolve_orders(parser, args, (on, '--candidates FILE or --expect STRING'))
+    if not on:
+        return None
+    if args.candidates is not None and args.expect is not None:
+        parser.error('--expect is the one-candidate form of --candidates: give one of them')
+    if search_requested(args) or args.nbest > 0:
+        parser.error('--candidates / --expect score given strings: not with --nbest, --beam, --lexicon, --match, --priors, --lm, --pattern or --refine-beams')
+    if args.auto_rotate is not None or args.upright_bias is not None:
+        parser.error('--candidates / --expect score the crop as it is: not with --auto-rotate')
+    if args.lines or args.line_overlap is not None or args.line_sep is not None:
+        parser.error('--candidates / --expect score one crop against one string: not with --lines')
+    if args.boxes:
+        parser.error('--candidates / --expect do not localise: not with --boxes')
+    return ScoreFlags(args.candidates, args.expect, *picked)
+
+
+def load_candidates(path):
+    """The candidate lists of a --candidates file: one line per crop, the strings separated by tabs (an empty line: one empty string)."""
+    with open(path, encoding='utf-8') as fh:
+        return [line.rstrip('\r\n').split('\t') for line in fh]
+
+
+def add_audit_flag(parser):
+    """--audit [K] [--orders O] [--length-norm] of test.py."""
+    parser.add_argument('--audit', type=int, nargs='?', const=AUDIT_TOP, default=SUPPRESS, metavar='K',
+                        help=f'After the table: per dataset the K (default {AUDIT_TOP}) samples whose reading the model prefers most over their label, with both '
+                             'log-probabilities; everything goes to <checkpoint>.audit.json')
+    add_order_flags(parser)
+
+
+def resolve_audit(parser, args, flags):
+    """(K, orders, normalize) of --audit, None without it; `flags`: the resolved search flags.  A contradiction ends in parser.error."""
+    _absent_flags(args, audit=None)
+    picked = resolve_orders(parser, args, (args.audit is not None, '--audit'))
+    if args.audit is None:
+        return None
+    if args.audit < 1:
+        parser.error('--audit K must be at least 1')
+    if flags is not None:
+        parser.error('--audit scores the greedy reading against the label: not with a search flag')
+    if args.auto_rotate is not None or args.upright_bias is not None:
+        parser.error('--audit scores the crop as it is: not with --auto-rotate')
+    return (args.audit,) + picked
 
 
 def orientation_prior(bias: float, views: int):

@@ -298,6 +298,24 @@ class PARSeq(nn.Module):
         `self.tokenizer.decode_lines(result)` turns it into strings.  Calls hold at most `max_batch` windows; a line never splits."""
         return self.model.read_lines(self.tokenizer, images, overlap=overlap, aspect=aspect, min_sep=min_sep, max_chars=max_chars, max_batch=max_batch)
 
+    def score(self, images: Tensor, candidates, orders='forward', combine: str = 'mix', normalize: bool = False, seed: Optional[int] = None):
+        """How likely is THIS string for this crop?  `candidates`: one list of strings per crop (ragged lists are
+        filled with absent rows; at most 16 per crop).  Every candidate gets its exact joint log-probability, <eos> included, under each
+        decoding order: `orders` = 'forward', 'mirrored', 'both', an int K (the first K orderings `gen_tgt_perms` draws for the longest
+        candidate, from `np.random.default_rng(seed)`) or a [K, T + 2] tensor of orderings.  `combine`: 'mix', the log of the orders'
+        mixture (a probability), or 'mean', the mean of the logs; `normalize` ranks by score / (length + 1).  A character outside the
+        training charset raises ValueError before any device work.  One library call, no host synchronisation: a `ScoreResult` on the
+        device; `self.tokenizer.decode_scores(result, candidates)` gives the ranked strings."""
+        from . import score as _score
+        flags = _score.score_flags(combine, normalize)
+        rows, T = _score.encode_candidates(self.tokenizer, candidates, self.model.max_label_length)
+        if len(rows) != len(images):
+            raise ValueError(f'score: {len(rows)} candidate lists for {len(images)} crops')
+        perms = _score.parse_orders(orders, T, self, seed)
+        dev = images.device
+        out = self.model.score(self.tokenizer, images, torch.from_numpy(rows).to(dev), _score.query_masks(perms).to(dev), flags)
+        return _score.ScoreResult(*out, perms=perms)
+
     # ---- evaluation glue used by the reference's test.py:121-126 ------------------------------------------------
     def _eval_step(self, batch, validation: bool):
         return eval_step(self, batch, validation)

@@ -179,6 +179,13 @@ class Tokenizer(BaseTokenizer):
         labels = [self._ids2tok(row[:k].tolist()) for row, k in zip(ids, lengths)]
         return labels, [[(ch, tuple(boxes[i][j])) for j, ch in enumerate(label)] for i, label in enumerate(labels)]
 
+    def decode_scores(self, result, candidates):
+        """A `ScoreResult` with the strings that were scored: per crop the candidates best first, each (string,
+        score, per-character log-probabilities [K][n + 1] — one list per decoding order, its last entry the <eos>'s).  Absent and invalid
+        rows are left out.  One copy to the host."""
+        from .score import decode_scores
+        return decode_scores(result, candidates)
+
     def decode_lines(self, result, boxes: bool = False):
         """A `LineResult` as strings: (labels, confidences), and with `boxes` a third list — per line the
         (character, (x0, y0, x1, y1)) of every character in reading order, in pixels of the line's own image.  A line that holds more

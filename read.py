@@ -15,6 +15,8 @@
     ./read.py pretrained=parseq --images scene.jpg --polygons scene.txt [--boxes]     read every polygon of the file (x1,y1,..,xK,yK per line): curved text
     ./read.py pretrained=parseq --images a.png --auto-rotate flip [--upright-bias 0.1]     read every crop upright and upside down, keep the better reading
     ./read.py pretrained=parseq --images line.png --lines [--line-overlap 0.25] [--line-sep 0.25] [--boxes]     read a whole text line as stitched windows
+    ./read.py pretrained=parseq --images a.png b.png --candidates cands.txt [--orders both] [--length-norm]     score the tab-separated strings of line i for image i, best first
+    ./read.py pretrained=parseq --images a.png --expect AB1234     how likely is this string for the crop, and how likely is what the model reads instead
 
 Differences from the reference, all on the device side of the same results: the files are decoded on the host (PIL),
 everything after that — the bicubic resize of the reference transform (bit-exact with Pillow), ToTensor + Normalize, the
@@ -28,8 +30,9 @@ from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.preprocess import resize_batch, rotated_size, unrotate_points
-from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, add_line_flags, add_orientation_flags, build_automaton, load_word_counts, load_word_list,  # noqa: F401
-                                      orientation_prior, resolve_lines, resolve_automaton, resolve_flags, resolve_match, resolve_orientation, resolve_refine, resolve_search)
+from parseq_amd.search_flags import (LEXICON_BEAM, LM_ORDER, MATCH_N, add_line_flags, add_orientation_flags, add_score_flags, build_automaton, load_candidates,  # noqa: F401
+                                      load_word_counts, load_word_list, orientation_prior, resolve_lines, resolve_automaton, resolve_flags, resolve_match,
+                                      resolve_orientation, resolve_refine, resolve_score, resolve_search)
 
 
 def turned_name(name, angle):
@@ -351,6 +354,48 @@ def read_lines_lines(model, files, lines, region_files=None, boxes=False, device
     return out
 
 
+@torch.inference_mode()
+def score_lines(model, names, batch, score):
+    """The lines --candidates / --expect print for the crops of `batch`, named `names`; `score` is the ScoreFlags of
+    `resolve_score`.  --candidates: per crop its best candidate where the reading goes, then every candidate best first with its
+    log-probability.  --expect: per crop the free reading, then the log-probability of the expected string and of the reading, one
+    `score` call on the pair.  A list that does not hold one entry per crop, or a character outside the training charset, is a ValueError."""
+    if score.expect is not None:
+        if len(score.expect) != len(names):
+            raise ValueError(f'--expect takes one string per crop: {len(score.expect)} strings for {len(names)} crops')
+        readings, _ = model.tokenizer.read(model(batch))
+        limit = model.model.max_label_length
+        pairs = [[want] + ([got] if len(got) <= limit else []) for want, got in zip(score.expect, readings)]
+        scores = model.score(batch, pairs, orders=score.orders, normalize=score.normalize).scores.cpu().tolist()
+        lines = []
+        for name, pair, row in zip(names, pairs, scores):
+            lines.append(f'{name}: {pair[1] if len(pair) > 1 else ""}')
+            lines.append(f'    {row[0]:9.4f}  expected  {pair[0]}')
+            lines += [f'    {row[1]:9.4f}  read      {pair[1]}'] if len(pair) > 1 else []
+        return lines
+    candidates = load_candidates(score.candidates)
+    if len(candidates) != len(names):
+        raise ValueError(f'{score.candidates}: one line of candidates per crop: {len(candidates)} lines for {len(names)} crops')
+    ranked = model.tokenizer.decode_scores(model.score(batch, candidates, orders=score.orders, normalize=score.normalize), candidates)
+    lines = []
+    for name, alts in zip(names, ranked):
+        lines.append(f'{name}: {alts[0][0] if alts else ""}')
+        lines += [f'    {logp:9.4f}  {label}' for label, logp, _ in alts]
+    return lines
+
+
+@torch.inference_mode()
+def score_files(model, files, score, region_files=None, polygons=False, device='cuda'):
+    """`score_lines` for image files, or with `region_files` for every region of every file (`load_region_batch`)."""
+    import numpy as np
+    if region_files is not None:
+        names, batch, _ = load_region_batch(model, files, region_files, device, polygons)
+    else:
+        crops = [torch.from_numpy(np.asarray(Image.open(f).convert('RGB')).copy()).to(device) for f in files]
+        names, batch = list(files), (resize_batch(crops, tuple(model.hparams.img_size)) if crops else None)
+    return score_lines(model, names, batch, score) if names else []
+
+
 def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('checkpoint', help="Model checkpoint (or 'pretrained=<model_id>')")
@@ -393,6 +438,7 @@ def build_parser():
     parser.add_argument('--refine-iters', type=int, default=None, dest='refine_iters', metavar='K', help='Iterations of --refine-beams edit (default 1)')
     add_orientation_flags(parser)      # --auto-rotate MODE [--upright-bias X]: a crop read turned is printed as file@angle
     add_line_flags(parser)             # --lines [--line-overlap F] [--line-sep F]: every image is a whole text line
+    add_score_flags(parser)            # --candidates FILE / --expect STRING .. [--orders O] [--length-norm]: score given strings
     return parser
 
 
@@ -404,6 +450,7 @@ def main(argv=None):
 
     if args.boxes and (args.nbest > 0 or args.lexicon is not None):
         parser.error('--boxes goes with the default reading only: not with --nbest or --lexicon')
+    score = resolve_score(parser, args)
     lines = resolve_lines(parser, args)
     kind, alpha, beta, match, beam, nbest, refine, refine_iters = resolve_flags(parser, args)
     files = args.images or []
@@ -414,7 +461,16 @@ def main(argv=None):
     region_files = args.polygons if polygons else args.regions
     if region_files is not None and len(region_files) != len(files):
         parser.error(f'--{"polygons" if polygons else "regions"} takes one file per image, in order: {len(region_files)} files for {len(files)} images')
+    if score is not None and score.expect is not None and region_files is None and len(score.expect) != len(files):
+        parser.error(f'--expect takes one string per image, in order: {len(score.expect)} strings for {len(files)} images')
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
+    if score is not None:
+        try:
+            for line in score_files(model, files, score, region_files, polygons, args.device):
+                print(line)
+        except ValueError as e:
+            raise SystemExit(f'read.py: {e}') from None
+        return
     if lines is not None:
         for line in read_lines_lines(model, files, lines, region_files, args.boxes, args.device):
             print(line)

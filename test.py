@@ -9,6 +9,7 @@
     ./test.py pretrained=parseq --data_root data --lm corpus.txt [--lm-order 3] [--lm-weight 0.3] [--char-bonus 0.5]     or --pattern REGEX
     ./test.py pretrained=parseq --data_root data --rotation 180 --auto-rotate flip [--upright-bias 0.1]     read every crop in several quarter turns, score the best
     ./test.py pretrained=parseq --data_root data --analyse [K]     after the table: which characters are confused, dropped or made up, and at which label lengths
+    ./test.py pretrained=parseq --data_root data --audit [K] [--orders both] [--length-norm]     after the table: the K labels the model disagrees with most
 
 A dataset is a sub-directory of `--data_root` that holds a `gt.txt`: one sample per line, the image path (relative to that
 sub-directory) and the label separated by the first run of whitespace — the input format of the reference's
@@ -37,6 +38,12 @@ readings and labels are made on the device beside the metrics.  After the table 
 operation totals, the accuracy by label length and the K most frequent confusions, deletions and insertions are printed per dataset and for
 all datasets together, and every table is written to `<checkpoint>.errors.json`.  It composes with --cased, --punctuation, --rotation and
 --auto-rotate; the analysis of an N-best is out of scope, so with a search flag it is refused.
+
+With `--audit [K]` (K = 20 by default) every dataset's `Evaluator` carries a `LabelAudit`: label and raw reading of every
+sample are scored by the model (`parseq_score`, two candidates per crop) beside the metrics.  After the table — which, like the log, is what
+it is without the flag — the K samples whose reading the model prefers most over their label are printed per dataset: path, label, reading,
+both log-probabilities; only samples whose adapted reading differs from the label are listed.  Everything goes to `<checkpoint>.audit.json`.
+It is refused next to a search flag and --auto-rotate.
 """
 import argparse
 import json
@@ -52,10 +59,10 @@ from PIL import Image
 
 from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.data import parse_gt_line, preprocess_label, read_gt  # noqa: F401  (the first two keep their names here)
-from parseq_amd.evaluate import BeamEvaluator, ErrorAnalysis, ErrorReport, Evaluator
+from parseq_amd.evaluate import BeamEvaluator, ErrorAnalysis, ErrorReport, Evaluator, LabelAudit
 from parseq_amd.preprocess import orientation_views, resize_batch
-from parseq_amd.search_flags import (add_evaluation_flags, add_orientation_flags, evaluation_width, evaluator_arguments, orientation_prior, resolve_evaluation_flags,
-                                      resolve_orientation)
+from parseq_amd.search_flags import (add_audit_flag, add_evaluation_flags, add_orientation_flags, evaluation_width, evaluator_arguments, orientation_prior,
+                                      resolve_audit, resolve_evaluation_flags, resolve_orientation)
 from parseq_amd.tokenizer import CharsetAdapter  # noqa: F401
 
 
@@ -114,17 +121,22 @@ class UprightReader:
 
 
 def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotation: int = 0, search: Optional[dict] = None, width: int = 0,
-                     orient=None, reports: Optional[dict] = None) -> Result:
+                     orient=None, reports: Optional[dict] = None, audit=None, audits: Optional[dict] = None) -> Result:
     """One dataset's row.  `search`: the keywords of `BeamEvaluator` (a beam search or a lexicon match instead of the greedy decode); the row is
     then a `BeamTableResult` whose Hit column counts the first `width` hypotheses per image (`search_flags.evaluation_width`).  `orient`: the
     (mode, bias) of --auto-rotate: every crop — turned by `rotation` first — is read in the views of that mode, the best view is what the
     evaluator scores, and the share of crops read turned is printed under the dataset's name.  `reports`: a dict that receives this dataset's
-    `ErrorReport` under `name` (--analyse; greedy evaluation only)."""
+    `ErrorReport` under `name` (--analyse; greedy evaluation only).  `audit`: the (K, orders, normalize) of --audit; `audits` then receives
+    (image files, `AuditReport`) under `name`."""
     hp = model.hparams
     samples = read_dataset(root, name, hp.charset_test, hp.max_label_length)
     system = model if orient is None else UprightReader(model, orient[1])
     errors = ErrorAnalysis(model) if reports is not None and search is None else None
-    evaluator = Evaluator(system, errors=errors) if search is None else BeamEvaluator(model, **search)
+    label_audit = LabelAudit(model, orders=audit[1], normalize=audit[2]) if audit is not None and search is None else None
+    if search is not None:
+        evaluator = BeamEvaluator(model, **search)
+    else:
+        evaluator = Evaluator(system, errors=errors) if label_audit is None else Evaluator(system, errors=errors, audit=label_audit)
     for at in range(0, len(samples), batch_size):
         chunk = samples[at:at + batch_size]
         crops = load_crops([f for f, _ in chunk], model.device)
@@ -137,6 +149,8 @@ def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotatio
     r = evaluator.result()
     if errors is not None:
         reports[name] = errors.result()
+    if label_audit is not None:
+        audits[name] = ([f for f, _ in samples], label_audit.result())
     if orient is not None:
         turned = int(system.turned)
         print(f'{name}: {turned} of {len(samples)} crops read turned ({100 * turned / max(len(samples), 1):.2f} %)')
@@ -223,6 +237,17 @@ def resolve_analysis(parser, args, flags) -> Optional[int]:
     return args.analyse
 
 
+def print_audit(name: str, files: List[str], report, top: int, file=None) -> List[dict]:
+    """What --audit prints for one dataset: how many readings differ from their label, then the `top` most suspicious of them — the image,
+    the label and its log-probability, the reading and its log-probability.  Returns those rows, the image path added."""
+    rows = [dict(r, path=files[r['index']]) for r in report.top(top)]
+    print(f'\n{name}: {int(report.mismatch.sum())} of {len(report.labels)} readings differ from their label, {report.unscorable} of them cannot be scored; '
+          f'the {len(rows)} most suspicious labels:', file=file)
+    for r in rows:
+        print(f"    {r['suspicion']:9.4f}  {r['path']}  label {r['label']!r} {r['label_score']:.4f}  read {r['reading']!r} {r['reading_score']:.4f}", file=file)
+    return rows
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser()
     parser.add_argument('checkpoint', help="Model checkpoint (or 'pretrained=<model_id>')")
@@ -235,6 +260,7 @@ def build_parser() -> argparse.ArgumentParser:
     add_evaluation_flags(parser)
     add_orientation_flags(parser)
     add_analysis_flag(parser)
+    add_audit_flag(parser)
     return parser
 
 
@@ -249,6 +275,8 @@ def main(argv=None) -> List[Result]:
         parser.error('--auto-rotate scores the greedy reading of the chosen view: not with a search flag')
     top = resolve_analysis(parser, args, flags)
     reports = {} if top is not None else None
+    audit = resolve_audit(parser, args, flags)
+    audits = {} if audit is not None else None
 
     charset_test = string.digits + string.ascii_lowercase
     if args.cased:
@@ -261,7 +289,7 @@ def main(argv=None) -> List[Result]:
     model = load_from_checkpoint(args.checkpoint, **kwargs).eval().to(args.device)
     search = evaluator_arguments(model, args, flags) if flags is not None else None
     width = evaluation_width(flags) if flags is not None else 0
-    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width, orient, reports) for name in find_datasets(args.data_root)]
+    results = [evaluate_dataset(model, args.data_root, name, args.batch_size, args.rotation, search, width, orient, reports, audit, audits) for name in find_datasets(args.data_root)]
     if not results:
         raise SystemExit(f'no dataset (a sub-directory with a gt.txt) under {args.data_root!r}')
     with open(args.checkpoint + '.log.txt', 'w') as log:
@@ -278,6 +306,12 @@ def main(argv=None) -> List[Result]:
         print_error_report('All datasets', combined, top)
         with open(args.checkpoint + '.errors.json', 'w', encoding='utf-8') as f:
             json.dump({'top': top, 'datasets': {name: report.to_dict() for name, report in reports.items()}, 'combined': combined.to_dict()}, f, ensure_ascii=False)
+    if audits is not None:
+        listed = {name: print_audit(name, files, report, audit[0]) for name, (files, report) in audits.items()}
+        with open(args.checkpoint + '.audit.json', 'w', encoding='utf-8') as f:
+            json.dump({'top': audit[0], 'orders': audit[1], 'length_norm': audit[2],
+                       'datasets': {name: {'samples': len(report.labels), 'mismatches': int(report.mismatch.sum()), 'unscorable': report.unscorable, 'top': listed[name]}
+                                    for name, (_, report) in audits.items()}}, f, ensure_ascii=False)
     return results
 
 
