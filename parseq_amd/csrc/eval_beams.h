@@ -1,9 +1,9 @@
 // Evaluation of an N-best on the device: the reference's metrics (strhub/models/base.py:132-143) for the first live
 // hypothesis of every image, plus what only a search has — at which rank the truth stands, and how near the nearest hypothesis comes —
 // for any BeamResult (beam.h, lexicon_match.h), without moving a string to the host.  Two launches, no atomics:
-//   eval_beam_rows_kernel    one wave per hypothesis (row b * W + w), the adapter and the distance of eval_metrics.h;
-//   eval_beam_images_kernel  ONE workgroup: thread t folds the W rows of images t, t + 256, ... and sums them in that order, then one
-//                            fixed tree over all totals adds the batch to the accumulator.
+//   eval_beam_rows_kernel    one wave per hypothesis (row b * W + w): eval_row_front and eval_wave_distance of eval_metrics.h;
+//   eval_beam_images_kernel  ONE workgroup: thread t folds the W rows of images t, t + 256, ... and eval_fold (eval_metrics.h) sums
+//                            them in that order, then over its fixed tree, into the accumulator.
 #pragma once
 
 #include "eval_metrics.h"
@@ -34,9 +34,9 @@ void eval_beam_rows_kernel(const int* __restrict__ tokens, const float* __restri
     const int r = blockIdx.x * 4 + wv;
     const bool active = r < rows_total;                      // wave-uniform: a wave past the rows only keeps the barrier company
     const bool live = active && eval_beam_live(scores[r]);   // wave-uniform too: a dead slot adapts nothing and writes the sentinel
-    const int plen = live ? min(max(lengths[r], 0), min(T, EVAL_MAX_PRED)) : 0;
-    int pc;
-    const int m = eval_adapt_row(tokens + (size_t)(active ? r : 0) * T, plen, C, table, spred[wv], lane, pc);
+    const int b = r / W;
+    const EvalRow row = eval_row_front(tokens + (size_t)(live ? r : 0) * T, live ? lengths[r] : 0, T, C, table, live ? gt_len[b] : 0, G, live,
+                                       spred[wv], lane);
     if (!active) return;
     if (!live) {
         if (lane == 0) {
@@ -46,13 +46,11 @@ void eval_beam_rows_kernel(const int* __restrict__ tokens, const float* __restri
         }
         return;
     }
-    const int b = r / W;
-    const int n = min(max(gt_len[b], 0), G);
-    const int dist = eval_row_distance(pc, m, gt + (size_t)b * G, n, lane);
+    const int dist = eval_wave_distance<false>(row.pc, row.m, gt + (size_t)b * G, row.n, lane);
     if (lane == 0) {
         int* o = rows + (size_t)r * 4;
-        o[0] = m; o[1] = n; o[2] = dist; o[3] = dist == 0;
-        hyp_ned[r] = (double)dist / (double)max(max(m, n), 1);
+        o[0] = row.m; o[1] = row.n; o[2] = dist; o[3] = dist == 0;
+        hyp_ned[r] = (double)dist / (double)max(max(row.m, row.n), 1);
     }
 }
 
@@ -62,15 +60,11 @@ static __global__ __launch_bounds__(256)
 void eval_beam_images_kernel(const int* __restrict__ rows, const double* __restrict__ hyp_ned, const float* __restrict__ scores,
                              const float* __restrict__ conf_scores, int B, int W, const int* __restrict__ gt_len, int G,
                              int* __restrict__ image_rows, double* __restrict__ img, BeamEvalAccum* __restrict__ acc) {
-    constexpr int NI = 6 + EVAL_MAX_BEAMS, ND = 3;
-    __shared__ long long si[NI][256];                        // 46 KiB + 6 KiB of LDS: the one workgroup has the compute unit to itself
-    __shared__ double sd[ND][256];
-    long long ti[NI];                                        // correct, label_length, top1_distance, oracle_distance, live, miss, first_hit[]
-    double td[ND] = {0.0, 0.0, 0.0};                         // ned, confidence, oracle_ned
-#pragma unroll
-    for (int k = 0; k < NI; ++k) ti[k] = 0;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        const int n = min(max(gt_len[b], 0), G);
+    long long ti[6 + EVAL_MAX_BEAMS];                        // correct, label_length, top1_distance, oracle_distance, live, miss, first_hit[]
+    double td[3];                                            // ned, confidence, oracle_ned
+    // eval_fold's LDS is 46 KiB + 6 KiB here: the one workgroup has the compute unit to itself
+    const bool first = eval_fold(B, ti, td, [&](int b) {
+        const int n = eval_label_length(gt_len[b], G);
         int top = -1, hit = EVAL_BEAM_NO_HIT, live = 0, odist = 0;
         double oned = 0.0;
         for (int w = 0; w < W; ++w) {
@@ -100,28 +94,13 @@ void eval_beam_images_kernel(const int* __restrict__ rows, const double* __restr
 #pragma unroll
         for (int k = 0; k < EVAL_MAX_BEAMS; ++k) ti[6 + k] += hit == k;
         td[0] += ned; td[1] += conf; td[2] += oned;
-    }
-    // the fixed tree of eval_reduce_kernel, all totals side by side: equal inputs, bit-identical sums
+    });
+    if (first) {
+        acc->num_samples += B; acc->correct += ti[0]; acc->label_length += ti[1]; acc->top1_distance += ti[2];
+        acc->oracle_correct += (long long)B - ti[5]; acc->oracle_distance += ti[3]; acc->live += ti[4]; acc->miss += ti[5];
 #pragma unroll
-    for (int k = 0; k < NI; ++k) si[k][threadIdx.x] = ti[k];
-#pragma unroll
-    for (int k = 0; k < ND; ++k) sd[k][threadIdx.x] = td[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-#pragma unroll
-            for (int k = 0; k < NI; ++k) si[k][threadIdx.x] += si[k][threadIdx.x + o];
-#pragma unroll
-            for (int k = 0; k < ND; ++k) sd[k][threadIdx.x] += sd[k][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        acc->num_samples += B; acc->correct += si[0][0]; acc->label_length += si[1][0]; acc->top1_distance += si[2][0];
-        acc->oracle_correct += (long long)B - si[5][0]; acc->oracle_distance += si[3][0]; acc->live += si[4][0]; acc->miss += si[5][0];
-#pragma unroll
-        for (int k = 0; k < EVAL_MAX_BEAMS; ++k) acc->first_hit[k] += si[6 + k][0];
-        acc->ned += sd[0][0]; acc->confidence += sd[1][0]; acc->oracle_ned += sd[2][0];
+        for (int k = 0; k < EVAL_MAX_BEAMS; ++k) acc->first_hit[k] += ti[6 + k];
+        acc->ned += td[0]; acc->confidence += td[1]; acc->oracle_ned += td[2];
     }
 }
 

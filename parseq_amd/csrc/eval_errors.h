@@ -1,7 +1,7 @@
 // Error analysis on the device: for every sample the canonical edit script between the adapted prediction and
 // the label, and integer tables of what went wrong — operation totals, accuracy by label length, errors by position, a confusion
-// matrix over the test charset's symbols.  The first step of a row is eval_adapt_row (eval_metrics.h), so the strings compared ARE
-// the ones eval_rows_kernel compares; the recurrence is eval_row_distance's with every column kept.
+// matrix over the test charset's symbols.  The front of a row is eval_row_front (eval_metrics.h), so the strings compared ARE the ones
+// eval_rows_kernel compares; the recurrence is the same call, eval_wave_distance, in its mode that keeps every column.
 #pragma once
 
 #include "eval_metrics.h"
@@ -40,7 +40,7 @@ static __device__ __forceinline__ void eval_add64(long long* p, long long v) {
 }
 
 // One wave per sample, four samples per workgroup; every wave of the workgroup takes every barrier (a wave past the batch idles between them).
-//   phase 1  adapter (eval_adapt_row), then Myers' recurrence over the label with the low 32 bits of every column's (Pv, Mv) kept in LDS
+//   phase 1  eval_row_front, then eval_wave_distance<true>: the label and the low 32 bits of every column's (Pv, Mv) kept in LDS
 //   phase 2  the trace back from (m, n): the first rule of {diagonal, up, left} that explains D[i][j], at most m + n wave-uniform steps
 //            on two stored columns each; the operations go to LDS in reverse order as code | prediction index << 2 | position << 8
 //   phase 3  lanes write the forward script (coalesced bytes) and add their operations to the tables: the confusion cell straight to
@@ -60,42 +60,12 @@ void eval_errors_kernel(const int* __restrict__ ids, const int* __restrict__ len
     const int b = blockIdx.x * 4 + w;
     const bool active = b < B;
     if (threadIdx.x < EVAL_ERR_HEAD + EVAL_LEN_BINS * 4) stab[threadIdx.x] = 0;
-    const int plen = active ? min(max(lengths[b], 0), min(L, EVAL_MAX_PRED)) : 0;
-    int pc;
-    const int m = eval_adapt_row(ids + (size_t)(active ? b : 0) * L, plen, C, table, spred[w], lane, pc);      // holds a barrier: stab is zero after it
-    const int n = active ? min(max(gt_len[b], 0), min(G, EVAL_MAX_GT)) : 0;
-    int dist = n;
+    const EvalRow r = eval_row_front(ids + (size_t)(active ? b : 0) * L, active ? lengths[b] : 0, L, C, table, active ? gt_len[b] : 0, G, active,
+                                     spred[w], lane);                          // holds a barrier: stab is zero after it
+    const int m = r.m, n = r.n;
 
-    // ---- phase 1: the recurrence, columns kept
-    if (active) {
-        const int* gt_row = gt + (size_t)b * G;
-        unsigned long long Pv = m > 0 ? (1ull << m) - 1ull : 0ull, Mv = 0ull;
-        const unsigned long long top = m > 0 ? 1ull << (m - 1) : 0ull;
-        if (lane == 0) scol[w][0] = make_uint2((unsigned)Pv, 0u);
-        dist = m;
-        for (int base = 0; base < n; base += 64) {
-            const int mine = (base + lane < n) ? gt_row[base + lane] : -2;
-            const int cnt = min(64, n - base);
-            uint2 keep = make_uint2(0u, 0u);
-            for (int i = 0; i < cnt; ++i) {
-                const int c = __shfl(mine, i, 64);
-                const unsigned long long Eq = __ballot(lane < m && pc == c);
-                const unsigned long long Xv = Eq | Mv;
-                const unsigned long long Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-                unsigned long long Ph = Mv | ~(Xh | Pv);
-                unsigned long long Mh = Pv & Xh;
-                dist += (Ph & top) ? 1 : 0;
-                dist -= (Mh & top) ? 1 : 0;
-                Ph = (Ph << 1) | 1ull;
-                Mh <<= 1;
-                Pv = Mh | ~(Xv | Ph);
-                Mv = Ph & Xv;
-                if (lane == i) keep = make_uint2((unsigned)Pv, (unsigned)Mv);      // lane i keeps column base + i + 1
-            }
-            if (lane < cnt) { scol[w][base + lane + 1] = keep; sgt[w][base + lane] = mine; }
-        }
-        if (m == 0) dist = n;                                // empty prediction: n deletions (the columns are not read then)
-    }
+    // ---- phase 1: the recurrence, columns and label kept (an empty prediction: n deletions; the columns are not read then)
+    const int dist = active ? eval_wave_distance<true>(r.pc, m, gt + (size_t)b * G, n, lane, scol[w], sgt[w]) : 0;
     __syncthreads();
 
     // ---- phase 2: the trace back (every lane computes the same steps; lane 0 records them)

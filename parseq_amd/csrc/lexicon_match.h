@@ -2,8 +2,8 @@
 // seeds the beam state with them.  All integer arithmetic; the result does not depend on the grid.
 //
 // The list is a table of 32-byte rows, one per entered word in ascending word id: bytes 0 .. 30 the class ids, byte 31 the length (1 .. 31).
-// A thread owns a word and walks a tile of LM_TC crops: the distance is Hyyro's bit-parallel form of Myers' algorithm with the READING as
-// the pattern — a reading has at most 32 characters, so its column of the DP fits one 32-bit word — and the word's characters as the text.
+// A thread owns a word and walks a tile of LM_TC crops: the distance is Hyyro's bit-parallel form of Myers' algorithm (myers_step,
+// myers.h: the one the evaluation kernels take too) with the READING as the pattern — a reading has at most 32 characters, so its column of the DP fits one 32-bit word — and the word's characters as the text.
 // The per-crop pattern masks peq[c][t] (bit i: character i of crop t's reading is class c) live in LDS with the crop index innermost, so
 // one 16-byte LDS read gives a word character's masks for the whole tile.
 //
@@ -13,6 +13,7 @@
 #pragma once
 #include <climits>
 #include "common.h"
+#include "myers.h"
 
 namespace pq {
 
@@ -28,21 +29,6 @@ constexpr unsigned LM_KEY_DEAD = 0xFFFFFFFFu;
 constexpr int LM_DEAD_DISTANCE = 0x7FFFFFFF;      // PARSEQ_LEXICON_MATCH_DEAD: the distance of a slot beyond the list
 
 static inline int lm_chunks(int nrows) { return (nrows + LM_CHUNK - 1) / LM_CHUNK; }
-
-// One Myers / Hyyro column step of the global (Levenshtein) distance: eq = the pattern positions the text character matches, hb = the
-// pattern's top bit.  Bits above the pattern's length never reach the ones below (carries and shifts go upwards only).
-__device__ __forceinline__ void lm_step(unsigned eq, unsigned hb, unsigned& pv, unsigned& mv, int& score) {
-    const unsigned xv = eq | mv;
-    const unsigned xh = (((eq & pv) + pv) ^ pv) | eq;
-    unsigned ph = mv | ~(xh | pv);
-    unsigned mh = pv & xh;
-    score += (ph & hb) ? 1 : 0;
-    score -= (mh & hb) ? 1 : 0;
-    ph = (ph << 1) | 1u;      // the DP's first row grows by one per text character
-    mh <<= 1;
-    pv = mh | ~(xv | ph);
-    mv = ph & xv;
-}
 
 // grid (ceil(nrows / 256), crop groups); a workgroup walks the crops [blockIdx.y * crops_per_block, ...) in tiles of LM_TC.
 //   readings [B][ldt] (ldt <= 32), lengths [B] or null; a reading ends before its first <eos> and at its length
@@ -116,10 +102,10 @@ void lexicon_match_kernel(const int* __restrict__ readings, int ldt, const int* 
                 if (4 * k + i < len) {
                     const unsigned c = (dw >> (8 * i)) & 255u;
                     const uint4 eq = s_peq[c];      // (a class id >= C: the row is not of this charset; its masks are whatever — refused on the host)
-                    lm_step(eq.x, hb[0], pv[0], mv[0], sc[0]);
-                    lm_step(eq.y, hb[1], pv[1], mv[1], sc[1]);
-                    lm_step(eq.z, hb[2], pv[2], mv[2], sc[2]);
-                    lm_step(eq.w, hb[3], pv[3], mv[3], sc[3]);
+                    myers_step(eq.x, hb[0], pv[0], mv[0], sc[0]);
+                    myers_step(eq.y, hb[1], pv[1], mv[1], sc[1]);
+                    myers_step(eq.z, hb[2], pv[2], mv[2], sc[2]);
+                    myers_step(eq.w, hb[3], pv[3], mv[3], sc[3]);
                 }
             }
         }

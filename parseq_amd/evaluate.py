@@ -80,23 +80,57 @@ def decode_ground_truth(encoded: np.ndarray, n: int) -> List[str]:
     return [''.join(map(chr, body[i, :encoded[i]])) for i in range(n)]
 
 
-def reduce_result(result: BatchResult, process_group=None) -> BatchResult:
-    """Totals summed over the ranks of `process_group` (None = the default group) — what `sync_dist=True` does to the logged values in
-    base.py:171-177, applied to the totals so that the quotients are those of the whole job.  Host tensors: works on gloo."""
+def _all_reduce_words(ints, floats, process_group):
+    """(`ints`, `floats`) summed over the ranks of `process_group` (None = the default group), as lists: one int64 and one float64
+    all-reduce of host tensors (works on gloo); an empty side is skipped."""
     import torch.distributed as dist
-    ints = torch.tensor([result.num_samples, result.correct, result.label_length, result.loss_numel or 0], dtype=torch.int64)
-    loss_sum = float(result.loss) * result.loss_numel if result.loss_numel else 0.0
-    floats = torch.tensor([result.ned, result.confidence, loss_sum], dtype=torch.float64)
-    dist.all_reduce(ints, group=process_group)
-    dist.all_reduce(floats, group=process_group)
-    n, correct, label_length, numel = ints.tolist()
-    ned, confidence, loss_sum = floats.tolist()
-    if result.loss_numel is None:
+    out = []
+    for words, dtype in ((ints, torch.int64), (floats, torch.float64)):
+        words = torch.as_tensor(words, dtype=dtype)
+        if words.numel():
+            dist.all_reduce(words, group=process_group)
+        out.append(words.tolist())
+    return out
+
+
+def _batch_result(n, correct, label_length, ned, confidence, loss_sum, numel, with_loss: bool) -> BatchResult:
+    """The greedy totals as a `BatchResult`; with the loss, `loss` is sum(loss * numel) / sum(numel) (base.py:146-164) as a float64 host scalar."""
+    if not with_loss:
         return BatchResult(n, correct, ned, confidence, label_length, None, None)
     return BatchResult(n, correct, ned, confidence, label_length, torch.tensor(loss_sum / numel if numel else float('nan'), dtype=torch.float64), numel)
 
 
-class Evaluator:
+def reduce_result(result: BatchResult, process_group=None) -> BatchResult:
+    """Totals summed over the ranks of `process_group` (None = the default group) — what `sync_dist=True` does to the logged values in
+    base.py:171-177, applied to the totals so that the quotients are those of the whole job.  Host tensors: works on gloo."""
+    loss_sum = float(result.loss) * result.loss_numel if result.loss_numel else 0.0
+    (n, correct, label_length, numel), (ned, confidence, loss_sum) = _all_reduce_words(
+        [result.num_samples, result.correct, result.label_length, result.loss_numel or 0], [result.ned, result.confidence, loss_sum], process_group)
+    return _batch_result(n, correct, label_length, ned, confidence, loss_sum, numel, result.loss_numel is not None)
+
+
+class _DeviceEvaluator:
+    """What `Evaluator`, `BeamEvaluator` and `ErrorAnalysis` share: the system must be on the GPU (there is no CPU path), its adapter as
+    a table on the device (`host_path` when it has none: see the module docstring), and the upload of a batch's labels."""
+
+    def __init__(self, system) -> None:
+        self.system = system
+        self.device = torch.device(system.device)
+        if self.device.type != 'cuda':
+            raise RuntimeError(f'{type(self).__name__} runs on the GPU (no CPU fallback); move the model to the device first')
+        table = adapter_table(system.tokenizer, system.charset_adapter)
+        self.host_path = table is None
+        self._table = None if self.host_path else torch.from_numpy(table).to(self.device)
+
+    def _upload_labels(self, labels, n: int):
+        """`labels` (strings, or the device tensor an earlier upload made of them) as `encode_ground_truth` lays them out, on the device:
+        (the whole tensor, its [n] lengths, its code points, G).  One pinned, asynchronous copy."""
+        encoded = labels if isinstance(labels, Tensor) else torch.from_numpy(encode_ground_truth(labels)).pin_memory()
+        encoded = encoded.to(device=self.device, dtype=torch.int32, non_blocking=True).contiguous()
+        return encoded, encoded[:n], encoded[n:], (encoded.numel() - n) // n if n else 0
+
+
+class Evaluator(_DeviceEvaluator):
     """Running totals of an evaluation over any system with `.forward`, `.tokenizer` and `.charset_adapter` (PARSeq, ViTSTR).
 
         ev = Evaluator(model)                  # validation=True adds the loss, as validation_step does
@@ -111,13 +145,8 @@ class Evaluator:
     the device path (ValueError on a model whose charsets select `host_path`)."""
 
     def __init__(self, system, validation: bool = False, errors: Optional['ErrorAnalysis'] = None, audit: Optional['LabelAudit'] = None) -> None:
-        self.system, self.validation, self.errors, self.audit = system, validation, errors, audit
-        self.device = torch.device(system.device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('Evaluator runs on the GPU (no CPU fallback); move the model to the device first')
-        table = adapter_table(system.tokenizer, system.charset_adapter)
-        self.host_path = table is None
-        self._table = None if self.host_path else torch.from_numpy(table).to(self.device)
+        super().__init__(system)
+        self.validation, self.errors, self.audit = validation, errors, audit
         if audit is not None and self.host_path:
             raise ValueError('Evaluator(audit=) needs the device path; this model\'s charsets select the host path')
         self._last_rows = None
@@ -143,7 +172,7 @@ class Evaluator:
         from . import _native
         from .system import forward_logits_loss
         n = len(labels)
-        encoded = torch.from_numpy(encode_ground_truth(labels)).pin_memory().to(self.device, non_blocking=True)
+        encoded, gt_len, gt, width = self._upload_labels(labels, n)
         if self.validation:
             logits, loss, numel = forward_logits_loss(self.system, images, labels)
             self._loss_sum += loss.double() * numel
@@ -160,11 +189,10 @@ class Evaluator:
         conf = torch.empty((n,), dtype=torch.float32, device=dev)
         rows = torch.empty((n, 4), dtype=torch.int32, device=dev)
         ws = torch.empty((n,), dtype=torch.float64, device=dev)
-        width = (encoded.numel() - n) // n
         with _native.guard(dev):
             _native.check(_native.lib().parseq_eval_metrics(
-                _native.ptr(logits), n, length, classes, self.system.tokenizer.eos_id, _native.ptr(self._table), _native.ptr(encoded[n:]),
-                _native.ptr(encoded), width, _native.ptr(ids), _native.ptr(lengths), _native.ptr(conf), _native.ptr(rows), _native.ptr(ws),
+                _native.ptr(logits), n, length, classes, self.system.tokenizer.eos_id, _native.ptr(self._table), _native.ptr(gt),
+                _native.ptr(gt_len), width, _native.ptr(ids), _native.ptr(lengths), _native.ptr(conf), _native.ptr(rows), _native.ptr(ws),
                 _native.ptr(self._accum), _native.stream_ptr(dev)))
         self._last_rows = rows
         if self.errors is not None:
@@ -172,28 +200,9 @@ class Evaluator:
         if self.audit is not None:
             self.audit.update_ids(images, labels, ids, lengths, rows[:, 3])
 
-    def _eval_step_with_errors(self, images: Tensor, labels: Sequence[str]) -> BatchResult:
-        """`eval_step` (system.py) with the ids kept for the error analysis: the same forward, the same sums in the same order."""
-        from .system import forward_logits_loss
-        if self.validation:
-            logits, loss, loss_numel = forward_logits_loss(self.system, images, labels)
-        else:
-            logits, loss, loss_numel = self.system.forward(images), None, None
-        tokenizer = self.system.tokenizer
-        ids, lengths, _, conf = tokenizer._postprocess(logits)
-        self.errors.update_ids(ids, lengths, labels)
-        correct = label_length = 0
-        ned = confidence = 0.0
-        for row, k, c, gt in zip(ids.cpu().numpy(), lengths.cpu().tolist(), conf.cpu().tolist(), labels):
-            confidence += c
-            pred = self.system.charset_adapter(tokenizer._ids2tok(row[:k].tolist()))
-            ned += edit_distance(pred, gt) / max(len(pred), len(gt), 1)
-            correct += int(pred == gt)
-            label_length += len(pred)
-        return BatchResult(len(labels), correct, ned, confidence, label_length, loss, loss_numel)
-
     def _update_host(self, images: Tensor, labels: Sequence[str]) -> None:
-        r = eval_step(self.system, (images, labels), self.validation)['output'] if self.errors is None else self._eval_step_with_errors(images, labels)
+        sink = None if self.errors is None else lambda ids, lengths: self.errors.update_ids(ids, lengths, labels)
+        r = eval_step(self.system, (images, labels), self.validation, sink)['output']
         h = self._host
         h[0] += r.num_samples; h[1] += r.correct; h[2] += r.label_length; h[3] += r.ned; h[4] += r.confidence
         if self.validation:
@@ -209,9 +218,7 @@ class Evaluator:
             n, correct, label_length = packed[:3].tolist()
             ned, confidence, loss_sum = packed[3:6].view(torch.float64).tolist()
             numel = int(packed[6])
-        if not self.validation:
-            return BatchResult(n, correct, ned, confidence, label_length, None, None)
-        return BatchResult(n, correct, ned, confidence, label_length, torch.tensor(loss_sum / numel if numel else float('nan'), dtype=torch.float64), numel)
+        return _batch_result(n, correct, label_length, ned, confidence, loss_sum, numel, self.validation)
 
     def per_sample(self) -> np.ndarray:
         """The last batch's rows, int32 [B, 4]: length of the adapted prediction, length of the label, edit distance, exact match."""
@@ -337,15 +344,10 @@ def host_beam_metrics(hypotheses, labels):
 def reduce_beam_result(result: BeamEvalResult, process_group=None) -> BeamEvalResult:
     """The sums of `result` added over the ranks of `process_group` (None = the default group), as `reduce_result` does for the greedy
     totals: the quotients are then those of the whole job.  Host tensors: works on gloo."""
-    import torch.distributed as dist
-    ints, floats = result._words()
-    ints, floats = torch.tensor(ints, dtype=torch.int64), torch.tensor(floats, dtype=torch.float64)
-    dist.all_reduce(ints, group=process_group)
-    dist.all_reduce(floats, group=process_group)
-    return BeamEvalResult._from_words(ints.tolist(), floats.tolist())
+    return BeamEvalResult._from_words(*_all_reduce_words(*result._words(), process_group))
 
 
-class BeamEvaluator:
+class BeamEvaluator(_DeviceEvaluator):
     """Running totals of an evaluation of N-best decoding: `Evaluator` for `beam_search` / `lexicon_match` and everything they compose with.
 
         ev = BeamEvaluator(model, beam_width=5, lexicon=lexicon)      # the search's own keywords
@@ -363,18 +365,12 @@ class BeamEvaluator:
     def __init__(self, system, beam_width: int = 5, lexicon=None, roots=None, automaton=None, alpha: float = 1.0, beta: float = 0.0,
                  refine: Optional[str] = None, refine_iters: int = 1, match: Optional[int] = None, rescore: bool = True, keep_reading: bool = False,
                  ignore_case: bool = False) -> None:
-        self.system = system
-        self.device = torch.device(system.device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('BeamEvaluator runs on the GPU (no CPU fallback); move the model to the device first')
+        super().__init__(system)
         if match is not None and lexicon is None:
             raise ValueError('BeamEvaluator: match= needs a lexicon')
         self.beam_width, self.match = beam_width, match
         self._search = dict(lexicon=lexicon, roots=roots, automaton=automaton, alpha=alpha, beta=beta, refine=refine, refine_iters=refine_iters)
         self._match = dict(rescore=rescore, keep_reading=keep_reading, ignore_case=ignore_case)
-        table = adapter_table(system.tokenizer, system.charset_adapter)
-        self.host_path = table is None
-        self._table = None if self.host_path else torch.from_numpy(table).to(self.device)
         self.reset()
 
     def reset(self) -> None:
@@ -403,7 +399,7 @@ class BeamEvaluator:
             return
         from . import _native
         dev = self.device
-        encoded = torch.from_numpy(encode_ground_truth(labels)).pin_memory().to(dev, non_blocking=True)
+        _, gt_len, gt, gt_width = self._upload_labels(labels, n)
         _, width, steps = result.tokens.shape
         tokens = result.tokens.to(torch.int32).contiguous()
         scores = result.scores.to(torch.float32).contiguous()
@@ -412,11 +408,10 @@ class BeamEvaluator:
         hyp_rows = torch.empty((n * width, 4), dtype=torch.int32, device=dev)
         image_rows = torch.empty((n, 8), dtype=torch.int32, device=dev)
         ws = torch.empty((n * (width + 3),), dtype=torch.float64, device=dev)
-        gt_width = (encoded.numel() - n) // n if n else 0
         with _native.guard(dev):
             _native.check(_native.lib().parseq_eval_beams(
                 _native.ptr(tokens), _native.ptr(scores), _native.ptr(lengths), _native.ptr(conf), n, width, steps, self._table.numel(),
-                _native.ptr(self._table), _native.ptr(encoded[n:]), _native.ptr(encoded), gt_width, _native.ptr(hyp_rows), _native.ptr(image_rows),
+                _native.ptr(self._table), _native.ptr(gt), _native.ptr(gt_len), gt_width, _native.ptr(hyp_rows), _native.ptr(image_rows),
                 _native.ptr(ws), _native.ptr(self._accum), _native.stream_ptr(dev)))
         self._last = (hyp_rows, image_rows, width)
 
@@ -632,10 +627,7 @@ class ErrorReport:
 def reduce_report(report: ErrorReport, process_group=None) -> ErrorReport:
     """The tables of `report` added over the ranks of `process_group` (None = the default group), as `reduce_result` does for the totals.
     One int64 all-reduce of a host tensor: works on gloo.  The ranks must analyse the same symbol set."""
-    import torch.distributed as dist
-    words = torch.from_numpy(report._words())
-    dist.all_reduce(words, group=process_group)
-    return ErrorReport._from_words(report.symbols, words.numpy())
+    return ErrorReport._from_words(report.symbols, _all_reduce_words(report._words(), [], process_group)[0])
 
 
 def _host_symbols(tokenizer, charset_adapter) -> List[str]:
@@ -650,7 +642,7 @@ def _host_symbols(tokenizer, charset_adapter) -> List[str]:
     return sorted(chars)
 
 
-class ErrorAnalysis:
+class ErrorAnalysis(_DeviceEvaluator):
     """Running edit scripts and error tables of an evaluation, beside `Evaluator`'s totals:
 
         errors = ErrorAnalysis(model)
@@ -663,20 +655,14 @@ class ErrorAnalysis:
     charsets select `host_path` (see the module docstring) is analysed by `host_edit_script` per sample: the same tables."""
 
     def __init__(self, system) -> None:
-        self.system = system
-        self.device = torch.device(system.device)
-        if self.device.type != 'cuda':
-            raise RuntimeError('ErrorAnalysis runs on the GPU (no CPU fallback); move the model to the device first')
-        table = adapter_table(system.tokenizer, system.charset_adapter)
-        self.host_path = table is None
-        self.symbols = _host_symbols(system.tokenizer, system.charset_adapter) if self.host_path else [chr(c) for c in symbol_table(table)]
+        super().__init__(system)
+        self.symbols = _host_symbols(system.tokenizer, system.charset_adapter) if self.host_path else [chr(c) for c in symbol_table(self._table.cpu().numpy())]
         if not 1 <= len(self.symbols) <= MAX_SYMBOLS:
             raise ValueError(f'{len(self.symbols)} symbols: the error analysis takes 1 to {MAX_SYMBOLS}')
         self._words = _CONFUSION + (len(self.symbols) + 2) ** 2
         if self.host_path:
             self._index = {ch: i for i, ch in enumerate(self.symbols)}
         else:
-            self._table = torch.from_numpy(table).to(self.device)
             self._symbols = torch.tensor([ord(ch) for ch in self.symbols], dtype=torch.int32).to(self.device)
         self.reset()
 
@@ -704,17 +690,15 @@ class ErrorAnalysis:
             return
         from . import _native
         dev = self.device
-        encoded = labels if isinstance(labels, Tensor) else torch.from_numpy(encode_ground_truth(labels)).pin_memory().to(dev, non_blocking=True)
-        encoded = encoded.to(device=dev, dtype=torch.int32).contiguous()
+        _, gt_len, gt, width = self._upload_labels(labels, n)
         ids, lengths = ids.to(device=dev, dtype=torch.int32).contiguous(), lengths.to(device=dev, dtype=torch.int32).contiguous()
-        width = (encoded.numel() - n) // n
         scripts = torch.empty((n, SCRIPT_WIDTH), dtype=torch.int8, device=dev)
         script_len = torch.empty((n,), dtype=torch.int32, device=dev)
         rows = torch.empty((n, 4), dtype=torch.int32, device=dev)
         with _native.guard(dev):
             _native.check(_native.lib().parseq_eval_errors(
                 _native.ptr(ids), _native.ptr(lengths), n, length, self._table.numel(), _native.ptr(self._table), _native.ptr(self._symbols),
-                len(self.symbols), _native.ptr(encoded[n:]), _native.ptr(encoded), width, _native.ptr(scripts), _native.ptr(script_len), _native.ptr(rows),
+                len(self.symbols), _native.ptr(gt), _native.ptr(gt_len), width, _native.ptr(scripts), _native.ptr(script_len), _native.ptr(rows),
                 _native.ptr(self._accum), _native.stream_ptr(dev)))
         self._last = (scripts, script_len, rows)
 

@@ -4,7 +4,8 @@
 in `parser.error`.  The resolvers read `args.nbest` and `args.boxes` too; a command line without those flags sets them (test.py: the
 N-best is the whole beam, no boxes).  --auto-rotate / --upright-bias have their rules at the end of the module: they
 choose the crops every other flag then works on, so they compose with all of them but --polygons.  --candidates / --expect of read.py and
---audit of test.py score given strings instead of searching for one: they refuse every search flag."""
+--audit of test.py score given strings instead of searching for one: they refuse every search flag, as does
+--analyse of test.py."""
 from argparse import SUPPRESS
 from collections import namedtuple
 
@@ -366,6 +367,24 @@ def resolve_audit(parser, args, flags):
     if args.auto_rotate is not None or args.upright_bias is not None:
         parser.error('--audit scores the crop as it is: not with --auto-rotate')
     return (args.audit,) + picked
+
+
+def add_analysis_flag(parser) -> None:
+    """--analyse [K] of test.py."""
+    parser.add_argument('--analyse', type=int, nargs='?', const=20, default=None, metavar='K',
+                        help='After the table: operation totals, accuracy by label length and the K (default 20) most frequent confusions, deletions '
+                             'and insertions per dataset; every table goes to <checkpoint>.errors.json')
+
+
+def resolve_analysis(parser, args, flags):
+    """K of --analyse, None without it; `flags`: the resolved search flags.  A contradiction ends in parser.error."""
+    if args.analyse is None:
+        return None
+    if args.analyse < 1:
+        parser.error('--analyse K must be at least 1')
+    if flags is not None:
+        parser.error('--analyse describes the greedy reading: not with a search flag (the analysis of an N-best is out of scope)')
+    return args.analyse
 
 
 def orientation_prior(bias: float, views: int):

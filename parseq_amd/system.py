@@ -84,8 +84,9 @@ def forward_logits_loss(system, images: Tensor, labels):
     return logits, loss, numel
 
 
-def eval_step(system, batch, validation: bool):
-    """BaseSystem._eval_step (strhub/models/base.py:112-143) for any system with `.forward`, `.tokenizer`, `.charset_adapter`."""
+def eval_step(system, batch, validation: bool, sink=None):
+    """BaseSystem._eval_step (strhub/models/base.py:112-143) for any system with `.forward`, `.tokenizer`, `.charset_adapter`.
+    `sink(ids, lengths)`, if given, receives the device tensors of the greedy pick the strings are made from."""
     images, labels = batch
     with torch.inference_mode():
         if validation:
@@ -94,7 +95,7 @@ def eval_step(system, batch, validation: bool):
             # at test time no max_length is given (base.py:123-130): the test charset may shorten the labels
             logits, loss, loss_numel = system.forward(images), None, None
         # base.py:132-137 on the device: soft-max, greedy pick, first-EOS cut and prob.prod() in one kernel (row N1)
-        preds, confs = system.tokenizer.read(logits)
+        preds, confs = system.tokenizer.read(logits, sink)
     correct = total = label_length = 0
     ned = confidence = 0.0
     for pred, conf, gt in zip(preds, confs.tolist(), labels):

@@ -135,9 +135,12 @@ class Tokenizer(BaseTokenizer):
         labels = [self._ids2tok(row[:k].tolist()) for row, k in zip(ids_h, len_h)]
         return labels, [probs[i, :min(k + 1, width)] for i, k in enumerate(len_h)]
 
-    def read(self, logits: Tensor) -> Tuple[List[str], Tensor]:
-        """(labels, confidence [N] on the host): what `read.py` / `_eval_step` consume (`prob.prod()` per label)."""
+    def read(self, logits: Tensor, sink=None) -> Tuple[List[str], Tensor]:
+        """(labels, confidence [N] on the host): what `read.py` / `_eval_step` consume (`prob.prod()` per label).  `sink(ids, lengths)`, if
+        given, receives the device tensors the labels are made from."""
         ids, lengths, _, conf = self._postprocess(logits)
+        if sink is not None:
+            sink(ids, lengths)
         ids_h, len_h = ids.cpu().numpy(), lengths.cpu().tolist()
         return [self._ids2tok(row[:k].tolist()) for row, k in zip(ids_h, len_h)], conf.cpu()
 

@@ -61,8 +61,8 @@ from parseq_amd import load_from_checkpoint, parse_model_args
 from parseq_amd.data import parse_gt_line, preprocess_label, read_gt  # noqa: F401  (the first two keep their names here)
 from parseq_amd.evaluate import BeamEvaluator, ErrorAnalysis, ErrorReport, Evaluator, LabelAudit
 from parseq_amd.preprocess import orientation_views, resize_batch
-from parseq_amd.search_flags import (add_audit_flag, add_evaluation_flags, add_orientation_flags, evaluation_width, evaluator_arguments, orientation_prior,
-                                      resolve_audit, resolve_evaluation_flags, resolve_orientation)
+from parseq_amd.search_flags import (add_analysis_flag, add_audit_flag, add_evaluation_flags, add_orientation_flags, evaluation_width, evaluator_arguments,
+                                      orientation_prior, resolve_analysis, resolve_audit, resolve_evaluation_flags, resolve_orientation)
 from parseq_amd.tokenizer import CharsetAdapter  # noqa: F401
 
 
@@ -155,54 +155,45 @@ def evaluate_dataset(model, root: str, name: str, batch_size: int = 512, rotatio
         turned = int(system.turned)
         print(f'{name}: {turned} of {len(samples)} crops read turned ({100 * turned / max(len(samples), 1):.2f} %)')
     n = r.num_samples
-    if search is not None:
-        return BeamTableResult(name, n, 100 * r.accuracy, 100 * (1 - r.ned) if n else 0.0, 100 * r.confidence, r.label_length, 100 * r.hit_at(width),
-                               100 * (1 - r.oracle_ned) if n else 0.0, r.mrr)
-    if not n:
-        return Result(name, 0, 0.0, 0.0, 0.0, 0.0)
-    return Result(name, n, 100 * r.correct / n, 100 * (1 - r.ned / n), 100 * r.confidence / n, r.label_length / n)
+    if search is None:
+        row, cells = Result, (100 * r.correct / n, 100 * (1 - r.ned / n), 100 * r.confidence / n, r.label_length / n) if n else ()
+    else:
+        row, cells = BeamTableResult, (100 * r.accuracy, 100 * (1 - r.ned), 100 * r.confidence, r.label_length, 100 * r.hit_at(width), 100 * (1 - r.oracle_ned), r.mrr)
+    return row(name, n, *cells) if n else row(name, 0, 0.0, 0.0, 0.0, 0.0)      # an empty dataset: a row of zeros, in either table
+
+
+_HEADS = ('# samples', 'Accuracy', '1 - NED', 'Confidence', 'Label Length')
+_FIELDS = ('accuracy', 'ned', 'confidence', 'label_length')
+
+
+def _print_table(results: List[Result], heads, fields, formats, widths, file) -> None:
+    """One Markdown table: a row per dataset — its name, its samples under `heads[0]`, then `fields` in `formats` under the other
+    `heads`, right-aligned in `widths` — then the sample-weighted `Combined` row."""
+    name_width = max([len(r.dataset) for r in results] + [len('Combined')])
+    total = sum(r.num_samples for r in results)
+
+    def row(name: str, samples: int, values) -> str:
+        cells = [f'{samples:d}'] + [format(v, f) for v, f in zip(values, formats)]
+        return ' | '.join(['| ' + name.ljust(name_width)] + [c.rjust(w) for c, w in zip(cells, widths)]) + ' |'
+
+    print(' | '.join(['| ' + 'Dataset'.ljust(name_width)] + [h.rjust(w) for h, w in zip(heads, widths)]) + ' |', file=file)
+    print('|:' + '-' * name_width + ':|' + '|'.join('-' * (w + 1) + ':' for w in widths) + '|', file=file)
+    for r in results:
+        print(row(r.dataset, r.num_samples, [getattr(r, f) for f in fields]), file=file)
+    print('|-' + '-' * name_width + '-|' + '|'.join('-' * (w + 2) for w in widths) + '|', file=file)
+    print(row('Combined', total, [sum(r.num_samples * getattr(r, f) for r in results) / total if total else 0.0 for f in fields]), file=file)
 
 
 def print_results_table(results: List[Result], file=None) -> None:
     """The reference's Markdown table (test.py:40-66): one row per dataset, then the sample-weighted `Combined` row."""
-    width = max([len(r.dataset) for r in results] + [len('Combined')])
-    heads = ('# samples', 'Accuracy', '1 - NED', 'Confidence', 'Label Length')
-
-    def row(r: Result) -> str:
-        cells = (f'{r.num_samples:d}', f'{r.accuracy:.2f}', f'{r.ned:.2f}', f'{r.confidence:.2f}', f'{r.label_length:.2f}')
-        return ' | '.join(['| ' + r.dataset.ljust(width)] + [c.rjust(len(h)) for c, h in zip(cells, heads)]) + ' |'
-
-    print(' | '.join(['| ' + 'Dataset'.ljust(width)] + list(heads)) + ' |', file=file)
-    print('|:' + '-' * width + ':|' + '|'.join('-' * (len(h) + 1) + ':' for h in heads) + '|', file=file)
-    total = sum(r.num_samples for r in results)
-    for r in results:
-        print(row(r), file=file)
-
-    def mean(field: str) -> float:
-        return sum(r.num_samples * getattr(r, field) for r in results) / total if total else 0.0
-    print('|-' + '-' * width + '-|' + '|'.join('-' * (len(h) + 2) for h in heads) + '|', file=file)
-    print(row(Result('Combined', total, mean('accuracy'), mean('ned'), mean('confidence'), mean('label_length'))), file=file)
+    _print_table(results, _HEADS, _FIELDS, ('.2f',) * 4, [len(h) for h in _HEADS], file)
 
 
 def print_beam_results_table(results: List[BeamTableResult], width: int, file=None) -> None:
     """The table of an N-best evaluation: the reference's columns, then Hit@W, Oracle 1 - NED and MRR; the same layout and `Combined` row."""
-    name_width = max([len(r.dataset) for r in results] + [len('Combined')])
-    heads = ('# samples', 'Accuracy', '1 - NED', 'Confidence', 'Label Length', f'Hit@{width}', 'Oracle 1 - NED', 'MRR')
-    fields = ('accuracy', 'ned', 'confidence', 'label_length', 'hit', 'oracle_ned', 'mrr')
-
-    def row(r: BeamTableResult) -> str:
-        cells = [f'{r.num_samples:d}'] + [f'{getattr(r, f):.2f}' for f in fields[:-1]] + [f'{r.mrr:.4f}']
-        return ' | '.join(['| ' + r.dataset.ljust(name_width)] + [c.rjust(w) for c, w in zip(cells, widths)]) + ' |'
-
+    heads = _HEADS + (f'Hit@{width}', 'Oracle 1 - NED', 'MRR')
     widths = [max(len(h), 6) for h in heads]             # '100.00' and '0.1234' fit under the short heads too
-    print(' | '.join(['| ' + 'Dataset'.ljust(name_width)] + [h.rjust(w) for h, w in zip(heads, widths)]) + ' |', file=file)
-    print('|:' + '-' * name_width + ':|' + '|'.join('-' * (w + 1) + ':' for w in widths) + '|', file=file)
-    total = sum(r.num_samples for r in results)
-    for r in results:
-        print(row(r), file=file)
-    means = [sum(r.num_samples * getattr(r, f) for r in results) / total if total else 0.0 for f in fields]
-    print('|-' + '-' * name_width + '-|' + '|'.join('-' * (w + 2) for w in widths) + '|', file=file)
-    print(row(BeamTableResult('Combined', total, *means)), file=file)
+    _print_table(results, heads, _FIELDS + ('hit', 'oracle_ned', 'mrr'), ('.2f',) * 6 + ('.4f',), widths, file)
 
 
 def print_error_report(name: str, report: ErrorReport, top: int, file=None) -> None:
@@ -218,23 +209,6 @@ def print_error_report(name: str, report: ErrorReport, top: int, file=None) -> N
                         ('deletions (label characters not read)', [(repr(a), c) for a, c in report.top_deleted(top)]),
                         ('insertions (characters read that the label lacks)', [(repr(a), c) for a, c in report.top_inserted(top)])):
         print(f'Most frequent {title}: ' + (', '.join(f'{what} x {count}' for what, count in rows) if rows else 'none'), file=file)
-
-
-def add_analysis_flag(parser) -> None:
-    parser.add_argument('--analyse', type=int, nargs='?', const=20, default=None, metavar='K',
-                        help='After the table: operation totals, accuracy by label length and the K (default 20) most frequent confusions, deletions '
-                             'and insertions per dataset; every table goes to <checkpoint>.errors.json')
-
-
-def resolve_analysis(parser, args, flags) -> Optional[int]:
-    """K of --analyse, None without it; a contradiction ends in parser.error."""
-    if args.analyse is None:
-        return None
-    if args.analyse < 1:
-        parser.error('--analyse K must be at least 1')
-    if flags is not None:
-        parser.error('--analyse describes the greedy reading: not with a search flag (the analysis of an N-best is out of scope)')
-    return args.analyse
 
 
 def print_audit(name: str, files: List[str], report, top: int, file=None) -> List[dict]:

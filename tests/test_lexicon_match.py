@@ -201,6 +201,58 @@ def test_operator_refusals():
     torch.cuda.synchronize()
 
 
+def test_one_definition_of_the_distance():
+    """Lexicon matching, the metrics kernel and the error analysis share one column step (csrc/myers.h) and, the latter two, one loop over
+    the label: for the same 5 x 4 pairs — readings of 0, 1, 2, 31, 32 characters over 37 classes, words of 1, 2, 30, 31 — the three
+    operators and `parseq_amd.system.edit_distance` on the host give the same integers."""
+    from parseq_amd.system import edit_distance
+    nat, lib = native()
+    C, eos_id, L = 37, 0, 32
+    rng = random.Random(23)
+    alphabet = list(range(1, C))
+    readings = _readings(rng, alphabet, [0, 1, 2, 31, 32], L, eos_id, filler=C - 1)
+    lens = [0, 1, 2, 31, 32]
+    words = [[rng.choice(alphabet) for _ in range(n)] for n in (1, 2, 30, 31)]
+    words[2][:20], words[3][5:31] = readings[3][:20], readings[4][:26]      # the long pairs are near, not only far
+    text = lambda ids: ''.join(chr(48 + i) for i in ids)      # noqa: E731
+    want = [[edit_distance(text(r[:n]), text(w)) for w in words] for r, n in zip(readings, lens)]
+    assert want[0] == [1, 2, 30, 31] and want[3][2] < 30 and want[4][3] < 31      # the empty reading; the near pairs
+
+    ids, dist = _run_op(readings, None, words, list(range(4)), 4, C, eos_id)      # N = every word: (distance, id) order
+    assert [[dict(zip(i, d))[w] for w in range(4)] for i, d in zip(ids, dist)] == want, 'lexicon match'
+
+    # the same pairs, one row each, for the evaluation kernels: identity adapter (class id = code point), the word as the label
+    pairs = [(b, w) for b in range(5) for w in range(4)]
+    n, G = len(pairs), 31
+    table = torch.arange(C, dtype=torch.int32)
+    table[eos_id] = -1
+    gt = torch.zeros((n, G), dtype=torch.int32)
+    logits = torch.zeros((n, L, C))
+    for r, (b, w) in enumerate(pairs):
+        gt[r, :len(words[w])] = torch.tensor(words[w], dtype=torch.int32)
+        for pos, i in enumerate((readings[b][:lens[b]] + [eos_id])[:L]):
+            logits[r, pos, i] = 9.0
+    gt_len = torch.tensor([len(words[w]) for _, w in pairs], dtype=torch.int32, device=DEV)
+    table, gt, logits = table.to(DEV), gt.to(DEV), logits.to(DEV)
+    symbols = torch.arange(1, C, dtype=torch.int32, device=DEV)
+    ids_out = torch.empty((n, L), dtype=torch.int32, device=DEV)
+    lengths, conf = torch.empty((n,), dtype=torch.int32, device=DEV), torch.empty((n,), dtype=torch.float32, device=DEV)
+    rows, rows2 = torch.full((n, 4), -7, dtype=torch.int32, device=DEV), torch.full((n, 4), -7, dtype=torch.int32, device=DEV)
+    ws, totals = torch.empty(n, dtype=torch.float64, device=DEV), torch.zeros(5, dtype=torch.int64, device=DEV)
+    nat.check(lib.parseq_eval_metrics(nat.ptr(logits), n, L, C, eos_id, nat.ptr(table), nat.ptr(gt), nat.ptr(gt_len), G, nat.ptr(ids_out), nat.ptr(lengths),
+                                      nat.ptr(conf), nat.ptr(rows), nat.ptr(ws), nat.ptr(totals), nat.stream_ptr(logits)))
+    scripts = torch.empty((n, 256 + 32), dtype=torch.int8, device=DEV)
+    script_len = torch.empty((n,), dtype=torch.int32, device=DEV)
+    acc = torch.zeros(272 + (C - 1 + 2) ** 2, dtype=torch.int64, device=DEV)
+    nat.check(lib.parseq_eval_errors(nat.ptr(ids_out), nat.ptr(lengths), n, L, C, nat.ptr(table), nat.ptr(symbols), C - 1, nat.ptr(gt), nat.ptr(gt_len), G,
+                                     nat.ptr(scripts), nat.ptr(script_len), nat.ptr(rows2), nat.ptr(acc), nat.stream_ptr(logits)))
+    torch.cuda.synchronize()
+    flat = [want[b][w] for b, w in pairs]
+    assert lengths.cpu().tolist() == [lens[b] for b, _ in pairs]
+    assert rows[:, 2].cpu().tolist() == flat, 'metrics kernel'
+    assert rows2[:, 2].cpu().tolist() == flat, 'error analysis'
+
+
 # -------------------------------------------------------------------------------------------------------------------
 # 2. the whole call
 # -------------------------------------------------------------------------------------------------------------------
